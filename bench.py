@@ -16,9 +16,17 @@ pyramid buffers of an instance — sized for 288 GB of HBM; 128 per call is 7 % 
 
 Multi-GPU: one process per GPU; each rank owns its own frames (weak scaling: detection is per image and needs no
 collective); the timed region is bracketed by a barrier + device synchronize and the maximum over ranks is reported.
-After the timed region every rank also runs its shard of BASELINE config 4 (50k x 50k 2-NN, query rows sharded, ONE
-RCCL all-gather of the reference descriptors) and rank 0 prints the CRC-32 of the concatenated records: it must be the
+With --full, after the timed region every rank also runs its shard of BASELINE config 4 (50k x 50k 2-NN, query rows sharded,
+ONE RCCL all-gather of the reference descriptors) and rank 0 prints the CRC-32 of the concatenated records: it must be the
 same number at N = 1, 2, 4, 8. PyTorch is used for torch.distributed (RCCL) and device buffers only.
+
+A plain run sets up, warms up, times --steps steps and prints the line: the contract fields, roofline, stage_ms_per_call and
+the other figures read from the same timed steps. --full adds the legs marked below, the fp16_mode and matching_serialised
+re-runs and the sharded config-4 match (each takes runs of its own: ~45 s in all); --no-extras / --no-cpu-baseline drop
+parts of --full.
+
+--dump-outputs DIR (rank 0): after the timed steps, what a caller of the timed path receives, as .npy files in float32 /
+float64 (dump_outputs below). The frames come from fixed seeds, so runs with the same arguments see the same inputs.
 
 Objects on the JSON line besides the contract fields:
   roofline          the WHOLE scale-space + DoG pass (round 6): every scale-space launch of EVERY octave (fused up-sampling + seed blur, the
@@ -32,6 +40,7 @@ Objects on the JSON line besides the contract fields:
                     24 B per scanned pixel; <= traffic by construction). `octave0_and_scan` = rounds 1-5's definition (octave 0's five
                     launches + the scan) with its own `frac`, `algorithmic` and `per_launch` rows; `survey_8d` = SURVEY.md 8(d)'s pricing of
                     the reference's schedule (72.25 + 20 B/px), kept for comparison with rounds 1-3 only.
+  --full only:
   roofline_c3       the same for BASELINE config 3 (64 x 1920x1080, detect only), 5 steps
   plain_api         the 20 reference entry points ONLY (C caller, instance from vksift_createInstance): detect into N buffers then read them,
                     the same with two buffer sets, the two-buffer ping-pong — what deferred submission gives a caller of the reference
@@ -79,8 +88,12 @@ def parse_args():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--no-match", action="store_true", help="detect only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_host_input / single_image_ms / roofline_c3 / sharded match")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the legs that take runs of their own: host protocols, plain API, "
+                                                        "single image, configs 3 / 4 / 5, fp16 and serialised-matching re-runs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip value_host_input / single_image_ms / roofline_c3 / sharded match")
     ap.add_argument("--host-input", action="store_true", help="time the PCIe-inclusive protocol as the main loop (not the headline value)")
     ap.add_argument("--serialize-match", action="store_true",
                     help="the next detection's scale-space starts BEHIND the matching queued before it instead of beside it "
@@ -755,11 +768,75 @@ def multigpu_mod():
     return multigpu
 
 
+def gen_frames(api, seeds, W, H):
+    """api.gen_synthetic_image for every seed, on up to 16 host threads (the generator is C called through ctypes, which releases
+    the GIL; one 640x480 frame is ~0.1 s of host time). Same bytes as a serial loop."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(max_workers=min(16, usable_cores())) as ex:
+        return np.stack(list(ex.map(lambda s: api.gen_synthetic_image(s, W, H), seeds)))
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_BUFFERS = 16
+FEATURE_SCALARS = ("x", "y", "scale_x", "scale_y", "scale_idx", "octave_idx", "sigma", "orientation", "intensity")
+MATCH_FIELDS = ("idx_a", "idx_b1", "idx_b2", "dist_a_b1", "dist_a_b2")
+
+
+def dump_outputs(inst, nbuf, do_match, out_dir, seed=0x5EED):
+    """--dump-outputs: what a caller of the timed path receives once its last step has ended (the buffers then hold that step's
+    last sub-batch, buffer i matched against itself as pair i), written as DIR/<name>.npy:
+      feature_counts   float64 [nbuf]       features of every buffer
+      match_counts     float64 [nbuf]       records of every self-match pair (with matching)
+      sample_buffers   float64 [n]          a fixed seeded sample of DUMP_SAMPLE_BUFFERS buffers, ascending; it ends early rather
+                                            than let the files pass DUMP_MAX_BYTES
+      features         float32 [rows, 9]    the records of the sampled buffers, FEATURE_SCALARS columns (all exact in float32)
+      descriptors      float32 [rows, 128]
+      feature_buffer   float64 [rows]       buffer of each row
+      matches          float32 [mrows, 5]   the sampled buffers' 2-NN records, MATCH_FIELDS columns (with matching)
+      match_buffer     float64 [mrows]
+    Returns {name: bytes written}."""
+    counts = np.array([inst.getFeaturesNumber(i) for i in range(nbuf)], np.float64)
+    out = {"feature_counts": counts}
+    if do_match:
+        out["match_counts"] = np.array([inst.getMatchesNumberBatch(i) for i in range(nbuf)], np.float64)
+    total = sum(a.nbytes for a in out.values())
+    sample = np.sort(np.random.default_rng(seed).permutation(nbuf)[:min(DUMP_SAMPLE_BUFFERS, nbuf)])
+    taken = []
+    rows = {"features": [np.zeros((0, len(FEATURE_SCALARS)), np.float32)], "descriptors": [np.zeros((0, 128), np.float32)],
+            "feature_buffer": [np.zeros(0)]}
+    if do_match:
+        rows.update(matches=[np.zeros((0, len(MATCH_FIELDS)), np.float32)], match_buffer=[np.zeros(0)])
+    for i in (int(x) for x in sample):
+        f = inst.downloadFeatures(i)
+        m = inst.downloadMatchesBatch(i) if do_match else None
+        size = 8 + len(f) * (4 * len(FEATURE_SCALARS) + 4 * 128 + 8) + (len(m) * (4 * len(MATCH_FIELDS) + 8) if do_match else 0)
+        if total + size > DUMP_MAX_BYTES:
+            break
+        total += size
+        taken.append(i)
+        rows["features"].append(np.stack([f[k].astype(np.float32) for k in FEATURE_SCALARS], axis=1))
+        rows["descriptors"].append(f["descriptor"].astype(np.float32))
+        rows["feature_buffer"].append(np.full(len(f), float(i)))
+        if do_match:
+            rows["matches"].append(np.stack([m[k].astype(np.float32) for k in MATCH_FIELDS], axis=1))
+            rows["match_buffer"].append(np.full(len(m), float(i)))
+    out["sample_buffers"] = np.array(taken, np.float64)
+    out.update({name: np.concatenate(parts) for name, parts in rows.items()})
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.nbytes for name, a in out.items()}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def main():
     args = parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))                       # this process becomes the launcher of N ranks
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -809,7 +886,7 @@ def main():
     # Up to 128 generated frames per rank (85 ms of host time each) and, for longer batches, their three mirror images: B distinct
     # frames; the sub-batches of a step rotate through them with a different first frame.
     ngen = min(B, 128)
-    gen = np.stack([api.gen_synthetic_image(0x5EED0000 + rank * 128 + i, W, H) for i in range(ngen)])
+    gen = gen_frames(api, [0x5EED0000 + rank * 128 + i for i in range(ngen)], W, H)
     variants = [gen, gen[:, :, ::-1], gen[:, ::-1, :], gen[:, ::-1, ::-1]]
     host = np.ascontiguousarray(np.concatenate([variants[(k // ngen) % 4][: min(ngen, B - k)] for k in range(0, B, ngen)]))
     assert host.shape[0] == B or B > 4 * ngen
@@ -867,6 +944,8 @@ def main():
     placement = inst.getScaleSpacePlacement()
     match_ms = inst.getMatchTime() if do_match else None
     inst.setProfiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(inst, B, do_match, args.dump_outputs)      # before any leg below reuses the instance's buffers
 
     # The headline object first: the extra legs below run under a watchdog that prints it if one of them stalls (a collective
     # that one rank never enters would otherwise cost the whole line).
@@ -900,7 +979,8 @@ def main():
                 "parallelism": f"batch split x{world}, no collectives",
                 "input": "host images, upload inside the timed region" if args.host_input else "resident in HBM",
                 **({"tune": args.tune + " (development A/B, not the shipped configuration)"} if args.tune else {}),
-                "protocols": "value_host_input: the REFERENCE's own protocol and SURVEY.md 8(d)'s definition of the metric "
+                "protocols": "(the value_host_input* and single_image_ms legs run with --full) "
+                             "value_host_input: the REFERENCE's own protocol and SURVEY.md 8(d)'s definition of the metric "
                              "(src/perf/wrappers/vulkansift_wrapper.cpp:30-33: host image in, count + features + matches downloaded, strictly "
                              "serial) — the figure to compare with the reference's published runtimes. value: batched detection on HBM-resident "
                              "frames, nothing downloaded (kernel-side figure, the bench contract's definition of `value`: inputs resident when the "
@@ -943,22 +1023,23 @@ def main():
     watchdog.start()
 
     extras = {}
-    if not args.no_extras and world == 1:
+    extras_on = args.full and not args.no_extras
+    if extras_on and world == 1:
         # (before the sharded-match leg: once RCCL has created its streams, HIP maps this library's streams onto the hardware queues
         # differently and the per-stage intervals of an overlapped detection get attributed differently — same step time)
         extras["value_host_input"] = reference_protocol(api, inst, frames, W, H, B, do_match, 6)
     inst.close()
-    if not args.no_extras and world == 1:
+    if extras_on and world == 1:
         try:
             extras["value_host_input_pipelined"] = pipelined_protocol(api, dev.index, frames, W, H, B, do_match, 12)
         except Exception as e:  # noqa: BLE001
             extras["value_host_input_pipelined"] = {"error": repr(e)[:300]}
-    if not args.no_extras and world == 1:
+    if extras_on and world == 1:
         try:
             extras["plain_api"] = plain_api_protocol(api, dev.index, frames[:128], W, H, do_match)
         except Exception as e:  # noqa: BLE001
             extras["plain_api"] = {"error": repr(e)[:300]}
-    if not args.no_extras and world == 1:
+    if extras_on and world == 1:
         # in a fresh process: how HIP maps an instance's dozen streams onto the four hardware queues depends on the streams the
         # process created before (the 640x480 instance above), and with it the attribution of an overlapped detection's time to
         # its stages — same step time, stage intervals up to 2x apart. A fresh process is the reproducible case.
@@ -988,7 +1069,7 @@ def main():
                                    "stage_ms_per_call": d16["stage_ms_per_call"]}
         except Exception as e:  # noqa: BLE001
             extras["fp16_mode"] = {"error": repr(e)[:300]}
-    if not args.no_extras and world == 1 and do_match:
+    if extras_on and world == 1 and do_match:
         # the same workload with the matching of a step serialised in front of the next detection's scale-space instead of running beside it
         # (fresh process): what the blur launches and the scan reach when nothing shares the chip with them. The shipped schedule overlaps
         # them because it is ~1 % faster in frames/s; its stage times — and the headline roofline.frac — therefore include the contention.
@@ -1001,13 +1082,13 @@ def main():
                                              "note": "not the shipped schedule: scale-space behind the previous matching (VKSIFT_TUNE_PYR_GATE = 1)"}
         except Exception as e:  # noqa: BLE001
             extras["matching_serialised"] = {"error": repr(e)[:300]}
-    if not args.no_extras:
+    if extras_on:
         # BASELINE config 5 (north_star's multi-GPU workload): every rank, weak scaling; its collectives are timing barriers only
         try:
             extras["config5"] = c5_leg(api, torch, dist, dev, rank, world, use_dist=use_dist)
         except Exception as e:  # noqa: BLE001
             extras["config5"] = {"error": repr(e)[:300]}
-    if not args.no_extras:
+    if extras_on:
         # every rank takes part (the all-gather is a collective); a failure of this leg must not cost the headline line
         try:
             ms, crc = sharded_match(api, torch, dist, dev, rank, world, args.match_rows)
@@ -1032,10 +1113,10 @@ def main():
         for k in ("value_host_input", "value_host_input_pipelined"):
             if isinstance(out.get(k), (int, float)) and out["value"] > 0:
                 out[k + "_over_value"] = out[k] / out["value"]
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0's host cores, after the timed region (the other ranks are idle by now). At N = 1 the full sample incl. a 1920x1080
             # frame per core; at N > 1 (where the bench contract does not ask for it) one frame per core, so the line still carries it
-            out["cpu_baseline"] = cpu_baseline(frames, do_match, per_worker=2 if world == 1 else 1, hd_frame=(world == 1 and not args.no_extras))
+            out["cpu_baseline"] = cpu_baseline(frames, do_match, per_worker=2 if world == 1 else 1, hd_frame=(world == 1 and extras_on))
             out["cpu_baseline"]["measured_at_n_gpus"] = world
     watchdog.cancel()
     if rank == 0:

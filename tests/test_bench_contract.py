@@ -76,3 +76,75 @@ def test_whole_pass_roofline_prices_every_octave():
     assert abs(r2["frac"] - 58.0e9 * 2 / 22.0e-3 / 1e9 / 8000.0) < 1e-9 and abs(r2["traffic_over_algorithmic"] - 58.0e9 * 2 / alg) < 1e-9
     assert abs(r2["octave0_and_scan"]["frac"] - 50.0e9 * 2 / 18.0e-3 / 1e9 / 8000.0) < 1e-9 and r2["all_launches"] == pmc["all_octaves"]["launches"]
     assert abs(r2["frac"] - r2["achieved"] / r2["peak"]) < 1e-12 and r2["algorithmic"]["frac"] == r["frac"]
+
+
+class _FakeTimedPathInstance:
+    """what dump_outputs reads from an instance after the timed steps: per-buffer feature records and per-pair match records"""
+
+    def __init__(self, nbuf, rows_per_buffer=lambda i: 3 + 5 * i):
+        import numpy as np
+        from vulkansift_amd import api
+
+        rng = np.random.default_rng(1)
+        self.feats, self.matches = [], []
+        for i in range(nbuf):
+            n = rows_per_buffer(i)
+            f = np.zeros(n, api.FEATURE_DTYPE)
+            for k in ("x", "y", "scale_x", "scale_y", "sigma", "orientation", "intensity"):
+                f[k] = rng.random(n, dtype=np.float32) * 640
+            f["scale_idx"], f["octave_idx"] = rng.integers(0, 3, n), rng.integers(-1, 5, n)
+            f["descriptor"] = rng.integers(0, 256, (n, 128))
+            m = np.zeros(n, api.MATCH_DTYPE)
+            m["idx_a"], m["idx_b1"], m["idx_b2"] = np.arange(n), np.arange(n), rng.integers(0, n, n)
+            m["dist_a_b2"] = rng.random(n, dtype=np.float32)
+            self.feats.append(f)
+            self.matches.append(m)
+
+    def getFeaturesNumber(self, i):
+        return len(self.feats[i])
+
+    def downloadFeatures(self, i):
+        return self.feats[i].copy()
+
+    def getMatchesNumberBatch(self, k):
+        return len(self.matches[k])
+
+    def downloadMatchesBatch(self, k):
+        return self.matches[k].copy()
+
+
+def test_dump_outputs_are_float_arrays_of_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files, the same seeded sample of buffers every run, the records unchanged"""
+    import numpy as np
+
+    b = _bench()
+    inst = _FakeTimedPathInstance(40)
+    b.dump_outputs(inst, 40, True, str(tmp_path / "a"))
+    b.dump_outputs(inst, 40, True, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "features.npy" in names and "matches.npy" in names
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.tobytes() == y.tobytes(), n
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert list(got["feature_counts"]) == [len(f) for f in inst.feats] and list(got["match_counts"]) == [len(m) for m in inst.matches]
+    sample = [int(i) for i in got["sample_buffers"]]
+    assert len(sample) == b.DUMP_SAMPLE_BUFFERS and sample == sorted(set(sample))
+    for i in sample:
+        rows, f = got["feature_buffer"] == i, inst.feats[i]
+        assert np.array_equal(got["descriptors"][rows], f["descriptor"].astype(np.float32))
+        for c, k in enumerate(b.FEATURE_SCALARS):
+            assert np.array_equal(got["features"][rows, c], f[k].astype(np.float32)), k
+        mrows, m = got["match_buffer"] == i, inst.matches[i]
+        for c, k in enumerate(b.MATCH_FIELDS):
+            assert np.array_equal(got["matches"][mrows, c], m[k].astype(np.float32)), k
+
+
+def test_dump_outputs_stay_within_the_size_limit(tmp_path, monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 40_000)
+    inst = _FakeTimedPathInstance(40)
+    written = b.dump_outputs(inst, 40, False, str(tmp_path))
+    assert 0 < sum(written.values()) <= 40_000 and "matches" not in written
+    assert 0 < written["sample_buffers"] // 8 < b.DUMP_SAMPLE_BUFFERS
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) < 40_000 + 128 * len(written)

@@ -9,10 +9,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def test_descriptor_and_orientation_kernels_keep_their_registers():
+def test_descriptor_and_orientation_kernels_keep_their_registers(tmp_path):
     import descriptor_floor as df
-    df.kernel_isa()  # compiles features.hip with the build's own flags to /tmp/_features_floor.s
-    txt = open("/tmp/_features_floor.s").read()
+    out = str(tmp_path / "features.s")
+    df.kernel_isa(out=out)  # compiles features.hip with the build's own flags
+    txt = open(out).read()
     meta = re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", txt)
     seen = 0
     for name, scratch, vgpr in meta:

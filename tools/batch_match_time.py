@@ -1,6 +1,7 @@
 """Time the batched self-match of B 640x480 frames alone (no detection running beside it): usage batch_match_time.py [B] [repeats]"""
 import sys, time
-sys.path.insert(0, '/root/repo')
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from vulkansift_amd import api
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 512

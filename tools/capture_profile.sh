@@ -36,7 +36,7 @@ timeout 300 rocprofv3 --kernel-trace --memory-copy-trace -d $OUT/lat -- python $
 cd $R
 python tools/latency_timeline.py gpurun_out/$TAG/lat > profiles/${TAG}_latency_timeline.txt 2>&1
 rm -rf $OUT/lat
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 cp $OUT/bench.json profiles/${TAG}_bench.json
 mkdir -p $OUT/profiles; cp profiles/${TAG}_* $OUT/profiles/
 # the raw traces are large: only the report travels back

@@ -1,6 +1,7 @@
 """While a 512-frame detection is in flight: how long does a 20 MB device-to-host copy take (pinned linear / pageable / strided)?"""
 import sys, time, ctypes as C
-sys.path.insert(0, '/root/repo')
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from vulkansift_amd import api
 L = api.lib()

@@ -169,10 +169,9 @@ KERNEL = "_ZN12_GLOBAL__N_112k_descriptorILi2ELb1ELb0EEEv5MultiINS_8FeatArgsEE"
 ORI_KERNEL = "_ZN12_GLOBAL__N_113k_orientationILb1ELb0EEEv5MultiINS_8FeatArgsEE"
 
 
-def kernel_isa(kernel=None):
+def kernel_isa(kernel=None, out="/tmp/_features_floor.s"):
     kernel = kernel or KERNEL
     src = os.path.join(ROOT, "vulkansift_amd", "csrc", "hip", "features.hip")
-    out = "/tmp/_features_floor.s"
     import vulkansift_amd.build as b  # the flags the shipped kernels are compiled with
     cmd = [b.HIPCC] + [f for f in b.HIPFLAGS if f != "-fPIC"] + b._extra_flags("hip/features.hip") + b.INCLUDES + ["-S", "--cuda-device-only", "-o", out, src]
     subprocess.run(cmd, check=True, capture_output=True, cwd="/tmp")

@@ -2,7 +2,8 @@
 """det-mode oracle (== the HIP kernels bit for bit) against its libm mode on the cases of tests/test_gpu_configs.py::test_libm_oracle_within_tolerance_configs: the
 numbers the bounds of that test were set from. CPU only:  python tools/libm_gap.py"""
 import sys, numpy as np
-sys.path.insert(0,'/root/repo')
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import oracle as O
 from vulkansift_amd import api
 
