@@ -60,7 +60,9 @@ extern "C"
    * while the GPU has no detection to work on. The first detect
    * call after another entry point is launched at once unless the caller's previous run of detect calls held two or more, so
    * detect + read and the two-buffer ping-pong keep their latency. VKSIFT_DEFER=0 launches every call at once. Results are
-   * identical either way. These counters say what the instance did: batches launched from staged images, and images in them. */
+   * identical either way; the scale-space accessors (vksift_downloadScaleSpaceImage, vksift_downloadDoGImage) show the last plain
+   * detection either way, and image 0 of the batch after a vksift_ext_detectFeaturesBatch* call. These counters say what the
+   * instance did: batches launched from staged images, and images in them. */
   VKSIFT_EXPORT void vksift_ext_getDeferredStats(vksift_Instance instance, uint64_t *nb_batches, uint64_t *nb_images);
 
   /* Stage timings (milliseconds, HIP events on the instance stream) of the last detect call.

@@ -748,6 +748,7 @@ static void detect_impl(vksift_Instance inst, const uint8_t *const *images, cons
     inst->cur_h = h;
   }
   inst->cur_batch = count;
+  inst->shown_img = prestaged ? count - 1u : 0u;
   const uint64_t seq = inst->det_seq + 1u;
   for (uint32_t i = 0; i < count; i++)
   {
@@ -758,6 +759,7 @@ static void detect_impl(vksift_Instance inst, const uint8_t *const *images, cons
   seq_assigned = true;
 
   DetectCtx c;
+  memset(&c, 0, sizeof(c));
   c.inst = inst, c.L = &inst->lay, c.PS = PS;
   c.prof = inst->profiling;
   /* Overlapping detections (VKSIFT_PYR_PINGPONG=1): with two pyramid buffers the scale-space construction of this call
@@ -770,14 +772,13 @@ static void detect_impl(vksift_Instance inst, const uint8_t *const *images, cons
   c.w = w, c.h = h, c.count = count, c.first_buf = first_buf;
   c.img_bytes = (size_t)w * h;
   c.nblur = 0, c.nblur_all = 0;
-  memset(c.tail, 0, sizeof(c.tail));
-  /* (VKSIFT_TUNE_TAIL_MULTI = 1: every octave in full, one launch per octave and scale — A/B and the bit-identity matrix) */
-  c.tail_batch = !c.fork && count >= 8u && c.L->n_oct > 1u && vksift_hip_tune_get(VKSIFT_TUNE_TAIL_MULTI) == 0;
   c.capturing = false;
   c.gpu_busy = detect_running(inst);
   /* forked scale-space + LDS chain are latency measures for ONE image (or a handful): a batch on a single-buffer instance
    * (batch_cap < 8 or VKSIFT_PYR_PINGPONG=0) fills the chip with its per-scale launches and takes those */
   c.fork = inst->fork_scales && !c.overlap && !c.prof && count <= VKSIFT_FORK_MAX_COUNT && (uint64_t)count * w * h <= inst->fork_max_pixels;
+  /* (VKSIFT_TUNE_TAIL_MULTI = 1: every octave in full, one launch per octave and scale — A/B and the bit-identity matrix) */
+  c.tail_batch = !c.fork && count >= 8u && c.L->n_oct > 1u && vksift_hip_tune_get(VKSIFT_TUNE_TAIL_MULTI) == 0;
   /* feature posting for single-image detections whose records fit the slot (every section is capacity-bounded) */
   /* once the instance has matched (its cache blocks exist) a detection leaves the matcher's rows of its buffers behind itself */
   c.dense = inst->d_cache_desc != NULL && inst->d_cache_norm != NULL && c.L->n_oct > 0 && c.L->n_oct == inst->bufs[first_buf].nb_sections &&

@@ -682,6 +682,7 @@ int resize_detect_scratch(vksift_Instance inst, const PyrLayout *L, uint32_t new
   free_detect_scratch(inst, cap_blocks);
   inst->pyr_free_valid[0] = inst->pyr_free_valid[1] = false;
   inst->cur_w = inst->cur_h = 0; /* no scale-space to download until the next detection */
+  inst->shown_img = 0;
   int rc = 0;
   /* (a capacity growth happens once per size, outside any detection that runs: it may search for fast memory; a stride growth sits in
    * the middle of a detect call of whatever the caller is doing and takes plain allocations) */

@@ -129,6 +129,8 @@ struct vksift_Instance_T
 
   /* current scale-space */
   uint32_t cur_w, cur_h, cur_batch;
+  uint32_t shown_img;      /* image of the last launch the scale-space accessors show: the last one of a batch launched from staged
+                            * vksift_detectFeatures calls (the reference shows the last image detected), image 0 otherwise */
   PyrLayout lay;
 
   /* device memory */
