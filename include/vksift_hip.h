@@ -91,7 +91,8 @@ extern "C"
    * never while another thread is inside a library call. */
   enum
   {
-    VKSIFT_TUNE_WG_TARGET = 0,  /* waves per strip-march launch aimed at (0 = built-in) */
+    VKSIFT_TUNE_WG_TARGET = 0,  /* waves per strip-march launch aimed at, for every strip-march launcher (0 = built-in; when set it also
+                                 * replaces VKSIFT_TUNE_SEED_WG) */
     VKSIFT_TUNE_WIDE_MASK = 1,  /* bit n: n-tap launches take the four-texels-per-lane form (-1 = built-in) */
     VKSIFT_TUNE_MULTI_MAX = 2,  /* octaves per multi-octave launch, 1..8 (0 = built-in 8): the cutting of longer octave lists into runs is
                                  * otherwise only reached by images of 4097 pixels and more on the shortest side */
@@ -115,6 +116,10 @@ extern "C"
   int vksift_hip_tune_get(int knob);
 
   /* ------------------------------------------------------------------ pyramid */
+  /* The launchers below that can decline a shape (vksift_hip_blur_pair, _blur_downsample, _blur_multi, _seed_upsampled, _seed_direct,
+   * _octave_chain) return -1 when it is not covered and nothing was launched: the caller then issues the separate calls named in the
+   * launcher's comment. 0: launched; a positive value: a hipError_t (invalid arguments or a failed launch). */
+
   /* A batch of same-sized planes. */
   typedef struct
   {
@@ -142,29 +147,31 @@ extern "C"
   int vksift_hip_blur(vksift_hip_Plane src, vksift_hip_Plane dst, const float *taps, uint32_t ntaps, uint32_t batch, vksift_hip_stream s);
 
   /* TWO consecutive scale steps in one launch: dst1 = blur(src, taps1), dst2 = blur(dst1, taps2) — the source plane is read once and
-   * scale s never re-read (12 bytes per texel instead of 16). Bit-identical to two vksift_hip_blur calls. Returns -1 without
-   * launching anything when the tap counts, the texel type or the shape are not covered: the caller then issues the two calls. */
+   * scale s never re-read (12 bytes per texel instead of 16). Bit-identical to two vksift_hip_blur calls. -1 when the tap counts, the
+   * texel type or the shape are not covered: the caller then issues the two calls. */
   int vksift_hip_blur_pair(vksift_hip_Plane src, vksift_hip_Plane dst1, vksift_hip_Plane dst2, const float *taps1, uint32_t ntaps1, const float *taps2,
                            uint32_t ntaps2, uint32_t batch, vksift_hip_stream s);
 
-  /* vksift_hip_blur that also seeds the next octave: next(x, y) = dst(2x+1, 2y+1), the vkCmdBlitImage(NEAREST) of
-   * sift_detector.c:1003-1034 for exactly halved sizes, stored from the registers that hold the blurred rows (the separate
-   * pass re-reads the whole plane). Bit-identical to vksift_hip_blur + vksift_hip_downsample. Returns -1 without launching
-   * anything when the shape or the selected kernel does not cover it: the caller then issues the two separate calls. */
-  /* One scale of n <= 8 octaves in ONE launch: dst[i] = blur(src[i]) for every i with the same taps (scales S+1 and S+2 of a detection's octaves
-   * feed nothing but the extrema scan, so they can be queued per scale instead of per octave). Returns -1 without launching anything when a
-   * plane is outside the strip-march kernel's domain, the texel types differ or the tap count has no multi-octave instantiation (9, 11, 13,
-   * 15 taps exist): the caller then takes vksift_hip_blur per plane. Same kernel body: bit-identical to those launches. */
   /* the kernel vksift_hip_blur takes for this shape: 0 generic tiles, 1 two texels per lane (what vksift_hip_blur_multi launches), 2 four texels per lane */
   int vksift_hip_blur_form(vksift_hip_Plane src, vksift_hip_Plane dst, uint32_t ntaps, uint32_t batch);
+
+  /* One scale of n <= 8 octaves in ONE launch: dst[i] = blur(src[i]) for every i with the same taps (scales S+1 and S+2 of a detection's octaves
+   * feed nothing but the extrema scan, so they can be queued per scale instead of per octave). -1 when a plane is outside the strip-march
+   * kernel's domain, the texel types differ or the tap count has no multi-octave instantiation (9, 11, 13, 15 taps exist): the caller then
+   * takes vksift_hip_blur per plane. Same kernel body: bit-identical to those launches. */
   int vksift_hip_blur_multi(const vksift_hip_Plane *src, const vksift_hip_Plane *dst, uint32_t n, const float *taps, uint32_t ntaps, uint32_t batch,
                             vksift_hip_stream s);
+
+  /* vksift_hip_blur that also seeds the next octave: next(x, y) = dst(2x+1, 2y+1), the vkCmdBlitImage(NEAREST) of
+   * sift_detector.c:1003-1034 for exactly halved sizes, stored from the registers that hold the blurred rows (the separate
+   * pass re-reads the whole plane). Bit-identical to vksift_hip_blur + vksift_hip_downsample. -1 when the shape or the selected
+   * kernel does not cover it: the caller then issues the two separate calls. */
   int vksift_hip_blur_downsample(vksift_hip_Plane src, vksift_hip_Plane dst, vksift_hip_Plane next, const float *taps, uint32_t ntaps, uint32_t batch,
                                  vksift_hip_stream s);
 
   /* vkCmdCopyBufferToImage + vkCmdBlitImage(LINEAR, exact 2:1) + the seed blur (sift_detector.c:881-1001 for octave 0) in one
    * pass: dst = blur(upsample2x(src / 255)); the up-sampled plane is never written. Bit-identical to vksift_hip_input_blit
-   * followed by vksift_hip_blur. Returns -1 when the shape is not covered (the caller then issues the two separate calls). */
+   * followed by vksift_hip_blur. -1 when the shape is not covered: the caller then issues the two separate calls. */
   int vksift_hip_seed_upsampled(const uint8_t *src, uint32_t sw, uint32_t sh, uint64_t src_img_stride, vksift_hip_Plane dst, const float *taps, uint32_t ntaps,
                                 uint32_t batch, vksift_hip_stream s);
 
@@ -180,7 +187,7 @@ extern "C"
    * layers[o * n_layers + l] = layer l of octave o; layer 0 of octave 0 of the run is the input (already in memory), every other plane is
    * written: layer l = blur(layer l - 1, taps[l]) (sift_detector.c:927-1001), layer 0 of the next octave = nearest 2:1 of layer S
    * (:1003-1034). taps: n_layers rows of VKSIFT_HIP_MAX_TAPS. Bit-identical to the vksift_hip_blur / vksift_hip_downsample sequence.
-   * Returns -1 without launching anything when the planes are not covered (fp16, width not a multiple of 4, too large for the LDS). */
+   * -1 when the planes are not covered (fp16, width not a multiple of 4, too large for the LDS). */
   int vksift_hip_octave_chain(const vksift_hip_Plane *layers, uint32_t n_oct, uint32_t n_layers, uint32_t S, const float *taps, const uint32_t *ntaps,
                               uint32_t batch, vksift_hip_stream s);
 

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 #include "multi.h"
@@ -336,6 +337,16 @@ __device__ __forceinline__ void unit_of_bytes(unsigned d, float t[4])
   t[0] = unit_of_byte<0>(d), t[1] = unit_of_byte<1>(d), t[2] = unit_of_byte<2>(d), t[3] = unit_of_byte<3>(d);
 }
 
+// Byte offset of the fp32 float4 that holds the virtual columns gx4 .. gx4+3 of a row of width W (a multiple of 4); rv is set when they
+// are mirrored: the four virtual columns then map to m3+3, m3+2, m3+1, m3 of that float4.
+__device__ __forceinline__ unsigned mirrored_col_off(int gx4, int W, bool &rv)
+{
+  if (gx4 >= 0 && gx4 + 3 < W)
+    return (unsigned)gx4 * 4u;
+  rv = true;
+  return (unsigned)mirror_idx(gx4 + 3, W) * 4u;
+}
+
 // (the body is shared by k_blur_lean — one plane set per launch, the launch grid is the work grid — and k_blur_lean_multi — several
 // octaves' planes in one flat launch, csrc/hip/multi.h: gx/gy/gz and bx/by/bz are then the octave's virtual grid)
 template <int NT, int SRC, bool F16>
@@ -361,6 +372,8 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
   // XCD-aware work mapping: workgroup b is observed to run on XCD b % 8 (each XCD has its own L2). Give every XCD a
   // contiguous range of the (image, segment, strip) space, strips fastest, so that the workgroups that share halo
   // columns and warm-up rows run on the same XCD at about the same time and find them in its L2.
+  // (Written out in each strip-march kernel: as a shared __device__ function, every form tried changed the gfx950 code of k_blur_lean_multi,
+  // k_blur_wide and the pair kernels.)
   uint32_t bs = bx_, bseg = by_, bimg = bz_;
   {
     const uint32_t total = gx_ * gy_ * gz_;
@@ -777,7 +790,7 @@ __global__ void __launch_bounds__(64) k_blur_wide(StreamArgs a)
   const int W = a.w, H = a.h;
   uint32_t bs = blockIdx.x, bseg = blockIdx.y, bimg = blockIdx.z;
   {
-    // XCD-aware work mapping, as k_blur_lean
+    // XCD-aware work mapping, as k_blur_lean (and written out for the same reason)
     const uint32_t total = gridDim.x * gridDim.y * gridDim.z;
     const uint32_t b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     uint32_t wi = b;
@@ -807,19 +820,13 @@ __global__ void __launch_bounds__(64) k_blur_wide(StreamArgs a)
   const int spitch4 = a.spitch * 4, dpitch4 = a.dpitch * 4, dspitch4 = a.ds_pitch * 4; // row pitches in bytes
 
   // ---- lane constants: the float4 column this lane stages in every row ...
-  auto col_off = [&](int gx4, bool &rv) -> unsigned {
-    if (gx4 >= 0 && gx4 + 3 < W)
-      return (unsigned)gx4 * 4u;
-    rv = true;
-    return (unsigned)mirror_idx(gx4 + 3, W) * 4u; // the four virtual columns map to m3+3, m3+2, m3+1, m3
-  };
   bool rev = false, rev_x = false;
-  const unsigned ld_off = col_off(x0 - RA + 4 * lane, rev);
+  const unsigned ld_off = mirrored_col_off(x0 - RA + 4 * lane, W, rev);
   // ... and the (row, column) beyond the 64th float4 it stages once per group
   const int xr = lane / NX, xq = 64 + lane % NX;
   unsigned ldx_col = BUF_OOB;
   if (lane < NXT)
-    ldx_col = col_off(x0 - RA + 4 * xq, rev_x);
+    ldx_col = mirrored_col_off(x0 - RA + 4 * xq, W, rev_x);
   const unsigned ldx_off = lane < NXT ? ldx_col + (unsigned)(xr * spitch4) : BUF_OOB;
   float *const sx = s_grp + xr * SW + 4 * xq;
   const int px = x0 + 4 * lane;
@@ -1014,7 +1021,7 @@ __global__ void __launch_bounds__(64) k_blur_pair(PairArgs a)
   const int lane = threadIdx.x;
   const int W = a.w, H = a.h;
   uint32_t bs = blockIdx.x, bseg = blockIdx.y, bimg = blockIdx.z;
-  {
+  { // XCD-aware work mapping as k_blur_lean's, unconditional form (written out there why)
     const uint32_t total = gridDim.x * gridDim.y * gridDim.z;
     const uint32_t b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     uint32_t wi = b;
@@ -1251,7 +1258,7 @@ __global__ void __launch_bounds__(64) k_blur_pair_wide(PairArgs a)
   const int lane = threadIdx.x;
   const int W = a.w, H = a.h;
   uint32_t bs = blockIdx.x, bseg = blockIdx.y, bimg = blockIdx.z;
-  {
+  { // XCD-aware work mapping as k_blur_lean's, unconditional form (written out there why)
     const uint32_t total = gridDim.x * gridDim.y * gridDim.z;
     const uint32_t b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     uint32_t wi = b;
@@ -1275,18 +1282,12 @@ __global__ void __launch_bounds__(64) k_blur_pair_wide(PairArgs a)
   const __amdgpu_buffer_rsrc_t rd2 = plane_rsrc<false>(a.dst2, (size_t)bimg * a.dst2_img_stride, a.d2pitch, H);
   const int spitch4 = a.spitch * 4, d1pitch4 = a.d1pitch * 4, d2pitch4 = a.d2pitch * 4;
 
-  auto col_off = [&](int gx4, bool &rv) -> unsigned {
-    if (gx4 >= 0 && gx4 + 3 < W)
-      return (unsigned)gx4 * 4u;
-    rv = true;
-    return (unsigned)mirror_idx(gx4 + 3, W) * 4u; // the four virtual columns map to m3+3, m3+2, m3+1, m3
-  };
   bool rev = false, rev_x = false;
-  const unsigned ld_off = col_off(x0 - RA1 + 4 * lane, rev);
+  const unsigned ld_off = mirrored_col_off(x0 - RA1 + 4 * lane, W, rev);
   const int xr = lane / NX, xq = 64 + lane % NX;
   unsigned ldx_col = BUF_OOB;
   if (lane < NXT)
-    ldx_col = col_off(x0 - RA1 + 4 * xq, rev_x);
+    ldx_col = mirrored_col_off(x0 - RA1 + 4 * xq, W, rev_x);
   const unsigned ldx_off = lane < NXT ? ldx_col + (unsigned)(xr * spitch4) : BUF_OOB;
   float *const sx = s_grp + xr * SW + 4 * xq;
   const int px = x0 + 4 * lane;
@@ -1734,6 +1735,153 @@ __global__ void __launch_bounds__(256) k_dog_plane(const float *__restrict__ lo,
   out[(size_t)y * w + x] = d;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side: the launch description of the strip marches (k_blur_lean, _wide, _multi, _pair, _pair_wide). Every decision their
+// launchers share is made here, once.
+// ---------------------------------------------------------------------------------------------
+// VKSIFT_BLUR_KERNEL=tile: the generic tile kernel for every blur, no strip march (debugging). VKSIFT_BLUR_PAIR=0: every scale its own
+// launch (A/B runs, tests). Read once per process.
+struct BlurEnv
+{
+  bool force_tile, pair;
+};
+const BlurEnv &blur_env()
+{
+  static const BlurEnv env = [] {
+    const char *k = getenv("VKSIFT_BLUR_KERNEL"), *p = getenv("VKSIFT_BLUR_PAIR");
+    return BlurEnv{k != NULL && strcmp(k, "tile") == 0, p == NULL || atoi(p) != 0};
+  }();
+  return env;
+}
+
+void pack_taps(float (&k)[VKSIFT_HIP_MAX_TAPS], const float *taps, uint32_t ntaps)
+{
+  for (uint32_t i = 0; i < VKSIFT_HIP_MAX_TAPS; i++)
+    k[i] = i < ntaps ? taps[i] : 0.f;
+}
+
+// opts kernels into `bytes` of dynamic LDS, above the 64 KiB default, on the first call that succeeds
+int lds_opt_in(bool &done, int bytes, const void *k1, const void *k2 = NULL)
+{
+  hipError_t e = hipSuccess;
+  if (!done)
+  {
+    e = hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && k2 != NULL)
+      e = hipFuncSetAttribute(k2, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done = e == hipSuccess;
+  }
+  return (int)e;
+}
+
+// Strips of a march of strip_w-column strips over a w-wide plane, each computing `halo` columns on either side for its neighbours (it owns
+// strip_w - 2 halo), with ntaps taps; 0 when the march does not cover the plane: the width is not a multiple of 4, or one mirror reflection
+// does not reach every staged column
+uint32_t march_strips(uint32_t w, uint32_t ntaps, uint32_t strip_w, uint32_t halo = 0u)
+{
+  const uint32_t ra = ((ntaps - 1u) + 3u) & ~3u, own = strip_w - 2u * halo, strips = (w + own - 1u) / own;
+  return (w % 4u) == 0 && halo + ra <= w && strips * own + halo + ra <= 2u * w ? strips : 0u;
+}
+
+// shortest march (output rows per wave) a launch of this size is cut into: launches that cannot fill the chip are bound by the length of
+// one wave's march (2R warm-up rows + its own), not by bandwidth
+uint32_t march_rows(uint32_t waves64)
+{
+  const int t = vksift_hip_tune_get(VKSIFT_TUNE_MIN_MARCH);
+  // (one 640x480 image: 8-row marches 0.302-0.313 ms against 0.314-0.326 with 16 rows, four alternations of 4 000 detections each)
+  const uint32_t smallest = t > 0 ? (uint32_t)t : 8u;
+  return waves64 >= 2048u ? 64u : (waves64 >= 512u ? 32u : (waves64 >= 192u ? 16u : smallest));
+}
+
+// Grid (strips, row segments, batch) of a strip march, rows per segment (a multiple of 8) -> *seg. Enough workgroups to give every CU
+// ~40 waves over the launch (wg_target; VKSIFT_TUNE_WG_TARGET replaces it: 2560 long-lived waves left the slowest CU to set the time), but
+// segments long enough that the 2R-row warm-up stays a small fraction: at least march_rows() rows (short_marches: launches that cannot fill
+// the GPU anyway are latency bound and take shorter marches) or 64.
+dim3 march_grid(uint32_t strips, uint32_t h, uint32_t batch, uint32_t wg_target, bool short_marches, int *seg)
+{
+  if (vksift_hip_tune_get(VKSIFT_TUNE_WG_TARGET) > 0)
+    wg_target = (uint32_t)vksift_hip_tune_get(VKSIFT_TUNE_WG_TARGET);
+  const uint32_t min_rows = short_marches ? march_rows(strips * batch * ((h + 63u) / 64u)) : 64u, max_seg = (h + min_rows - 1u) / min_rows;
+  uint32_t nseg = (wg_target + strips * batch - 1u) / (strips * batch);
+  nseg = nseg > max_seg ? max_seg : (nseg < 1u ? 1u : nseg);
+  const uint32_t rows = ((h + nseg - 1u) / nseg + 7u) & ~7u;
+  *seg = (int)rows;
+  return dim3(strips, (h + rows - 1u) / rows, batch);
+}
+
+// workgroups aimed at by a two-texel plane blur (k_blur_lean, k_blur_lean_multi): from 11 taps on, fewer, longer marches — the 2R-row
+// warm-up of a 13-tap segment is 12 rows, and these launches are the VALU co-limited ones. 512 x 640x480 planes, tools/blur_ab.py: 11 taps
+// 267 -> 256 us, 13 taps 301 -> 287 us with 240-row instead of 120-row segments; 320x240: 13 taps 95 -> 87 us; 9 taps and fewer: no
+// difference
+uint32_t lean_wg_target(uint32_t ntaps) { return ntaps >= 11u ? 3072u : 10240u; }
+
+const vksift_hip_Plane NO_PLANE = {NULL, 0, 0, 0, 0, 0, 0};
+
+// StreamArgs of a march from src (w x h) into dst, storing the 2:1 down-sample into ds as well unless that is NO_PLANE. For the seed forms src
+// is the u8 images seen as a plane: pitch = their width, img_stride in bytes.
+StreamArgs stream_args(const vksift_hip_Plane &src, const vksift_hip_Plane &dst, const vksift_hip_Plane &ds, const float *taps, uint32_t ntaps)
+{
+  StreamArgs a;
+  a.src = src.base, a.dst = dst.base;
+  a.src_img_stride = src.img_stride, a.dst_img_stride = dst.img_stride;
+  a.spitch = (int)src.pitch, a.dpitch = (int)dst.pitch;
+  a.w = (int)src.w, a.h = (int)src.h;
+  a.seg = 0;
+  a.ds = ds.base, a.ds_img_stride = ds.img_stride, a.ds_pitch = (int)ds.pitch;
+  a.rev = (int)dst.reverse;
+  pack_taps(a.taps.k, taps, ntaps);
+  return a;
+}
+
+PairArgs pair_args(const vksift_hip_Plane &src, const vksift_hip_Plane &dst1, const vksift_hip_Plane &dst2, const float *taps1, uint32_t ntaps1,
+                          const float *taps2, uint32_t ntaps2)
+{
+  PairArgs a;
+  a.src = src.base, a.dst1 = dst1.base, a.dst2 = dst2.base;
+  a.src_img_stride = src.img_stride, a.dst1_img_stride = dst1.img_stride, a.dst2_img_stride = dst2.img_stride;
+  a.spitch = (int)src.pitch, a.d1pitch = (int)dst1.pitch, a.d2pitch = (int)dst2.pitch;
+  a.w = (int)src.w, a.h = (int)src.h;
+  a.seg = 0;
+  a.rev = (int)dst2.reverse;
+  pack_taps(a.t1.k, taps1, ntaps1);
+  pack_taps(a.t2.k, taps2, ntaps2);
+  return a;
+}
+
+// One tap-count switch for k_blur_lean<N, SRC, F16> (host side): 2..20 taps for a plane source (SRC 0), 2..12 for the two seed forms.
+// -1 (nothing launched) for a tap count without an instantiation.
+template <int SRC, int N>
+int launch_lean(dim3 grid, const StreamArgs &a, bool f16, hipStream_t s)
+{
+  if constexpr (SRC != 0 && N > 12)
+    return -1;
+  else
+  {
+    if (f16)
+      hipLaunchKernelGGL((k_blur_lean<N, SRC, true>), grid, dim3(64), 0, s, a);
+    else
+      hipLaunchKernelGGL((k_blur_lean<N, SRC, false>), grid, dim3(64), 0, s, a);
+    return (int)hipGetLastError();
+  }
+}
+
+template <int SRC>
+int blur_lean_launch(uint32_t ntaps, dim3 grid, const StreamArgs &a, bool f16, hipStream_t s)
+{
+  switch (ntaps)
+  {
+#define VKSIFT_CASE(N) \
+  case N:              \
+    return launch_lean<SRC, N>(grid, a, f16, s);
+    VKSIFT_CASE(2) VKSIFT_CASE(3) VKSIFT_CASE(4) VKSIFT_CASE(5) VKSIFT_CASE(6) VKSIFT_CASE(7) VKSIFT_CASE(8) VKSIFT_CASE(9) VKSIFT_CASE(10)
+    VKSIFT_CASE(11) VKSIFT_CASE(12) VKSIFT_CASE(13) VKSIFT_CASE(14) VKSIFT_CASE(15) VKSIFT_CASE(16) VKSIFT_CASE(17) VKSIFT_CASE(18)
+    VKSIFT_CASE(19) VKSIFT_CASE(20)
+#undef VKSIFT_CASE
+  default:
+    return -1;
+  }
+}
+
 } // namespace
 
 extern "C"
@@ -1762,83 +1910,38 @@ extern "C"
     return (int)hipGetLastError();
   }
 
-  static int blur_tile_launch(vksift_hip_Plane src, vksift_hip_Plane dst, const Taps &t, uint32_t ntaps, uint32_t batch, vksift_hip_stream s)
+  static int blur_tile_launch(vksift_hip_Plane src, vksift_hip_Plane dst, const float *taps, uint32_t ntaps, uint32_t batch, vksift_hip_stream s)
   {
-    int R = (int)ntaps - 1;
-    int SH = TILE + 2 * R, SS = TILE + 2 * R + 1;
-    size_t lds_bytes = sizeof(float) * ((size_t)SH * SS + (size_t)SH * TILE);
-    static bool lds_attr_set = false;
-    if (!lds_attr_set)
-    {
-      /* largest tile (R = 19) needs 68 KiB of the CU's 160 KiB LDS: above the 64 KiB default opt-in limit */
-      const int Rm = VKSIFT_HIP_MAX_TAPS - 1;
-      const int max_bytes = (int)(sizeof(float) * ((TILE + 2 * Rm) * (TILE + 2 * Rm + 1) + (TILE + 2 * Rm) * TILE));
-      hipError_t ae = hipFuncSetAttribute((const void *)k_blur_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
-      if (ae == hipSuccess)
-        ae = hipFuncSetAttribute((const void *)k_blur_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
-      if (ae != hipSuccess)
-        return (int)ae;
-      lds_attr_set = true;
-    }
+    /* s_src[TILE + 2R][TILE + 2R + 1] + s_mid[TILE + 2R][TILE]; the largest tile (R = 19) needs 68 KiB of the CU's 160 KiB */
+    auto lds_bytes = [](int R) { return sizeof(float) * (size_t)(TILE + 2 * R) * (size_t)(2 * TILE + 2 * R + 1); };
+    static bool lds_set = false;
+    if (int e = lds_opt_in(lds_set, (int)lds_bytes(VKSIFT_HIP_MAX_TAPS - 1), (const void *)k_blur_tile<false>, (const void *)k_blur_tile<true>))
+      return e;
+    Taps t;
+    pack_taps(t.k, taps, ntaps);
     dim3 grid((src.w + TILE - 1) / TILE, (src.h + TILE - 1) / TILE, batch);
     if (src.fp16)
-      hipLaunchKernelGGL(k_blur_tile<true>, grid, dim3(256), lds_bytes, (hipStream_t)s, src.base, src.img_stride, (int)src.pitch, dst.base, dst.img_stride,
-                         (int)dst.pitch, (int)src.w, (int)src.h, t, (int)ntaps);
+      hipLaunchKernelGGL(k_blur_tile<true>, grid, dim3(256), lds_bytes((int)ntaps - 1), (hipStream_t)s, src.base, src.img_stride, (int)src.pitch, dst.base,
+                         dst.img_stride, (int)dst.pitch, (int)src.w, (int)src.h, t, (int)ntaps);
     else
-      hipLaunchKernelGGL(k_blur_tile<false>, grid, dim3(256), lds_bytes, (hipStream_t)s, src.base, src.img_stride, (int)src.pitch, dst.base, dst.img_stride,
-                         (int)dst.pitch, (int)src.w, (int)src.h, t, (int)ntaps);
+      hipLaunchKernelGGL(k_blur_tile<false>, grid, dim3(256), lds_bytes((int)ntaps - 1), (hipStream_t)s, src.base, src.img_stride, (int)src.pitch, dst.base,
+                         dst.img_stride, (int)dst.pitch, (int)src.w, (int)src.h, t, (int)ntaps);
     return (int)hipGetLastError();
-  }
-
-  /* Row segments of the streaming kernel: enough workgroups to give every CU ~40 waves over the launch (2560 long-lived waves
-   * left the slowest CU to set the time), but segments long enough that the 2R-row warm-up stays a small fraction; launches
-   * that cannot fill the GPU anyway (small octaves, small batches) are latency bound and take shorter marches. */
-  /* shortest march (output rows per wave) a launch of this size is cut into: launches that cannot fill the chip are bound by the length of
-   * one wave's march (2R warm-up rows + its own), not by bandwidth */
-  static uint32_t march_rows(uint32_t waves64)
-  {
-    const int t = vksift_hip_tune_get(VKSIFT_TUNE_MIN_MARCH);
-    /* (one 640x480 image: 8-row marches 0.302-0.313 ms against 0.314-0.326 with 16 rows, four alternations of 4 000 detections each) */
-    const uint32_t smallest = t > 0 ? (uint32_t)t : 8u;
-    return waves64 >= 2048u ? 64u : (waves64 >= 512u ? 32u : (waves64 >= 192u ? 16u : smallest));
-  }
-
-  static dim3 stream_grid(uint32_t w, uint32_t h, uint32_t batch, uint32_t wg_target, int *seg_out, uint32_t strip_w = 128u)
-  {
-    const uint32_t strips = (w + strip_w - 1u) / strip_w;
-    if (vksift_hip_tune_get(VKSIFT_TUNE_WG_TARGET) > 0)
-      wg_target = (uint32_t)vksift_hip_tune_get(VKSIFT_TUNE_WG_TARGET);
-    uint32_t nseg = (wg_target + strips * batch - 1u) / (strips * batch);
-    const uint32_t waves64 = strips * batch * ((h + 63u) / 64u);
-    const uint32_t seg_rows = march_rows(waves64);
-    const uint32_t max_seg = (h + seg_rows - 1u) / seg_rows;
-    if (nseg > max_seg)
-      nseg = max_seg;
-    if (nseg < 1)
-      nseg = 1;
-    const uint32_t seg = ((h + nseg - 1u) / nseg + 7u) & ~7u;
-    nseg = (h + seg - 1u) / seg;
-    *seg_out = (int)seg;
-    return dim3(strips, nseg, batch);
   }
 
   constexpr int WIDE_DEFAULT_MASK = (1 << 9) | (1 << 11) | (1 << 13);
   /* which kernel a blur of this shape takes: 0 the generic tile kernel, 1 the two-texel strip march (k_blur_lean), 2 the four-texel one (k_blur_wide) */
   static int blur_form(const vksift_hip_Plane &src, const vksift_hip_Plane &dst, uint32_t ntaps, uint32_t batch)
   {
-    const uint32_t ra = ((ntaps - 1u) + 3u) & ~3u;
-    const uint32_t nstrips = (src.w + 127u) / 128u;
-    const bool lean = ntaps >= 2 && (src.w % 4u) == 0 && ra <= src.w && nstrips * 128u + ra <= 2u * src.w;
-    if (!lean)
+    if (ntaps < 2 || march_strips(src.w, ntaps, 128u) == 0)
       return 0;
     /* four texels per lane on 256-column strips (k_blur_wide): fp32 planes whose width wastes little of the last strip */
-    const int wide_mask = vksift_hip_tune_get(VKSIFT_TUNE_WIDE_MASK) >= 0 ? vksift_hip_tune_get(VKSIFT_TUNE_WIDE_MASK) : WIDE_DEFAULT_MASK;
-    const uint32_t wstrips = (src.w + 255u) / 256u;
+    const int tuned = vksift_hip_tune_get(VKSIFT_TUNE_WIDE_MASK), wide_mask = tuned >= 0 ? tuned : WIDE_DEFAULT_MASK;
+    const uint32_t wstrips = march_strips(src.w, ntaps, 256u);
     /* (launches that cannot fill the chip — a single image, the coarse octaves of a small batch — are latency bound and want the larger
      * number of shorter-lived waves the 128-column strips give them: one 640x480 image 0.355 -> 0.378 ms with wide strips everywhere) */
-    const bool fills = (uint64_t)wstrips * batch * ((src.h + 63u) / 64u) >= 2048u || vksift_hip_tune_get(VKSIFT_TUNE_WIDE_MASK) >= 0;
-    if (fills && !src.fp16 && !dst.fp16 && ((wide_mask >> ntaps) & 1) && (src.w % 4u) == 0 && ra <= src.w && wstrips * 256u + ra <= 2u * src.w &&
-        wstrips * 256u - src.w <= 64u && ((src.pitch | dst.pitch) & 3u) == 0)
+    const bool fills = (uint64_t)wstrips * batch * ((src.h + 63u) / 64u) >= 2048u || tuned >= 0;
+    if (fills && wstrips != 0 && !src.fp16 && !dst.fp16 && ((wide_mask >> ntaps) & 1) && wstrips * 256u - src.w <= 64u && ((src.pitch | dst.pitch) & 3u) == 0)
       return 2;
     return 1;
   }
@@ -1848,34 +1951,15 @@ extern "C"
   {
     if (ntaps < 1 || ntaps > VKSIFT_HIP_MAX_TAPS || src.base == dst.base || dst.base == NULL)
       return (int)hipErrorInvalidValue;
-    Taps t;
-    for (uint32_t i = 0; i < VKSIFT_HIP_MAX_TAPS; i++)
-      t.k[i] = i < ntaps ? taps[i] : 0.f;
-    static int force_tile = -1;
-    if (force_tile < 0)
-    {
-      const char *e = getenv("VKSIFT_BLUR_KERNEL"); /* "tile": the generic fallback kernel everywhere (debugging) */
-      force_tile = (e && e[0] == 't') ? 1 : 0;
-    }
-    const uint32_t ra = ((ntaps - 1u) + 3u) & ~3u;
-    const int form = force_tile ? 0 : blur_form(src, dst, ntaps, batch);
+    const int form = blur_env().force_tile ? 0 : blur_form(src, dst, ntaps, batch);
     if (form == 0)
-      return ds.base ? -1 : blur_tile_launch(src, dst, t, ntaps, batch, s);
-
-    StreamArgs a;
-    a.ds = ds.base, a.ds_img_stride = ds.img_stride, a.ds_pitch = (int)ds.pitch;
-    a.src = src.base, a.dst = dst.base;
-    a.src_img_stride = src.img_stride, a.dst_img_stride = dst.img_stride;
-    a.spitch = (int)src.pitch, a.dpitch = (int)dst.pitch;
-    a.w = (int)src.w, a.h = (int)src.h;
-    a.rev = (int)dst.reverse;
-    a.taps = t;
-    hipStream_t hs = (hipStream_t)s;
-    (void)ra;
+      return ds.base ? -1 : blur_tile_launch(src, dst, taps, ntaps, batch, s);
+    StreamArgs a = stream_args(src, dst, ds, taps, ntaps);
+    const hipStream_t hs = (hipStream_t)s;
     if (form == 2)
     {
       /* (from 11 taps on half as many, twice as long marches: 512 x 1280x960, tools/blur_ab.py: 11 taps 928 -> 905 us, 13 taps 988 -> 939 us) */
-      const dim3 wgrid = stream_grid(src.w, src.h, batch, ntaps >= 11u ? 5120u : 10240u, &a.seg, 256u);
+      const dim3 wgrid = march_grid(march_strips(src.w, ntaps, 256u), src.h, batch, ntaps >= 11u ? 5120u : 10240u, true, &a.seg);
       switch (ntaps)
       {
 #define VKSIFT_CASE(N)                                              \
@@ -1884,65 +1968,31 @@ extern "C"
     return (int)hipGetLastError();
         VKSIFT_CASE(5) VKSIFT_CASE(7) VKSIFT_CASE(9) VKSIFT_CASE(11) VKSIFT_CASE(13)
 #undef VKSIFT_CASE
-      default:
+      default: /* (a VKSIFT_TUNE_WIDE_MASK bit without a four-texel instantiation: the two-texel form) */
         break;
       }
     }
-    /* (11 taps and more: fewer, longer marches — the 2R-row warm-up of a 13-tap segment is 12 rows, and these launches are the VALU
-     * co-limited ones. 512 x 640x480 planes, tools/blur_ab.py: 11 taps 267 -> 256 us, 13 taps 301 -> 287 us with 240-row instead of 120-row
-     * segments; 320x240: 13 taps 95 -> 87 us; 9 taps and fewer: no difference) */
-    const dim3 grid = stream_grid(src.w, src.h, batch, ntaps >= 11u ? 3072u : 10240u, &a.seg);
-    switch (ntaps)
-    {
-#define VKSIFT_CASE(N)                                                        \
-  case N:                                                                     \
-    if (src.fp16)                                                             \
-      hipLaunchKernelGGL((k_blur_lean<N, 0, true>), grid, dim3(64), 0, hs, a);  \
-    else                                                                      \
-      hipLaunchKernelGGL((k_blur_lean<N, 0, false>), grid, dim3(64), 0, hs, a); \
-    break;
-      VKSIFT_CASE(2) VKSIFT_CASE(3) VKSIFT_CASE(4) VKSIFT_CASE(5) VKSIFT_CASE(6) VKSIFT_CASE(7) VKSIFT_CASE(8) VKSIFT_CASE(9) VKSIFT_CASE(10)
-      VKSIFT_CASE(11) VKSIFT_CASE(12) VKSIFT_CASE(13) VKSIFT_CASE(14) VKSIFT_CASE(15) VKSIFT_CASE(16) VKSIFT_CASE(17) VKSIFT_CASE(18)
-      VKSIFT_CASE(19) VKSIFT_CASE(20)
-#undef VKSIFT_CASE
-    default:
-      return (int)hipErrorInvalidValue;
-    }
-    return (int)hipGetLastError();
+    const dim3 grid = march_grid(march_strips(src.w, ntaps, 128u), src.h, batch, lean_wg_target(ntaps), true, &a.seg);
+    return blur_lean_launch<0>(ntaps, grid, a, src.fp16 != 0, hs);
   }
 
-  /* One scale of n octaves (src[i] -> dst[i], same taps) in ONE launch of the two-texel strip march; -1 (nothing launched) when a plane is
-   * not covered by that kernel, the texel types differ or the tap count has no multi-octave instantiation: the caller then takes
-   * vksift_hip_blur per plane. Bit-identical to those launches (the same kernel body). */
   int vksift_hip_blur_multi(const vksift_hip_Plane *src, const vksift_hip_Plane *dst, uint32_t n, const float *taps, uint32_t ntaps, uint32_t batch,
                             vksift_hip_stream s)
   {
     if (n == 0 || batch == 0)
       return 0;
-    if (n > (uint32_t)MULTI_MAX || ntaps < 2 || ntaps > VKSIFT_HIP_MAX_TAPS || getenv("VKSIFT_BLUR_KERNEL"))
-      return -1;
-    if (ntaps != 9 && ntaps != 11 && ntaps != 13 && ntaps != 15)
+    if (n > (uint32_t)MULTI_MAX || blur_env().force_tile || (ntaps != 9 && ntaps != 11 && ntaps != 13 && ntaps != 15))
       return -1;
     Multi<StreamArgs> m;
     m.n = 0;
-    const uint32_t ra = ((ntaps - 1u) + 3u) & ~3u;
     for (uint32_t i = 0; i < n; i++)
     {
       const vksift_hip_Plane &p = src[i], &d = dst[i];
-      const uint32_t nstrips = (p.w + 127u) / 128u;
-      if (p.base == NULL || d.base == NULL || p.base == d.base || p.fp16 != src[0].fp16 || d.fp16 != src[0].fp16 || d.w != p.w || d.h != p.h || (p.w % 4u) != 0 ||
-          ra > p.w || nstrips * 128u + ra > 2u * p.w)
+      const uint32_t strips = march_strips(p.w, ntaps, 128u);
+      if (p.base == NULL || d.base == NULL || p.base == d.base || p.fp16 != src[0].fp16 || d.fp16 != src[0].fp16 || d.w != p.w || d.h != p.h || strips == 0)
         return -1;
-      StreamArgs a;
-      a.ds = NULL, a.ds_img_stride = 0, a.ds_pitch = 0;
-      a.src = p.base, a.dst = d.base;
-      a.src_img_stride = p.img_stride, a.dst_img_stride = d.img_stride;
-      a.spitch = (int)p.pitch, a.dpitch = (int)d.pitch;
-      a.w = (int)p.w, a.h = (int)p.h;
-      a.rev = (int)d.reverse;
-      for (uint32_t k = 0; k < VKSIFT_HIP_MAX_TAPS; k++)
-        a.taps.k[k] = k < ntaps ? taps[k] : 0.f;
-      const dim3 g = stream_grid(p.w, p.h, batch, ntaps >= 11u ? 3072u : 10240u, &a.seg);
+      StreamArgs a = stream_args(p, d, NO_PLANE, taps, ntaps);
+      const dim3 g = march_grid(strips, p.h, batch, lean_wg_target(ntaps), true, &a.seg);
       if (!multi_add(m, a, g.x, g.y, g.z))
         return -1;
     }
@@ -1968,79 +2018,62 @@ extern "C"
   int vksift_hip_blur_pair(vksift_hip_Plane src, vksift_hip_Plane dst1, vksift_hip_Plane dst2, const float *taps1, uint32_t ntaps1, const float *taps2,
                            uint32_t ntaps2, uint32_t batch, vksift_hip_stream s)
   {
-    static int pair_env = -1;
-    if (pair_env < 0)
-    {
-      const char *e = getenv("VKSIFT_BLUR_PAIR"); /* 0: every scale its own launch (A/B runs, tests) */
-      pair_env = e ? atoi(e) : 1;
-    }
     const bool combo = ntaps1 == 5 && ntaps2 == 7; /* scales 1 and 2 of the default configuration (3 scales per octave, sampler-interpolated taps) */
-    if (!pair_env || !combo || src.fp16 || dst1.fp16 || dst2.fp16 || src.base == NULL || dst1.base == NULL || dst2.base == NULL || getenv("VKSIFT_BLUR_KERNEL"))
+    if (!blur_env().pair || blur_env().force_tile || !combo || src.fp16 || dst1.fp16 || dst2.fp16 || src.base == NULL || dst1.base == NULL || dst2.base == NULL)
       return -1;
-    const uint32_t W = src.w, H = src.h;
-    const uint32_t r2 = ntaps2 - 1u, hc = (r2 + 3u) & ~3u, ow = 128u - 2u * hc, ra1 = ((ntaps1 - 1u) + 3u) & ~3u;
-    const uint32_t strips = (W + ow - 1u) / ow;
-    /* one mirror reflection has to cover every staged column and every virtual row of a march */
-    if ((W % 4u) != 0 || hc + ra1 > W || (strips - 1u) * ow + 128u + ra1 > 2u * W + hc || H < 64u || dst1.w != W || dst2.w != W || dst1.h != H || dst2.h != H)
+    /* a strip computes scale s on HC = R2 rounded up to 4 columns beyond the ones it owns on either side; one mirror reflection has to cover
+     * every staged column and every virtual row of a march */
+    const uint32_t W = src.w, H = src.h, hc = ((ntaps2 - 1u) + 3u) & ~3u, strips = march_strips(W, ntaps1, 128u, hc);
+    if (strips == 0 || H < 64u || dst1.w != W || dst2.w != W || dst1.h != H || dst2.h != H)
       return -1;
+    PairArgs a = pair_args(src, dst1, dst2, taps1, ntaps1, taps2, ntaps2);
+    /* four texels per lane on 256-column strips (k_blur_pair_wide) for launches that fill the chip, of planes at least 1024 texels wide: on
+     * 512 x 640x480 planes the two-texel form is the faster one (377 against 387 us), on 320x240 by 9 % (109 / 119 us; tools/blur_ab.py) */
+    const uint32_t wstrips = march_strips(W, ntaps1, 256u, hc);
+    const int pw = vksift_hip_tune_get(VKSIFT_TUNE_PAIR_FORM); /* 0: built-in, 1: two texels per lane, 2: four */
+    const bool fills = (uint64_t)wstrips * batch * ((H + 63u) / 64u) >= 2048u && W >= 1024u;
+    if (pw != 1 && (fills || pw == 2) && wstrips != 0 && ((src.pitch | dst1.pitch | dst2.pitch) & 3u) == 0)
     {
-      /* four texels per lane on 256-column strips (k_blur_pair_wide) for launches that fill the chip */
-      const uint32_t hcw = (r2 + 3u) & ~3u, oww = 256u - 2u * hcw, wstrips = (W + oww - 1u) / oww;
-      const int pw = vksift_hip_tune_get(VKSIFT_TUNE_PAIR_FORM); /* 0: built-in, 1: two texels per lane, 2: four */
-      /* ... of planes at least 1024 texels wide: on 512 x 640x480 planes the two-texel form is the faster one (377 against 387 us), on 320x240
-       * by 9 % (109 / 119 us; tools/blur_ab.py) */
-      const bool fills = (uint64_t)wstrips * batch * ((H + 63u) / 64u) >= 2048u && W >= 1024u;
-      if (pw != 1 && (fills || pw == 2) && hcw + ra1 <= W && (wstrips - 1u) * oww + 256u + ra1 <= 2u * W + hcw && ((src.pitch | dst1.pitch | dst2.pitch) & 3u) == 0)
-      {
-        PairArgs aw;
-        aw.src = src.base, aw.dst1 = dst1.base, aw.dst2 = dst2.base;
-        aw.src_img_stride = src.img_stride, aw.dst1_img_stride = dst1.img_stride, aw.dst2_img_stride = dst2.img_stride;
-        aw.spitch = (int)src.pitch, aw.d1pitch = (int)dst1.pitch, aw.d2pitch = (int)dst2.pitch;
-        aw.w = (int)W, aw.h = (int)H;
-        aw.rev = (int)dst2.reverse;
-        for (uint32_t i = 0; i < VKSIFT_HIP_MAX_TAPS; i++)
-          aw.t1.k[i] = i < ntaps1 ? taps1[i] : 0.f, aw.t2.k[i] = i < ntaps2 ? taps2[i] : 0.f;
-        uint32_t nsegw = (10240u + wstrips * batch - 1u) / (wstrips * batch);
-        const uint32_t max_segw = (H + 63u) / 64u;
-        nsegw = nsegw > max_segw ? max_segw : (nsegw < 1u ? 1u : nsegw);
-        const uint32_t segw = ((H + nsegw - 1u) / nsegw + 7u) & ~7u;
-        nsegw = (H + segw - 1u) / segw;
-        aw.seg = (int)segw;
-        hipLaunchKernelGGL((k_blur_pair_wide<5, 7>), dim3(wstrips, nsegw, batch), dim3(64), 0, (hipStream_t)s, aw);
-        return (int)hipGetLastError();
-      }
+      const dim3 grid = march_grid(wstrips, H, batch, 10240u, false, &a.seg);
+      hipLaunchKernelGGL((k_blur_pair_wide<5, 7>), grid, dim3(64), 0, (hipStream_t)s, a);
+      return (int)hipGetLastError();
     }
-    PairArgs a;
-    a.src = src.base, a.dst1 = dst1.base, a.dst2 = dst2.base;
-    a.src_img_stride = src.img_stride, a.dst1_img_stride = dst1.img_stride, a.dst2_img_stride = dst2.img_stride;
-    a.spitch = (int)src.pitch, a.d1pitch = (int)dst1.pitch, a.d2pitch = (int)dst2.pitch;
-    a.w = (int)W, a.h = (int)H;
-    a.rev = (int)dst2.reverse;
-    for (uint32_t i = 0; i < VKSIFT_HIP_MAX_TAPS; i++)
-      a.t1.k[i] = i < ntaps1 ? taps1[i] : 0.f, a.t2.k[i] = i < ntaps2 ? taps2[i] : 0.f;
-    /* row segments as stream_grid(): the strip count differs (128 - 2 HC owned columns per wave) */
-    uint32_t nseg = (10240u + strips * batch - 1u) / (strips * batch);
-    /* launches that cannot fill the GPU (a single image, the coarse octaves of a small batch) are latency bound: shorter marches,
-     * as stream_grid() — one 640x480 image: 4 pair launches of 27 us each with 64-row segments */
-    const uint32_t waves64 = strips * batch * ((H + 63u) / 64u);
-    const uint32_t seg_rows = march_rows(waves64);
-    const uint32_t max_seg = (H + seg_rows - 1u) / seg_rows;
-    if (nseg > max_seg)
-      nseg = max_seg;
-    if (nseg < 1)
-      nseg = 1;
-    const uint32_t seg = ((H + nseg - 1u) / nseg + 7u) & ~7u;
-    nseg = (H + seg - 1u) / seg;
-    a.seg = (int)seg;
-    const dim3 grid(strips, nseg, batch);
+    /* (short marches for the launches that cannot fill the GPU — one 640x480 image: 4 pair launches of 27 us each with 64-row segments) */
+    const dim3 grid = march_grid(strips, H, batch, 10240u, true, &a.seg);
     hipLaunchKernelGGL((k_blur_pair<5, 7>), grid, dim3(64), 0, (hipStream_t)s, a);
     return (int)hipGetLastError();
   }
 
+  /* the seed blur straight from the u8 images, 2..12 taps: up-sampled 2:1 (ups, k_blur_lean<N, 1, F16>, sources of at least 4 columns) or at
+   * the plane's own resolution (k_blur_lean<N, 2, F16>); -1 when not applicable: the caller runs vksift_hip_input_blit + vksift_hip_blur */
+  static int seed_launch(bool ups, const uint8_t *src, uint32_t sw, uint32_t sh, uint64_t src_img_stride, vksift_hip_Plane dst, const float *taps,
+                         uint32_t ntaps, uint32_t batch, vksift_hip_stream s)
+  {
+    const uint32_t W = dst.w, H = dst.h, f = ups ? 2u : 1u, strips = march_strips(W, ntaps, 128u);
+    if (ntaps < 2 || ntaps > (ups ? 12u : (uint32_t)VKSIFT_HIP_MAX_TAPS) || W != f * sw || H != f * sh || (ups && sw < 4) || strips == 0)
+      return -1;
+    const vksift_hip_Plane u8 = {(float *)src, W, H, sw, src_img_stride, 0, 0};
+    StreamArgs a = stream_args(u8, dst, NO_PLANE, taps, ntaps);
+    const int seed_wg = vksift_hip_tune_get(VKSIFT_TUNE_SEED_WG);
+    const dim3 grid = march_grid(strips, H, batch, ups && seed_wg > 0 ? (uint32_t)seed_wg : 10240u, true, &a.seg);
+    return ups ? blur_lean_launch<1>(ntaps, grid, a, dst.fp16 != 0, (hipStream_t)s) : blur_lean_launch<2>(ntaps, grid, a, dst.fp16 != 0, (hipStream_t)s);
+  }
+
+  int vksift_hip_seed_upsampled(const uint8_t *src, uint32_t sw, uint32_t sh, uint64_t src_img_stride, vksift_hip_Plane dst, const float *taps, uint32_t ntaps,
+                                uint32_t batch, vksift_hip_stream s)
+  {
+    return seed_launch(true, src, sw, sh, src_img_stride, dst, taps, ntaps, batch, s);
+  }
+
+  int vksift_hip_seed_direct(const uint8_t *src, uint32_t sw, uint32_t sh, uint64_t src_img_stride, vksift_hip_Plane dst, const float *taps, uint32_t ntaps,
+                             uint32_t batch, vksift_hip_stream s)
+  {
+    return seed_launch(false, src, sw, sh, src_img_stride, dst, taps, ntaps, batch, s);
+  }
+
   int vksift_hip_blur(vksift_hip_Plane src, vksift_hip_Plane dst, const float *taps, uint32_t ntaps, uint32_t batch, vksift_hip_stream s)
   {
-    const vksift_hip_Plane none = {NULL, 0, 0, 0, 0, 0, 0};
-    return blur_impl(src, dst, none, taps, ntaps, batch, s);
+    return blur_impl(src, dst, NO_PLANE, taps, ntaps, batch, s);
   }
 
   int vksift_hip_blur_downsample(vksift_hip_Plane src, vksift_hip_Plane dst, vksift_hip_Plane next, const float *taps, uint32_t ntaps, uint32_t batch,
@@ -2049,90 +2082,6 @@ extern "C"
     if (next.base == NULL || dst.base == NULL || next.w * 2u != src.w || next.h * 2u != src.h)
       return -1;
     return blur_impl(src, dst, next, taps, ntaps, batch, s);
-  }
-
-  int vksift_hip_seed_upsampled(const uint8_t *src, uint32_t sw, uint32_t sh, uint64_t src_img_stride, vksift_hip_Plane dst, const float *taps, uint32_t ntaps,
-                                uint32_t batch, vksift_hip_stream s)
-  {
-    const uint32_t W = dst.w, H = dst.h;
-    const uint32_t ra = ((ntaps - 1u) + 3u) & ~3u;
-    const uint32_t strips = (W + 127u) / 128u;
-    if (ntaps < 2 || ntaps > 12 || W != 2 * sw || H != 2 * sh || (W % 4u) != 0 || sw < 4 || ra > W || strips * 128u + ra > 2u * W)
-      return -1; /* not applicable: the caller runs vksift_hip_input_blit + vksift_hip_blur */
-    StreamArgs a;
-    a.ds = NULL, a.ds_img_stride = 0, a.ds_pitch = 0;
-    a.src = (const float *)src, a.dst = dst.base;
-    a.src_img_stride = src_img_stride, a.dst_img_stride = dst.img_stride;
-    a.spitch = (int)sw, a.dpitch = (int)dst.pitch;
-    a.w = (int)W, a.h = (int)H;
-    a.rev = (int)dst.reverse;
-    for (uint32_t i = 0; i < VKSIFT_HIP_MAX_TAPS; i++)
-      a.taps.k[i] = i < ntaps ? taps[i] : 0.f;
-    const uint32_t seed_wg = vksift_hip_tune_get(VKSIFT_TUNE_SEED_WG) > 0 ? (uint32_t)vksift_hip_tune_get(VKSIFT_TUNE_SEED_WG) : 10240u;
-    uint32_t nseg = (seed_wg + strips * batch - 1u) / (strips * batch); /* as the other launches (stream_grid): 2560 long-lived waves left the tail to a few CUs */
-    const uint32_t waves64 = strips * batch * ((H + 63u) / 64u);
-    const uint32_t seg_rows = march_rows(waves64); /* latency-bound launches: shorter marches (stream_grid) */
-    uint32_t max_seg = (H + seg_rows - 1u) / seg_rows;
-    if (nseg > max_seg)
-      nseg = max_seg;
-    if (nseg < 1)
-      nseg = 1;
-    uint32_t seg = ((H + nseg - 1u) / nseg + 7u) & ~7u;
-    nseg = (H + seg - 1u) / seg;
-    a.seg = (int)seg;
-    dim3 grid(strips, nseg, batch);
-    switch (ntaps)
-    {
-#define VKSIFT_CASE(N)                                                                        \
-  case N:                                                                                     \
-    if (dst.fp16)                                                                             \
-      hipLaunchKernelGGL((k_blur_lean<N, 1, true>), grid, dim3(64), 0, (hipStream_t)s, a);   \
-    else                                                                                      \
-      hipLaunchKernelGGL((k_blur_lean<N, 1, false>), grid, dim3(64), 0, (hipStream_t)s, a);  \
-    break;
-      VKSIFT_CASE(2) VKSIFT_CASE(3) VKSIFT_CASE(4) VKSIFT_CASE(5) VKSIFT_CASE(6) VKSIFT_CASE(7) VKSIFT_CASE(8) VKSIFT_CASE(9) VKSIFT_CASE(10)
-      VKSIFT_CASE(11) VKSIFT_CASE(12)
-#undef VKSIFT_CASE
-    default:
-      return -1;
-    }
-    return (int)hipGetLastError();
-  }
-
-  int vksift_hip_seed_direct(const uint8_t *src, uint32_t sw, uint32_t sh, uint64_t src_img_stride, vksift_hip_Plane dst, const float *taps, uint32_t ntaps,
-                             uint32_t batch, vksift_hip_stream s)
-  {
-    const uint32_t W = dst.w, H = dst.h;
-    const uint32_t ra = ((ntaps - 1u) + 3u) & ~3u;
-    const uint32_t strips = (W + 127u) / 128u;
-    if (ntaps < 2 || ntaps > VKSIFT_HIP_MAX_TAPS || W != sw || H != sh || (W % 4u) != 0 || ra > W || strips * 128u + ra > 2u * W)
-      return -1; /* not applicable: the caller runs vksift_hip_input_blit + vksift_hip_blur */
-    StreamArgs a;
-    a.ds = NULL, a.ds_img_stride = 0, a.ds_pitch = 0;
-    a.src = (const float *)src, a.dst = dst.base;
-    a.src_img_stride = src_img_stride, a.dst_img_stride = dst.img_stride;
-    a.spitch = (int)sw, a.dpitch = (int)dst.pitch;
-    a.w = (int)W, a.h = (int)H;
-    a.rev = (int)dst.reverse;
-    for (uint32_t i = 0; i < VKSIFT_HIP_MAX_TAPS; i++)
-      a.taps.k[i] = i < ntaps ? taps[i] : 0.f;
-    const dim3 grid = stream_grid(W, H, batch, 10240u, &a.seg);
-    switch (ntaps)
-    {
-#define VKSIFT_CASE(N)                                                                        \
-  case N:                                                                                     \
-    if (dst.fp16)                                                                             \
-      hipLaunchKernelGGL((k_blur_lean<N, 2, true>), grid, dim3(64), 0, (hipStream_t)s, a);      \
-    else                                                                                      \
-      hipLaunchKernelGGL((k_blur_lean<N, 2, false>), grid, dim3(64), 0, (hipStream_t)s, a);     \
-    break;
-      VKSIFT_CASE(2) VKSIFT_CASE(3) VKSIFT_CASE(4) VKSIFT_CASE(5) VKSIFT_CASE(6) VKSIFT_CASE(7) VKSIFT_CASE(8) VKSIFT_CASE(9) VKSIFT_CASE(10)
-      VKSIFT_CASE(11) VKSIFT_CASE(12)
-#undef VKSIFT_CASE
-    default:
-      return -1;
-    }
-    return (int)hipGetLastError();
   }
 
   int vksift_hip_downsample(vksift_hip_Plane src, vksift_hip_Plane dst, uint32_t batch, vksift_hip_stream s)
@@ -2181,17 +2130,11 @@ extern "C"
       if (ntaps[l] < 1 || ntaps[l] > VKSIFT_HIP_MAX_TAPS || (l > 0 && ntaps[l] > min_side))
         return -1; /* (a radius that reaches past one reflection: the per-scale launches handle it) */
       a.nt[l] = (int)ntaps[l];
-      for (uint32_t i = 0; i < VKSIFT_HIP_MAX_TAPS; i++)
-        a.k[l][i] = i < ntaps[l] ? taps[l * VKSIFT_HIP_MAX_TAPS + i] : 0.f;
+      pack_taps(a.k[l], taps + l * VKSIFT_HIP_MAX_TAPS, ntaps[l]);
     }
-    static bool lds_attr_set = false;
-    if (!lds_attr_set)
-    {
-      const hipError_t ae = hipFuncSetAttribute((const void *)k_octave_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CH_LDS_FLOATS * sizeof(float)));
-      if (ae != hipSuccess)
-        return (int)ae;
-      lds_attr_set = true;
-    }
+    static bool lds_set = false;
+    if (int e = lds_opt_in(lds_set, (int)(CH_LDS_FLOATS * sizeof(float)), (const void *)k_octave_chain))
+      return e;
     const size_t lds_bytes = sizeof(float) * 2u * (size_t)a.o[0].w * a.o[0].h;
     hipLaunchKernelGGL(k_octave_chain, dim3(batch), dim3(CH_THREADS), lds_bytes, (hipStream_t)s, a);
     return (int)hipGetLastError();
