@@ -39,6 +39,7 @@ extern "C"
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
 #define VKSIFT_HIP_MAX_ORI 18  /* a 36-bin circular histogram has at most 18 strict local maxima */
+#define VKSIFT_HIP_MAX_OCTAVE_SIDE 16383u /* candidate coordinates are packed 14 + 14 bits: octaves up to 16383 x 16383 texels */
 
   typedef void *vksift_hip_stream;
   typedef void *vksift_hip_graph; /* an instantiated hipGraph (hipGraphExec_t) */

@@ -775,7 +775,7 @@ __global__ void __launch_bounds__(256) k_cand_emit(Multi<ExtremaArgs> m)
 
 static int make_extrema_args(const vksift_hip_OctaveJob *job, ExtremaArgs *out)
 {
-  if (job->w >= 16384u || job->h >= 16384u || job->S > 14u)
+  if (job->w > VKSIFT_HIP_MAX_OCTAVE_SIDE || job->h > VKSIFT_HIP_MAX_OCTAVE_SIDE || job->S > 14u)
     return (int)hipErrorInvalidValue; /* candidate coordinates are packed 14 + 14 + 4 bits */
   ExtremaArgs a;
   a.gauss = job->gauss;
@@ -914,7 +914,11 @@ static int extract_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t ba
   /* at most 512 chunk workgroups per image, and ~64 k per octave whatever the batch (they stride over the chunks; idle ones only
    * cost dispatch: 512 frames with 512 per image 1.25 ms for the stage without the scan, with 128 per image 0.86 ms) */
   const uint32_t rcap = 65536u / batch < 16u ? 16u : (65536u / batch > 512u ? 512u : 65536u / batch);
-  VKSIFT_MULTI(mr, batch, ((a.cand_cap + 255u) / 256u) > rcap ? rcap : ((a.cand_cap + 255u) / 256u), 1u)
+  /* (and no more than a quarter of the list's capacity, S*w*h/4 texels, asks for: the capacity holds the densest image there can be, a
+   * 2x2-periodic texture — natural images stay far below a quarter of it, and the workgroups of a denser octave stride over its chunks) */
+#define VKSIFT_REFINE_CHUNKS(a) (((uint64_t)(a).S * (uint32_t)(a).w * (uint32_t)(a).h / 4u + 64u + 255u) / 256u)
+  VKSIFT_MULTI(mr, batch, VKSIFT_REFINE_CHUNKS(a) > rcap ? rcap : (uint32_t)VKSIFT_REFINE_CHUNKS(a), 1u)
+#undef VKSIFT_REFINE_CHUNKS
   const dim3 rgrid(mr.start[mr.n]);
   /* the refinement addresses an image's octave through one buffer resource with 32-bit offsets where it fits (always, short of
    * 4096 x 4096 octaves with many scales); the pointer form serves the rest */

@@ -126,6 +126,14 @@ bool resolution_valid(vksift_Instance inst, uint32_t w, uint32_t h)
     logError(LOG_TAG, "Image of %d x %d = %llu pixels is below the 1024-pixel minimum.", w, h, (unsigned long long)size);
     return false;
   }
+  /* the largest octave is the first (twice the input with up-sampling); the extrema scan packs candidate coordinates in 14 bits each */
+  uint32_t ow[VKSIFT_MAX_OCTAVES], oh[VKSIFT_MAX_OCTAVES];
+  if (vksift_hm_octaves_for(&inst->cfg, inst->max_octaves, w, h, ow, oh) > 0 && (ow[0] > VKSIFT_HIP_MAX_OCTAVE_SIDE || oh[0] > VKSIFT_HIP_MAX_OCTAVE_SIDE))
+  {
+    logError(LOG_TAG, "Image of %d x %d: its first octave (%u x %u) exceeds the %u texels per side this build supports.", w, h, ow[0], oh[0],
+             VKSIFT_HIP_MAX_OCTAVE_SIDE);
+    return false;
+  }
   return true;
 }
 

@@ -27,9 +27,12 @@ void compute_layout(vksift_Instance inst, uint32_t w, uint32_t h, PyrLayout *L)
     L->seg_off[o] = so;
     so += (uint64_t)inst->S * L->h[o] * ((L->w[o] + 63) / 64);
     L->cand_off[o] = co;
-    /* strict 3x3x3 maxima cannot be denser than 1/8 of the texels (no two are adjacent), nor can minima: 1/4 together is a
-     * bound no image exceeds, so candidates are only ever lost through the section capacity, like in the reference */
-    L->cand_cap[o] = (uint64_t)inst->S * L->w[o] * L->h[o] / 4u + 64u;
+    /* Room for every candidate any image can produce, so that they are only ever lost through the section capacity, like in the
+     * reference. A strict 26-neighbour maximum is a strict maximum of its own layer's 8-neighbourhood, so the strict maxima of a
+     * layer are pairwise non-adjacent (8-connectivity). Cut the (w-2) x (h-2) interior into ceil((w-2)/2) x ceil((h-2)/2) blocks
+     * of at most 2x2 texels: the texels of a block are pairwise adjacent, so a block holds at most one maximum, and likewise at
+     * most one minimum. A 2x2-periodic texture reaches the bound (tests/test_extraction_limits.py). ceil((n-2)/2) = (n-1)/2. */
+    L->cand_cap[o] = (uint64_t)inst->S * 2u * ((L->w[o] - 1u) / 2u) * ((L->h[o] - 1u) / 2u) + 64u;
     co += L->cand_cap[o];
   }
   L->seg_total = so;
