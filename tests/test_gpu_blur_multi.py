@@ -1,5 +1,5 @@
-"""Scales S+1 and S+2 as ONE launch per scale over several octaves (k_blur_lean_multi, vksift_hip_blur_multi: pyramid.hip; enqueue_tail:
-vksift_detect.c) against one launch per octave and scale (VKSIFT_TUNE_TAIL_MULTI = 1) and the oracle. Both forms of use: the forked
+"""Scales S+1 and S+2 as ONE launch per scale over several octaves (k_blur_lean_multi, vksift_hip_blur_multi: pyramid.hip; enqueue_tail,
+planned per octave by plan_detection: vksift_detect.c) against one launch per octave and scale (VKSIFT_TUNE_TAIL_MULTI = 1) and the oracle. Both forms of use: the forked
 scale-space of a small detection (every octave in the tail, on the side stream) and a batch (octave 0 and every octave that takes the
 four-texel kernel in full, the coarser ones in the tail). Every plane and every feature has to be the same bit for bit."""
 import numpy as np

@@ -328,7 +328,7 @@ def test_random_scale_space_reads_follow_the_model(vk, oracle, monkeypatch, defe
 # ---- the launch form of a batch ------------------------------------------------------------------------------------------------------
 def test_batch_of_8_takes_the_tail_launches_deterministically(vk):
     """a batch of 8 images with two tail octaves or more queues scales S+1, S+2 of its coarser octaves as multi-octave launches
-    (c.tail_batch in detect_impl), unless VKSIFT_TUNE_TAIL_MULTI = 1: fewer blur launches, the same launches on every call, the same
+    (DetectCtx::tail_batch, plan_detection in vksift_detect.c), unless VKSIFT_TUNE_TAIL_MULTI = 1: fewer blur launches, the same launches on every call, the same
     feature bytes as the per-octave form"""
     w, h, n = 1536, 1024, 8
     imgs = [vk.gen_synthetic_image_family(7700 + i, w, h, i % 3) for i in range(n)]

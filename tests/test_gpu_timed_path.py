@@ -4,7 +4,7 @@ bench.py's step is: a batch_capacity = 512 instance (two pyramid buffers, overla
 vksift_ext_detectFeaturesBatchDevice on 512 device-resident 640x480 frames, vksift_ext_matchFeaturesBatch(ids, ids) of all 512
 self-pairs (launch sequences of 64 inside), the next step queued right behind it WITHOUT a host synchronisation. The reference makes a new detection wait
 for the running pipelines (src/vulkansift/vulkansift.c:326-327, include/vulkansift/vulkansift.h:43-47); here the ordering is done
-with events between streams (vksift_detect.c: ev_pyr_free, ev_desc_start, ev_input_free), which is exactly what these tests load:
+with events between streams (vksift_detect.c, prepare_detection / enqueue_seed / enqueue_keypoint_stages: ev_pyr_free, ev_input_free, ev_desc_start), which is exactly what these tests load:
 
 * three (or two) steps back to back, each on a DIFFERENT frame set, so a buffer recycled too early or a stale pyramid shows;
 * after the last step: every buffer byte-equal to the plain single-image vksift_detectFeatures on the same frame, sampled

@@ -20,7 +20,7 @@
  * (vulkansift_types.h:148-152 of the reference).
  *
  * This file: defaults, validation, runtime life-cycle. vksift_instance.c: instances, layout, synchronisation helpers.
- * vksift_detect.c: the detection pipeline. vksift_buffers.c: feature accessors + scale-space inspection.
+ * vksift_detect.c: the detection pipeline (vksift_stage.c: image staging, vksift_defer.c: deferred submission). vksift_buffers.c: feature accessors + scale-space inspection.
  * vksift_match.c: matching. vksift_ext.c: extensions. Shared private definitions: vksift_internal.h.
  */
 #include "vksift_internal.h"

@@ -158,8 +158,8 @@ static vksift_Result create_instance(vksift_Instance *instance_ptr, const vksift
   {
     /* Overlap mode: the (bandwidth-bound) scale-space construction of detection N+1 runs on its own stream, beside the matching
      * queued behind detection N's descriptors (rounds 2-3 also ran it under the descriptors themselves, out of a second scale-space
-     * buffer: within 1 % in frames/s, and every stage interval measured the contention instead of the kernel — vksift_detect.c:
-     * ev_desc_start). With that gate the next scale-space starts only when every reader of the previous one is done, so ONE buffer
+     * buffer: within 1 % in frames/s, and every stage interval measured the contention instead of the kernel — vksift_detect.c,
+     * enqueue_keypoint_stages: ev_desc_start). With that gate the next scale-space starts only when every reader of the previous one is done, so ONE buffer
      * serves (half the memory; and the measured placement, place_pyramid_buffers, has to find one fast range, not two).
      * Default: instances created for batches of 8 images and more (vksift_ext_createBatchInstance) — a single-image instance keeps
      * the hipGraph replay of small detections, which excludes overlapped calls. VKSIFT_PYR_PINGPONG=0 / 1 forces the mode off / on,

@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_detect.c, vksift_buffers.c, vksift_match.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -109,7 +109,7 @@ struct vksift_Instance_T
   uint32_t det_cap;        /* images one detection launch sequence can take (>= batch_cap): input staging, scale-space, extraction scratch.
                             * Grows when a caller of the plain API turns out to batch (deferred submission, below) */
 
-  /* Deferred submission of vksift_detectFeatures (vksift_detect.c: defer_detect). The reference's caller hands over ONE image per call
+  /* Deferred submission of vksift_detectFeatures (vksift_defer.c: defer_detect). The reference's caller hands over ONE image per call
    * (vulkansift.c:315-344); a caller that issues several such calls in a row, into consecutive SIFT buffers, before it asks for
    * anything gets them launched as ONE batched detection: the call stages its image in the pinned input block and returns, and the
    * batch is launched by the first call that needs a result (every other entry point: defer_sync) or when it is full. The first
@@ -297,14 +297,22 @@ VKSIFT_INTERNAL void set_buffer_sections(vksift_Instance inst, uint32_t buf, uin
 VKSIFT_INTERNAL void mark_detect_done(vksift_Instance inst);
 VKSIFT_INTERNAL bool detect_running(vksift_Instance inst);
 VKSIFT_INTERNAL int wait_detect_seq(vksift_Instance inst, uint64_t seq);
-static inline bool counts_valid(const struct vksift_Instance_T *inst, uint32_t buf);
 VKSIFT_INTERNAL bool match_running(vksift_Instance inst);
 VKSIFT_INTERNAL int wait_all(vksift_Instance inst);
 VKSIFT_INTERNAL int grow_image_scratch(vksift_Instance inst, const PyrLayout *L);
 VKSIFT_INTERNAL int resize_detect_scratch(vksift_Instance inst, const PyrLayout *L, uint32_t new_cap);
-VKSIFT_INTERNAL vksift_hip_Plane plane_at(vksift_Instance inst, uint32_t o, uint64_t base_off, uint32_t layer);
+
+/* vksift_stage.c: images [i0, i1) -> dst (the pinned staging buffer), by a small pool of copy threads */
+VKSIFT_INTERNAL void stage_images(uint8_t *dst, const uint8_t *const *images, uint32_t i0, uint32_t i1, size_t img_bytes);
 
 /* vksift_detect.c */
+VKSIFT_INTERNAL bool detect_args_valid(vksift_Instance inst, uint32_t count, uint32_t w, uint32_t h, uint32_t first_buf, bool report);
+VKSIFT_INTERNAL void detect_impl(vksift_Instance inst, const uint8_t *const *images, const uint8_t *d_images, bool prestaged, uint32_t count, uint32_t w,
+                                 uint32_t h, uint32_t first_buf, const char *fn);
+VKSIFT_INTERNAL void account_set(vksift_Instance inst, ProfSet *ps);
+VKSIFT_INTERNAL void account_timings(vksift_Instance inst);
+
+/* vksift_defer.c */
 VKSIFT_INTERNAL void flush_deferred(vksift_Instance inst);
 /* Every entry point but vksift_detectFeatures starts with this: what was deferred is launched, and the run of detect calls ends */
 static inline void defer_sync(vksift_Instance inst)
@@ -317,8 +325,6 @@ static inline void defer_sync(vksift_Instance inst)
     inst->epoch_detects = 0;
   }
 }
-VKSIFT_INTERNAL void account_set(vksift_Instance inst, ProfSet *ps);
-VKSIFT_INTERNAL void account_timings(vksift_Instance inst);
 
 /* vksift_buffers.c */
 VKSIFT_INTERNAL void wait_for_buffer(vksift_Instance inst, uint32_t buf);
