@@ -188,7 +188,8 @@ extern "C"
    * layers[o * n_layers + l] = layer l of octave o; layer 0 of octave 0 of the run is the input (already in memory), every other plane is
    * written: layer l = blur(layer l - 1, taps[l]) (sift_detector.c:927-1001), layer 0 of the next octave = nearest 2:1 of layer S
    * (:1003-1034). taps: n_layers rows of VKSIFT_HIP_MAX_TAPS. Bit-identical to the vksift_hip_blur / vksift_hip_downsample sequence.
-   * -1 when the planes are not covered (fp16, width not a multiple of 4, too large for the LDS). */
+   * -1 when the planes are not covered (fp16, width or pitch not a multiple of 4, a base that is not 16-byte aligned, sides below 8, too
+   * large for the LDS) or a layer's tap count exceeds the shortest side of any plane of the run (one mirror reflection must cover the radius). */
   int vksift_hip_octave_chain(const vksift_hip_Plane *layers, uint32_t n_oct, uint32_t n_layers, uint32_t S, const float *taps, const uint32_t *ntaps,
                               uint32_t batch, vksift_hip_stream s);
 

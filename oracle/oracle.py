@@ -108,6 +108,14 @@ def lib():
         L.orc_match_2nn_desc.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_filter_matches.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_filter_matches.restype = C.c_uint32
+        L.orc_blur_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int]
+        L.orc_blur_plane.restype = None
+        L.orc_blit_input.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.orc_blit_input.restype = None
+        L.orc_blit_nearest.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.orc_blit_nearest.restype = None
+        L.orc_store_f16.argtypes = [C.c_void_p, C.c_size_t]
+        L.orc_store_f16.restype = None
         for fn in ("orc_dm_expf", "orc_dm_exp2f", "orc_dm_sinf", "orc_dm_cosf"):
             getattr(L, fn).argtypes = [C.c_float]
             getattr(L, fn).restype = C.c_float
@@ -172,6 +180,41 @@ def effective_taps(cfg):
     n = np.zeros(S + 3, np.uint32)
     lib().orc_effective_taps(C.byref(cfg), k.ctypes.data_as(C.POINTER(C.c_float)), n.ctypes.data_as(C.POINTER(C.c_uint32)))
     return k, n
+
+
+def blur_plane(src, taps, fp16=False):
+    """One separable blur of a dense (h, w) float32 plane with one-sided taps (centre first, 1..20 of them): blur_plane of the oracle."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    taps = np.ascontiguousarray(taps, dtype=np.float32)
+    assert src.ndim == 2 and src.size > 0 and taps.ndim == 1 and 1 <= len(taps) <= MAX_KERNEL
+    dst = np.empty_like(src)
+    lib().orc_blur_plane(src.ctypes.data, dst.ctypes.data, src.shape[1], src.shape[0], taps.ctypes.data, len(taps), 1 if fp16 else 0)
+    return dst
+
+
+def blit_input(u8, dw, dh):
+    """u8 (h, w) image -> float32 (dh, dw) plane: blit_input of the oracle (value / 255, LINEAR filter, clamp to edge)."""
+    u8 = np.ascontiguousarray(u8, dtype=np.uint8)
+    assert u8.ndim == 2 and u8.size > 0 and dw > 0 and dh > 0
+    dst = np.empty((dh, dw), np.float32)
+    lib().orc_blit_input(u8.ctypes.data, u8.shape[1], u8.shape[0], dst.ctypes.data, dw, dh)
+    return dst
+
+
+def blit_nearest(src, dw, dh):
+    """float32 (h, w) plane -> (dh, dw) plane: blit_nearest of the oracle (NEAREST filter)."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    assert src.ndim == 2 and src.size > 0 and dw > 0 and dh > 0
+    dst = np.empty((dh, dw), np.float32)
+    lib().orc_blit_nearest(src.ctypes.data, src.shape[1], src.shape[0], dst.ctypes.data, dw, dh)
+    return dst
+
+
+def store_f16(plane):
+    """A copy of a float32 array with every value rounded through binary16: store_as_f16 of the oracle."""
+    out = np.array(plane, dtype=np.float32, order="C", copy=True)
+    lib().orc_store_f16(out.ctypes.data, out.size)
+    return out
 
 
 class Pyramid:

@@ -427,6 +427,21 @@ static void blit_nearest(const float *src, int sw, int sh, float *dst, int dw, i
   }
 }
 
+/* The three plane operations above on their own, for tests that drive the HIP launchers plane by plane (tests/hip_planes.py): thin
+ * wrappers, no arithmetic of their own. Dense w x h planes; src and dst must not overlap. */
+void orc_blur_plane(const float *src, float *dst, uint32_t w, uint32_t h, const float *taps, uint32_t ntaps, int fp16)
+{
+  float *tmp = (float *)malloc(sizeof(float) * ((size_t)w * h + 1u));
+  blur_plane(src, dst, tmp, (int)w, (int)h, taps, (int)ntaps, fp16);
+  free(tmp);
+}
+void orc_blit_input(const uint8_t *u8, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh) { blit_input(u8, (int)sw, (int)sh, dst, (int)dw, (int)dh); }
+void orc_blit_nearest(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh)
+{
+  blit_nearest(src, (int)sw, (int)sh, dst, (int)dw, (int)dh);
+}
+void orc_store_f16(float *plane, size_t n) { store_as_f16(plane, n); }
+
 orc_Pyramid *orc_pyramid_build(const orc_Config *cfg, const uint8_t *img, uint32_t w, uint32_t h)
 {
   orc_Pyramid *p = (orc_Pyramid *)calloc(1, sizeof(orc_Pyramid));

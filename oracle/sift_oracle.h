@@ -14,6 +14,7 @@
 #ifndef SIFT_ORACLE_H
 #define SIFT_ORACLE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -98,6 +99,17 @@ extern "C"
   void orc_pyramid_resolution(const orc_Pyramid *p, uint32_t o, uint32_t *w, uint32_t *h);
   const float *orc_pyramid_gauss(const orc_Pyramid *p, uint32_t o, uint32_t s); /* s < S+3, w*h floats */
   const float *orc_pyramid_dog(const orc_Pyramid *p, uint32_t o, uint32_t s);   /* s < S+2 */
+
+  /* The plane operations orc_pyramid_build is made of, one call each (dense w x h planes, no aliasing):
+   * one separable blur with one-sided direct taps (centre first), mirrored-repeat borders; fp16 != 0: the horizontal pass's output and the
+   * result are rounded through binary16 (the source is expected to hold binary16 values already: orc_store_f16) */
+  void orc_blur_plane(const float *src, float *dst, uint32_t w, uint32_t h, const float *taps, uint32_t ntaps, int fp16);
+  /* u8 / 255 -> fp32, LINEAR blit to dw x dh (a plain conversion when the sizes match) */
+  void orc_blit_input(const uint8_t *u8, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh);
+  /* NEAREST blit of an fp32 plane to dw x dh */
+  void orc_blit_nearest(const float *src, uint32_t sw, uint32_t sh, float *dst, uint32_t dw, uint32_t dh);
+  /* every value rounded to binary16 (nearest even) and widened again, in place */
+  void orc_store_f16(float *plane, size_t n);
 
   /* ---- detection ---- */
   /* Runs K4+K5+K6 on a built pyramid. Features come out in the reference's packed order: octave

@@ -2122,8 +2122,11 @@ extern "C"
     uint32_t min_side = 0xFFFFFFFFu;
     for (uint32_t o = 0; o < n_oct; o++)
     {
-      min_side = a.o[o].w < (int)min_side ? (uint32_t)a.o[o].w : min_side;
-      min_side = a.o[o].h < (int)min_side ? (uint32_t)a.o[o].h : min_side;
+      /* (compared as unsigned: with `a.o[o].w < (int)min_side` the initial 0xFFFFFFFF read as -1, no side was ever smaller and the check
+       * below declined nothing — found by tests/test_gpu_pyramid_launchers.py) */
+      const uint32_t ow = (uint32_t)a.o[o].w, oh = (uint32_t)a.o[o].h;
+      min_side = ow < min_side ? ow : min_side;
+      min_side = oh < min_side ? oh : min_side;
     }
     for (uint32_t l = 0; l < n_layers; l++)
     {
