@@ -54,6 +54,31 @@ extern "C"
   VKSIFT_EXPORT uint32_t vksift_ext_getFilteredMatchesNumber(vksift_Instance instance, uint32_t pair);
   VKSIFT_EXPORT void vksift_ext_downloadFilteredMatches(vksift_Instance instance, uint32_t pair, vksift_ext_FilteredMatch *matches);
 
+  /* ---- GPU-side geometric verification --------------------------------------------------------------------------------
+   * What callers do next with filtered matches: a RANSAC homography per pair, here for every pair of the last vksift_ext_matchFeaturesFiltered call in
+   * three launches, without downloading matches or features. nb_hypotheses (1 .. 65536) four-point samples per pair, drawn from a counter-based generator
+   * keyed by (seed, pair, hypothesis); a match is an inlier when the forward transfer error of its A keypoint is below threshold_px (and it is not mapped
+   * behind the plane); the model with the most inliers wins, ties to the lowest hypothesis. Deterministic: the same inputs give the same bytes on every run
+   * (tests/np_verify.py restates the estimator bit for bit). No refit on the inliers: the mask is what a caller's own least-squares refinement needs.
+   * Asynchronous like the matching entry points: queued behind the matching, the pairs' buffers stay busy (vksift_isBufferAvailable), the accessors wait. The
+   * SIFT buffers of the pairs must still hold the features that were matched. A new matching invalidates the results like it invalidates the filtered matches.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued): no filtered matching to verify, nb_hypotheses 0 or above 65536, threshold_px not a positive finite number,
+   * pair out of range. */
+  typedef struct
+  {
+    float H[9];            /* row-major, pixel coordinates of A -> B, H[8] == 1 */
+    uint32_t nb_matches;   /* filtered matches of the pair */
+    uint32_t nb_inliers;
+    uint32_t best_hypothesis;
+    uint32_t valid;        /* 0: fewer than 4 matches, no hypothesis with 4 inliers, or a model that cannot be normalised; everything else is zero then */
+  } vksift_ext_Homography; /* 52 bytes */
+  VKSIFT_EXPORT void vksift_ext_verifyHomography(vksift_Instance instance, uint32_t nb_hypotheses, float threshold_px, uint64_t seed);
+  VKSIFT_EXPORT void vksift_ext_getHomography(vksift_Instance instance, uint32_t pair, vksift_ext_Homography *out);
+  /* vksift_ext_getFilteredMatchesNumber(pair) bytes, in the order of the filtered matches: 1 = inlier of the returned model */
+  VKSIFT_EXPORT void vksift_ext_downloadInlierMask(vksift_Instance instance, uint32_t pair, uint8_t *mask);
+  /* Time (ms) of the last verification (its three launches + the result posting), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getVerifyTime(vksift_Instance instance);
+
   /* Deferred submission of vksift_detectFeatures (no counterpart in the reference, no change of its contract): consecutive plain
    * detect calls into consecutive SIFT buffers, with nothing asked in between, are staged and launched as ONE batched detection by
    * the first call that needs a result — any other entry point — or when 128 images (VKSIFT_DEFER_MAX) are staged, or 16 (VKSIFT_DEFER_CHUNK)

@@ -357,6 +357,32 @@ extern "C"
                                  uint64_t cache_norm_stride, uint64_t redo_slot_stride, uint64_t match_slot_stride, uint32_t n_slot_stride,
                                  uint32_t *partial_scratch, vksift_hip_stream s);
 
+  /* ------------------------------------------------------------------ geometric verification (verify.hip; no counterpart in the reference) */
+  /* Correspondences of filtered matches: for slot i and each of its min(filtered_n[i], max_n) records {idx_a, idx_b, ..} (16 bytes, the output of
+   * vksift_hip_filter_matches at filtered + i*filtered_slot_stride) the x, y fields of the two features as {xa, ya, xb, yb} at corr + i*corr_slot_stride
+   * (bytes, multiple of 16). idx_a / idx_b are download-order rows; slot_tab holds four words per slot {buffer A, buffer B, layout A, layout B}: a layout word
+   * with bit 31 set names a buffer of (word & 0x7fffffff) dense records (uploaded features), any other value entry `word` of layouts[], 33 words each
+   * {nsec, off[16], cap[16]}, whose stored counts min(found, cap) are read on the device (found_base + buffer*found_buf_stride) like vksift_hip_gather_sections
+   * does. slot_tab / layouts are read by the kernel (device or mapped pinned memory). A record naming a row its buffer does not hold gives a NaN
+   * correspondence. One launch whatever nslots. */
+  int vksift_hip_gather_correspondences(const uint8_t *feats_base, uint64_t buf_stride, const uint32_t *found_base, uint32_t found_buf_stride,
+                                        const uint32_t *slot_tab, const uint32_t *layouts, const uint8_t *filtered, uint64_t filtered_slot_stride,
+                                        const uint32_t *filtered_n, uint32_t max_n, uint32_t nslots, float *corr, uint64_t corr_slot_stride, vksift_hip_stream s);
+  /* Deterministic RANSAC homography of nslots correspondence sets in two launches. Slot i: n = min(n_dev[i*n_stride], max_n) correspondences of four floats
+   * at corr + i*corr_slot_stride (bytes; 16-byte aligned). Hypothesis j of slot i samples four distinct indices from splitmix64 keyed by (seed, i, j) — the
+   * same hypothesis whatever nb_hypotheses —, solves the four-point homography in closed form (fp32, coordinates up to VKSIFT_HIP_MAX_OCTAVE_SIDE) and counts the
+   * correspondences with d > 0 and forward transfer error below threshold_px; the best is the largest count, ties to the lowest j. results + 52*i: float H[9]
+   * (row-major, pixel coordinates, H[8] == 1), uint32 nb_matches (= n), nb_inliers, best_hypothesis, valid; masks + i*mask_slot_stride: n bytes, 1 = inlier of
+   * H by the same test (their sum is nb_inliers). n < 4, a best count below 4, h22 == 0 or a non-finite entry: valid = 0 and H, nb_inliers, best_hypothesis and
+   * the mask are zero. No refinement on the inliers (a least-squares refit cannot be pinned bit for bit; the mask is what a caller's own refit needs).
+   * tests/np_verify.py restates every output bit for bit. scratch: scratch_u32 >= vksift_hip_ransac_scratch_u32(nslots, nb_hypotheses) words, need not be
+   * initialised. hipErrorInvalidValue, nothing launched: nb_hypotheses 0 or above 65536, threshold_px not positive and finite, too little scratch, strides below
+   * max_n records. */
+  size_t vksift_hip_ransac_scratch_u32(uint32_t nslots, uint32_t nb_hypotheses);
+  int vksift_hip_ransac_homography(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
+                                   uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
+                                   uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
+
 #ifdef __cplusplus
 }
 #endif

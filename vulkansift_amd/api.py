@@ -72,7 +72,8 @@ FEATURE_DTYPE = np.dtype(
 )
 MATCH_DTYPE = np.dtype([("idx_a", "<u4"), ("idx_b1", "<u4"), ("idx_b2", "<u4"), ("dist_a_b1", "<f4"), ("dist_a_b2", "<f4")])
 FILTERED_MATCH_DTYPE = np.dtype([("idx_a", "<u4"), ("idx_b", "<u4"), ("dist_a_b1", "<f4"), ("dist_a_b2", "<f4")])
-assert FEATURE_DTYPE.itemsize == 164 and MATCH_DTYPE.itemsize == 20 and FILTERED_MATCH_DTYPE.itemsize == 16
+HOMOGRAPHY_DTYPE = np.dtype([("H", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("best_hypothesis", "<u4"), ("valid", "<u4")])
+assert FEATURE_DTYPE.itemsize == 164 and MATCH_DTYPE.itemsize == 20 and FILTERED_MATCH_DTYPE.itemsize == 16 and HOMOGRAPHY_DTYPE.itemsize == 52
 
 _lib = None
 
@@ -124,6 +125,14 @@ def lib():
     L.vksift_ext_getFilteredMatchesNumber.argtypes = [inst, u32]
     L.vksift_ext_getFilteredMatchesNumber.restype = u32
     L.vksift_ext_downloadFilteredMatches.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_verifyHomography.argtypes = [inst, u32, C.c_float, C.c_uint64]
+    L.vksift_ext_verifyHomography.restype = None
+    L.vksift_ext_getHomography.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_getHomography.restype = None
+    L.vksift_ext_downloadInlierMask.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_downloadInlierMask.restype = None
+    L.vksift_ext_getVerifyTime.argtypes = [inst]
+    L.vksift_ext_getVerifyTime.restype = C.c_float
     L.vksift_ext_setProfiling.argtypes = [inst, C.c_bool]
     L.vksift_ext_getDetectTimings.argtypes = [inst, C.POINTER(vksift_ext_DetectTimings)]
     L.vksift_ext_getAccumulatedDetectTimings.argtypes = [inst, C.POINTER(vksift_ext_DetectTimings), C.POINTER(u32), C.c_bool]
@@ -176,6 +185,11 @@ def lib():
     L.vksift_hip_match_2nn_desc.restype = C.c_int
     L.vksift_hip_gather_descriptors.argtypes = [C.c_void_p, u32, C.c_void_p, C.c_void_p]
     L.vksift_hip_gather_descriptors.restype = C.c_int
+    L.vksift_hip_ransac_scratch_u32.argtypes = [u32, u32]
+    L.vksift_hip_ransac_scratch_u32.restype = C.c_size_t
+    L.vksift_hip_ransac_homography.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, u32, u32, u32, u32, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p,
+                                               C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.vksift_hip_ransac_homography.restype = C.c_int
     _lib = L
     return L
 
@@ -259,6 +273,30 @@ def gen_synthetic_descriptors(seed, rows):
     out = np.empty((rows, 128), np.uint8)
     lib().vksift_ext_genSyntheticDescriptors(seed, rows, out.ctypes.data)
     return out
+
+
+def ransac_homography(corr, n, nb_hypotheses, threshold_px, seed, scratch_u32=None):
+    """vksift_hip_ransac_homography on torch tensors: corr float32 [nslots, max_n, 4] and n int32 [nslots] on the GPU. Returns (error code,
+    results as a HOMOGRAPHY_DTYPE array, masks uint8 [nslots, max_n]); on an error nothing was launched and the other two are None.
+    scratch_u32: words of scratch to hand over instead of what vksift_hip_ransac_scratch_u32 asks for (the refusal tests)."""
+    import torch
+
+    assert corr.is_cuda and corr.dtype == torch.float32 and corr.is_contiguous() and corr.dim() == 3 and corr.shape[2] == 4
+    assert n.is_cuda and n.dtype == torch.int32 and n.is_contiguous() and n.numel() == corr.shape[0]
+    nslots, max_n = int(corr.shape[0]), int(corr.shape[1])
+    need = int(lib().vksift_hip_ransac_scratch_u32(nslots, nb_hypotheses))
+    words = need if scratch_u32 is None else scratch_u32
+    # poisoned: the scratch needs no initialisation, the outputs are written for every slot
+    scratch = torch.full((max(words, 1),), -1, dtype=torch.int32, device=corr.device)
+    results = torch.full((nslots, 13), -1, dtype=torch.int32, device=corr.device)
+    masks = torch.full((nslots, max(max_n, 1)), 0x55, dtype=torch.uint8, device=corr.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    err = lib().vksift_hip_ransac_homography(corr.data_ptr(), max_n * 16, n.data_ptr(), 1, max_n, nslots, nb_hypotheses, threshold_px, seed, results.data_ptr(),
+                                             masks.data_ptr(), max(max_n, 1), scratch.data_ptr(), words, stream)
+    torch.cuda.synchronize()
+    if err:
+        return err, None, None
+    return 0, results.cpu().numpy().view(np.uint8).reshape(nslots, 52).copy().view(HOMOGRAPHY_DTYPE).reshape(nslots), masks.cpu().numpy()
 
 
 class Instance:
@@ -357,6 +395,29 @@ class Instance:
             lib().vksift_ext_downloadFilteredMatches(self._h, pair, out.ctypes.data)
             _check_pending()
         return out
+
+    def verifyHomography(self, nb_hypotheses=1024, threshold_px=2.5, seed=0):
+        """RANSAC homography of every pair of the last matchFeaturesFiltered call, on the GPU (vksift_ext_verifyHomography)."""
+        lib().vksift_ext_verifyHomography(self._h, nb_hypotheses, threshold_px, seed)
+        _check_pending()
+
+    def getHomography(self, pair=0):
+        """structured scalar (HOMOGRAPHY_DTYPE): H 3x3 float32 (pixels of A -> B, H[2, 2] == 1), nb_matches, nb_inliers, best_hypothesis, valid"""
+        out = np.zeros(1, HOMOGRAPHY_DTYPE)
+        lib().vksift_ext_getHomography(self._h, pair, out.ctypes.data)
+        _check_pending()
+        return out[0]
+
+    def downloadInlierMask(self, pair=0):
+        n = lib().vksift_ext_getFilteredMatchesNumber(self._h, pair)
+        _check_pending()
+        out = np.zeros(n, np.uint8)
+        lib().vksift_ext_downloadInlierMask(self._h, pair, out.ctypes.data)
+        _check_pending()
+        return out.astype(bool)
+
+    def getVerifyTime(self):
+        return lib().vksift_ext_getVerifyTime(self._h)
 
     def getMatchesNumberBatch(self, pair):
         n = lib().vksift_ext_getMatchesNumberBatch(self._h, pair)

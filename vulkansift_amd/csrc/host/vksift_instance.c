@@ -369,6 +369,16 @@ void vksift_destroyInstance(vksift_Instance *instance_ptr)
   vksift_hip_free(inst->d_filtered);
   vksift_hip_free(inst->d_filtered_n);
   vksift_hip_host_free(inst->h_filtered_n);
+  free(inst->filt_ids);
+  vksift_hip_free(inst->d_corr);
+  vksift_hip_free(inst->d_vmask);
+  vksift_hip_free(inst->d_vres);
+  vksift_hip_free(inst->d_vscratch);
+  vksift_hip_host_free(inst->h_vres);
+  vksift_hip_host_free(inst->h_vtab);
+  vksift_hip_event_destroy(inst->ev_vtab);
+  vksift_hip_event_destroy(inst->ev_v[0]);
+  vksift_hip_event_destroy(inst->ev_v[1]);
   vksift_hip_host_free(inst->h_match_n);
   vksift_hip_host_free(inst->h_matches);
   free(inst->bufs);

@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -183,6 +183,20 @@ struct vksift_Instance_T
   uint32_t *d_filtered_n, *h_filtered_n;
   uint64_t filtered_slot_stride;
   uint32_t filtered_slots_used;
+  /* geometric verification (vksift_ext_verifyHomography, vksift_verify.c): the pairs of the last filtered matching, and scratch allocated on first use */
+  uint32_t *filt_ids;       /* 2 * batch_cap: buffers A then buffers B of the last vksift_ext_matchFeaturesFiltered */
+  float *d_corr;            /* per slot: filtered_slot_stride bytes of {xa, ya, xb, yb} */
+  uint8_t *d_vmask;         /* per slot: vmask_slot_stride bytes */
+  uint64_t vmask_slot_stride;
+  uint32_t *d_vres, *h_vres; /* 13 words (vksift_ext_Homography) per slot; the host copy is posted like h_filtered_n */
+  uint32_t *d_vscratch;
+  size_t vscratch_u32;
+  uint32_t *h_vtab;         /* mapped pinned memory read by the gather launch: 4 words per slot, then the section tables (33 words each) */
+  vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab */
+  bool vtab_pending;
+  uint32_t verify_slots_used;
+  vksift_hip_event ev_v[2];
+  bool verify_timing_valid;
   uint64_t desc_slot_stride, match_slot_stride; /* bytes */
   uint64_t redo_slot_stride;                    /* u32 elements */
   uint32_t match_slots_used;
@@ -333,5 +347,6 @@ VKSIFT_INTERNAL uint32_t buffer_counts(vksift_Instance inst, uint32_t buf, uint3
 /* vksift_match.c */
 VKSIFT_INTERNAL MatchScratch fwd_scratch(vksift_Instance inst);
 VKSIFT_INTERNAL int refresh_match_cache(vksift_Instance inst, const uint32_t *ids, uint32_t count);
+VKSIFT_INTERNAL void wait_match(vksift_Instance inst);
 
 #endif

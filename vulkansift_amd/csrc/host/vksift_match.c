@@ -165,6 +165,7 @@ static bool ensure_filter_scratch(vksift_Instance inst)
   ENSURE_D(inst->d_filtered, inst->filtered_slot_stride * bc);
 #undef ENSURE_D
   ok = ok && (inst->h_filtered_n != NULL || (inst->h_filtered_n = vksift_hip_host_malloc(sizeof(uint32_t) * bc)) != NULL);
+  ok = ok && (inst->filt_ids != NULL || (inst->filt_ids = (uint32_t *)malloc(sizeof(uint32_t) * 2u * bc)) != NULL);
   return ok;
 }
 
@@ -199,6 +200,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
   if (inst->desc_start_valid && vksift_hip_tune_get(VKSIFT_TUNE_PYR_GATE) == 1)
     vksift_hip_event_record(inst->ev_desc_start, inst->stream); /* experiment: the next scale-space behind this matching, not beside it */
   inst->filtered_slots_used = 0;
+  inst->verify_slots_used = 0;
   inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
   if (filter)
   {
@@ -221,6 +223,9 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
     }
     HIP_CHECK(vksift_hip_post_words(inst->h_filtered_n, inst->d_filtered_n, count, inst->stream), "filtered count read-back");
     inst->filtered_slots_used = count;
+    /* the pairs, for vksift_ext_verifyHomography */
+    memcpy(inst->filt_ids, ids_a, sizeof(uint32_t) * count);
+    memcpy(inst->filt_ids + inst->batch_cap, ids_b, sizeof(uint32_t) * count);
   }
   vksift_hip_range_pop();
   range_open = false;
@@ -265,7 +270,7 @@ void vksift_ext_matchFeaturesFiltered(vksift_Instance instance, uint32_t count, 
   match_impl(instance, gpu_buffer_ids_A, gpu_buffer_ids_B, count, "vksift_ext_matchFeaturesFiltered()", true, ratio, cross_check);
 }
 
-static void wait_match(vksift_Instance inst)
+void wait_match(vksift_Instance inst)
 {
   vksift_hip_set_device(inst->device);
   defer_sync(inst);

@@ -1,0 +1,170 @@
+/*
+ * vksift_verify.c — geometric verification of the last filtered matching (vksift_ext_verifyHomography and its accessors). No counterpart
+ * in the reference: its callers download matches and features and run a CPU RANSAC per pair. The model is named by the entry point
+ * only; everything else here (scratch, pair tables, posting, accessors) would serve a second model unchanged.
+ */
+#include "vksift_internal.h"
+
+#define VERIFY_RES_WORDS 13u /* sizeof(vksift_ext_Homography) / 4 */
+#define VERIFY_LAYOUT_WORDS 33u
+#define VERIFY_MAX_HYPOTHESES 65536u
+
+_Static_assert(sizeof(vksift_ext_Homography) == 4u * VERIFY_RES_WORDS, "vksift_ext_Homography is the kernel's 13-word result record");
+
+/* correspondences, masks, results and reduction keys of batch_cap pairs; allocated by the first verification (detect-only and match-only
+ * users never pay), each block only if it does not exist yet so that a call that ran out of memory is retried without leaking */
+static bool ensure_verify_scratch(vksift_Instance inst)
+{
+  const uint32_t bc = inst->batch_cap;
+  inst->vmask_slot_stride = ((uint64_t)inst->cfg.max_nb_sift_per_buffer + 255u) & ~(uint64_t)255u;
+  inst->vscratch_u32 = vksift_hip_ransac_scratch_u32(bc, VERIFY_MAX_HYPOTHESES);
+  bool ok = true;
+#define ENSURE_D(ptr, bytes) ok = ok && ((ptr) != NULL || ((ptr) = vksift_hip_malloc(bytes)) != NULL)
+#define ENSURE_H(ptr, bytes) ok = ok && ((ptr) != NULL || ((ptr) = vksift_hip_host_malloc(bytes)) != NULL)
+  ENSURE_D(inst->d_corr, inst->filtered_slot_stride * bc);
+  ENSURE_D(inst->d_vmask, inst->vmask_slot_stride * bc);
+  ENSURE_D(inst->d_vres, sizeof(uint32_t) * VERIFY_RES_WORDS * bc);
+  ENSURE_D(inst->d_vscratch, sizeof(uint32_t) * inst->vscratch_u32);
+  ENSURE_H(inst->h_vres, sizeof(uint32_t) * VERIFY_RES_WORDS * bc);
+  ENSURE_H(inst->h_vtab, sizeof(uint32_t) * ((size_t)4u * bc + (size_t)VERIFY_LAYOUT_WORDS * 2u * bc));
+#undef ENSURE_D
+#undef ENSURE_H
+  if (!inst->ev_vtab)
+    inst->ev_vtab = vksift_hip_event_create();
+  for (int i = 0; i < 2; i++)
+    if (!inst->ev_v[i])
+      inst->ev_v[i] = vksift_hip_event_create();
+  return ok && inst->ev_vtab && inst->ev_v[0] && inst->ev_v[1];
+}
+
+/* layout word of a buffer for vksift_hip_gather_correspondences: its section table is appended to `layouts` unless an equal one is there */
+static uint32_t layout_word(const BufferInfo *b, uint32_t *layouts, uint32_t *nlay)
+{
+  if (b->nb_sections == 0)
+    return 0x80000000u | b->nb_stored; /* uploaded: one dense run of records */
+  uint32_t t[VERIFY_LAYOUT_WORDS] = {0};
+  t[0] = b->nb_sections;
+  for (uint32_t o = 0; o < b->nb_sections; o++)
+    t[1u + o] = b->sec_off[o], t[17u + o] = b->sec_cap[o];
+  for (uint32_t k = *nlay; k-- > 0;) /* the last one first: the buffers of a batched detection all share one */
+    if (memcmp(layouts + (size_t)k * VERIFY_LAYOUT_WORDS, t, sizeof(t)) == 0)
+      return k;
+  memcpy(layouts + (size_t)*nlay * VERIFY_LAYOUT_WORDS, t, sizeof(t));
+  return (*nlay)++;
+}
+
+void vksift_ext_verifyHomography(vksift_Instance instance, uint32_t nb_hypotheses, float threshold_px, uint64_t seed)
+{
+  vksift_Instance inst = instance;
+  bool range_open = false;
+  vksift_hip_set_device(inst->device);
+  defer_sync(inst);
+  const uint32_t count = inst->filtered_slots_used;
+  if (count == 0 || nb_hypotheses == 0 || nb_hypotheses > VERIFY_MAX_HYPOTHESES || !(threshold_px > 0.f) || !isfinite(threshold_px))
+  {
+    logError(LOG_TAG, "vksift_ext_verifyHomography() error: invalid input.");
+    inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
+    return;
+  }
+  if (!ensure_verify_scratch(inst))
+  {
+    logError(LOG_TAG, "vksift_ext_verifyHomography() error: out of device memory for the verification scratch.");
+    goto gpu_error;
+  }
+  /* the pair table is read by the gather launch out of pinned memory: the previous verification's launch must be through with it */
+  if (inst->vtab_pending)
+  {
+    HIP_CHECK(vksift_hip_event_sync(inst->ev_vtab), "event synchronisation");
+    inst->vtab_pending = false;
+  }
+  {
+    uint32_t *layouts = inst->h_vtab + (size_t)4u * inst->batch_cap, nlay = 0;
+    for (uint32_t i = 0; i < count; i++)
+    {
+      const uint32_t a = inst->filt_ids[i], b = inst->filt_ids[inst->batch_cap + i];
+      uint32_t *t = inst->h_vtab + (size_t)4u * i;
+      t[0] = a, t[1] = b;
+      t[2] = layout_word(&inst->bufs[a], layouts, &nlay);
+      t[3] = layout_word(&inst->bufs[b], layouts, &nlay);
+    }
+  }
+  if (inst->profiling)
+    vksift_hip_event_record(inst->ev_v[0], inst->stream);
+  vksift_hip_range_push("Verification");
+  range_open = true;
+  HIP_CHECK(vksift_hip_gather_correspondences(inst->d_feats, inst->buf_stride, inst->d_found, VKSIFT_MAX_OCTAVES, inst->h_vtab,
+                                              inst->h_vtab + (size_t)4u * inst->batch_cap, inst->d_filtered, inst->filtered_slot_stride, inst->d_filtered_n,
+                                              inst->cfg.max_nb_sift_per_buffer, count, inst->d_corr, inst->filtered_slot_stride, inst->stream),
+            "correspondence gather");
+  HIP_CHECK(vksift_hip_event_record(inst->ev_vtab, inst->stream), "event record");
+  inst->vtab_pending = true;
+  HIP_CHECK(vksift_hip_ransac_homography(inst->d_corr, inst->filtered_slot_stride, inst->d_filtered_n, 1, inst->cfg.max_nb_sift_per_buffer, count, nb_hypotheses,
+                                         threshold_px, seed, (uint8_t *)inst->d_vres, inst->d_vmask, inst->vmask_slot_stride, inst->d_vscratch, inst->vscratch_u32,
+                                         inst->stream),
+            "RANSAC");
+  HIP_CHECK(vksift_hip_post_words(inst->h_vres, inst->d_vres, (size_t)VERIFY_RES_WORDS * count, inst->stream), "verification read-back");
+  vksift_hip_range_pop();
+  range_open = false;
+  if (inst->profiling)
+  {
+    vksift_hip_event_record(inst->ev_v[1], inst->stream);
+    inst->verify_timing_valid = true;
+  }
+  /* same contract as the matching it follows: the accessors wait for ev_match, the pairs' buffers stay busy until it has passed */
+  (void)match_running(inst);
+  HIP_CHECK(vksift_hip_event_record(inst->ev_match, inst->stream), "event record");
+  inst->match_pending = true;
+  for (uint32_t i = 0; i < count; i++)
+    inst->match_busy[inst->filt_ids[i]] = inst->match_busy[inst->filt_ids[inst->batch_cap + i]] = true;
+  inst->verify_slots_used = count;
+  return;
+gpu_error:
+  if (range_open)
+    vksift_hip_range_pop();
+  logError(LOG_TAG, "vksift_ext_verifyHomography() error: Failed to start the verification pipeline.");
+  inst->error_cb(VKSIFT_VULKAN_ERROR);
+}
+
+void vksift_ext_getHomography(vksift_Instance instance, uint32_t pair, vksift_ext_Homography *out)
+{
+  wait_match(instance);
+  if (pair >= instance->verify_slots_used || out == NULL)
+  {
+    logError(LOG_TAG, "vksift_ext_getHomography() error: invalid input.");
+    instance->error_cb(VKSIFT_INVALID_INPUT_ERROR);
+    return;
+  }
+  memcpy(out, instance->h_vres + (size_t)VERIFY_RES_WORDS * pair, sizeof(*out));
+}
+
+void vksift_ext_downloadInlierMask(vksift_Instance instance, uint32_t pair, uint8_t *mask)
+{
+  vksift_Instance inst = instance;
+  wait_match(inst);
+  if (pair >= inst->verify_slots_used)
+  {
+    logError(LOG_TAG, "vksift_ext_downloadInlierMask() error: invalid input.");
+    inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
+    return;
+  }
+  const uint32_t n = inst->h_filtered_n[pair];
+  if (n > 0)
+  {
+    HIP_CHECK(vksift_hip_memcpy_d2h(mask, inst->d_vmask + (uint64_t)pair * inst->vmask_slot_stride, n, inst->dl_stream), "inlier mask read-back");
+    HIP_CHECK(vksift_hip_stream_sync(inst->dl_stream), "inlier mask read-back");
+  }
+  return;
+gpu_error:
+  logError(LOG_TAG, "vksift_ext_downloadInlierMask() error when downloading the inlier mask from GPU memory.");
+  inst->error_cb(VKSIFT_VULKAN_ERROR);
+}
+
+float vksift_ext_getVerifyTime(vksift_Instance instance)
+{
+  defer_sync(instance);
+  if (!instance->profiling || !instance->verify_timing_valid)
+    return -1.f;
+  vksift_hip_set_device(instance->device);
+  wait_all(instance);
+  return vksift_hip_event_elapsed_ms(instance->ev_v[0], instance->ev_v[1]);
+}
