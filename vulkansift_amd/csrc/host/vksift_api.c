@@ -19,7 +19,7 @@
  * Built as C with -fexceptions: user error callbacks may throw through these frames
  * (vulkansift_types.h:148-152 of the reference).
  *
- * This file: defaults, validation, runtime life-cycle. vksift_instance.c: instances, layout, synchronisation helpers.
+ * This file: defaults, validation, runtime life-cycle. vksift_instance.c: instances, switches, synchronisation helpers. vksift_mem.c: layout, and every block, stream and event of an instance.
  * vksift_detect.c: the detection pipeline (vksift_stage.c: image staging, vksift_defer.c: deferred submission). vksift_buffers.c: feature accessors + scale-space inspection.
  * vksift_match.c: matching. vksift_ext.c: extensions. Shared private definitions: vksift_internal.h.
  */

@@ -85,9 +85,7 @@ static bool download_from_batch(vksift_Instance inst, vksift_Feature *feats_ptr,
      * cached (for another detection) is gone from here on, and the cache is valid again only once every copy and event is queued */
     inst->dl_valid = false;
     /* every buffer of the batch shares the section table of `b` (one resolution per batched detection) */
-    if (!inst->dl_row)
-      inst->dl_row = (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)inst->cfg.sift_buffer_count + 1u));
-    if (!inst->dl_row)
+    if (!mem_ensure(&inst->dl_row, sizeof(uint32_t) * ((size_t)inst->cfg.sift_buffer_count + 1u), MEM_HEAP))
       return false;
     uint32_t rows = 0, max_rows = 0;
     for (uint32_t i = 0; i < count; i++)
@@ -104,24 +102,8 @@ static bool download_from_batch(vksift_Instance inst, vksift_Feature *feats_ptr,
     }
     inst->dl_row[count] = rows;
     const size_t bytes = (size_t)rows * FEAT_BYTES;
-    /* the staging pair follows the workload down as well as up: a block more than four times what this detection needs (and
-     * beyond 64 MB) is released instead of being kept for the life of the instance */
-    if (bytes > inst->dl_cap || (inst->dl_cap > ((size_t)64 << 20) && inst->dl_cap / 4u > bytes + 4096u))
-    {
-      vksift_hip_free(inst->d_dl);
-      vksift_hip_host_free(inst->h_dl);
-      const size_t cap = bytes + bytes / 4u + 4096u;
-      inst->d_dl = (uint8_t *)vksift_hip_malloc(cap);
-      inst->h_dl = (uint8_t *)vksift_hip_host_malloc(cap);
-      inst->dl_cap = (inst->d_dl && inst->h_dl) ? cap : 0;
-      if (!inst->dl_cap)
-      {
-        vksift_hip_free(inst->d_dl);
-        vksift_hip_host_free(inst->h_dl);
-        inst->d_dl = inst->h_dl = NULL;
-        return false;
-      }
-    }
+    if (!mem_fit_staging(inst, bytes, true)) /* (follows the workload down as well as up) */
+      return false;
     uint32_t ids[64];
     for (uint32_t i0 = 0; i0 < count; i0 += 64)
     {
@@ -230,24 +212,9 @@ static bool download_one_packed(vksift_Instance inst, vksift_Feature *feats_ptr,
   const size_t bytes = (size_t)n * FEAT_BYTES;
   if (bytes > ((size_t)64 << 20))
     return false; /* large single detections: the section copies stream at the bus rate anyway */
-  if (bytes > inst->dl_cap)
-  {
-    inst->dl_valid = false; /* the batch cache lives in the same staging pair */
-    vksift_hip_free(inst->d_dl);
-    vksift_hip_host_free(inst->h_dl);
-    const size_t cap = bytes + bytes / 4u + 4096u;
-    inst->d_dl = (uint8_t *)vksift_hip_malloc(cap);
-    inst->h_dl = (uint8_t *)vksift_hip_host_malloc(cap);
-    inst->dl_cap = (inst->d_dl && inst->h_dl) ? cap : 0;
-    if (!inst->dl_cap)
-    {
-      vksift_hip_free(inst->d_dl);
-      vksift_hip_host_free(inst->h_dl);
-      inst->d_dl = inst->h_dl = NULL;
-      return false;
-    }
-  }
-  inst->dl_valid = false;
+  inst->dl_valid = false; /* the batch cache lives in the same staging pair */
+  if (!mem_fit_staging(inst, bytes, false))
+    return false;
   const uint32_t zero = 0;
   if (vksift_hip_pack_features(inst->d_feats, inst->buf_stride, &buf, &zero, 1, b->nb_sections, b->sec_off, b->sec_cap, inst->d_found, VKSIFT_MAX_OCTAVES,
                                inst->d_dl, n, NULL, inst->dl_stream) != 0)

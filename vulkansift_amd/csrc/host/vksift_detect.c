@@ -295,14 +295,12 @@ static int prepare_detection(DetectCtx *c)
     if (!inst->h_post[0])
     {
       const size_t cap = (size_t)inst->cfg.max_nb_sift_per_buffer * FEAT_BYTES + 4096u;
-      inst->h_post[0] = (uint8_t *)vksift_hip_host_malloc(cap);
-      inst->h_post[1] = (uint8_t *)vksift_hip_host_malloc(cap);
-      inst->post_cap = (inst->h_post[0] && inst->h_post[1]) ? cap : 0;
+      const bool p0 = mem_ensure(&inst->h_post[0], cap, MEM_PINNED), p1 = mem_ensure(&inst->h_post[1], cap, MEM_PINNED);
+      inst->post_cap = (p0 && p1) ? cap : 0;
       if (!inst->post_cap)
       {
-        vksift_hip_host_free(inst->h_post[0]);
-        vksift_hip_host_free(inst->h_post[1]);
-        inst->h_post[0] = inst->h_post[1] = NULL;
+        mem_release(&inst->h_post[0], MEM_PINNED);
+        mem_release(&inst->h_post[1], MEM_PINNED);
         inst->post_enabled = false;
       }
     }

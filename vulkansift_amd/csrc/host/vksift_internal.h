@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -96,6 +96,8 @@ typedef struct
   uint64_t alg_bytes, scan_bytes;
 } ProfSet;
 
+/* Fields grouped by who uses them. Every pointer to device (d_), pinned (h_) or heap memory and every event and stream of the struct is
+ * listed once in the tables of vksift_mem.c (blocks[], handles[]), which creation, growth and release walk. */
 struct vksift_Instance_T
 {
   vksift_Config cfg;
@@ -108,8 +110,11 @@ struct vksift_Instance_T
   uint32_t batch_cap;      /* capacity the instance was created with: match slots, and the bound of the vksift_ext_*Batch entries */
   uint32_t det_cap;        /* images one detection launch sequence can take (>= batch_cap): input staging, scale-space, extraction scratch.
                             * Grows when a caller of the plain API turns out to batch (deferred submission, below) */
+  /* blur taps */
+  float taps[(VKSIFT_MAX_SCALES + 3) * VKSIFT_MAX_TAPS];
+  uint32_t ntaps[VKSIFT_MAX_SCALES + 3];
 
-  /* Deferred submission of vksift_detectFeatures (vksift_defer.c: defer_detect). The reference's caller hands over ONE image per call
+  /* ---- deferred submission of vksift_detectFeatures (vksift_defer.c: defer_detect). The reference's caller hands over ONE image per call
    * (vulkansift.c:315-344); a caller that issues several such calls in a row, into consecutive SIFT buffers, before it asks for
    * anything gets them launched as ONE batched detection: the call stages its image in the pinned input block and returns, and the
    * batch is launched by the first call that needs a result (every other entry point: defer_sync) or when it is full. The first
@@ -123,62 +128,87 @@ struct vksift_Instance_T
   bool defer_grow;         /* the last deferred batch filled det_cap: double it before the next one is staged */
   uint64_t defer_batches, defer_images; /* statistics (vksift_ext_getDeferredStats) */
 
-  /* blur taps */
-  float taps[(VKSIFT_MAX_SCALES + 3) * VKSIFT_MAX_TAPS];
-  uint32_t ntaps[VKSIFT_MAX_SCALES + 3];
-
-  /* current scale-space */
-  uint32_t cur_w, cur_h, cur_batch;
-  uint32_t shown_img;      /* image of the last launch the scale-space accessors show: the last one of a batch launched from staged
-                            * vksift_detectFeatures calls (the reference shows the last image detected), image 0 otherwise */
-  PyrLayout lay;
-
-  /* device memory */
-  float *d_pyr;            /* pyramid storage of the current detection (= d_pyr_buf[pyr_cur]); texel offsets scale with pyr_texel_bytes() */
-  uint32_t place_n;        /* candidate ranges timed by place_pyramid_buffers (0: plain allocation), their rates, the chosen ones */
-  float place_gbps[8];
-  uint32_t place_chosen[2];
-  float *d_pyr_buf[2];     /* the scale-space buffer(s): ONE by default (the overlap gate makes a second unnecessary), two with VKSIFT_PYR_PINGPONG=2 */
-  int pyr_cur;
+  /* ---- how a detection is scheduled (read_switches, vksift_instance.c) */
   bool pyr_pingpong;       /* overlap mode: the scale-space of a detection is built on its own stream, beside what is queued behind the previous detection's descriptors */
   uint32_t overlap_min_count; /* ... for detections of at least this many images (1; 8 on an instance whose capacity grew by deferred submission) */
   bool overlap_forced;     /* VKSIFT_PYR_PINGPONG was given: the mode is the caller's */
   uint32_t pyr_nbuf;       /* scale-space buffers of the instance: 1, or 2 with VKSIFT_PYR_PINGPONG=2 (the next scale-space may then start before the previous detection's readers are done) */
-  bool pyr_free_valid[2];
-  uint64_t pyr_img_stride; /* floats reserved per image */
-  uint8_t *d_input, *h_input;
-  uint8_t *d_feats;
-  uint64_t buf_stride; /* bytes */
-  uint32_t *d_found, *h_found;
-  uint64_t *d_seg_mask;
-  uint32_t *d_seg_off;
-  uint64_t seg_cap; /* elements reserved per image */
-  uint32_t *d_cand_xy, *d_cand_flag, *d_cand_n;
-  uint64_t cand_cap; /* candidates reserved per image */
-  float *d_ori_ang;
-  uint32_t *d_ori_cnt;
-  uint64_t ori_cap; /* keypoints reserved per image */
-  float *d_desc_fp;
-  uint32_t desc_fp_len;
-  uint8_t *d_matches, *h_matches;
-  uint32_t *d_redo;        /* per match slot: row flags for the exact scalar replay (k_match_redo) */
-  /* per SIFT buffer: the matcher's view of it (dense descriptor rows in download order, shifted norms, row count), filled by a
-   * device-side gather when the buffer is first matched after a detection / upload */
-  uint8_t *d_cache_desc;
-  uint32_t *d_cache_norm, *d_cache_n;
-  uint64_t cache_norm_stride; /* u32 elements */
-  bool *cache_valid;
-  bool *cache_queued;      /* scratch of refresh_match_cache: the buffer is already in the current gather pass */
-  uint32_t *d_match_partial; /* partial top-2 lists of the stream-decomposed single-pair matcher (NULL when max_nb <= VKSIFT_HIP_MATCH_SMALL_NA) */
-  uint32_t *d_match_n, *h_match_n; /* per match slot: {N_A, N_B, spare, spare} of the last matching pipeline */
-  /* filtered matching (vksift_ext_matchFeaturesFiltered): scratch of the reverse (B->A) matching and the survivors; allocated on first use */
-  MatchScratch rev;
+  /* small detections (one image): the scales behind scale S of an octave are off the path to the next octave; they run on the
+   * (otherwise idle) scale-space stream beside the octaves below — forked per octave, joined in front of the keypoint stages */
+  int fork_streams;              /* branch streams of a forked detection: 1 (two measured no faster in stream order, slower in a graph) */
+  bool fork_scales; /* VKSIFT_FORK_SCALES (default 1) */
+  uint64_t fork_max_pixels; /* ... for detections of at most this many input pixels (16 Mpx) */
+  uint32_t lds_chain_max; /* largest plane (texels) an octave of the chain may have: VKSIFT_LDS_CHAIN_MAX, at most 19200 (the LDS) */
+  bool lds_chain_refuse; /* VKSIFT_LDS_CHAIN=refuse: test hook, the chain launch declines and the per-scale launches take over */
+  bool lds_chain; /* VKSIFT_LDS_CHAIN (default 1): the trailing octaves that fit the LDS are built by one launch (vksift_hip_octave_chain) */
+  bool alt_order; /* always on: launches of a blur chain alternate their dispatch direction (vksift_hip_Plane::reverse) */
   /* hipGraph replay of the detection launch sequence (latency of small workloads is launch bound) */
   bool use_graphs;
   uint64_t graph_max_pixels; /* detections of at most this many input pixels (batch total) are replayed from a graph */
   DetectGraph graphs[VKSIFT_GRAPH_CACHE];
   uint64_t graph_stamp;
   uint32_t graph_miss_run; /* consecutive cache misses: a caller that never repeats a key gets no replays, only capture costs */
+
+  /* ---- current scale-space */
+  uint32_t cur_w, cur_h, cur_batch;
+  uint32_t shown_img;      /* image of the last launch the scale-space accessors show: the last one of a batch launched from staged
+                            * vksift_detectFeatures calls (the reference shows the last image detected), image 0 otherwise */
+  PyrLayout lay;
+  float *d_pyr;            /* pyramid storage of the current detection (= d_pyr_buf[pyr_cur]); texel offsets scale with pyr_texel_bytes() */
+  int pyr_cur;
+  bool pyr_free_valid[2];
+
+  /* ---- detection scratch: re-allocated by resize_detect_scratch when the per-image strides or the capacity grow */
+  float *d_pyr_buf[2];     /* the scale-space buffer(s): ONE by default (the overlap gate makes a second unnecessary), two with VKSIFT_PYR_PINGPONG=2 */
+  uint32_t place_n;        /* candidate ranges timed by place_pyramid_buffers (0: plain allocation), their rates, the chosen ones */
+  float place_gbps[8];
+  uint32_t place_chosen[2];
+  uint64_t pyr_img_stride; /* floats reserved per image */
+  uint64_t *d_seg_mask;    /* per stride */
+  uint32_t *d_seg_off;
+  uint64_t seg_cap; /* elements reserved per image */
+  uint32_t *d_cand_xy, *d_cand_flag;
+  uint64_t cand_cap; /* candidates reserved per image */
+  uint8_t *d_input, *h_input; /* per capacity */
+  uint32_t *d_cand_n;
+  float *d_ori_ang;
+  uint32_t *d_ori_cnt;
+  uint64_t ori_cap; /* keypoints reserved per image */
+
+  /* ---- the SIFT buffers (fixed at creation) */
+  uint8_t *d_feats;
+  uint64_t buf_stride; /* bytes */
+  uint32_t *d_found, *h_found;
+  BufferInfo *bufs;
+  float *d_desc_fp;
+  uint32_t desc_fp_len;
+
+  /* ---- matcher */
+  uint8_t *d_matches, *h_matches; /* (h_matches: pinned, the packed download of a batched matching, allocated by it) */
+  uint32_t *d_redo;        /* per match slot: row flags for the exact scalar replay (k_match_redo) */
+  uint32_t *d_match_n, *h_match_n; /* per match slot: {N_A, N_B, spare, spare} of the last matching pipeline */
+  uint64_t desc_slot_stride, match_slot_stride; /* bytes */
+  uint64_t redo_slot_stride;                    /* u32 elements */
+  uint32_t match_slots_used;
+  /* per SIFT buffer: the matcher's view of it (dense descriptor rows in download order, shifted norms, row count), filled by a
+   * device-side gather when the buffer is first matched after a detection / upload; desc, norm and the partial lists: first matching */
+  uint8_t *d_cache_desc;
+  uint32_t *d_cache_norm, *d_cache_n;
+  uint64_t cache_norm_stride; /* u32 elements */
+  bool *cache_valid;
+  bool *cache_queued;      /* scratch of refresh_match_cache: the buffer is already in the current gather pass */
+  uint32_t *d_match_partial; /* partial top-2 lists of the stream-decomposed single-pair matcher (NULL when max_nb <= VKSIFT_HIP_MATCH_SMALL_NA) */
+  bool match_pending;
+  bool *match_busy; /* per SIFT buffer: read by the matching pipeline in flight (all pairs of a batched call) */
+  uint32_t curr_nb_matches;
+  /* packed download of the records of a batched matching (h_matches) */
+  size_t md_cap, md_pitch;
+  bool md_valid;
+  bool md_asked, md_direct;  /* (asked once per matching) the caller's destination of this matching's records is page-locked: per-pair DMA, no packed copy */
+  uint32_t md_hits;
+
+  /* ---- filtered matching (vksift_ext_matchFeaturesFiltered): scratch of the reverse (B->A) matching and the survivors; allocated on first use */
+  MatchScratch rev;
   uint8_t *d_filtered;
   uint32_t *d_filtered_n, *h_filtered_n;
   uint64_t filtered_slot_stride;
@@ -192,85 +222,65 @@ struct vksift_Instance_T
   uint32_t *d_vscratch;
   size_t vscratch_u32;
   uint32_t *h_vtab;         /* mapped pinned memory read by the gather launch: 4 words per slot, then the section tables (33 words each) */
-  vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab */
   bool vtab_pending;
   uint32_t verify_slots_used;
-  vksift_hip_event ev_v[2];
   bool verify_timing_valid;
-  uint64_t desc_slot_stride, match_slot_stride; /* bytes */
-  uint64_t redo_slot_stride;                    /* u32 elements */
-  uint32_t match_slots_used;
-  vksift_hip_event ev_staging;      /* host image staging buffer consumed by the H2D copy */
-  vksift_hip_event ev_up[VKSIFT_UP_GROUPS]; /* group g of a batch has arrived in d_input */
-  bool staging_pending;
-  BufferInfo *bufs;
 
-  vksift_hip_stream stream;
-  vksift_hip_stream pyr_stream; /* scale-space construction when detections overlap (two pyramid buffers) */
-  vksift_hip_stream up_stream;  /* host-to-device copies of the input images */
-  vksift_hip_stream dl_stream;  /* result downloads: the accessors have waited for the pipeline that produced what they read; their copies must
-                                 * not queue behind a LATER detection already on the instance stream (a caller that pipelines) */
-  vksift_hip_event ev_pyr_done;
-  vksift_hip_event ev_pyr_free[2]; /* last reader of pyramid buffer i has finished */
-  vksift_hip_event ev_desc_start;  /* the previous detection's descriptor stage has been issued up to here: the next scale-space may start */
-  bool desc_start_valid;
-  vksift_hip_event ev_input_free;  /* the last reader of d_input (seed pass of the most recent detection) has run */
-  bool input_free_valid;
-  /* small detections (one image): the scales behind scale S of an octave are off the path to the next octave; they run on the
-   * (otherwise idle) scale-space stream beside the octaves below — forked per octave, joined in front of the keypoint stages */
-  vksift_hip_event ev_fork[VKSIFT_MAX_OCTAVES], ev_join[2];
-  vksift_hip_stream side_stream; /* second branch stream (the first is pyr_stream) */
-  int fork_streams;              /* branch streams of a forked detection: 1 (two measured no faster in stream order, slower in a graph) */
-  bool fork_scales; /* VKSIFT_FORK_SCALES (default 1) */
-  uint64_t fork_max_pixels; /* ... for detections of at most this many input pixels (16 Mpx) */
-  uint32_t lds_chain_max; /* largest plane (texels) an octave of the chain may have: VKSIFT_LDS_CHAIN_MAX, at most 19200 (the LDS) */
-  bool lds_chain_refuse; /* VKSIFT_LDS_CHAIN=refuse: test hook, the chain launch declines and the per-scale launches take over */
-  bool lds_chain; /* VKSIFT_LDS_CHAIN (default 1): the trailing octaves that fit the LDS are built by one launch (vksift_hip_octave_chain) */
-  bool alt_order; /* always on: launches of a blur chain alternate their dispatch direction (vksift_hip_Plane::reverse) */
-  vksift_hip_event ev_match;
-  bool match_pending;
-  DetectSlot det_ring[VKSIFT_DETECT_RING];
-  uint64_t det_seq, det_done; /* last detection issued / highest one known to have completed */
-  /* batched download: the first vksift_downloadFeatures() after a detection of VKSIFT_DL_BATCH_MIN images and more packs the
-   * features of ALL its buffers on the device and fetches them with one copy into pinned memory; the downloads of the
+  /* ---- download staging. Batched download: the first vksift_downloadFeatures() after a detection of VKSIFT_DL_BATCH_MIN images and more
+   * packs the features of ALL its buffers on the device and fetches them with one copy into pinned memory; the downloads of the
    * other buffers are host copies out of it (one copy per section and buffer costs 80 us per buffer otherwise) */
-  uint8_t *d_dl, *h_dl;
+  uint8_t *d_dl, *h_dl; /* the staging pair (mem_fit_staging) */
   size_t dl_cap;       /* bytes of each */
   uint32_t *dl_row;    /* sift_buffer_count + 1 row offsets of the cached buffers */
   uint32_t dl_first, dl_count;
   bool dl_valid;
   bool dl_direct;            /* the packed copy of the current detection is fetched by DMA into page-locked destinations: nothing went to h_dl */
-  vksift_hip_event dl_ev[VKSIFT_DL_CHUNKS]; /* the packed copy arrives in pieces */
   size_t dl_chunk_end[VKSIFT_DL_CHUNKS];
   uint32_t dl_chunks, dl_chunks_done;
   uint64_t dl_seq;      /* the detection the packed copy belongs to */
-  /* Feature posting: a single-image detection ends with the pack kernel storing the dense records of its buffer straight into
+  uint64_t dl_hits_seq; /* the detection dl_hits counts for */
+  uint32_t dl_hits; /* vksift_downloadFeatures calls on buffers of that detection, before its packed copy exists */
+
+  /* ---- feature posting: a single-image detection ends with the pack kernel storing the dense records of its buffer straight into
    * mapped pinned memory (slot = buffer index & 1), so that vksift_getFeaturesNumber + vksift_downloadFeatures cost ONE host wait
    * and a host copy — instead of wait, pack launch, device-to-host copy, second wait (~60 us of a 0.45 ms detection).
    * Costs bus time when nobody downloads: switched off after VKSIFT_POST_IDLE posted detections in a row that were never
    * fetched, on again by the next download of a single detection. VKSIFT_POST_FEATURES=0 disables. */
-  uint8_t *h_post[2];
+  uint8_t *h_post[2];     /* allocated by the first detection that posts */
   size_t post_cap;        /* bytes of each */
   uint64_t post_seq[2];   /* detection whose records the slot holds (0: none) */
   uint32_t post_buf[2];
   bool post_fetched[2];   /* the slot's records were downloaded at least once */
   bool post_enabled, post_on;
   uint32_t post_idle;
-  uint64_t dl_hits_seq; /* the detection dl_hits counts for */
-  uint32_t dl_hits; /* vksift_downloadFeatures calls on buffers of that detection, before its packed copy exists */
-  /* packed download of the records of a batched matching (h_matches: pinned) */
-  size_t md_cap, md_pitch;
-  bool md_valid;
-  bool md_asked, md_direct;  /* (asked once per matching) the caller's destination of this matching's records is page-locked: per-pair DMA, no packed copy */
-  uint32_t md_hits;
-  bool *match_busy; /* per SIFT buffer: read by the matching pipeline in flight (all pairs of a batched call) */
-  uint32_t curr_nb_matches;
 
-  /* profiling */
+  /* ---- streams and events (ProfSet and DetectSlot hold more events) */
+  vksift_hip_stream stream;
+  vksift_hip_stream pyr_stream; /* scale-space construction when detections overlap (two pyramid buffers) */
+  vksift_hip_stream up_stream;  /* host-to-device copies of the input images */
+  vksift_hip_stream dl_stream;  /* result downloads: the accessors have waited for the pipeline that produced what they read; their copies must
+                                 * not queue behind a LATER detection already on the instance stream (a caller that pipelines) */
+  vksift_hip_stream side_stream; /* second branch stream of a forked detection (the first is pyr_stream) */
+  vksift_hip_event ev_pyr_done;
+  vksift_hip_event ev_pyr_free[2]; /* last reader of pyramid buffer i has finished */
+  vksift_hip_event ev_desc_start;  /* the previous detection's descriptor stage has been issued up to here: the next scale-space may start */
+  vksift_hip_event ev_input_free;  /* the last reader of d_input (seed pass of the most recent detection) has run */
+  vksift_hip_event ev_fork[VKSIFT_MAX_OCTAVES], ev_join[2]; /* forked detections */
+  vksift_hip_event ev_staging;      /* host image staging buffer consumed by the H2D copy */
+  vksift_hip_event ev_up[VKSIFT_UP_GROUPS]; /* group g of a batch has arrived in d_input */
+  vksift_hip_event ev_match;
+  vksift_hip_event ev_m[2];         /* profiling: the matching interval */
+  vksift_hip_event dl_ev[VKSIFT_DL_CHUNKS]; /* the packed copy arrives in pieces (created by the first one) */
+  vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab (created, like ev_v, by the first verification) */
+  vksift_hip_event ev_v[2];
+  bool desc_start_valid, input_free_valid, staging_pending;
+  DetectSlot det_ring[VKSIFT_DETECT_RING];
+  uint64_t det_seq, det_done; /* last detection issued / highest one known to have completed */
+
+  /* ---- profiling */
   bool profiling;
   ProfSet prof[2]; /* two event sets: the host may enqueue one detection ahead of the one being timed */
   int prof_cur;
-  vksift_hip_event ev_m[2];
   bool match_timing_valid;
   double acc_ms[8]; /* upload, pyramid (octave 0), extrema stage, orientation, descriptor, total, extrema scan kernel alone, pyramid (all octaves) */
   uint32_t acc_calls;
@@ -305,8 +315,21 @@ VKSIFT_INTERNAL void default_error_callback(vksift_Result err);
 VKSIFT_INTERNAL bool buffer_idx_valid(vksift_Instance inst, uint32_t idx);
 VKSIFT_INTERNAL bool resolution_valid(vksift_Instance inst, uint32_t w, uint32_t h);
 
-/* vksift_instance.c */
+/* vksift_mem.c */
+typedef enum { MEM_DEVICE, MEM_PINNED, MEM_HEAP } MemKind;
 VKSIFT_INTERNAL void compute_layout(vksift_Instance inst, uint32_t w, uint32_t h, PyrLayout *L);
+/* field: address of a pointer of the instance. Allocates `bytes` of that kind unless the block exists (a group that ran out of memory
+ * half-way is retried without leaking); false: out of memory. mem_release frees it and clears the pointer. */
+VKSIFT_INTERNAL bool mem_ensure(void *field, size_t bytes, MemKind kind);
+VKSIFT_INTERNAL void mem_release(void *field, MemKind kind);
+/* the staging pair d_dl / h_dl holds `bytes` (re-allocated with 25 % on top when it does not, or when may_shrink and it is far too
+ * large); false: out of memory, both pointers NULL and dl_cap 0 */
+VKSIFT_INTERNAL bool mem_fit_staging(vksift_Instance inst, size_t bytes, bool may_shrink);
+VKSIFT_INTERNAL bool mem_create(vksift_Instance inst, const PyrLayout *L);
+VKSIFT_INTERNAL int mem_resize_scratch(vksift_Instance inst, const PyrLayout *L, uint32_t new_cap);
+VKSIFT_INTERNAL void mem_destroy(vksift_Instance inst);
+
+/* vksift_instance.c */
 VKSIFT_INTERNAL void set_buffer_sections(vksift_Instance inst, uint32_t buf, uint32_t n_oct, uint32_t w, uint32_t h);
 VKSIFT_INTERNAL void mark_detect_done(vksift_Instance inst);
 VKSIFT_INTERNAL bool detect_running(vksift_Instance inst);

@@ -48,17 +48,11 @@ static uint32_t rows_bound(vksift_Instance inst, uint32_t id)
  * the next call; nothing is leaked in between. */
 static int ensure_match_cache(vksift_Instance inst)
 {
-  if (!inst->d_cache_desc)
-    inst->d_cache_desc = (uint8_t *)vksift_hip_malloc(inst->desc_slot_stride * inst->cfg.sift_buffer_count);
-  if (!inst->d_cache_norm)
-    inst->d_cache_norm = (uint32_t *)vksift_hip_malloc(sizeof(uint32_t) * inst->cache_norm_stride * inst->cfg.sift_buffer_count);
-  if (!inst->d_match_partial && inst->cfg.max_nb_sift_per_buffer > VKSIFT_HIP_MATCH_SMALL_NA)
-  {
-    inst->d_match_partial = (uint32_t *)vksift_hip_malloc(sizeof(uint32_t) * (size_t)inst->cfg.max_nb_sift_per_buffer * 5u * VKSIFT_HIP_MATCH_CHUNKS);
-    if (!inst->d_match_partial)
-      return 2; /* hipErrorOutOfMemory */
-  }
-  return (inst->d_cache_desc && inst->d_cache_norm) ? 0 : 2;
+  const uint32_t nb = inst->cfg.max_nb_sift_per_buffer;
+  const bool desc = mem_ensure(&inst->d_cache_desc, inst->desc_slot_stride * inst->cfg.sift_buffer_count, MEM_DEVICE);
+  const bool norm = mem_ensure(&inst->d_cache_norm, sizeof(uint32_t) * inst->cache_norm_stride * inst->cfg.sift_buffer_count, MEM_DEVICE);
+  const bool part = nb <= VKSIFT_HIP_MATCH_SMALL_NA || mem_ensure(&inst->d_match_partial, sizeof(uint32_t) * (size_t)nb * 5u * VKSIFT_HIP_MATCH_CHUNKS, MEM_DEVICE);
+  return (desc && norm && part) ? 0 : 2; /* hipErrorOutOfMemory */
 }
 
 int refresh_match_cache(vksift_Instance inst, const uint32_t *ids, uint32_t count)
@@ -155,18 +149,10 @@ static bool ensure_filter_scratch(vksift_Instance inst)
 {
   const uint32_t bc = inst->batch_cap;
   inst->filtered_slot_stride = (((uint64_t)inst->cfg.max_nb_sift_per_buffer * 16u) + 255u) & ~(uint64_t)255u;
-  /* each block only if it does not exist yet: a call that ran out of memory half-way is retried without leaking */
-  bool ok = true;
-#define ENSURE_D(ptr, bytes) ok = ok && ((ptr) != NULL || ((ptr) = vksift_hip_malloc(bytes)) != NULL)
-  ENSURE_D(inst->rev.matches, inst->match_slot_stride * bc);
-  ENSURE_D(inst->rev.redo, sizeof(uint32_t) * inst->redo_slot_stride * bc);
-  ENSURE_D(inst->rev.match_n, sizeof(uint32_t) * 4 * bc);
-  ENSURE_D(inst->d_filtered_n, sizeof(uint32_t) * bc);
-  ENSURE_D(inst->d_filtered, inst->filtered_slot_stride * bc);
-#undef ENSURE_D
-  ok = ok && (inst->h_filtered_n != NULL || (inst->h_filtered_n = vksift_hip_host_malloc(sizeof(uint32_t) * bc)) != NULL);
-  ok = ok && (inst->filt_ids != NULL || (inst->filt_ids = (uint32_t *)malloc(sizeof(uint32_t) * 2u * bc)) != NULL);
-  return ok;
+  return mem_ensure(&inst->rev.matches, inst->match_slot_stride * bc, MEM_DEVICE) && mem_ensure(&inst->rev.redo, sizeof(uint32_t) * inst->redo_slot_stride * bc, MEM_DEVICE) &&
+         mem_ensure(&inst->rev.match_n, sizeof(uint32_t) * 4 * bc, MEM_DEVICE) && mem_ensure(&inst->d_filtered_n, sizeof(uint32_t) * bc, MEM_DEVICE) &&
+         mem_ensure(&inst->d_filtered, inst->filtered_slot_stride * bc, MEM_DEVICE) && mem_ensure(&inst->h_filtered_n, sizeof(uint32_t) * bc, MEM_PINNED) &&
+         mem_ensure(&inst->filt_ids, sizeof(uint32_t) * 2u * bc, MEM_HEAP);
 }
 
 static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count, const char *fn, bool filter, float ratio,
@@ -313,10 +299,9 @@ static bool packed_match_download(vksift_Instance inst, uint32_t pair, vksift_Ma
     const size_t pitch = (size_t)max_n * MATCH_BYTES, bytes = pitch * inst->match_slots_used;
     if (bytes > inst->md_cap)
     {
-      vksift_hip_host_free(inst->h_matches);
-      inst->h_matches = (uint8_t *)vksift_hip_host_malloc(bytes + bytes / 4u + 4096u);
-      inst->md_cap = inst->h_matches ? bytes + bytes / 4u + 4096u : 0;
-      if (!inst->h_matches)
+      mem_release(&inst->h_matches, MEM_PINNED);
+      inst->md_cap = mem_ensure(&inst->h_matches, bytes + bytes / 4u + 4096u, MEM_PINNED) ? bytes + bytes / 4u + 4096u : 0;
+      if (!inst->md_cap)
         return false;
     }
     if (vksift_hip_memcpy2d_d2h(inst->h_matches, pitch, inst->d_matches, inst->match_slot_stride, pitch, inst->match_slots_used, inst->dl_stream) != 0 ||

@@ -12,23 +12,17 @@
 _Static_assert(sizeof(vksift_ext_Homography) == 4u * VERIFY_RES_WORDS, "vksift_ext_Homography is the kernel's 13-word result record");
 
 /* correspondences, masks, results and reduction keys of batch_cap pairs; allocated by the first verification (detect-only and match-only
- * users never pay), each block only if it does not exist yet so that a call that ran out of memory is retried without leaking */
+ * users never pay) */
 static bool ensure_verify_scratch(vksift_Instance inst)
 {
   const uint32_t bc = inst->batch_cap;
   inst->vmask_slot_stride = ((uint64_t)inst->cfg.max_nb_sift_per_buffer + 255u) & ~(uint64_t)255u;
   inst->vscratch_u32 = vksift_hip_ransac_scratch_u32(bc, VERIFY_MAX_HYPOTHESES);
-  bool ok = true;
-#define ENSURE_D(ptr, bytes) ok = ok && ((ptr) != NULL || ((ptr) = vksift_hip_malloc(bytes)) != NULL)
-#define ENSURE_H(ptr, bytes) ok = ok && ((ptr) != NULL || ((ptr) = vksift_hip_host_malloc(bytes)) != NULL)
-  ENSURE_D(inst->d_corr, inst->filtered_slot_stride * bc);
-  ENSURE_D(inst->d_vmask, inst->vmask_slot_stride * bc);
-  ENSURE_D(inst->d_vres, sizeof(uint32_t) * VERIFY_RES_WORDS * bc);
-  ENSURE_D(inst->d_vscratch, sizeof(uint32_t) * inst->vscratch_u32);
-  ENSURE_H(inst->h_vres, sizeof(uint32_t) * VERIFY_RES_WORDS * bc);
-  ENSURE_H(inst->h_vtab, sizeof(uint32_t) * ((size_t)4u * bc + (size_t)VERIFY_LAYOUT_WORDS * 2u * bc));
-#undef ENSURE_D
-#undef ENSURE_H
+  const bool ok = mem_ensure(&inst->d_corr, inst->filtered_slot_stride * bc, MEM_DEVICE) && mem_ensure(&inst->d_vmask, inst->vmask_slot_stride * bc, MEM_DEVICE) &&
+                  mem_ensure(&inst->d_vres, sizeof(uint32_t) * VERIFY_RES_WORDS * bc, MEM_DEVICE) &&
+                  mem_ensure(&inst->d_vscratch, sizeof(uint32_t) * inst->vscratch_u32, MEM_DEVICE) &&
+                  mem_ensure(&inst->h_vres, sizeof(uint32_t) * VERIFY_RES_WORDS * bc, MEM_PINNED) &&
+                  mem_ensure(&inst->h_vtab, sizeof(uint32_t) * ((size_t)4u * bc + (size_t)VERIFY_LAYOUT_WORDS * 2u * bc), MEM_PINNED);
   if (!inst->ev_vtab)
     inst->ev_vtab = vksift_hip_event_create();
   for (int i = 0; i < 2; i++)
