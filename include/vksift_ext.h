@@ -76,7 +76,26 @@ extern "C"
   VKSIFT_EXPORT void vksift_ext_getHomography(vksift_Instance instance, uint32_t pair, vksift_ext_Homography *out);
   /* vksift_ext_getFilteredMatchesNumber(pair) bytes, in the order of the filtered matches: 1 = inlier of the returned model */
   VKSIFT_EXPORT void vksift_ext_downloadInlierMask(vksift_Instance instance, uint32_t pair, uint8_t *mask);
-  /* Time (ms) of the last verification (its three launches + the result posting), HIP events; needs profiling on. -1 when there is none. */
+  /* The same for a fundamental matrix: "are these matches consistent with some rigid two-view geometry?". nb_hypotheses seven-point samples per pair from the
+   * same generator; each gives up to three models (the real roots of the seven-point cubic, numbered in increasing order); a match is an inlier when its
+   * Sampson distance is below threshold_px; the model with the most inliers wins, ties to the lowest (hypothesis, root). Deterministic, restated bit for bit by
+   * tests/np_verify_f.py. Contract, busy buffers, errors and invalidation as for vksift_ext_verifyHomography. The two models keep separate results and masks:
+   * after one vksift_ext_matchFeaturesFiltered both may be run and both read (each accessor is an error until its own model has been verified) — comparing the
+   * two inlier counts is how a caller recognises a planar scene or a pure rotation, which this estimator does not handle (seven coplanar points do not
+   * determine F). No rank or orientation test beyond the seven-point construction, no refit on the inliers. */
+  typedef struct
+  {
+    float F[9];            /* row-major, pixel coordinates: (xb, yb, 1) F (xa, ya, 1)^T = 0; largest |entry| in [1, 2) */
+    uint32_t nb_matches;   /* filtered matches of the pair */
+    uint32_t nb_inliers;
+    uint32_t best_hypothesis;
+    uint32_t best_root;
+    uint32_t valid;        /* 0: fewer than 7 matches, no model with 8 inliers, or a model that is not finite; everything else is zero then */
+  } vksift_ext_Fundamental; /* 56 bytes */
+  VKSIFT_EXPORT void vksift_ext_verifyFundamental(vksift_Instance instance, uint32_t nb_hypotheses, float threshold_px, uint64_t seed);
+  VKSIFT_EXPORT void vksift_ext_getFundamental(vksift_Instance instance, uint32_t pair, vksift_ext_Fundamental *out);
+  VKSIFT_EXPORT void vksift_ext_downloadFundamentalInlierMask(vksift_Instance instance, uint32_t pair, uint8_t *mask);
+  /* Time (ms) of the last verification of either model (its three launches + the result posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getVerifyTime(vksift_Instance instance);
 
   /* Deferred submission of vksift_detectFeatures (no counterpart in the reference, no change of its contract): consecutive plain

@@ -382,6 +382,15 @@ extern "C"
   int vksift_hip_ransac_homography(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
                                    uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
                                    uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
+  /* The same for a fundamental matrix (same arguments, scratch and refusals; seven-point samples). Each hypothesis gives up to three models (the real roots of
+   * the seven-point cubic, numbered in increasing order), model id = 4*j + root; a correspondence is an inlier when its Sampson distance is below threshold_px;
+   * the best is the largest count, ties to the lowest model id. results + 56*i: float F[9] (row-major, pixel coordinates, (xb, yb, 1) F (xa, ya, 1)^T = 0, largest
+   * |entry| in [1, 2)), uint32 nb_matches (= n), nb_inliers, best_hypothesis, best_root, valid; masks as above. n < 7, a best count below 8 (the seven sample
+   * points fit their own model) or a non-finite model: valid = 0 and everything else zero. No rank or orientation test beyond the seven-point construction, no
+   * handling of the planar degeneracy, no refit. tests/np_verify_f.py restates every output bit for bit. */
+  int vksift_hip_ransac_fundamental(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
+                                    uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
+                                    uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
 
 #ifdef __cplusplus
 }

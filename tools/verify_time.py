@@ -1,8 +1,10 @@
-"""Time vksift_ext_verifyHomography on the benchmark workload: B frames 640x480, consecutive pairs, matchFeaturesFiltered(0.8, True), then
-verifyHomography(nb_hypotheses, 2.5) timed by HIP events (vksift_ext_getVerifyTime): warm-ups, then repetitions; median and spread.
-The only other RANSAC on the box is the numpy restatement (tests/np_verify.py), timed on a few of the same pairs for scale.
+"""Time vksift_ext_verifyHomography (--model h, the default) or vksift_ext_verifyFundamental (--model f) on the benchmark workload: B frames
+640x480, consecutive pairs, matchFeaturesFiltered(0.8, True), then the verification (nb_hypotheses, 2.5) timed by HIP events
+(vksift_ext_getVerifyTime): warm-ups, then repetitions; median and spread. The only other RANSAC on the box is the numpy restatement
+(tests/np_verify.py, tests/np_verify_f.py), timed on a few of the same pairs for scale.
 
-usage: verify_time.py [B=512] [nb_hypotheses=1024] [repeats=20] [warmups=3] [--json out.json] [--once]   (--once: one verification, for a kernel trace)"""
+usage: verify_time.py [B=512] [nb_hypotheses=1024] [repeats=20] [warmups=3] [--model h|f] [--json out.json] [--once]
+       (--once: one verification, for a kernel trace)"""
 import json
 import os
 import sys
@@ -15,7 +17,16 @@ import numpy as np
 
 from vulkansift_amd import api
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
+MODEL = "h"
+argv = []
+for i, arg in enumerate(sys.argv[1:], 1):
+    if sys.argv[i - 1] in ("--model", "--json"):
+        if sys.argv[i - 1] == "--model":
+            MODEL = arg
+        continue
+    argv.append(arg)
+assert MODEL in ("h", "f"), "--model h|f"
+args = [a for a in argv if not a.startswith("--")]
 B = int(args[0]) if len(args) > 0 else 512
 NH = int(args[1]) if len(args) > 1 else 1024
 REP = int(args[2]) if len(args) > 2 else 20
@@ -35,16 +46,19 @@ with api.Instance(cfg, batch_capacity=B) as inst:
     n_f = np.array([len(inst.downloadFilteredMatches(k)) for k in range(B)])
     ms = []
     for it in range(1 if once else WARM + REP):
-        inst.verifyHomography(NH, 2.5, it)
+        (inst.verifyFundamental if MODEL == "f" else inst.verifyHomography)(NH, 2.5, it)
         t = inst.getVerifyTime()
         if once or it >= WARM:
             ms.append(t)
-    valid = sum(int(inst.getHomography(k)["valid"]) for k in range(B))
-    out = {"pairs": B, "nb_hypotheses": NH, "threshold_px": 2.5, "repeats": len(ms), "verify_ms_median": float(np.median(ms)), "verify_ms_min": float(np.min(ms)),
+    valid = sum(int((inst.getFundamental if MODEL == "f" else inst.getHomography)(k)["valid"]) for k in range(B))
+    out = {"model": MODEL, "pairs": B, "nb_hypotheses": NH, "threshold_px": 2.5, "repeats": len(ms), "verify_ms_median": float(np.median(ms)), "verify_ms_min": float(np.min(ms)),
            "verify_ms_max": float(np.max(ms)), "filtered_matches_per_pair_mean": float(n_f.mean()), "filtered_matches_per_pair_min": int(n_f.min()),
            "filtered_matches_per_pair_max": int(n_f.max()), "valid_pairs": valid, "match_ms": float(inst.getMatchTime())}
     if not once:
-        import np_verify as V
+        if MODEL == "f":
+            import np_verify_f as V
+        else:
+            import np_verify as V
 
         ks = list(range(0, B, max(1, B // 4)))[:4]
         t0 = time.perf_counter()

@@ -73,6 +73,8 @@ FEATURE_DTYPE = np.dtype(
 MATCH_DTYPE = np.dtype([("idx_a", "<u4"), ("idx_b1", "<u4"), ("idx_b2", "<u4"), ("dist_a_b1", "<f4"), ("dist_a_b2", "<f4")])
 FILTERED_MATCH_DTYPE = np.dtype([("idx_a", "<u4"), ("idx_b", "<u4"), ("dist_a_b1", "<f4"), ("dist_a_b2", "<f4")])
 HOMOGRAPHY_DTYPE = np.dtype([("H", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("best_hypothesis", "<u4"), ("valid", "<u4")])
+FUNDAMENTAL_DTYPE = np.dtype([("F", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("best_hypothesis", "<u4"), ("best_root", "<u4"), ("valid", "<u4")])
+assert FUNDAMENTAL_DTYPE.itemsize == 56
 assert FEATURE_DTYPE.itemsize == 164 and MATCH_DTYPE.itemsize == 20 and FILTERED_MATCH_DTYPE.itemsize == 16 and HOMOGRAPHY_DTYPE.itemsize == 52
 
 _lib = None
@@ -131,6 +133,12 @@ def lib():
     L.vksift_ext_getHomography.restype = None
     L.vksift_ext_downloadInlierMask.argtypes = [inst, u32, C.c_void_p]
     L.vksift_ext_downloadInlierMask.restype = None
+    L.vksift_ext_verifyFundamental.argtypes = [inst, u32, C.c_float, C.c_uint64]
+    L.vksift_ext_verifyFundamental.restype = None
+    L.vksift_ext_getFundamental.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_getFundamental.restype = None
+    L.vksift_ext_downloadFundamentalInlierMask.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_downloadFundamentalInlierMask.restype = None
     L.vksift_ext_getVerifyTime.argtypes = [inst]
     L.vksift_ext_getVerifyTime.restype = C.c_float
     L.vksift_ext_setProfiling.argtypes = [inst, C.c_bool]
@@ -190,6 +198,8 @@ def lib():
     L.vksift_hip_ransac_homography.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, u32, u32, u32, u32, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p,
                                                C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
     L.vksift_hip_ransac_homography.restype = C.c_int
+    L.vksift_hip_ransac_fundamental.argtypes = L.vksift_hip_ransac_homography.argtypes
+    L.vksift_hip_ransac_fundamental.restype = C.c_int
     _lib = L
     return L
 
@@ -275,10 +285,7 @@ def gen_synthetic_descriptors(seed, rows):
     return out
 
 
-def ransac_homography(corr, n, nb_hypotheses, threshold_px, seed, scratch_u32=None):
-    """vksift_hip_ransac_homography on torch tensors: corr float32 [nslots, max_n, 4] and n int32 [nslots] on the GPU. Returns (error code,
-    results as a HOMOGRAPHY_DTYPE array, masks uint8 [nslots, max_n]); on an error nothing was launched and the other two are None.
-    scratch_u32: words of scratch to hand over instead of what vksift_hip_ransac_scratch_u32 asks for (the refusal tests)."""
+def _ransac(entry, words_per_result, dtype, corr, n, nb_hypotheses, threshold_px, seed, scratch_u32):
     import torch
 
     assert corr.is_cuda and corr.dtype == torch.float32 and corr.is_contiguous() and corr.dim() == 3 and corr.shape[2] == 4
@@ -288,15 +295,27 @@ def ransac_homography(corr, n, nb_hypotheses, threshold_px, seed, scratch_u32=No
     words = need if scratch_u32 is None else scratch_u32
     # poisoned: the scratch needs no initialisation, the outputs are written for every slot
     scratch = torch.full((max(words, 1),), -1, dtype=torch.int32, device=corr.device)
-    results = torch.full((nslots, 13), -1, dtype=torch.int32, device=corr.device)
+    results = torch.full((nslots, words_per_result), -1, dtype=torch.int32, device=corr.device)
     masks = torch.full((nslots, max(max_n, 1)), 0x55, dtype=torch.uint8, device=corr.device)
     stream = torch.cuda.current_stream().cuda_stream
-    err = lib().vksift_hip_ransac_homography(corr.data_ptr(), max_n * 16, n.data_ptr(), 1, max_n, nslots, nb_hypotheses, threshold_px, seed, results.data_ptr(),
-                                             masks.data_ptr(), max(max_n, 1), scratch.data_ptr(), words, stream)
+    err = entry(corr.data_ptr(), max_n * 16, n.data_ptr(), 1, max_n, nslots, nb_hypotheses, threshold_px, seed, results.data_ptr(), masks.data_ptr(),
+                max(max_n, 1), scratch.data_ptr(), words, stream)
     torch.cuda.synchronize()
     if err:
         return err, None, None
-    return 0, results.cpu().numpy().view(np.uint8).reshape(nslots, 52).copy().view(HOMOGRAPHY_DTYPE).reshape(nslots), masks.cpu().numpy()
+    return 0, results.cpu().numpy().view(np.uint8).reshape(nslots, 4 * words_per_result).copy().view(dtype).reshape(nslots), masks.cpu().numpy()
+
+
+def ransac_homography(corr, n, nb_hypotheses, threshold_px, seed, scratch_u32=None):
+    """vksift_hip_ransac_homography on torch tensors: corr float32 [nslots, max_n, 4] and n int32 [nslots] on the GPU. Returns (error code,
+    results as a HOMOGRAPHY_DTYPE array, masks uint8 [nslots, max_n]); on an error nothing was launched and the other two are None.
+    scratch_u32: words of scratch to hand over instead of what vksift_hip_ransac_scratch_u32 asks for (the refusal tests)."""
+    return _ransac(lib().vksift_hip_ransac_homography, 13, HOMOGRAPHY_DTYPE, corr, n, nb_hypotheses, threshold_px, seed, scratch_u32)
+
+
+def ransac_fundamental(corr, n, nb_hypotheses, threshold_px, seed, scratch_u32=None):
+    """vksift_hip_ransac_fundamental, as ransac_homography; the results are a FUNDAMENTAL_DTYPE array"""
+    return _ransac(lib().vksift_hip_ransac_fundamental, 14, FUNDAMENTAL_DTYPE, corr, n, nb_hypotheses, threshold_px, seed, scratch_u32)
 
 
 class Instance:
@@ -413,6 +432,28 @@ class Instance:
         _check_pending()
         out = np.zeros(n, np.uint8)
         lib().vksift_ext_downloadInlierMask(self._h, pair, out.ctypes.data)
+        _check_pending()
+        return out.astype(bool)
+
+    def verifyFundamental(self, nb_hypotheses=1024, threshold_px=2.5, seed=0):
+        """RANSAC fundamental matrix of every pair of the last matchFeaturesFiltered call, on the GPU (vksift_ext_verifyFundamental); its results
+        are kept beside the homography's, not in their place."""
+        lib().vksift_ext_verifyFundamental(self._h, nb_hypotheses, threshold_px, seed)
+        _check_pending()
+
+    def getFundamental(self, pair=0):
+        """structured scalar (FUNDAMENTAL_DTYPE): F 3x3 float32 (pixels, (xb, yb, 1) F (xa, ya, 1)^T = 0, largest |entry| in [1, 2)), nb_matches,
+        nb_inliers, best_hypothesis, best_root, valid"""
+        out = np.zeros(1, FUNDAMENTAL_DTYPE)
+        lib().vksift_ext_getFundamental(self._h, pair, out.ctypes.data)
+        _check_pending()
+        return out[0]
+
+    def downloadFundamentalInlierMask(self, pair=0):
+        n = lib().vksift_ext_getFilteredMatchesNumber(self._h, pair)
+        _check_pending()
+        out = np.zeros(n, np.uint8)
+        lib().vksift_ext_downloadFundamentalInlierMask(self._h, pair, out.ctypes.data)
         _check_pending()
         return out.astype(bool)
 

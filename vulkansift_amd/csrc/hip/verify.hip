@@ -1,13 +1,14 @@
-// verify.hip — geometric verification of filtered matches: a batched, deterministic RANSAC homography estimator (no counterpart in the
-// reference, whose callers run a CPU RANSAC after downloading matches and features; the reference's own evaluation judges matches by
-// a homography, src/perf/perf_matching.cpp:30-79). Three launches serve every pair (slot) of a call:
+// verify.hip — geometric verification of filtered matches: batched, deterministic RANSAC estimators of a homography and of a fundamental
+// matrix (no counterpart in the reference, whose callers run a CPU RANSAC after downloading matches and features; the reference's own
+// evaluation judges matches by a homography, src/perf/perf_matching.cpp:30-79). Three launches serve every pair (slot) of a call:
 //   k_gather_corr      filtered matches {idx_a, idx_b} (download-order rows) -> {xa, ya, xb, yb} read from the SIFT buffers' sections
 //   k_ransac_score_h   one lane per hypothesis: counter-based sample, closed-form four-point homography, inlier count over the slot's
 //                      correspondences staged through LDS (broadcast 16-byte reads), best (count, lowest index) per workgroup
 //   k_ransac_final_h   best hypothesis per slot, its model in pixel coordinates, the inlier mask (same test: popcount == count)
-// Everything is integer arithmetic or correctly rounded fp32 add / sub / mul / div in a fixed order (the tree is built with
-// -ffp-contract=off and no fmaf is used here), so tests/np_verify.py restates it bit for bit. A second model (fundamental matrix) is a
-// second pair of score / final kernels beside these; the gather and the sampler are model-free.
+//   k_ransac_score_f / k_ransac_final_f   the same pair for the fundamental matrix: seven-point samples, up to three models per lane
+// Everything is integer arithmetic or correctly rounded fp32 add / sub / mul / div / sqrt in a fixed order (the tree is built with
+// -ffp-contract=off and no fmaf is used here), so tests/np_verify.py and tests/np_verify_f.py restate it bit for bit. The gather, the
+// sampler, the key reduction and the launch wrapper are model-free.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -38,28 +39,29 @@ __device__ __forceinline__ uint64_t splitmix64_next(uint64_t &state)
 
 __device__ __forceinline__ uint32_t draw_below(uint64_t &state, uint32_t m) { return (uint32_t)(((splitmix64_next(state) >> 32) * (uint64_t)m) >> 32); }
 
-// Four distinct indices below n (n >= 4), in draw order: draw k is uniform over the n - k indices left and stepped over the ones
-// already drawn (kept sorted in a <= b <= c). seed_key = the first splitmix64 output of the state `seed`.
-__device__ __forceinline__ void draw_sample(uint64_t seed_key, uint32_t slot, uint32_t hyp, uint32_t n, uint32_t &i0, uint32_t &i1, uint32_t &i2, uint32_t &i3)
+// K distinct indices below n (n >= K), in draw order: draw j is uniform over the n - j indices left and stepped over the ones already
+// drawn in increasing order (kept sorted in `sorted`, compile-time indices only). seed_key = the first splitmix64 output of the state `seed`.
+template <int K> __device__ __forceinline__ void draw_sample(uint64_t seed_key, uint32_t slot, uint32_t hyp, uint32_t n, uint32_t (&idx)[K])
 {
   uint64_t st = seed_key ^ (((uint64_t)slot << 32) | (uint64_t)hyp);
-  i0 = draw_below(st, n);
-  uint32_t r = draw_below(st, n - 1u);
-  r += r >= i0 ? 1u : 0u;
-  i1 = r;
-  uint32_t a = i0 < i1 ? i0 : i1, b = i0 < i1 ? i1 : i0;
-  r = draw_below(st, n - 2u);
-  r += r >= a ? 1u : 0u;
-  r += r >= b ? 1u : 0u;
-  i2 = r;
-  const uint32_t lo = b < i2 ? b : i2, c = b < i2 ? i2 : b;
-  b = a < lo ? lo : a;
-  a = a < lo ? a : lo;
-  r = draw_below(st, n - 3u);
-  r += r >= a ? 1u : 0u;
-  r += r >= b ? 1u : 0u;
-  r += r >= c ? 1u : 0u;
-  i3 = r;
+  uint32_t sorted[K];
+#pragma unroll
+  for (int j = 0; j < K; j++)
+  {
+    uint32_t r = draw_below(st, n - (uint32_t)j);
+#pragma unroll
+    for (int q = 0; q < j; q++)
+      r += r >= sorted[q] ? 1u : 0u;
+    idx[j] = r;
+    uint32_t v = r;
+#pragma unroll
+    for (int q = 0; q < j; q++)
+    {
+      const uint32_t lo = sorted[q] < v ? sorted[q] : v, hi = sorted[q] < v ? v : sorted[q];
+      sorted[q] = lo, v = hi;
+    }
+    sorted[j] = v;
+  }
 }
 
 __device__ __forceinline__ float4 scaled(float4 c) { return float4{c.x * kCoordScale, c.y * kCoordScale, c.z * kCoordScale, c.w * kCoordScale}; }
@@ -240,9 +242,9 @@ __global__ void __launch_bounds__(256) k_ransac_score_h(const float4 *__restrict
   const float4 *c = corr + (size_t)slot * corr_slot_stride;
   const uint32_t hyp = blk * kHypPerBlock + tid;
   const bool active = hyp < nb_hyp;
-  uint32_t i0, i1, i2, i3;
-  draw_sample(seed_key, slot, active ? hyp : 0u, n, i0, i1, i2, i3);
-  const Hom H = solve_h4(scaled(c[i0]), scaled(c[i1]), scaled(c[i2]), scaled(c[i3]));
+  uint32_t i4[4];
+  draw_sample<4>(seed_key, slot, active ? hyp : 0u, n, i4);
+  const Hom H = solve_h4(scaled(c[i4[0]]), scaled(c[i4[1]]), scaled(c[i4[2]]), scaled(c[i4[3]]));
   uint32_t cnt = 0;
   for (uint32_t base = 0; base < n; base += kHypPerBlock)
   {
@@ -304,9 +306,9 @@ __global__ void __launch_bounds__(256) k_ransac_final_h(const float4 *__restrict
   float o[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (valid) // uniform over the workgroup
   {
-    uint32_t i0, i1, i2, i3;
-    draw_sample(seed_key, slot, hyp, n, i0, i1, i2, i3);
-    H = solve_h4(scaled(c[i0]), scaled(c[i1]), scaled(c[i2]), scaled(c[i3]));
+    uint32_t i4[4];
+    draw_sample<4>(seed_key, slot, hyp, n, i4);
+    H = solve_h4(scaled(c[i4[0]]), scaled(c[i4[1]]), scaled(c[i4[2]]), scaled(c[i4[3]]));
     const float p2 = H.h2 * kCoordUnscale, p5 = H.h5 * kCoordUnscale, p6 = H.h6 * kCoordScale, p7 = H.h7 * kCoordScale;
     o[0] = H.h0 / H.h8, o[1] = H.h1 / H.h8, o[2] = p2 / H.h8;
     o[3] = H.h3 / H.h8, o[4] = H.h4 / H.h8, o[5] = p5 / H.h8;
@@ -330,12 +332,389 @@ __global__ void __launch_bounds__(256) k_ransac_final_h(const float4 *__restrict
   }
 }
 
+// ---- the second model: fundamental matrix ----------------------------------------------------------------------------------------------
+// Seven-point algorithm in fp32, one operation order (tests/np_verify_f.py restates it bit for bit). Per hypothesis up to three models
+// (the real roots of a cubic), model id = 4 * hypothesis + root. Not done here: no rank or orientation (chirality) test beyond what the
+// seven-point construction gives; no handling of the planar degeneracy (a caller runs both models on the same filtered matching and
+// compares the counts); no refit on the inliers.
+constexpr int kBisectSteps = 48; // halvings of a bracket no wider than 2 R: to the last bit of a root down to 2^-24 R
+
+struct Fund
+{
+  float f[9];
+};
+
+__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+
+// 2^(127 - e) for the exponent e of the largest magnitude `mbits`; ok: that magnitude is normal and below 2^127
+__device__ __forceinline__ float unit_scale(uint32_t mbits, bool &ok)
+{
+  const uint32_t e = mbits >> 23;
+  ok = e >= 1u && e <= 253u;
+  return __uint_as_float((254u - (ok ? e : 127u)) << 23);
+}
+
+// One side of the sample: x, y become s (x - cx), s (y - cy) with the centroid (cx, cy) (fixed-order sum times 1.0f / 7.0f) and the power
+// of two s that brings the largest |deviation| into [1, 2); u = s cx, v = s cy. s is NaN (and with it the whole solve) when there is no such power.
+__device__ __forceinline__ void condition7(float (&x)[7], float (&y)[7], float &s, float &u, float &v)
+{
+  const float seventh = 1.0f / 7.0f;
+  const float cx = ((((((x[0] + x[1]) + x[2]) + x[3]) + x[4]) + x[5]) + x[6]) * seventh;
+  const float cy = ((((((y[0] + y[1]) + y[2]) + y[3]) + y[4]) + y[5]) + y[6]) * seventh;
+  uint32_t m = 0u;
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+  {
+    x[i] = x[i] - cx, y[i] = y[i] - cy;
+    m = max(m, max(abs_bits(x[i]), abs_bits(y[i])));
+  }
+  bool ok;
+  const float f = unit_scale(m, ok);
+  s = ok ? f : __uint_as_float(0x7fc00000u);
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+    x[i] = x[i] * s, y[i] = y[i] * s;
+  u = s * cx, v = s * cy;
+}
+
+// Real roots of c0 + c1 a + c2 a^2 + c3 a^3 in increasing order into root[0..count), NaN beyond; a fixed number of steps. Degenerate
+// (no root): c3 zero or subnormal, a coefficient or the root bound not finite. Else monic b_i = c_i / c3, all roots inside (-R, R) with
+// R = 1 + max |b_i| (Cauchy); the critical points lo <= hi of the cubic (equal when it is monotone) split that into three intervals on
+// each of which it is monotone; an interval whose end points differ in `p(x) < 0` is bisected kBisectSteps times.
+__device__ __forceinline__ uint32_t cubic_roots(float c0, float c1, float c2, float c3, float (&root)[3])
+{
+  const uint32_t mc = max(max(abs_bits(c0), abs_bits(c1)), max(abs_bits(c2), abs_bits(c3)));
+  const float b2 = c2 / c3, b1 = c1 / c3, b0 = c0 / c3;
+  const float R = 1.0f + __uint_as_float(max(max(abs_bits(b2), abs_bits(b1)), abs_bits(b0)));
+  const bool deg = (abs_bits(c3) >> 23) == 0u || (mc >> 23) == 255u || (abs_bits(R) >> 23) == 255u;
+  const float disc = b2 * b2 - 3.0f * b1;
+  const float sq = sqrtf(disc > 0.f ? disc : 0.f);
+  const float ends[4] = {-R, (-b2 - sq) / 3.0f, (-b2 + sq) / 3.0f, R};
+  bool ng[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    ng[i] = (((ends[i] + b2) * ends[i] + b1) * ends[i] + b0) < 0.f;
+  float l[3], r[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+    l[i] = ends[i], r[i] = ends[i + 1];
+  for (int step = 0; step < kBisectSteps; step++)
+  {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+    {
+      const float m = (l[i] + r[i]) * 0.5f;
+      const bool same = ((((m + b2) * m + b1) * m + b0) < 0.f) == ng[i];
+      l[i] = same ? m : l[i], r[i] = same ? r[i] : m;
+    }
+  }
+  const float bad = __uint_as_float(0x7fc00000u);
+  root[0] = bad, root[1] = bad, root[2] = bad;
+  uint32_t cnt = 0u;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+  {
+    const bool has = ng[i] != ng[i + 1] && !deg;
+    const float x = (l[i] + r[i]) * 0.5f;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+      root[k] = (has && cnt == (uint32_t)k) ? x : root[k];
+    cnt += has ? 1u : 0u;
+  }
+  return cnt;
+}
+
+// The models through seven correspondences c_i = {xa, ya, xb, yb} (scaled): (xb, yb, 1) F (xa, ya, 1)^T = 0. Both sides conditioned
+// (condition7), the 7x9 system with rows (xb xa, xb ya, xb, yb xa, yb ya, yb, xa, ya, 1) reduced by Gauss-Jordan on its first seven
+// columns — for column k the rows k+1..6 are compared with row k in turn and exchanged when their |entry| (bit pattern) is strictly
+// larger; row k times 1 / pivot; every other row r minus a[r][k] times row k —, everything unrolled so that the system lives in
+// registers. The free columns give F1 = (-a[.][7], 1, 0) and F2 = (-a[.][8], 0, 1); det(F1 + a F2) is expanded along the last row;
+// each real root gives F^ = F1 + a F2, taken back as T_b^T F^ T_a and scaled by the power of two that brings its largest entry into
+// [1, 2). A model that is absent or not finite is all-NaN (no correspondence is an inlier of it). Returns the number of roots.
+__device__ __forceinline__ uint32_t solve_f7(const float4 (&c)[7], Fund (&M)[3])
+{
+  float xa[7], ya[7], xb[7], yb[7];
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+    xa[i] = c[i].x, ya[i] = c[i].y, xb[i] = c[i].z, yb[i] = c[i].w;
+  float sa, ua, va, sb, ub, vb;
+  condition7(xa, ya, sa, ua, va);
+  condition7(xb, yb, sb, ub, vb);
+  float a[7][9];
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+  {
+    a[i][0] = xb[i] * xa[i], a[i][1] = xb[i] * ya[i], a[i][2] = xb[i];
+    a[i][3] = yb[i] * xa[i], a[i][4] = yb[i] * ya[i], a[i][5] = yb[i];
+    a[i][6] = xa[i], a[i][7] = ya[i], a[i][8] = 1.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < 7; k++)
+  {
+#pragma unroll
+    for (int r = k + 1; r < 7; r++)
+    {
+      const bool sw = abs_bits(a[r][k]) > abs_bits(a[k][k]);
+#pragma unroll
+      for (int j = k; j < 9; j++)
+      {
+        const float top = a[k][j], low = a[r][j];
+        a[k][j] = sw ? low : top, a[r][j] = sw ? top : low;
+      }
+    }
+    const float inv = 1.0f / a[k][k];
+#pragma unroll
+    for (int j = k + 1; j < 9; j++)
+      a[k][j] = a[k][j] * inv;
+#pragma unroll
+    for (int r = 0; r < 7; r++)
+      if (r != k)
+      {
+        const float f = a[r][k];
+#pragma unroll
+        for (int j = k + 1; j < 9; j++)
+          a[r][j] = a[r][j] - f * a[k][j];
+      }
+  }
+  float p[7], q[7];
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+    p[i] = -a[i][7], q[i] = -a[i][8];
+  // det(P + a Q), P = (p0..p6, 1, 0), Q = (q0..q6, 0, 1), with m_i = p_i + a q_i: m0 (m4 a - m5) - m1 (m3 a - m5 m6) + m2 (m3 - m4 m6)
+  const float t1[3] = {-p[5], p[4] - q[5], q[4]};
+  const float t2[3] = {-(p[5] * p[6]), p[3] - (p[5] * q[6] + q[5] * p[6]), q[3] - q[5] * q[6]};
+  const float t3[3] = {p[3] - p[4] * p[6], q[3] - (p[4] * q[6] + q[4] * p[6]), -(q[4] * q[6])};
+  const float A[4] = {p[0] * t1[0], p[0] * t1[1] + q[0] * t1[0], p[0] * t1[2] + q[0] * t1[1], q[0] * t1[2]};
+  const float B[4] = {p[1] * t2[0], p[1] * t2[1] + q[1] * t2[0], p[1] * t2[2] + q[1] * t2[1], q[1] * t2[2]};
+  const float C[4] = {p[2] * t3[0], p[2] * t3[1] + q[2] * t3[0], p[2] * t3[2] + q[2] * t3[1], q[2] * t3[2]};
+  float root[3];
+  const uint32_t cnt = cubic_roots((A[0] - B[0]) + C[0], (A[1] - B[1]) + C[1], (A[2] - B[2]) + C[2], (A[3] - B[3]) + C[3], root);
+  const float bad = __uint_as_float(0x7fc00000u);
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+  {
+    const float al = root[k];
+    float fh[9], g[9], F[9];
+#pragma unroll
+    for (int i = 0; i < 7; i++)
+      fh[i] = p[i] + al * q[i];
+    fh[7] = 1.0f, fh[8] = al;
+#pragma unroll
+    for (int r = 0; r < 3; r++) // F^ T_a
+    {
+      g[3 * r] = fh[3 * r] * sa, g[3 * r + 1] = fh[3 * r + 1] * sa;
+      g[3 * r + 2] = (fh[3 * r + 2] - fh[3 * r] * ua) - fh[3 * r + 1] * va;
+    }
+    uint32_t m = 0u;
+#pragma unroll
+    for (int col = 0; col < 3; col++) // T_b^T (F^ T_a)
+    {
+      F[col] = sb * g[col], F[3 + col] = sb * g[3 + col];
+      F[6 + col] = (g[6 + col] - ub * g[col]) - vb * g[3 + col];
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+      m = max(m, abs_bits(F[i]));
+    bool ok;
+    const float f = unit_scale(m, ok);
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+      M[k].f[i] = ok ? F[i] * f : bad;
+  }
+  return cnt;
+}
+
+// Sampson distance below the threshold, without a division: with l = F (xa, ya, 1), m = F^T (xb, yb, 1) and r = (xb, yb, 1) l, the
+// correspondence is an inlier iff r^2 < t^2 ((l0^2 + l1^2) + (m0^2 + m1^2)). A NaN anywhere fails the comparison.
+__device__ __forceinline__ bool is_inlier_f(const Fund &F, float4 c, float t2)
+{
+  const float l0 = (F.f[0] * c.x + F.f[1] * c.y) + F.f[2];
+  const float l1 = (F.f[3] * c.x + F.f[4] * c.y) + F.f[5];
+  const float l2 = (F.f[6] * c.x + F.f[7] * c.y) + F.f[8];
+  const float r = (c.z * l0 + c.w * l1) + l2;
+  const float m0 = (F.f[0] * c.z + F.f[3] * c.w) + F.f[6];
+  const float m1 = (F.f[1] * c.z + F.f[4] * c.w) + F.f[7];
+  const float g = (l0 * l0 + l1 * l1) + (m0 * m0 + m1 * m1);
+  return r * r < t2 * g;
+}
+
+__device__ __forceinline__ uint32_t solve_sample_f(const float4 *__restrict__ c, uint64_t seed_key, uint32_t slot, uint32_t hyp, uint32_t n, Fund (&M)[3])
+{
+  uint32_t idx[7];
+  draw_sample<7>(seed_key, slot, hyp, n, idx);
+  float4 sc[7];
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+    sc[i] = scaled(c[idx[i]]);
+  return solve_f7(sc, M);
+}
+
+// Stage 2 for the fundamental matrix: as k_ransac_score_h, three models per lane; key = count << 32 | ~(4 * hypothesis + root). Roots 1
+// and 2 are scored only when some lane of the wave has them (a wave-uniform branch; an absent root is all-NaN and counts nothing).
+__global__ void __launch_bounds__(256) k_ransac_score_f(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
+                                                        uint32_t n_stride, uint32_t max_n, uint32_t nb_hyp, uint32_t nblk, float t2, uint64_t seed_key,
+                                                        uint32_t *__restrict__ keys)
+{
+  __shared__ float4 tile[kHypPerBlock];
+  __shared__ unsigned long long wave_best[4];
+  const uint32_t slot = blockIdx.x / nblk, blk = blockIdx.x - slot * nblk;
+  const uint32_t tid = threadIdx.x;
+  uint32_t n = n_dev[(size_t)slot * n_stride];
+  n = n < max_n ? n : max_n;
+  uint32_t *kout = keys + 2u * (size_t)blockIdx.x;
+  if (n < 7u)
+  {
+    if (tid == 0)
+      kout[0] = 0u, kout[1] = 0u;
+    return;
+  }
+  const float4 *c = corr + (size_t)slot * corr_slot_stride;
+  const uint32_t hyp = blk * kHypPerBlock + tid;
+  const bool active = hyp < nb_hyp;
+  Fund M[3];
+  const uint32_t nroots = solve_sample_f(c, seed_key, slot, active ? hyp : 0u, n, M);
+  const bool any1 = __ballot(nroots > 1u) != 0ull, any2 = __ballot(nroots > 2u) != 0ull;
+  uint32_t cnt0 = 0, cnt1 = 0, cnt2 = 0;
+  for (uint32_t base = 0; base < n; base += kHypPerBlock)
+  {
+    __syncthreads();
+    if (base + tid < n)
+      tile[tid] = scaled(c[base + tid]);
+    __syncthreads();
+    const uint32_t m = n - base < kHypPerBlock ? n - base : kHypPerBlock;
+    for (uint32_t j = 0; j < m; j++)
+    {
+      const float4 q = tile[j]; // every lane reads the same 16 bytes: one broadcast LDS access
+      cnt0 += is_inlier_f(M[0], q, t2) ? 1u : 0u;
+      if (any1)
+        cnt1 += is_inlier_f(M[1], q, t2) ? 1u : 0u;
+      if (any2)
+        cnt2 += is_inlier_f(M[2], q, t2) ? 1u : 0u;
+    }
+  }
+  const uint32_t id = hyp * 4u;
+  unsigned long long key = ((unsigned long long)cnt0 << 32) | (unsigned long long)(~id);
+  const unsigned long long k1 = ((unsigned long long)cnt1 << 32) | (unsigned long long)(~(id + 1u));
+  const unsigned long long k2 = ((unsigned long long)cnt2 << 32) | (unsigned long long)(~(id + 2u));
+  key = k1 > key ? k1 : key;
+  key = k2 > key ? k2 : key;
+  key = wave_max_u64(active ? key : 0ull);
+  if ((tid & 63u) == 0u)
+    wave_best[tid >> 6] = key;
+  __syncthreads();
+  if (tid == 0)
+  {
+    for (int w = 1; w < 4; w++)
+      key = wave_best[w] > key ? wave_best[w] : key;
+    kout[0] = (uint32_t)key, kout[1] = (uint32_t)(key >> 32);
+  }
+}
+
+// Stage 3 for the fundamental matrix: the best key of the slot, the winner's model recomputed from its sample and root, brought to pixel
+// coordinates (powers of two: F_px = K F K with K = diag(2^-13, 2^-13, 1), times 2^26) and scaled again so that its largest entry lies in
+// [1, 2); result record (14 words: F[9], nb_matches, nb_inliers, best_hypothesis, best_root, valid) and one mask byte per correspondence.
+__global__ void __launch_bounds__(256) k_ransac_final_f(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
+                                                        uint32_t n_stride, uint32_t max_n, uint32_t nblk, float t2, uint64_t seed_key,
+                                                        const uint32_t *__restrict__ keys, uint32_t *__restrict__ results, uint8_t *__restrict__ masks,
+                                                        uint64_t mask_slot_stride)
+{
+  __shared__ unsigned long long wave_best[4];
+  const uint32_t slot = blockIdx.x, tid = threadIdx.x;
+  uint32_t n = n_dev[(size_t)slot * n_stride];
+  n = n < max_n ? n : max_n;
+  unsigned long long key = 0ull;
+  for (uint32_t b = tid; b < nblk; b += 256u)
+  {
+    const uint32_t *k = keys + 2u * ((size_t)slot * nblk + b);
+    const unsigned long long v = ((unsigned long long)k[1] << 32) | (unsigned long long)k[0];
+    key = v > key ? v : key;
+  }
+  key = wave_max_u64(key);
+  if ((tid & 63u) == 0u)
+    wave_best[tid >> 6] = key;
+  __syncthreads();
+  key = wave_best[0];
+  for (int w = 1; w < 4; w++)
+    key = wave_best[w] > key ? wave_best[w] : key;
+  const uint32_t cnt = (uint32_t)(key >> 32), id = ~(uint32_t)key, hyp = id >> 2, rt = id & 3u;
+  const float4 *c = corr + (size_t)slot * corr_slot_stride;
+  uint8_t *mask = masks + (size_t)slot * mask_slot_stride;
+  uint32_t *res = results + (size_t)slot * 14u;
+  bool valid = n >= 7u && cnt >= 8u;
+  Fund F = {};
+  float o[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (valid) // uniform over the workgroup
+  {
+    Fund M[3];
+    solve_sample_f(c, seed_key, slot, hyp, n, M);
+    F = M[0];
+#pragma unroll
+    for (int k = 1; k < 3; k++)
+#pragma unroll
+      for (int i = 0; i < 9; i++)
+        F.f[i] = rt == (uint32_t)k ? M[k].f[i] : F.f[i];
+    const float k1 = kCoordUnscale, k2 = kCoordUnscale * kCoordUnscale;
+    o[0] = F.f[0], o[1] = F.f[1], o[2] = F.f[2] * k1;
+    o[3] = F.f[3], o[4] = F.f[4], o[5] = F.f[5] * k1;
+    o[6] = F.f[6] * k1, o[7] = F.f[7] * k1, o[8] = F.f[8] * k2;
+    uint32_t m = 0u;
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+      m = max(m, abs_bits(o[i]));
+    const float f = unit_scale(m, valid);
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+      o[i] = o[i] * f;
+  }
+  for (uint32_t k = tid; k < n; k += 256u)
+    mask[k] = (valid && is_inlier_f(F, scaled(c[k]), t2)) ? 1u : 0u;
+  if (tid == 0)
+  {
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+      res[i] = valid ? __float_as_uint(o[i]) : 0u;
+    res[9] = n;
+    res[10] = valid ? cnt : 0u;
+    res[11] = valid ? hyp : 0u;
+    res[12] = valid ? rt : 0u;
+    res[13] = valid ? 1u : 0u;
+  }
+}
+
 uint64_t seed_key_of(uint64_t seed)
 {
   uint64_t z = seed + 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
+}
+
+using ScoreKernel = void (*)(const float4 *, uint64_t, const uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, float, uint64_t, uint32_t *);
+using FinalKernel = void (*)(const float4 *, uint64_t, const uint32_t *, uint32_t, uint32_t, uint32_t, float, uint64_t, const uint32_t *, uint32_t *, uint8_t *,
+                             uint64_t);
+
+// the refusals and the two launches of either model
+int ransac_launch(ScoreKernel score, FinalKernel final, const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n,
+                  uint32_t nslots, uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
+                  uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s)
+{
+  if (nslots < 1 || nb_hypotheses == 0 || nb_hypotheses > 65536u || !(threshold_px > 0.f) || !isfinite(threshold_px) ||
+      scratch_u32 < vksift_hip_ransac_scratch_u32(nslots, nb_hypotheses) || (corr_slot_stride & 15u) || ((uintptr_t)corr & 15u) || ((uintptr_t)results & 3u) ||
+      (nslots > 1 && (corr_slot_stride < 16u * (uint64_t)max_n || mask_slot_stride < max_n)))
+    return (int)hipErrorInvalidValue;
+  const uint32_t nblk = (nb_hypotheses + kHypPerBlock - 1u) / kHypPerBlock;
+  if ((uint64_t)nslots * nblk > 0x7fffffffull)
+    return (int)hipErrorInvalidValue;
+  const float ts = threshold_px * kCoordScale, t2 = ts * ts;
+  const uint64_t key = seed_key_of(seed);
+  hipLaunchKernelGGL(score, dim3(nslots * nblk), dim3(kHypPerBlock), 0, (hipStream_t)s, (const float4 *)corr, corr_slot_stride / 16u, n_dev, n_stride, max_n,
+                     nb_hypotheses, nblk, t2, key, scratch);
+  int e = (int)hipGetLastError();
+  if (e)
+    return e;
+  hipLaunchKernelGGL(final, dim3(nslots), dim3(256), 0, (hipStream_t)s, (const float4 *)corr, corr_slot_stride / 16u, n_dev, n_stride, max_n, nblk, t2, key,
+                     (const uint32_t *)scratch, (uint32_t *)results, masks, mask_slot_stride);
+  return (int)hipGetLastError();
 }
 
 } // namespace
@@ -362,22 +741,15 @@ extern "C"
                                    uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
                                    uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s)
   {
-    if (nslots < 1 || nb_hypotheses == 0 || nb_hypotheses > 65536u || !(threshold_px > 0.f) || !isfinite(threshold_px) ||
-        scratch_u32 < vksift_hip_ransac_scratch_u32(nslots, nb_hypotheses) || (corr_slot_stride & 15u) || ((uintptr_t)corr & 15u) || ((uintptr_t)results & 3u) ||
-        (nslots > 1 && (corr_slot_stride < 16u * (uint64_t)max_n || mask_slot_stride < max_n)))
-      return (int)hipErrorInvalidValue;
-    const uint32_t nblk = (nb_hypotheses + kHypPerBlock - 1u) / kHypPerBlock;
-    if ((uint64_t)nslots * nblk > 0x7fffffffull)
-      return (int)hipErrorInvalidValue;
-    const float ts = threshold_px * kCoordScale, t2 = ts * ts;
-    const uint64_t key = seed_key_of(seed);
-    hipLaunchKernelGGL(k_ransac_score_h, dim3(nslots * nblk), dim3(kHypPerBlock), 0, (hipStream_t)s, (const float4 *)corr, corr_slot_stride / 16u, n_dev, n_stride,
-                       max_n, nb_hypotheses, nblk, t2, key, scratch);
-    int e = (int)hipGetLastError();
-    if (e)
-      return e;
-    hipLaunchKernelGGL(k_ransac_final_h, dim3(nslots), dim3(256), 0, (hipStream_t)s, (const float4 *)corr, corr_slot_stride / 16u, n_dev, n_stride, max_n, nblk, t2,
-                       key, (const uint32_t *)scratch, (uint32_t *)results, masks, mask_slot_stride);
-    return (int)hipGetLastError();
+    return ransac_launch(k_ransac_score_h, k_ransac_final_h, corr, corr_slot_stride, n_dev, n_stride, max_n, nslots, nb_hypotheses, threshold_px, seed, results,
+                         masks, mask_slot_stride, scratch, scratch_u32, s);
+  }
+
+  int vksift_hip_ransac_fundamental(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
+                                    uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
+                                    uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s)
+  {
+    return ransac_launch(k_ransac_score_f, k_ransac_final_f, corr, corr_slot_stride, n_dev, n_stride, max_n, nslots, nb_hypotheses, threshold_px, seed, results,
+                         masks, mask_slot_stride, scratch, scratch_u32, s);
   }
 }

@@ -213,7 +213,7 @@ struct vksift_Instance_T
   uint32_t *d_filtered_n, *h_filtered_n;
   uint64_t filtered_slot_stride;
   uint32_t filtered_slots_used;
-  /* geometric verification (vksift_ext_verifyHomography, vksift_verify.c): the pairs of the last filtered matching, and scratch allocated on first use */
+  /* geometric verification (vksift_ext_verifyHomography / vksift_ext_verifyFundamental, vksift_verify.c): the pairs of the last filtered matching, and scratch allocated on first use */
   uint32_t *filt_ids;       /* 2 * batch_cap: buffers A then buffers B of the last vksift_ext_matchFeaturesFiltered */
   float *d_corr;            /* per slot: filtered_slot_stride bytes of {xa, ya, xb, yb} */
   uint8_t *d_vmask;         /* per slot: vmask_slot_stride bytes */
@@ -224,6 +224,10 @@ struct vksift_Instance_T
   uint32_t *h_vtab;         /* mapped pinned memory read by the gather launch: 4 words per slot, then the section tables (33 words each) */
   bool vtab_pending;
   uint32_t verify_slots_used;
+  /* the second model (vksift_ext_verifyFundamental) keeps results and masks of its own, so that both can be read after one matching */
+  uint8_t *d_fmask;            /* per slot: vmask_slot_stride bytes */
+  uint32_t *d_fres, *h_fres;   /* 14 words (vksift_ext_Fundamental) per slot */
+  uint32_t verify_f_slots_used;
   bool verify_timing_valid;
 
   /* ---- download staging. Batched download: the first vksift_downloadFeatures() after a detection of VKSIFT_DL_BATCH_MIN images and more

@@ -187,6 +187,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
     vksift_hip_event_record(inst->ev_desc_start, inst->stream); /* experiment: the next scale-space behind this matching, not beside it */
   inst->filtered_slots_used = 0;
   inst->verify_slots_used = 0;
+  inst->verify_f_slots_used = 0;
   inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
   if (filter)
   {

@@ -108,6 +108,7 @@ static const Block blocks[] = {
     LAZY(rev.matches, MEM_DEVICE), LAZY(rev.redo, MEM_DEVICE), LAZY(rev.match_n, MEM_DEVICE),
     LAZY(d_filtered, MEM_DEVICE), LAZY(d_filtered_n, MEM_DEVICE), LAZY(h_filtered_n, MEM_PINNED), LAZY(filt_ids, MEM_HEAP),
     LAZY(d_corr, MEM_DEVICE), LAZY(d_vmask, MEM_DEVICE), LAZY(d_vres, MEM_DEVICE), LAZY(d_vscratch, MEM_DEVICE), LAZY(h_vres, MEM_PINNED), LAZY(h_vtab, MEM_PINNED),
+    LAZY(d_fmask, MEM_DEVICE), LAZY(d_fres, MEM_DEVICE), LAZY(h_fres, MEM_PINNED),
     LAZY(d_dl, MEM_DEVICE), LAZY(h_dl, MEM_PINNED), LAZY(dl_row, MEM_HEAP), LAZY(h_post[0], MEM_PINNED), LAZY(h_post[1], MEM_PINNED),
 };
 #define N_BLOCKS (sizeof(blocks) / sizeof(blocks[0]))
