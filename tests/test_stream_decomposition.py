@@ -1,9 +1,12 @@
-"""The arithmetic of the single-pair matcher's stream decomposition (vulkansift_amd/csrc/hip/match.hip: stream_span, the piece loop of
-k_match_mfma, the piece count of k_match_merge), restated in Python and checked over many shapes: every (row block, B tile) pair
-is visited exactly once, the pieces of a row block are numbered 0..n-1 without gaps in increasing tile order, and no row block
-needs more partial lists than VKSIFT_HIP_MATCH_CHUNKS. (The kernels themselves are compared with the oracle by the -m gpu tests.)"""
+"""The arithmetic of the single-pair matcher's stream decomposition (vulkansift_amd/csrc/match_stream.h: stream_span, the piece walk
+stream_next of k_match_mfma and k_match_scan32, the piece count stream_pieces of k_match_merge and k_match_fix), restated in Python and
+checked over many shapes: every (row block, B tile) pair is visited exactly once, the pieces of a row block are numbered 0..n-1
+without gaps in increasing tile order, and no row block needs more partial lists than VKSIFT_HIP_MATCH_CHUNKS. The header itself is
+compiled into a host program and compared with the restatement on the same shapes, so the arithmetic checked here is the arithmetic
+the kernels execute. (The kernels themselves are compared with the oracle by the -m gpu tests.)"""
 import re
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -45,8 +48,11 @@ def merge_count(rb, tiles, span):
     return ((rb + 1) * tiles - 1) // span - (rb * tiles) // span + 1
 
 
-@pytest.mark.parametrize("na,nb", [(1, 2), (300, 33000), (1537, 2), (1537, 4097), (4000, 4000), (9000, 700), (33000, 5000), (50000, 50000),
-                                   (70001, 130), (100000, 100000), (257, 128), (256, 129), (1000000, 300)])
+SHAPES = [(1, 2), (300, 33000), (1537, 2), (1537, 4097), (4000, 4000), (9000, 700), (33000, 5000), (50000, 50000),
+          (70001, 130), (100000, 100000), (257, 128), (256, 129), (1000000, 300)]
+
+
+@pytest.mark.parametrize("na,nb", SHAPES)
 @pytest.mark.parametrize("G", [512, 608, 64])
 def test_every_tile_once_and_slots_dense(na, nb, G):
     ps, nblocks, tiles, span = pieces(na, nb, G)
@@ -73,3 +79,25 @@ def test_random_shapes():
         assert span * G >= nblocks * tiles                                       # the grid covers the list
         worst = max(merge_count(rb, tiles, span) for rb in {0, nblocks // 2, nblocks - 1})
         assert worst <= CHUNKS
+
+
+def test_header_agrees_with_the_restatement(tmp_path):
+    """csrc/match_stream.h, compiled with the host C++ compiler: stream_span, the full piece list of stream_next and stream_pieces of
+    every row block equal the Python restatement, for the parametrised shapes (every grid) and the 300 random shapes"""
+    exe = str(tmp_path / "stream_probe")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vulkansift_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "native", "stream_probe.cpp"), "-o", exe], check=True)
+    shapes = [(na, nb, G) for G in (512, 608, 64) for na, nb in SHAPES]
+    rng = np.random.default_rng(5)
+    shapes += [(int(rng.integers(1, 200000)), int(rng.integers(2, 200000)), int(rng.choice([64, 128, 512, 608]))) for _ in range(300)]
+    r = subprocess.run([exe], input="".join("%d %d %d 256 128\n" % s for s in shapes), capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    lines = iter(r.stdout.splitlines())
+    for na, nb, G in shapes:
+        ps, nblocks, tiles, span = pieces(na, nb, G)
+        assert next(lines).split() == ["S", str(span), str(nblocks), str(tiles)], (na, nb, G)
+        for piece in ps:
+            assert next(lines) == "P %d %d %d %d %d" % piece, (na, nb, G, piece)
+        counts = next(lines).split()
+        assert counts[0] == "M" and [int(c) for c in counts[1:]] == [merge_count(rb, tiles, span) for rb in range(nblocks)], (na, nb, G)
+    assert next(lines, None) is None

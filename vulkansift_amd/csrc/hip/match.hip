@@ -51,6 +51,7 @@
 #include <type_traits>
 
 #include "vksift_hip.h"
+#include "match_stream.h"
 
 namespace
 {
@@ -116,15 +117,6 @@ __global__ void k_slot_counts(const uint32_t *__restrict__ cache_n, uint32_t cac
   n_out[(size_t)slot * n_slot_stride + 1] = cache_n[(size_t)ids.b[slot] * cache_n_stride];
 }
 
-// Stream decomposition of the large single-pair matcher (k_match_mfma with `stream` set, k_match_merge): the list of
-// (row block, B tile) pairs, row block major, is cut into runs of `span` tiles, one per workgroup of a grid of G. A row block
-// is then covered by at most floor(tiles / span) + 2 runs, which must not exceed VKSIFT_HIP_MATCH_CHUNKS partial lists.
-__device__ __forceinline__ uint32_t stream_span(uint32_t nblocks, uint32_t tiles, uint32_t G)
-{
-  const uint32_t even = (nblocks * tiles + G - 1u) / G, floor_ = (tiles + (uint32_t)VKSIFT_HIP_MATCH_CHUNKS - 3u) / ((uint32_t)VKSIFT_HIP_MATCH_CHUNKS - 2u);
-  return max(max(even, floor_), 1u);
-}
-
 // compute units of the current device (workgroup slots of the stream decomposition)
 uint32_t device_cus()
 {
@@ -146,28 +138,24 @@ uint32_t device_cus()
   return cached[dev];
 }
 
-// VKSIFT_MATCH_SCAN=0: single pairs with large reference sets take the stream-decomposed pruning kernel instead of the cell scan
-bool match_use_scan()
+// The VKSIFT_MATCH_*=0 switches (A/B and the bit-identity matrix only, same results), read once:
+//   VKSIFT_MATCH_SCAN=0: single pairs with large reference sets take the stream-decomposed pruning kernel instead of the cell scan
+//   VKSIFT_MATCH_PK=0: no packed-key kernel, batches of pairs go through the pruning kernels only
+enum MatchSwitch
 {
-  static int cached = -1;
-  if (cached < 0)
-  {
-    const char *e = getenv("VKSIFT_MATCH_SCAN");
-    cached = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return cached == 1;
-}
-
-// VKSIFT_MATCH_PK=0: batches of pairs go through the pruning kernels only (A/B switch, same results)
-bool match_use_pk()
+  MATCH_SCAN,
+  MATCH_PK
+};
+bool match_use(MatchSwitch w)
 {
-  static int cached = -1;
-  if (cached < 0)
+  static const char *const name[2] = {"VKSIFT_MATCH_SCAN", "VKSIFT_MATCH_PK"};
+  static int cached[2] = {-1, -1};
+  if (cached[w] < 0)
   {
-    const char *e = getenv("VKSIFT_MATCH_PK");
-    cached = (e && atoi(e) == 0) ? 0 : 1;
+    const char *e = getenv(name[w]);
+    cached[w] = (e && atoi(e) == 0) ? 0 : 1;
   }
-  return cached == 1;
+  return cached[w] == 1;
 }
 
 struct Top2
@@ -175,7 +163,7 @@ struct Top2
   uint32_t q1, k1, q2, k2; // squared distances and index keys of best / second
 };
 
-constexpr uint32_t Q_EXACT = 1u << 22;
+constexpr uint32_t Q_EXACT = 1u << 22; // below this, integer order of d2 == order of sqrtf(float(d2))
 constexpr uint32_t SYNC_TILES = 8;  // tiles between two exchanges of the row-wide pruning bound in the steady state (power of two)
 
 // Accumulator-space form of the pruning test (see k_match_mfma): D > acc_threshold(an, eff) is implied by an + par - 2 D < eff.
@@ -200,7 +188,7 @@ __device__ __forceinline__ void merge_ror(uint32_t &m1, uint32_t &m2)
   const uint32_t hi = max(m1, r1);
   m1 = min(m1, r1);
   m2 = min(hi, min(m2, r2));
-} // below this, integer order of d2 == order of sqrtf(float(d2))
+}
 
 // median of three = the second largest of {m1, m2, x} when m1 >= m2 (v_med3_u32)
 __device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) { return max(min(a, b), min(max(a, b), c)); }
@@ -233,9 +221,190 @@ __device__ __forceinline__ Top2 merge2(const Top2 &a, const Top2 &b)
   return r;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The steps the kernels below share, each defined once.
+
+// What a workgroup matches: the descriptor rows, shifted norms, record and flag arrays of one slot and its row counts.
+struct SlotView
+{
+  const uint32_t *desc_a, *desc_b, *norm_a, *norm_b;
+  uint32_t *matches, *redo;
+  uint32_t na, nb;
+};
+
+// Row counts produced on the device (asynchronous path); a reference set is at least two rows (quirk Q6: b[0], b[1] are read unconditionally)
+__device__ __forceinline__ void device_counts(const uint32_t *n, uint32_t &na, uint32_t &nb)
+{
+  na = n[0];
+  nb = n[1] < 2u ? 2u : n[1];
+}
+
+// `base` (the launch's arguments) moved to `slot`: cache entries for descriptors and norms when ss.use_ids, the slot's own record and
+// flag arrays, and the device-side counts when there are any. The size regime a kernel serves is tested by the kernel.
+__device__ __forceinline__ SlotView bind_slot(const SlotView &base, uint32_t slot, const uint32_t *n_dev, const SlotStrides &ss, const SlotIds &ids)
+{
+  SlotView v = base;
+  if (n_dev)
+    device_counts(n_dev + (size_t)slot * ss.n, v.na, v.nb);
+  const uint32_t ea = ss.use_ids ? ids.a[slot] : slot, eb = ss.use_ids ? ids.b[slot] : slot;
+  v.desc_a += (size_t)ea * ss.desc_a, v.desc_b += (size_t)eb * ss.desc_b;
+  v.norm_a += (size_t)ea * ss.norm_a, v.norm_b += (size_t)eb * ss.norm_b;
+  v.matches += (size_t)slot * ss.matches;
+  v.redo += (size_t)slot * ss.redo;
+  return v;
+}
+
+typedef int v16i __attribute__((ext_vector_type(16))); // accumulator of v_mfma_i32_32x32x32_i8
+
+__device__ __forceinline__ v4i to_int8(uint4 v) { return v4i{(int)(v.x ^ 0x80808080u), (int)(v.y ^ 0x80808080u), (int)(v.z ^ 0x80808080u), (int)(v.w ^ 0x80808080u)}; }
+
+// Query fragments of row r (the caller clamps r to na - 1), XOR 0x80 -> int8. 16x16x64 MFMA: lane group grp supplies K bytes
+// grp*16.. of each 64-byte half; 32x32x32 MFMA: lane half h supplies K bytes (2 s + h)*16.. of step s.
+__device__ __forceinline__ void load_query_16x64(const uint32_t *desc_a, uint32_t r, int grp, v4i (&f)[2])
+{
+  const uint4 *p = (const uint4 *)(desc_a + (size_t)r * 32);
+  f[0] = to_int8(p[grp]), f[1] = to_int8(p[4 + grp]);
+}
+__device__ __forceinline__ void load_query_32x32(const uint32_t *desc_a, uint32_t r, int h, v4i (&f)[4])
+{
+  const uint4 *p = (const uint4 *)(desc_a + (size_t)r * 32);
+#pragma unroll
+  for (int s = 0; s < 4; s++)
+    f[s] = to_int8(p[2 * s + h]);
+}
+
+// position of 16-byte chunk c of staged row r inside the row (LDS swizzle): B tiles sit in LDS without padding, 16-byte chunks
+// XOR-swizzled by ((row >> 1) & 7), so the four 16-lane groups of a ds_read_b128 hit 16 distinct bank quads (the 144-byte pitch
+// of k_match_mfma: 33 % conflict cycles, SQ_LDS_BANK_CONFLICT)
+__device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 7); }
+
+// The two LDS layouts of a staged B tile: where 16-byte chunk c of row r goes
+struct LdsPitch144 // 16x16x64 kernels
+{
+  static __device__ __forceinline__ uint8_t *at(uint8_t *s_b, int r, int c) { return s_b + r * B_STRIDE + c * 16; }
+};
+struct LdsSwizzled // 32x32x32 kernels
+{
+  static __device__ __forceinline__ uint8_t *at(uint8_t *s_b, int r, int c) { return s_b + r * 128 + swz(r, c) * 16; }
+};
+
+// B-tile pipeline: a tile of BTT rows travels global -> registers -> LDS one tile ahead of the MFMAs, so that the global-load
+// latency of tile t+1 hides behind the MFMA + epilogue work of tile t (a second register set for two tiles ahead costs the 64-row
+// form of k_match_mfma an occupancy step and gains the others nothing: measured). NTH threads, NLD 16-byte loads each.
+template <int NLD>
+struct TileRegs
+{
+  uint4 d[NLD];
+  uint32_t n; // shifted norm of row t0 + threadIdx.x (threads below BTT)
+};
+template <int NTH, int BTT>
+__device__ __forceinline__ void fetch_tile(TileRegs<(BTT * 8 + NTH - 1) / NTH> &pf, const uint32_t *desc_b, const uint32_t *norm_b, uint32_t nb, uint32_t t0)
+{
+#pragma unroll
+  for (int q = 0; q < (BTT * 8 + NTH - 1) / NTH; q++)
+  {
+    const int i = threadIdx.x + q * NTH;
+    const int r = i >> 3, c = i & 7;
+    pf.d[q] = make_uint4(0, 0, 0, 0);
+    if (i < BTT * 8 && t0 + r < nb)
+      pf.d[q] = ((const uint4 *)(desc_b + (size_t)(t0 + r) * 32))[c];
+  }
+  pf.n = (threadIdx.x < BTT && t0 + threadIdx.x < nb) ? norm_b[t0 + threadIdx.x] : 0u;
+}
+// Stage a fetched tile (zero rows beyond nb) into `s_b`, converting to int8; column_word(x, n, live) stores what the kernel keeps
+// per column x of the tile beside it (n = shifted norm, 0 beyond nb; live = the column exists).
+template <int NTH, int BTT, typename Layout, typename ColumnWord>
+__device__ __forceinline__ void stage_tile(const TileRegs<(BTT * 8 + NTH - 1) / NTH> &pf, uint8_t *s_b, uint32_t nb, uint32_t t0, ColumnWord column_word)
+{
+#pragma unroll
+  for (int q = 0; q < (BTT * 8 + NTH - 1) / NTH; q++)
+  {
+    const int i = threadIdx.x + q * NTH;
+    const int r = i >> 3, c = i & 7;
+    uint4 v = pf.d[q];
+    v.x ^= 0x80808080u, v.y ^= 0x80808080u, v.z ^= 0x80808080u, v.w ^= 0x80808080u;
+    if (i < BTT * 8)
+      *(uint4 *)Layout::at(s_b, r, c) = v;
+  }
+  if ((int)threadIdx.x < BTT)
+    column_word((int)threadIdx.x, pf.n, t0 + threadIdx.x < nb);
+}
+
+// the Top2 of lane (lane ^ x)
+__device__ __forceinline__ Top2 shfl_xor_top2(const Top2 &s, int x)
+{
+  Top2 o;
+  o.q1 = __shfl_xor(s.q1, x, 64), o.k1 = __shfl_xor(s.k1, x, 64);
+  o.q2 = __shfl_xor(s.q2, x, 64), o.k2 = __shfl_xor(s.k2, x, 64);
+  return o;
+}
+
+// One record {a index, best, second, distances as float bits} at m. swap: quirk Q7, d(b0) == d(b1) relabels columns 0 and 1.
+__device__ __forceinline__ void write_record_f(uint32_t *m, uint32_t a_index, uint32_t k1, uint32_t k2, float d1, float d2, bool swap)
+{
+  m[0] = a_index;
+  m[1] = (swap && k1 < 2) ? (k1 ^ 1u) : k1;
+  m[2] = (swap && k2 < 2) ? (k2 ^ 1u) : k2;
+  m[3] = __float_as_uint(d1);
+  m[4] = __float_as_uint(d2);
+}
+__device__ __forceinline__ void write_record(uint32_t *m, uint32_t a_index, const Top2 &s, bool swap)
+{
+  write_record_f(m, a_index, s.k1, s.k2, sqrtf((float)s.q1), sqrtf((float)s.q2), swap);
+}
+
+// A partial top-2 list of row r in slot `chunk` of `nchunks`: [row][chunk][4], then one flag word per (row, chunk): bit0 = Q7 swap,
+// bit1 = redo. k_match_merge combines them.
+__device__ __forceinline__ void write_partial(uint32_t *partial, uint32_t na, uint32_t nchunks, uint32_t r, uint32_t chunk, const Top2 &s, uint32_t flags)
+{
+  uint32_t *pp = partial + ((size_t)r * nchunks + chunk) * 4;
+  pp[0] = s.q1, pp[1] = s.k1, pp[2] = s.q2, pp[3] = s.k2;
+  partial[(size_t)na * nchunks * 4 + (size_t)r * nchunks + chunk] = flags;
+}
+
+// The reference's float loop (Get2NearestNeighbors.comp:43-103) for the two replay kernels: the row's descriptor words in registers
+// and |a|^2, the float distance to a row of B, the strict-'<' insertion of a scan in index order.
+__device__ __forceinline__ uint32_t replay_load_row(const uint32_t *desc_a, uint32_t row, uint32_t (&a)[32])
+{
+  uint32_t na2 = 0;
+#pragma unroll
+  for (int j = 0; j < 32; j++)
+  {
+    a[j] = desc_a[(size_t)row * 32 + j];
+    na2 = __builtin_amdgcn_udot4(a[j], a[j], na2, false);
+  }
+  return na2;
+}
+__device__ __forceinline__ float replay_dist(const uint32_t (&a)[32], uint32_t na2, const uint32_t *desc_b, uint32_t bi)
+{
+  const uint32_t *pb = desc_b + (size_t)bi * 32;
+  uint32_t dot = 0, nb2 = 0;
+#pragma unroll
+  for (int j = 0; j < 32; j++)
+  {
+    const uint32_t v = pb[j];
+    dot = __builtin_amdgcn_udot4(a[j], v, dot, false);
+    nb2 = __builtin_amdgcn_udot4(v, v, nb2, false);
+  }
+  return sqrtf((float)(na2 + nb2 - 2u * dot));
+}
+struct ReplayTop2
+{
+  float d1, d2;
+  uint32_t i1, i2;
+};
+__device__ __forceinline__ ReplayTop2 replay_insert(const ReplayTop2 &t, float d, uint32_t bi)
+{
+  if (d < t.d1)
+    return ReplayTop2{d, t.d1, bi, t.i1};
+  if (d < t.d2)
+    return ReplayTop2{t.d1, d, t.i1, bi};
+  return t;
+}
+
 // AT = 16-row A tiles per wave. Block = 4 waves = 64*AT A rows; B streams through LDS.
-// gridDim.z > 1: B is split into gridDim.z chunks of whole 64-row tiles; every chunk writes its partial top-2 per A row to
-// `partial` ([row][chunk][4], then one flag word per (row, chunk): bit0 = Q7 swap, bit1 = redo) and k_match_merge combines them.
+// gridDim.z > 1: B is split into gridDim.z chunks of whole BTT-row tiles; every chunk writes its partial top-2 per A row to
+// `partial` (write_partial) and k_match_merge combines them.
 template <int AT, int NW = 4, int BTT = BT>
 __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restrict__ desc_a, const uint32_t *__restrict__ norm_a, uint32_t na,
                                                     uint32_t a_index_base, const uint32_t *__restrict__ desc_b, const uint32_t *__restrict__ norm_b,
@@ -243,11 +412,9 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
                                                     const uint32_t *__restrict__ n_dev, uint32_t na_lo, uint32_t na_hi, SlotStrides ss,
                                                     uint32_t *__restrict__ partial, SlotIds ids, uint32_t stream)
 {
-  // stream != 0 (single pair, grid = (G, 1, 1)): the (row block, B tile) pairs, row block major, are cut into G equal runs of
-  // `span` tiles (stream_span); a workgroup works through its run, which may end one row block and start the next. Every
-  // (row block, workgroup) piece writes a partial list (slot = workgroup - first workgroup of the block), k_match_merge
-  // combines them. All resident workgroups get the same number of tiles whatever N_A is; a grid of row blocks x chunks
-  // leaves up to a third of the CUs' workgroup slots idle (measured: 588 workgroups on 768 slots at 50k x 50k).
+  // stream != 0 (single pair, grid = (G, 1, 1)): the stream decomposition of match_stream.h; a workgroup works through its run
+  // of tiles piece by piece, k_match_merge combines the pieces' partial lists. A grid of row blocks x chunks leaves up to a third
+  // of the CUs' workgroup slots idle (measured: 588 workgroups on 768 slots at 50k x 50k).
   const uint32_t nchunks = stream ? (uint32_t)VKSIFT_HIP_MATCH_CHUNKS : gridDim.z;
   uint32_t chunk = blockIdx.z;
   // ss.slot_fast: grid = (slots, row blocks) — see the batched launch
@@ -257,25 +424,14 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
   // for a batch of small sets every workgroup reads a few counts and ends (a grid sized for the capacity put thousands of
   // idle workgroups in front of the next detection's launches)
   const uint32_t slot0 = ss.slot_fast ? blockIdx.x : blockIdx.y, slot_step = ss.slot_fast ? gridDim.x : gridDim.y;
-  const uint32_t *const desc_a_0 = desc_a, *const desc_b_0 = desc_b, *const norm_a_0 = norm_a, *const norm_b_0 = norm_b, *const n_dev_0 = n_dev;
-  uint32_t *const matches_0 = matches, *const redo_0 = redo;
+  const SlotView base{desc_a, desc_b, norm_a, norm_b, matches, redo, na, nb};
   for (uint32_t slot = slot0; slot == slot0 || slot < ss.nslots_loop; slot += slot_step)
   {
-  const uint32_t ea = ss.use_ids ? ids.a[slot] : slot, eb = ss.use_ids ? ids.b[slot] : slot;
-  desc_a = desc_a_0 + (size_t)ea * ss.desc_a, desc_b = desc_b_0 + (size_t)eb * ss.desc_b;
-  norm_a = norm_a_0 + (size_t)ea * ss.norm_a, norm_b = norm_b_0 + (size_t)eb * ss.norm_b;
-  matches = matches_0 + (size_t)slot * ss.matches;
-  redo = redo_0 + (size_t)slot * ss.redo;
-  if (n_dev_0)
-  {
-    n_dev = n_dev_0 + (size_t)slot * ss.n;
-    // asynchronous path: the row counts were produced on the device by k_gather_sections; this instantiation only
-    // serves na in (na_lo, na_hi] (the host launches one kernel per regime, the others skip the slot here)
-    na = n_dev[0];
-    nb = n_dev[1] < 2u ? 2u : n_dev[1];
-    if (na <= na_lo || na > na_hi || nb <= ss.pk_nb_max)
-      continue;
-  }
+  const SlotView v = bind_slot(base, slot, n_dev, ss, ids);
+  // asynchronous path: the row counts were produced on the device by k_gather_sections; this instantiation only
+  // serves na in (na_lo, na_hi] (the host launches one kernel per regime, the others skip the slot here)
+  if (n_dev && (v.na <= na_lo || v.na > na_hi || v.nb <= ss.pk_nb_max))
+    continue;
   // Operand roles are swapped with respect to the textbook A x B^T: the B descriptors are the MFMA's A operand and the query
   // rows its B operand, so the 16x16 result block is indexed [B column][A row] and lane (col = lane & 15, grp = lane >> 4)
   // holds, for ITS A row `col` of the tile, the four B columns grp*4 + j of the block. Consequences:
@@ -292,10 +448,10 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 15, grp = lane >> 4;
-  const uint32_t tiles = (nb + BTT - 1) / BTT, tiles_per_chunk = (tiles + gridDim.z - 1) / gridDim.z;
+  const uint32_t tiles = (v.nb + BTT - 1) / BTT, tiles_per_chunk = (tiles + gridDim.z - 1) / gridDim.z;
   uint32_t tb = chunk * tiles_per_chunk * BTT;
-  uint32_t te = min(nb, tb + tiles_per_chunk * BTT);
-  const uint32_t nblocks = (na + 16u * NW * AT - 1u) / (16u * NW * AT);
+  uint32_t te = min(v.nb, tb + tiles_per_chunk * BTT);
+  const uint32_t nblocks = (v.na + 16u * NW * AT - 1u) / (16u * NW * AT);
   const uint32_t span = stream ? stream_span(nblocks, tiles, gridDim.x) : 0u;
   uint32_t pos = blockIdx.x * span;
   const uint32_t pos_end = min(pos + span, nblocks * tiles);
@@ -307,13 +463,11 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
     {
       if (pos >= pos_end)
         break;
-      rb = pos / tiles;
-      const uint32_t t_first = pos - rb * tiles, t_cnt = min(tiles - t_first, pos_end - pos);
-      tb = t_first * BTT, te = min(nb, (t_first + t_cnt) * BTT);
-      chunk = blockIdx.x - (rb * tiles) / span;
-      pos += t_cnt;
+      const stream_piece p = stream_next(&pos, pos_end, tiles, span, blockIdx.x);
+      rb = p.rb, chunk = p.slot;
+      tb = p.t_first * BTT, te = min(v.nb, (p.t_first + p.t_cnt) * BTT);
     }
-    else if (rb * (16u * NW * AT) >= na)
+    else if (rb * (16u * NW * AT) >= v.na)
       break;
     const uint32_t row_base = (rb * NW + wave) * (16 * AT);
 
@@ -324,13 +478,10 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
     for (int t = 0; t < AT; t++)
     {
       uint32_t r = row_base + t * 16 + col;
-      if (r >= na)
-        r = na - 1;
-      const uint4 *p = (const uint4 *)(desc_a + (size_t)r * 32);
-      uint4 v0 = p[grp], v1 = p[4 + grp];
-      afrag[t][0] = v4i{(int)(v0.x ^ 0x80808080u), (int)(v0.y ^ 0x80808080u), (int)(v0.z ^ 0x80808080u), (int)(v0.w ^ 0x80808080u)};
-      afrag[t][1] = v4i{(int)(v1.x ^ 0x80808080u), (int)(v1.y ^ 0x80808080u), (int)(v1.z ^ 0x80808080u), (int)(v1.w ^ 0x80808080u)};
-      an[t] = norm_a[r];
+      if (r >= v.na)
+        r = v.na - 1;
+      load_query_16x64(v.desc_a, r, grp, afrag[t]);
+      an[t] = v.norm_a[r];
     }
 
     Top2 st[AT];
@@ -349,50 +500,18 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
     uint32_t swap_bits = 0;  // bit t: d2(b0) == d2(b1) for that A row (quirk Q7)
     uint32_t risky_bits = 0; // bit t: a candidate >= 2^22 was inserted -> the row goes to k_match_redo
 
-    // B tiles are prefetched one tile ahead into registers (2 x 16 B per thread) so that the global-load latency of
-    // tile t+1 hides behind the MFMA + epilogue work of tile t.
-    // B tiles travel global -> registers -> LDS one tile ahead of the MFMAs (a second register set for two tiles ahead costs
-    // the 64-row form an occupancy step and gains the others nothing: measured)
-    constexpr int NTH = 64 * NW, NLD = (BTT * 8 + NTH - 1) / NTH;
-    struct TileRegs
-    {
-      uint4 d[NLD];
-      uint32_t n;
-    };
-    TileRegs pf0;
-    auto fetch_tile = [&](uint32_t t0, TileRegs &pf) {
-#pragma unroll
-      for (int q = 0; q < NLD; q++)
-      {
-        int i = threadIdx.x + q * NTH;
-        int r = i >> 3, c = i & 7;
-        pf.d[q] = make_uint4(0, 0, 0, 0);
-        if (i < BTT * 8 && t0 + r < nb)
-          pf.d[q] = ((const uint4 *)(desc_b + (size_t)(t0 + r) * 32))[c];
-      }
-      pf.n = (threadIdx.x < BTT && t0 + threadIdx.x < nb) ? norm_b[t0 + threadIdx.x] : 0u;
-    };
-    // stage a fetched tile (zero beyond nb) into buffer `bufi`, converting to int8
-    auto stage_tile = [&](uint32_t t0, int bufi, const TileRegs &pf) {
-#pragma unroll
-      for (int q = 0; q < NLD; q++)
-      {
-        int i = threadIdx.x + q * NTH;
-        int r = i >> 3, c = i & 7;
-        uint4 v = pf.d[q];
-        v.x ^= 0x80808080u, v.y ^= 0x80808080u, v.z ^= 0x80808080u, v.w ^= 0x80808080u;
-        if (i < BTT * 8)
-          *(uint4 *)(s_b2[bufi] + r * B_STRIDE + c * 16) = v;
-      }
-      if (threadIdx.x < BTT)
-      {
-        s_nb2[bufi][threadIdx.x] = pf.n;
-        s_nbh2[bufi][threadIdx.x] = t0 + threadIdx.x < nb ? -(int)(pf.n >> 1) : ACC_DEAD; // te is nb or a tile boundary: < te inside a tile == < nb
-      }
+    constexpr int NTH = 64 * NW;
+    TileRegs<(BTT * 8 + NTH - 1) / NTH> pf0;
+    auto fetch = [&](uint32_t t0) { fetch_tile<NTH, BTT>(pf0, v.desc_b, v.norm_b, v.nb, t0); };
+    auto stage = [&](uint32_t t0, int bufi) {
+      stage_tile<NTH, BTT, LdsPitch144>(pf0, s_b2[bufi], v.nb, t0, [&](int x, uint32_t n, bool live) {
+        s_nb2[bufi][x] = n;
+        s_nbh2[bufi][x] = live ? -(int)(n >> 1) : ACC_DEAD; // te is nb or a tile boundary: < te inside a tile == < nb
+      });
     };
     __syncthreads(); // the previous row block has finished reading both buffers
-    fetch_tile(tb, pf0);
-    stage_tile(tb, 0, pf0);
+    fetch(tb);
+    stage(tb, 0);
     __syncthreads();
 
     int buf = 0;
@@ -400,7 +519,7 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
     {
       const bool more = t0 + BTT < te;
       if (more)
-        fetch_tile(t0 + BTT, pf0); // in flight during this tile's MFMAs
+        fetch(t0 + BTT); // in flight during this tile's MFMAs
       const uint8_t *s_b = s_b2[buf];
       const int *s_nbh = s_nbh2[buf];
       const uint32_t *s_nb = s_nb2[buf];
@@ -452,7 +571,7 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
           {
             // columns beyond B carry ACC_DEAD accumulators: they only get here in the first block (B is padded to >= 2 rows,
             // so columns 0 and 1 are always real)
-            if (!(acc[t][j] > thr[t]) || bc0 + j >= nb)
+            if (!(acc[t][j] > thr[t]) || bc0 + j >= v.nb)
               continue;
             // (with a Q7 tie the two columns keep their arrival keys 0, 1 — equal d2, so "key 0 first" already is the order
             // index 1, index 0 once the final k ^ 1 of the swapped rows is applied)
@@ -490,7 +609,7 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
         }
       }
       if (more)
-        stage_tile(t0 + BTT, buf ^ 1, pf0); // nobody reads that buffer any more (barrier at the end of the previous tile)
+        stage(t0 + BTT, buf ^ 1); // nobody reads that buffer any more (barrier at the end of the previous tile)
       __syncthreads();
     }
 
@@ -505,31 +624,17 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
       Top2 s = st[t];
 #pragma unroll
       for (int x = 16; x <= 32; x <<= 1)
-      {
-        Top2 o;
-        o.q1 = __shfl_xor(s.q1, x, 64), o.k1 = __shfl_xor(s.k1, x, 64);
-        o.q2 = __shfl_xor(s.q2, x, 64), o.k2 = __shfl_xor(s.k2, x, 64);
-        s = merge2(s, o);
-      }
+        s = merge2(s, shfl_xor_top2(s, x));
       const uint32_t r = row_base + t * 16 + col;
       const uint32_t sw = (swap_bits >> t) & 1u, rk = (risky_bits >> t) & 1u;
-      if (grp == 0 && r < na)
+      if (grp == 0 && r < v.na)
       {
         if (nchunks > 1)
-        {
-          uint32_t *pp = partial + ((size_t)r * nchunks + chunk) * 4;
-          pp[0] = s.q1, pp[1] = s.k1, pp[2] = s.q2, pp[3] = s.k2;
-          partial[(size_t)na * nchunks * 4 + (size_t)r * nchunks + chunk] = sw | (rk << 1);
-        }
+          write_partial(partial, v.na, nchunks, r, chunk, s, sw | (rk << 1));
         else
         {
-          uint32_t *m = matches + (size_t)r * 5;
-          m[0] = a_index_base + r;
-          m[1] = (sw && s.k1 < 2) ? (s.k1 ^ 1u) : s.k1;
-          m[2] = (sw && s.k2 < 2) ? (s.k2 ^ 1u) : s.k2;
-          m[3] = __float_as_uint(sqrtf((float)s.q1));
-          m[4] = __float_as_uint(sqrtf((float)s.q2));
-          redo[r] = rk;
+          write_record(v.matches + (size_t)r * 5, a_index_base + r, s, sw);
+          v.redo[r] = rk;
         }
       }
     }
@@ -538,19 +643,10 @@ __global__ void __launch_bounds__(64 * NW) k_match_mfma(const uint32_t *__restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// shared by the v_mfma_i32_32x32x32_i8 kernels below (k_match_scan32, k_match_pk)
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-// position of 16-byte chunk c of staged row r inside the row (LDS swizzle): B tiles sit in LDS without padding, 16-byte chunks
-// XOR-swizzled by ((row >> 1) & 7), so the four 16-lane groups of a ds_read_b128 hit 16 distinct bank quads (the 144-byte pitch
-// of k_match_mfma: 33 % conflict cycles, SQ_LDS_BANK_CONFLICT)
-__device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 7); }
-
-// ---------------------------------------------------------------------------------------------------------------------------
 // k_match_scan32 + k_match_fix + k_match_redo_rows: the matcher for LARGE reference sets (beyond VKSIFT_HIP_MATCH_PK_NB rows).
 //
 // Every pruning kernel above pays for an insertion with a wave-wide detour, and a row sees ~2 ln N of them whatever the bound
-// (k_match_mfma: 7 of its 10 issued instructions per MFMA are that detour; k_match32: 9 of 12). This scan has no detour and no
+// (k_match_mfma: 7 of its 10 issued instructions per MFMA are that detour). This scan has no detour and no
 // index arithmetic at all. A lane (one query row per tile, 16 accumulators per 32-column sub-block = one CELL) only keeps, branch
 // free, its two best cells: the largest accumulator of the sub-block (8 v_max3) folded into (M1, cell1, M2, cell2) by compares and
 // selects — 20 VALU per 4 MFMAs (128 matrix-pipe cycles). Which columns of those cells are the two nearest neighbours, and their
@@ -585,7 +681,7 @@ __device__ __forceinline__ void cell_update(Cell3 &s, int m, uint32_t idx)
   s.m1 = max(s.m1, m);
 }
 
-// Partial lists: 16 words per (row, piece): per lane h two uint4 [m1 i1 m2 i2][m3 i3 m4 -]. Work decomposition, staging and LDS layout of k_match32.
+// Partial lists: 16 words per (row, piece): per lane h two uint4 [m1 i1 m2 i2][m3 i3 m4 -]. Stream decomposition (match_stream.h), swizzled B tiles.
 template <int AT, int NW, int BTT, int PIPE = 1>
 __global__ void __launch_bounds__(64 * NW) k_match_scan32(const uint32_t *__restrict__ desc_a, uint32_t na, const uint32_t *__restrict__ desc_b,
                                                       const uint32_t *__restrict__ norm_b, uint32_t nb, uint32_t *__restrict__ partial,
@@ -606,47 +702,18 @@ __global__ void __launch_bounds__(64 * NW) k_match_scan32(const uint32_t *__rest
   uint32_t pos = blockIdx.x * span;
   const uint32_t pos_end = min(pos + span, nblocks * tiles);
 
-  constexpr int NTH = 64 * NW, NLD = (BTT * 8 + NTH - 1) / NTH;
-  struct TileRegs
-  {
-    uint4 d[NLD];
-    uint32_t n;
-  };
-  auto fetch_tile = [&](uint32_t t0, TileRegs &pf) {
-#pragma unroll
-    for (int q = 0; q < NLD; q++)
-    {
-      const int i = threadIdx.x + q * NTH;
-      const int r = i >> 3, c = i & 7;
-      pf.d[q] = make_uint4(0, 0, 0, 0);
-      if (i < BTT * 8 && t0 + r < nb)
-        pf.d[q] = ((const uint4 *)(desc_b + (size_t)(t0 + r) * 32))[c];
-    }
-    pf.n = (threadIdx.x < BTT && t0 + threadIdx.x < nb) ? norm_b[t0 + threadIdx.x] : 0u;
-  };
-  auto stage_tile = [&](uint32_t t0, int bufi, const TileRegs &pf) {
-#pragma unroll
-    for (int q = 0; q < NLD; q++)
-    {
-      const int i = threadIdx.x + q * NTH;
-      const int r = i >> 3, c = i & 7;
-      uint4 v = pf.d[q];
-      v.x ^= 0x80808080u, v.y ^= 0x80808080u, v.z ^= 0x80808080u, v.w ^= 0x80808080u;
-      if (i < BTT * 8)
-        *(uint4 *)(s_b2[bufi] + r * 128 + swz(r, c) * 16) = v;
-    }
-    if ((int)threadIdx.x < BTT)
-      s_nbh2[bufi][threadIdx.x] = t0 + threadIdx.x < nb ? -(int)(pf.n >> 1) : ACC_DEAD;
+  constexpr int NTH = 64 * NW;
+  TileRegs<(BTT * 8 + NTH - 1) / NTH> pf0;
+  auto fetch = [&](uint32_t t0) { fetch_tile<NTH, BTT>(pf0, desc_b, norm_b, nb, t0); };
+  auto stage = [&](uint32_t t0, int bufi) {
+    stage_tile<NTH, BTT, LdsSwizzled>(pf0, s_b2[bufi], nb, t0, [&](int x, uint32_t n, bool live) { s_nbh2[bufi][x] = live ? -(int)(n >> 1) : ACC_DEAD; });
   };
 
   while (pos < pos_end)
   {
-    const uint32_t rb = pos / tiles;
-    const uint32_t t_first = pos - rb * tiles, t_cnt = min(tiles - t_first, pos_end - pos);
-    const uint32_t tb = t_first * BTT, te = min(nb, (t_first + t_cnt) * BTT);
-    const uint32_t chunk = blockIdx.x - (rb * tiles) / span;
-    pos += t_cnt;
-    const uint32_t row_base = (rb * NW + wave) * (32 * AT);
+    const stream_piece p = stream_next(&pos, pos_end, tiles, span, blockIdx.x);
+    const uint32_t tb = p.t_first * BTT, te = min(nb, (p.t_first + p.t_cnt) * BTT), chunk = p.slot;
+    const uint32_t row_base = (p.rb * NW + wave) * (32 * AT);
 
     v4i afrag[AT][4];
 #pragma unroll
@@ -655,30 +722,23 @@ __global__ void __launch_bounds__(64 * NW) k_match_scan32(const uint32_t *__rest
       uint32_t r = row_base + t * 32 + j;
       if (r >= na)
         r = na - 1;
-      const uint4 *p = (const uint4 *)(desc_a + (size_t)r * 32);
-#pragma unroll
-      for (int s = 0; s < 4; s++)
-      {
-        const uint4 v = p[2 * s + h];
-        afrag[t][s] = v4i{(int)(v.x ^ 0x80808080u), (int)(v.y ^ 0x80808080u), (int)(v.z ^ 0x80808080u), (int)(v.w ^ 0x80808080u)};
-      }
+      load_query_32x32(desc_a, r, h, afrag[t]);
     }
     Cell3 st[AT];
 #pragma unroll
     for (int t = 0; t < AT; t++)
       st[t] = Cell3{CELL_MIN, CELL_MIN, CELL_MIN, CELL_NONE, CELL_NONE, CELL_NONE, CELL_MIN};
 
-    TileRegs pf0;
     __syncthreads(); // the previous piece has finished reading both buffers
-    fetch_tile(tb, pf0);
-    stage_tile(tb, 0, pf0);
+    fetch(tb);
+    stage(tb, 0);
     __syncthreads();
     int buf = 0;
     for (uint32_t t0 = tb; t0 < te; t0 += BTT, buf ^= 1)
     {
       const bool more = t0 + BTT < te;
       if (more)
-        fetch_tile(t0 + BTT, pf0);
+        fetch(t0 + BTT);
       const uint8_t *s_b = s_b2[buf];
       const int *s_nbh = s_nbh2[buf];
       auto issue = [&](int sub, v16i *acc) {
@@ -742,7 +802,7 @@ __global__ void __launch_bounds__(64 * NW) k_match_scan32(const uint32_t *__rest
         }
       }
       if (more)
-        stage_tile(t0 + BTT, buf ^ 1, pf0);
+        stage(t0 + BTT, buf ^ 1);
       __syncthreads();
     }
 #pragma unroll
@@ -793,8 +853,7 @@ __global__ void __launch_bounds__(256) k_match_fix(const uint32_t *__restrict__ 
     {
       const uint32_t tiles = (nb + tile_rows - 1u) / tile_rows;
       const uint32_t span = stream_span((na + block_rows - 1u) / block_rows, tiles, stream_grid);
-      const uint32_t rb = r / block_rows;
-      const uint32_t n = ((rb + 1u) * tiles - 1u) / span - (rb * tiles) / span + 1u;
+      const uint32_t n = stream_pieces(r / block_rows, tiles, span);
       const uint4 *pp = (const uint4 *)(partial + (size_t)r * VKSIFT_HIP_MATCH_CHUNKS * 16u);
       for (uint32_t c = 0; c < n; c++)
       {
@@ -869,22 +928,12 @@ __global__ void __launch_bounds__(256) k_match_fix(const uint32_t *__restrict__ 
       Top2 t2{q, on ? col : QMAX, QMAX, QMAX};
 #pragma unroll
       for (int x = 1; x < 64; x <<= 1)
-      {
-        Top2 o;
-        o.q1 = __shfl_xor(t2.q1, x, 64), o.k1 = __shfl_xor(t2.k1, x, 64);
-        o.q2 = __shfl_xor(t2.q2, x, 64), o.k2 = __shfl_xor(t2.k2, x, 64);
-        t2 = merge2(t2, o);
-      }
+        t2 = merge2(t2, shfl_xor_top2(t2, x));
       s = merge2(s, t2);
     }
     if (lane == 0)
     {
-      uint32_t *m = matches + (size_t)r * 5;
-      m[0] = a_index_base + r;
-      m[1] = (sw && s.k1 < 2) ? (s.k1 ^ 1u) : s.k1;
-      m[2] = (sw && s.k2 < 2) ? (s.k2 ^ 1u) : s.k2;
-      m[3] = __float_as_uint(sqrtf((float)s.q1));
-      m[4] = __float_as_uint(sqrtf((float)s.q2));
+      write_record(matches + (size_t)r * 5, a_index_base + r, s, sw);
       if (tie || s.q2 >= Q_EXACT || s.k2 == QMAX)
         redo_list[1u + atomicAdd(redo_list, 1u)] = r;
     }
@@ -905,38 +954,17 @@ __global__ void __launch_bounds__(256) k_match_redo_rows(const uint32_t *__restr
   {
     const uint32_t row = redo_list[1u + k];
     uint32_t a[32];
-    uint32_t na2 = 0;
-#pragma unroll
-    for (int jj = 0; jj < 32; jj++)
-    {
-      a[jj] = desc_a[(size_t)row * 32 + jj];
-      na2 = __builtin_amdgcn_udot4(a[jj], a[jj], na2, false);
-    }
-    float bd = __builtin_inff(), sd = __builtin_inff();
-    uint32_t bi = QMAX, si = QMAX;
+    const uint32_t na2 = replay_load_row(desc_a, row, a);
+    ReplayTop2 t{__builtin_inff(), __builtin_inff(), QMAX, QMAX};
     for (uint32_t c = threadIdx.x; c < nb; c += 256u)
     {
-      const uint4 *pb = (const uint4 *)(desc_b + (size_t)c * 32);
-      uint32_t dot = 0, nb2 = 0;
-#pragma unroll
-      for (int jj = 0; jj < 8; jj++)
-      {
-        const uint4 v = pb[jj];
-        dot = __builtin_amdgcn_udot4(a[4 * jj + 0], v.x, dot, false), nb2 = __builtin_amdgcn_udot4(v.x, v.x, nb2, false);
-        dot = __builtin_amdgcn_udot4(a[4 * jj + 1], v.y, dot, false), nb2 = __builtin_amdgcn_udot4(v.y, v.y, nb2, false);
-        dot = __builtin_amdgcn_udot4(a[4 * jj + 2], v.z, dot, false), nb2 = __builtin_amdgcn_udot4(v.z, v.z, nb2, false);
-        dot = __builtin_amdgcn_udot4(a[4 * jj + 3], v.w, dot, false), nb2 = __builtin_amdgcn_udot4(v.w, v.w, nb2, false);
-      }
-      const float d = sqrtf((float)(na2 + nb2 - 2u * dot));
+      const float d = replay_dist(a, na2, desc_b, c);
       if (c < 2u)
         s_d01[c] = d;
-      if (d < bd)
-        sd = bd, si = bi, bd = d, bi = c;
-      else if (d < sd)
-        sd = d, si = c;
+      t = replay_insert(t, d, c);
     }
-    s_d[threadIdx.x][0] = bd, s_d[threadIdx.x][1] = sd;
-    s_i[threadIdx.x][0] = bi, s_i[threadIdx.x][1] = si;
+    s_d[threadIdx.x][0] = t.d1, s_d[threadIdx.x][1] = t.d2;
+    s_i[threadIdx.x][0] = t.i1, s_i[threadIdx.x][1] = t.i2;
     __syncthreads();
     for (uint32_t step = 128; step >= 1; step >>= 1)
     {
@@ -957,14 +985,7 @@ __global__ void __launch_bounds__(256) k_match_redo_rows(const uint32_t *__restr
     }
     if (threadIdx.x == 0)
     {
-      const bool sw = s_d01[0] == s_d01[1];
-      const uint32_t k1 = s_i[0][0], k2 = s_i[0][1];
-      uint32_t *m = matches + (size_t)row * 5;
-      m[0] = a_index_base + row;
-      m[1] = (sw && k1 < 2) ? (k1 ^ 1u) : k1;
-      m[2] = (sw && k2 < 2) ? (k2 ^ 1u) : k2;
-      m[3] = __float_as_uint(s_d[0][0]);
-      m[4] = __float_as_uint(s_d[0][1]);
+      write_record_f(matches + (size_t)row * 5, a_index_base + row, s_i[0][0], s_i[0][1], s_d[0][0], s_d[0][1], s_d01[0] == s_d01[1]);
     }
     __syncthreads();
   }
@@ -991,7 +1012,7 @@ __global__ void __launch_bounds__(256) k_match_redo_rows(const uint32_t *__restr
 // row) and compared with the keys' fields; because the top-2 of a multiset does not depend on arrival order, two genuine keys at
 // the top prove that no wrapped key (d2 >= 2^20, which can only look closer than it is) was ahead of them. A mismatch sends the
 // row to k_match_redo, like d2 >= 2^22 in the other kernels. Quirk Q7: the tie of columns 0 and 1 is read off their two keys.
-// Layout, staging and swizzle as in k_match32 (32x32x32 i8 MFMA, operand roles swapped, one query row per lane pair).
+// 32x32x32 i8 MFMA, operand roles swapped as in k_match_mfma, one query row per lane pair, swizzled B tiles.
 // Reference sets beyond 4096 rows: the scan goes in SUPER-CHUNKS of 4096 columns (the index field holds the column modulo 4096);
 // after each one the four chains are folded into a running exact (d2, index) top-2 and restart from zero — a merge of exact
 // top-2 lists, so the multiset argument above carries over to the union. A single large pair is also split over blockIdx.z
@@ -1007,20 +1028,10 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4,
   constexpr uint32_t ROWS = 32u * NW, SC = 4096u;
   const uint32_t slot = ss.slot_fast ? blockIdx.x : blockIdx.y;
   const uint32_t rb0 = ss.slot_fast ? blockIdx.y : blockIdx.x, rb_step = ss.slot_fast ? gridDim.y : gridDim.x;
-  const uint32_t ea = ss.use_ids ? ids.a[slot] : slot, eb = ss.use_ids ? ids.b[slot] : slot;
-  desc_a += (size_t)ea * ss.desc_a, desc_b += (size_t)eb * ss.desc_b;
-  norm_a += (size_t)ea * ss.norm_a, norm_b += (size_t)eb * ss.norm_b;
-  matches += (size_t)slot * ss.matches;
-  redo += (size_t)slot * ss.redo;
-  if (n_dev)
-  {
-    n_dev += (size_t)slot * ss.n;
-    na = n_dev[0];
-    nb = n_dev[1] < 2u ? 2u : n_dev[1];
-    if (nb > ss.pk_nb_max)
-      return; // larger reference sets belong to the pruning kernels (which skip what this one takes)
-  }
-  if (na == 0)
+  const SlotView v = bind_slot(SlotView{desc_a, desc_b, norm_a, norm_b, matches, redo, na, nb}, slot, n_dev, ss, ids);
+  if (n_dev && v.nb > ss.pk_nb_max)
+    return; // larger reference sets belong to the pruning kernels (which skip what this one takes)
+  if (v.na == 0)
     return;
   __shared__ __attribute__((aligned(16))) uint8_t s_b2[2][BTT * 128];
   __shared__ __attribute__((aligned(16))) uint32_t s_ck2[2][BTT];
@@ -1028,56 +1039,22 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4,
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane & 31, h = lane >> 5;
   const uint32_t nz = gridDim.z, z = blockIdx.z;
-  constexpr int NTH = 64 * NW, NLD = (BTT * 8 + NTH - 1) / NTH;
-  struct TileRegs
-  {
-    uint4 d[NLD];
-    uint32_t n;
-  };
-  auto fetch_tile = [&](uint32_t t0, TileRegs &pf) {
-#pragma unroll
-    for (int q = 0; q < NLD; q++)
-    {
-      const int i = threadIdx.x + q * NTH;
-      const int r = i >> 3, c = i & 7;
-      pf.d[q] = make_uint4(0, 0, 0, 0);
-      if (i < BTT * 8 && t0 + r < nb)
-        pf.d[q] = ((const uint4 *)(desc_b + (size_t)(t0 + r) * 32))[c];
-    }
-    pf.n = (threadIdx.x < BTT && t0 + threadIdx.x < nb) ? norm_b[t0 + threadIdx.x] : 0u;
-  };
-  auto stage_tile = [&](uint32_t t0, int bufi, const TileRegs &pf) {
-#pragma unroll
-    for (int q = 0; q < NLD; q++)
-    {
-      const int i = threadIdx.x + q * NTH;
-      const int r = i >> 3, c = i & 7;
-      uint4 v = pf.d[q];
-      v.x ^= 0x80808080u, v.y ^= 0x80808080u, v.z ^= 0x80808080u, v.w ^= 0x80808080u;
-      if (i < BTT * 8)
-        *(uint4 *)(s_b2[bufi] + r * 128 + swz(r, c) * 16) = v;
-    }
-    if ((int)threadIdx.x < BTT)
-      s_ck2[bufi][threadIdx.x] = 4095u - ((t0 + threadIdx.x) & 4095u) - (pf.n << 12);
+  constexpr int NTH = 64 * NW;
+  TileRegs<(BTT * 8 + NTH - 1) / NTH> pf0;
+  auto fetch = [&](uint32_t t0) { fetch_tile<NTH, BTT>(pf0, v.desc_b, v.norm_b, v.nb, t0); };
+  auto stage = [&](uint32_t t0, int bufi) {
+    stage_tile<NTH, BTT, LdsSwizzled>(pf0, s_b2[bufi], v.nb, t0, [&](int x, uint32_t n, bool) { s_ck2[bufi][x] = 4095u - ((t0 + x) & 4095u) - (n << 12); });
   };
 
-  for (uint32_t rb = rb0; rb * ROWS < na; rb += rb_step)
+  for (uint32_t rb = rb0; rb * ROWS < v.na; rb += rb_step)
   {
     const uint32_t row_base = (rb * NW + wave) * 32u;
     uint32_t r = row_base + j;
-    if (r >= na)
-      r = na - 1;
+    if (r >= v.na)
+      r = v.na - 1;
     v4i afrag[4];
-    {
-      const uint4 *p = (const uint4 *)(desc_a + (size_t)r * 32);
-#pragma unroll
-      for (int s = 0; s < 4; s++)
-      {
-        const uint4 v = p[2 * s + h];
-        afrag[s] = v4i{(int)(v.x ^ 0x80808080u), (int)(v.y ^ 0x80808080u), (int)(v.z ^ 0x80808080u), (int)(v.w ^ 0x80808080u)};
-      }
-    }
-    const uint32_t an = norm_a[r];
+    load_query_32x32(v.desc_a, r, h, afrag);
+    const uint32_t an = v.norm_a[r];
     const int ra = (int)((1u << 20) - 1u - an) >> 1;  // arithmetic: floor((2^20 - 1 - an) / 2)
     const uint32_t pa = ((1u << 20) - 1u - an) & 1u;
     v16i cra;
@@ -1088,32 +1065,31 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4,
     uint32_t bad = 0;                // a folded key that cannot be genuine (field below 2): the row is replayed
     uint32_t sw = 0;                 // quirk Q7: d2(b0) == d2(b1)
 
-    for (uint32_t sc0 = z * SC; sc0 < nb; sc0 += nz * SC)
+    for (uint32_t sc0 = z * SC; sc0 < v.nb; sc0 += nz * SC)
     {
-      const uint32_t sc_end = min(nb, sc0 + SC);
+      const uint32_t sc_end = min(v.nb, sc0 + SC);
       // four independent (best, second) pairs, merged after the super-chunk: the med3 / max updates of one pair form a dependent chain
       // (16 steps per sub-block otherwise); a multiset's top-2 does not care how it was partitioned
       uint32_t k1[4] = {0, 0, 0, 0}, k2[4] = {0, 0, 0, 0};
-      TileRegs pf0;
       __syncthreads(); // the previous scan has finished reading both buffers
-      fetch_tile(sc0, pf0);
-      stage_tile(sc0, 0, pf0);
+      fetch(sc0);
+      stage(sc0, 0);
       __syncthreads();
       int buf = 0;
       for (uint32_t t0 = sc0; t0 < sc_end; t0 += BTT, buf ^= 1)
       {
         const bool more = t0 + BTT < sc_end;
         if (more)
-          fetch_tile(t0 + BTT, pf0);
+          fetch(t0 + BTT);
         const uint8_t *s_b = s_b2[buf];
         const uint32_t *s_ck = s_ck2[buf];
-        const bool partial_tile = t0 + BTT > nb; // columns beyond B in this tile (staged as zero rows): their keys are forced to 0
+        const bool partial_tile = t0 + BTT > v.nb; // columns beyond B in this tile (staged as zero rows): their keys are forced to 0
         // (issuing the MFMAs of sub-block s+1 between the key updates of sub-block s — a second accumulator set, sched_group_barrier —
         // was tried: 200+ VGPRs whatever the unrolling, two waves per SIMD, 0.55 -> 0.61 ms per 512 pairs; not kept)
 #pragma unroll
         for (int sub = 0; sub < BTT / 32; sub++)
         {
-          if (t0 + sub * 32 >= nb)
+          if (t0 + sub * 32 >= v.nb)
             break;
           const uint8_t *prow = s_b + (sub * 32 + j) * 128;
           v4i bf[4];
@@ -1139,7 +1115,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4,
           {
 #pragma unroll
             for (int i = 0; i < 16; i++)
-              if (t0 + sub * 32 + 8 * (i >> 2) + 4 * h + (i & 3) >= nb)
+              if (t0 + sub * 32 + 8 * (i >> 2) + 4 * h + (i & 3) >= v.nb)
                 key[i] = 0u;
           }
           if (sub == 0 && t0 == 0)
@@ -1158,7 +1134,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4,
           }
         }
         if (more)
-          stage_tile(t0 + BTT, buf ^ 1, pf0);
+          stage(t0 + BTT, buf ^ 1);
         __syncthreads();
       }
       // fold the super-chunk: its two best keys (a key below 8192 before the parity term is "no column": field < 2 is never trusted)
@@ -1192,14 +1168,9 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4,
     }
 
     // the two lanes of a row
-    {
-      Top2 o;
-      o.q1 = __shfl_xor(st.q1, 32, 64), o.k1 = __shfl_xor(st.k1, 32, 64);
-      o.q2 = __shfl_xor(st.q2, 32, 64), o.k2 = __shfl_xor(st.k2, 32, 64);
-      st = merge2(st, o);
-      sw |= __shfl_xor(sw, 32, 64);
-      bad |= __shfl_xor(bad, 32, 64);
-    }
+    st = merge2(st, shfl_xor_top2(st, 32));
+    sw |= __shfl_xor(sw, 32, 64);
+    bad |= __shfl_xor(bad, 32, 64);
     // verification: exact d2 of the two reported columns from the descriptor bytes (this lane's half of K, the partner's by shuffle).
     // A piece (z) that holds fewer than two columns of B reports QMAX entries: nothing to verify there.
     bool ok = bad == 0u;
@@ -1208,43 +1179,34 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4,
     {
       const uint32_t qc = c == 0 ? st.q1 : st.q2, kc = c == 0 ? st.k1 : st.k2;
       const bool have = qc != QMAX;
-      const uint32_t col = have ? min(kc, nb - 1u) : 0u;
-      const uint4 *pb = (const uint4 *)(desc_b + (size_t)col * 32);
+      const uint32_t col = have ? min(kc, v.nb - 1u) : 0u;
+      const uint4 *pb = (const uint4 *)(v.desc_b + (size_t)col * 32);
       int dot = 0;
 #pragma unroll
       for (int s = 0; s < 4; s++)
       {
-        const uint4 v = pb[2 * s + h];
-        dot = __builtin_amdgcn_sdot4(afrag[s][0], (int)(v.x ^ 0x80808080u), dot, false);
-        dot = __builtin_amdgcn_sdot4(afrag[s][1], (int)(v.y ^ 0x80808080u), dot, false);
-        dot = __builtin_amdgcn_sdot4(afrag[s][2], (int)(v.z ^ 0x80808080u), dot, false);
-        dot = __builtin_amdgcn_sdot4(afrag[s][3], (int)(v.w ^ 0x80808080u), dot, false);
+        const uint4 w = pb[2 * s + h];
+        dot = __builtin_amdgcn_sdot4(afrag[s][0], (int)(w.x ^ 0x80808080u), dot, false);
+        dot = __builtin_amdgcn_sdot4(afrag[s][1], (int)(w.y ^ 0x80808080u), dot, false);
+        dot = __builtin_amdgcn_sdot4(afrag[s][2], (int)(w.z ^ 0x80808080u), dot, false);
+        dot = __builtin_amdgcn_sdot4(afrag[s][3], (int)(w.w ^ 0x80808080u), dot, false);
       }
       dot += __shfl_xor(dot, 32, 64);
-      const uint32_t qt = an + norm_b[col] - 2u * (uint32_t)dot;
-      if (have && (kc >= nb || qt != qc))
+      const uint32_t qt = an + v.norm_b[col] - 2u * (uint32_t)dot;
+      if (have && (kc >= v.nb || qt != qc))
         ok = false;
     }
     if (st.q1 != QMAX && st.q2 != QMAX && st.k1 == st.k2)
       ok = false;
     const uint32_t rr = row_base + j;
-    if (h == 0 && rr < na)
+    if (h == 0 && rr < v.na)
     {
       if (nz > 1)
-      {
-        uint32_t *pp = partial + ((size_t)rr * nz + z) * 4;
-        pp[0] = st.q1, pp[1] = st.k1, pp[2] = st.q2, pp[3] = st.k2;
-        partial[(size_t)na * nz * 4 + (size_t)rr * nz + z] = (z == 0 ? sw : 0u) | ((ok ? 0u : 1u) << 1);
-      }
+        write_partial(partial, v.na, nz, rr, z, st, (z == 0 ? sw : 0u) | ((ok ? 0u : 1u) << 1));
       else
       {
-        uint32_t *m = matches + (size_t)rr * 5;
-        m[0] = a_index_base + rr;
-        m[1] = (sw && st.k1 < 2) ? (st.k1 ^ 1u) : st.k1;
-        m[2] = (sw && st.k2 < 2) ? (st.k2 ^ 1u) : st.k2;
-        m[3] = __float_as_uint(sqrtf((float)st.q1));
-        m[4] = __float_as_uint(sqrtf((float)st.q2));
-        redo[rr] = (ok && st.q2 != QMAX) ? 0u : 1u;
+        write_record(v.matches + (size_t)rr * 5, a_index_base + rr, st, sw);
+        v.redo[rr] = (ok && st.q2 != QMAX) ? 0u : 1u;
       }
     }
   }
@@ -1258,8 +1220,7 @@ __global__ void __launch_bounds__(256) k_match_merge(const uint32_t *__restrict_
 {
   if (n_dev)
   {
-    na = n_dev[0];
-    nb = n_dev[1] < 2u ? 2u : n_dev[1];
+    device_counts(n_dev, na, nb);
     if (na <= na_lo || na > na_hi)
       return;
   }
@@ -1274,8 +1235,7 @@ __global__ void __launch_bounds__(256) k_match_merge(const uint32_t *__restrict_
   {
     const uint32_t tiles = (nb + tile_rows - 1u) / tile_rows;
     const uint32_t span = stream_span((na + block_rows - 1u) / block_rows, tiles, stream_grid);
-    const uint32_t rb = r / block_rows;
-    nchunks = ((rb + 1u) * tiles - 1u) / span - (rb * tiles) / span + 1u; // the stride stays VKSIFT_HIP_MATCH_CHUNKS
+    nchunks = stream_pieces(r / block_rows, tiles, span); // the stride stays VKSIFT_HIP_MATCH_CHUNKS
   }
   for (uint32_t c = 1; c < nchunks; c++)
   {
@@ -1283,13 +1243,7 @@ __global__ void __launch_bounds__(256) k_match_merge(const uint32_t *__restrict_
     s = merge2(s, o);
     flags |= fl[c] & 2u;
   }
-  const bool sw = flags & 1u;
-  uint32_t *m = matches + (size_t)r * 5;
-  m[0] = a_index_base + r;
-  m[1] = (sw && s.k1 < 2) ? (s.k1 ^ 1u) : s.k1;
-  m[2] = (sw && s.k2 < 2) ? (s.k2 ^ 1u) : s.k2;
-  m[3] = __float_as_uint(sqrtf((float)s.q1));
-  m[4] = __float_as_uint(sqrtf((float)s.q2));
+  write_record(matches + (size_t)r * 5, a_index_base + r, s, flags & 1u);
   redo[r] = (flags >> 1) & 1u;
 }
 
@@ -1303,20 +1257,10 @@ __global__ void __launch_bounds__(256) k_match_mfma_split(const uint32_t *__rest
                                                           uint32_t *__restrict__ redo, const uint32_t *__restrict__ n_dev, uint32_t na_lo, uint32_t na_hi,
                                                           SlotStrides ss, SlotIds ids)
 {
-  const uint32_t ea = ss.use_ids ? ids.a[blockIdx.y] : blockIdx.y, eb = ss.use_ids ? ids.b[blockIdx.y] : blockIdx.y;
-  desc_a += (size_t)ea * ss.desc_a, desc_b += (size_t)eb * ss.desc_b;
-  norm_a += (size_t)ea * ss.norm_a, norm_b += (size_t)eb * ss.norm_b;
-  matches += (size_t)blockIdx.y * ss.matches;
-  redo += (size_t)blockIdx.y * ss.redo;
-  if (n_dev)
-  {
-    n_dev += (size_t)blockIdx.y * ss.n;
-    na = n_dev[0];
-    nb = n_dev[1] < 2u ? 2u : n_dev[1];
-    if (na <= na_lo || na > na_hi || nb <= ss.pk_nb_max)
-      return;
-  }
-  if (blockIdx.x * 16u >= na)
+  const SlotView v = bind_slot(SlotView{desc_a, desc_b, norm_a, norm_b, matches, redo, na, nb}, blockIdx.y, n_dev, ss, ids);
+  if (n_dev && (v.na <= na_lo || v.na > na_hi || v.nb <= ss.pk_nb_max))
+    return; // another kernel's regime
+  if (blockIdx.x * 16u >= v.na)
     return;
   __shared__ __attribute__((aligned(16))) uint8_t s_b[2][BT * B_STRIDE];
   __shared__ uint32_t s_nb[2][BT];
@@ -1331,17 +1275,14 @@ __global__ void __launch_bounds__(256) k_match_mfma_split(const uint32_t *__rest
   uint32_t an[4];
   {
     uint32_t r = row_base + col;
-    if (r >= na)
-      r = na - 1;
-    const uint4 *p = (const uint4 *)(desc_a + (size_t)r * 32);
-    uint4 v0 = p[grp], v1 = p[4 + grp];
-    afrag[0] = v4i{(int)(v0.x ^ 0x80808080u), (int)(v0.y ^ 0x80808080u), (int)(v0.z ^ 0x80808080u), (int)(v0.w ^ 0x80808080u)};
-    afrag[1] = v4i{(int)(v1.x ^ 0x80808080u), (int)(v1.y ^ 0x80808080u), (int)(v1.z ^ 0x80808080u), (int)(v1.w ^ 0x80808080u)};
+    if (r >= v.na)
+      r = v.na - 1;
+    load_query_16x64(v.desc_a, r, grp, afrag);
 #pragma unroll
     for (int j = 0; j < 4; j++)
     {
       uint32_t rr = row_base + grp * 4 + j;
-      an[j] = norm_a[rr < na ? rr : na - 1];
+      an[j] = v.norm_a[rr < v.na ? rr : v.na - 1];
     }
   }
   Top2 st[4];
@@ -1350,46 +1291,22 @@ __global__ void __launch_bounds__(256) k_match_mfma_split(const uint32_t *__rest
     st[j] = Top2{QMAX, QMAX, QMAX, QMAX};
   uint32_t swap_bits = 0, risky_bits = 0;
 
-  constexpr int NLD = BT * 8 / 256;
-  uint4 pfb[NLD];
-  uint32_t pfn = 0;
-  auto fetch_tile = [&](uint32_t t0) {
-#pragma unroll
-    for (int q = 0; q < NLD; q++)
-    {
-      int i = threadIdx.x + q * 256;
-      int r = i >> 3, c = i & 7;
-      pfb[q] = make_uint4(0, 0, 0, 0);
-      if (t0 + r < nb)
-        pfb[q] = ((const uint4 *)(desc_b + (size_t)(t0 + r) * 32))[c];
-    }
-    pfn = (threadIdx.x < BT && t0 + threadIdx.x < nb) ? norm_b[t0 + threadIdx.x] : 0u;
-  };
-  fetch_tile(0);
+  TileRegs<BT * 8 / 256> pf0;
+  fetch_tile<256, BT>(pf0, v.desc_b, v.norm_b, v.nb, 0);
   if (threadIdx.x == 0)
     s_swap = 0, s_risky = 0;
 
   int buf = 0;
-  for (uint32_t t0 = 0; t0 < nb; t0 += BT, buf ^= 1)
+  for (uint32_t t0 = 0; t0 < v.nb; t0 += BT, buf ^= 1)
   {
     // double-buffered staging: one barrier per tile
-#pragma unroll
-    for (int q = 0; q < NLD; q++)
-    {
-      int i = threadIdx.x + q * 256;
-      int r = i >> 3, c = i & 7;
-      uint4 v = pfb[q];
-      v.x ^= 0x80808080u, v.y ^= 0x80808080u, v.z ^= 0x80808080u, v.w ^= 0x80808080u;
-      *(uint4 *)(s_b[buf] + r * B_STRIDE + c * 16) = v;
-    }
-    if (threadIdx.x < BT)
-      s_nb[buf][threadIdx.x] = pfn;
+    stage_tile<256, BT, LdsPitch144>(pf0, s_b[buf], v.nb, t0, [&](int x, uint32_t n, bool) { s_nb[buf][x] = n; });
     __syncthreads();
-    if (t0 + BT < nb)
-      fetch_tile(t0 + BT);
+    if (t0 + BT < v.nb)
+      fetch_tile<256, BT>(pf0, v.desc_b, v.norm_b, v.nb, t0 + BT);
 
     const uint32_t sub0 = t0 + 16u * wave;
-    if (sub0 < nb)
+    if (sub0 < v.nb)
     {
       const uint32_t bcol = sub0 + col;
       const uint8_t *pb = s_b[buf] + (16 * wave + col) * B_STRIDE + grp * 16;
@@ -1402,7 +1319,7 @@ __global__ void __launch_bounds__(256) k_match_mfma_split(const uint32_t *__rest
 #pragma unroll
       for (int j = 0; j < 4; j++)
       {
-        const uint32_t q = bcol < nb ? an[j] + bn - 2u * (uint32_t)acc[j] : QMAX;
+        const uint32_t q = bcol < v.nb ? an[j] + bn - 2u * (uint32_t)acc[j] : QMAX;
         uint32_t key = bcol;
         if (sub0 == 0)
         {
@@ -1437,12 +1354,7 @@ __global__ void __launch_bounds__(256) k_match_mfma_split(const uint32_t *__rest
     Top2 s = st[j];
 #pragma unroll
     for (int m = 1; m < 16; m <<= 1)
-    {
-      Top2 o;
-      o.q1 = __shfl_xor(s.q1, m, 64), o.k1 = __shfl_xor(s.k1, m, 64);
-      o.q2 = __shfl_xor(s.q2, m, 64), o.k2 = __shfl_xor(s.k2, m, 64);
-      s = merge2(s, o);
-    }
+      s = merge2(s, shfl_xor_top2(s, m));
     if (col == 0)
     {
       s_part[wave][grp * 4 + j][0] = s.q1, s_part[wave][grp * 4 + j][1] = s.k1;
@@ -1467,16 +1379,10 @@ __global__ void __launch_bounds__(256) k_match_mfma_split(const uint32_t *__rest
       s = merge2(s, o);
     }
     const uint32_t r = row_base + rr;
-    if (r < na)
+    if (r < v.na)
     {
-      const bool sw = (s_swap >> rr) & 1u;
-      uint32_t *m = matches + (size_t)r * 5;
-      m[0] = a_index_base + r;
-      m[1] = (sw && s.k1 < 2) ? (s.k1 ^ 1u) : s.k1;
-      m[2] = (sw && s.k2 < 2) ? (s.k2 ^ 1u) : s.k2;
-      m[3] = __float_as_uint(sqrtf((float)s.q1));
-      m[4] = __float_as_uint(sqrtf((float)s.q2));
-      redo[r] = (s_risky >> rr) & 1u;
+      write_record(v.matches + (size_t)r * 5, a_index_base + r, s, (s_swap >> rr) & 1u);
+      v.redo[r] = (s_risky >> rr) & 1u;
     }
   }
 }
@@ -1486,67 +1392,94 @@ __global__ void __launch_bounds__(256) k_match_mfma_split(const uint32_t *__rest
 // Never taken for real SIFT descriptors; adversarial inputs just run at scalar speed.
 __global__ void __launch_bounds__(64) k_match_redo(const uint32_t *__restrict__ desc_a, uint32_t na, uint32_t a_index_base,
                                                    const uint32_t *__restrict__ desc_b, uint32_t nb, uint32_t *__restrict__ matches,
-                                                   const uint32_t *__restrict__ redo, const uint32_t *__restrict__ n_dev, SlotStrides ss, SlotIds ids)
+                                                   uint32_t *__restrict__ redo, const uint32_t *__restrict__ n_dev, SlotStrides ss, SlotIds ids)
 {
-  const uint32_t ea = ss.use_ids ? ids.a[blockIdx.y] : blockIdx.y, eb = ss.use_ids ? ids.b[blockIdx.y] : blockIdx.y;
-  desc_a += (size_t)ea * ss.desc_a, desc_b += (size_t)eb * ss.desc_b;
-  matches += (size_t)blockIdx.y * ss.matches;
-  redo += (size_t)blockIdx.y * ss.redo;
-  if (n_dev)
+  const SlotView v = bind_slot(SlotView{desc_a, desc_b, nullptr, nullptr, matches, redo, na, nb}, blockIdx.y, n_dev, ss, ids);
+  for (uint32_t row = blockIdx.x * 64 + threadIdx.x; row < v.na; row += gridDim.x * 64)
   {
-    n_dev += (size_t)blockIdx.y * ss.n;
-    na = n_dev[0];
-    nb = n_dev[1] < 2u ? 2u : n_dev[1];
-  }
-  for (uint32_t row = blockIdx.x * 64 + threadIdx.x; row < na; row += gridDim.x * 64)
-  {
-    if (!redo[row])
+    if (!v.redo[row])
       continue;
     uint32_t a[32];
-    uint32_t na2 = 0;
-#pragma unroll
-    for (int j = 0; j < 32; j++)
-    {
-      a[j] = desc_a[(size_t)row * 32 + j];
-      na2 = __builtin_amdgcn_udot4(a[j], a[j], na2, false);
-    }
-    auto dist = [&](uint32_t bi) -> float {
-      const uint32_t *pb = desc_b + (size_t)bi * 32;
-      uint32_t dot = 0, nb2 = 0;
-#pragma unroll
-      for (int j = 0; j < 32; j++)
-      {
-        const uint32_t v = pb[j];
-        dot = __builtin_amdgcn_udot4(a[j], v, dot, false);
-        nb2 = __builtin_amdgcn_udot4(v, v, nb2, false);
-      }
-      return sqrtf((float)(na2 + nb2 - 2u * dot));
-    };
-    float d0 = dist(0), d1 = dist(1);
-    float best_d, second_d;
-    uint32_t best_i, second_i;
-    if (d0 < d1)
-      best_d = d0, best_i = 0, second_d = d1, second_i = 1;
-    else
-      best_d = d1, best_i = 1, second_d = d0, second_i = 0;
-    for (uint32_t bi = 2; bi < nb; bi++)
-    {
-      const float d = dist(bi);
-      if (d < best_d)
-      {
-        second_d = best_d, second_i = best_i;
-        best_d = d, best_i = bi;
-      }
-      else if (d < second_d)
-        second_d = d, second_i = bi;
-    }
-    uint32_t *m = matches + (size_t)row * 5;
-    m[0] = a_index_base + row;
-    m[1] = best_i;
-    m[2] = second_i;
-    m[3] = __float_as_uint(best_d);
-    m[4] = __float_as_uint(second_d);
+    const uint32_t na2 = replay_load_row(v.desc_a, row, a);
+    // unconditional initialisation from b[0], b[1]; d0 == d1 makes index 1 the best (quirk Q7)
+    const float d0 = replay_dist(a, na2, v.desc_b, 0), d1 = replay_dist(a, na2, v.desc_b, 1);
+    ReplayTop2 t = d0 < d1 ? ReplayTop2{d0, d1, 0u, 1u} : ReplayTop2{d1, d0, 1u, 0u};
+    for (uint32_t bi = 2; bi < v.nb; bi++)
+      t = replay_insert(t, replay_dist(a, na2, v.desc_b, bi), bi);
+    write_record_f(v.matches + (size_t)row * 5, a_index_base + row, t.i1, t.i2, t.d1, t.d2, false);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Launches. What every matcher kernel addresses, by name: a single pair given by pointers and counts (n_dev null, strides zero), or
+// the slots of a batch whose counts are on the device (na = nb = 0, n_dev set; descriptors and norms are the per-buffer cache).
+struct MatchJob
+{
+  hipStream_t hs;
+  const uint32_t *desc_a, *norm_a, *desc_b, *norm_b;
+  uint32_t na, nb, a_index_base;
+  uint32_t *matches, *redo;
+  const uint32_t *n_dev;
+  SlotStrides ss;
+  const SlotIds *ids;
+};
+constexpr uint32_t NA_ALL = 0xFFFFFFFFu; // upper end of the last size regime
+
+// k_match_mfma_split for the slots with N_A in (na_lo, na_hi]
+void launch_split(const MatchJob &j, dim3 grid, uint32_t na_lo, uint32_t na_hi)
+{
+  hipLaunchKernelGGL(k_match_mfma_split, grid, dim3(256), 0, j.hs, j.desc_a, j.norm_a, j.na, j.a_index_base, j.desc_b, j.norm_b, j.nb, j.matches, j.redo, j.n_dev,
+                     na_lo, na_hi, j.ss, *j.ids);
+}
+
+// the pruning kernel on a grid of row blocks x slots, for the slots with N_A in (na_lo, na_hi]: 16 AT rows per wave
+template <int AT>
+void launch_prune(const MatchJob &j, dim3 grid, uint32_t na_lo, uint32_t na_hi)
+{
+  hipLaunchKernelGGL(k_match_mfma<AT>, grid, dim3(256), 0, j.hs, j.desc_a, j.norm_a, j.na, j.a_index_base, j.desc_b, j.norm_b, j.nb, j.matches, j.redo, j.n_dev, na_lo,
+                     na_hi, j.ss, (uint32_t *)nullptr, *j.ids, 0u);
+}
+
+// k_match_merge over `rows` rows (the capacity when the count is on the device) of `nchunks` partial lists each; stream_grid != 0:
+// the lists of a stream decomposition on that grid with the given tile and row-block sizes
+void launch_merge(const MatchJob &j, uint32_t rows, const uint32_t *partial, uint32_t nchunks, uint32_t na_lo, uint32_t stream_grid, uint32_t tile_rows,
+                  uint32_t block_rows)
+{
+  hipLaunchKernelGGL(k_match_merge, dim3((rows + 255u) / 256u), dim3(256), 0, j.hs, partial, j.na, nchunks, j.a_index_base, j.matches, j.redo, j.n_dev, na_lo, NA_ALL,
+                     stream_grid, j.nb, tile_rows, block_rows);
+}
+
+// The stream decomposition (match_stream.h) for a single pair with N_A > na_lo: 8 waves x 32 rows per workgroup, 128-row B tiles,
+// two workgroups per CU, every workgroup the same number of tiles; then the merge of the pieces' partial lists. Measured on MI355X
+// against the three size regimes it replaced (rows x rows, whole call): 2k 0.033 -> 0.028 ms, 8k 0.099 -> 0.062, 16k 0.23 -> 0.126,
+// 32k 0.50 -> 0.28, 50k 0.60 -> 0.51 (31.7 % of the dense int8 peak), 100k 1.78 -> 1.48 (44 %).
+void launch_stream(const MatchJob &j, uint32_t rows, uint32_t na_lo, uint32_t *partial)
+{
+  const uint32_t G = 2u * device_cus();
+  hipLaunchKernelGGL((k_match_mfma<2, 8, 128>), dim3(G), dim3(512), 0, j.hs, j.desc_a, j.norm_a, j.na, j.a_index_base, j.desc_b, j.norm_b, j.nb, j.matches, j.redo,
+                     j.n_dev, na_lo, NA_ALL, j.ss, partial, *j.ids, 1u);
+  launch_merge(j, rows, partial, (uint32_t)VKSIFT_HIP_MATCH_CHUNKS, na_lo, G, 128u, 256u);
+}
+
+// The packed-key kernel on a single pair known to the host: row blocks of 32 NW rows x strided pieces of B (whole super-chunks of
+// 4096 columns) sized to put ~2 workgroups on every CU; more than one piece per row block: partial lists (5 * na * pieces u32,
+// pieces <= 8 <= VKSIFT_HIP_MATCH_CHUNKS) + k_match_merge.
+template <int NW, int BTT>
+void launch_pk_pieces(const MatchJob &j, uint32_t *partial)
+{
+  const uint32_t nsc = (j.nb + 4095u) / 4096u, want = 2u * device_cus(), nrb = (j.na + 32u * NW - 1u) / (32u * NW);
+  uint32_t nz = (want + nrb - 1u) / nrb;
+  nz = nz < nsc ? nz : nsc;
+  hipLaunchKernelGGL((k_match_pk<NW, BTT>), dim3(nrb, 1, nz), dim3(64 * NW), 0, j.hs, j.desc_a, j.norm_a, j.na, j.a_index_base, j.desc_b, j.norm_b, j.nb, j.matches,
+                     j.redo, j.n_dev, j.ss, *j.ids, partial);
+  if (nz > 1)
+    launch_merge(j, j.na, partial, nz, 0u, 0u, 0u, 0u);
+}
+
+// k_match_redo: the replay of the rows the kernels above flagged (grid-stride over the rows: the flags are all zero for real descriptors)
+void launch_redo(const MatchJob &j, dim3 grid)
+{
+  hipLaunchKernelGGL(k_match_redo, grid, dim3(64), 0, j.hs, j.desc_a, j.na, j.a_index_base, j.desc_b, j.nb, j.matches, j.redo, j.n_dev, j.ss, *j.ids);
 }
 
 } // namespace
@@ -1570,53 +1503,21 @@ extern "C"
       return (int)hipErrorInvalidValue; /* callers pad B to two rows (quirk Q6) */
     if (scratch == nullptr || scratch_u32 < vksift_hip_match_scratch_u32(na, nb) - 2u * (size_t)na - (size_t)nb)
       return (int)hipErrorInvalidValue; /* a buffer sized by an older formula: nothing is launched */
-    hipStream_t hs = (hipStream_t)s;
-    uint32_t *redo = scratch;
-    const uint32_t *da = (const uint32_t *)desc_a, *db = (const uint32_t *)desc_b;
-    const SlotStrides z{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const SlotIds noids{};
-    /* A small problem (a few hundred thousand distances): 16 A rows per workgroup with B split over its waves, one launch.
-     * Everything else: the stream decomposition (see k_match_mfma) — 8 waves x 32 rows per workgroup, 128-row B tiles, two
-     * workgroups per CU, every workgroup the same number of tiles. Measured on MI355X against the three size regimes it
-     * replaced (rows x rows, whole call): 2k 0.033 -> 0.028 ms, 8k 0.099 -> 0.062, 16k 0.23 -> 0.126, 32k 0.50 -> 0.28,
-     * 50k 0.60 -> 0.51 (31.7 % of the dense int8 peak), 100k 1.78 -> 1.48 (44 %). */
-    if (match_use_pk() && nb <= VKSIFT_HIP_MATCH_PK_NB && (uint64_t)na * nb >= 64000000ull)
+    uint32_t *redo = scratch, *partial = redo + na; /* scratch of the kernels that flag rows: redo[na], then the partial lists */
+    const MatchJob j{(hipStream_t)s, (const uint32_t *)desc_a, norm_a, (const uint32_t *)desc_b, norm_b, na, nb, a_index_base, (uint32_t *)matches, redo, nullptr, SlotStrides{}, &noids};
+    if (match_use(MATCH_PK) && nb <= VKSIFT_HIP_MATCH_PK_NB && (uint64_t)na * nb >= 64000000ull)
     {
       /* 8 k x 8 k up to 32 k reference rows: the branch-free packed-key kernel (its rate does not depend on the size: 13 k x 13 k
-       * 0.103 -> 0.078 ms, 32 k 0.275 -> 0.243; the pruning kernel passes it beyond 32 k rows, below 8 k the launches dominate). Row blocks x strided pieces of B (whole super-chunks of 4096 columns) sized to put ~2 workgroups on every
-       * CU; more than one piece per row block: partial lists + k_match_merge. Scratch: redo[na], then 5 * na * pieces u32
-       * (pieces <= 8 <= VKSIFT_HIP_MATCH_CHUNKS). */
-      uint32_t *partial = redo + na;
-      const uint32_t nsc = (nb + 4095u) / 4096u, want = 2u * device_cus();
-      SlotStrides zp = z;
-      zp.pk_nb_max = VKSIFT_HIP_MATCH_PK_NB;
+       * 0.103 -> 0.078 ms, 32 k 0.275 -> 0.243; the pruning kernel passes it beyond 32 k rows, below 8 k the launches dominate) */
       if (na <= 4096u)
-      {
-        const uint32_t nrb = (na + 63u) / 64u;
-        uint32_t nz = (want + nrb - 1u) / nrb;
-        nz = nz < nsc ? nz : nsc;
-        hipLaunchKernelGGL((k_match_pk<2, 64>), dim3(nrb, 1, nz), dim3(128), 0, hs, da, norm_a, na, a_index_base, db, norm_b, nb, (uint32_t *)matches, redo,
-                           (const uint32_t *)nullptr, zp, noids, partial);
-        if (nz > 1)
-          hipLaunchKernelGGL(k_match_merge, dim3((na + 255u) / 256u), dim3(256), 0, hs, (const uint32_t *)partial, na, nz, a_index_base, (uint32_t *)matches, redo,
-                             (const uint32_t *)nullptr, 0u, 0xFFFFFFFFu, 0u, nb, 0u, 0u);
-      }
+        launch_pk_pieces<2, 64>(j, partial);
       else
-      {
-        const uint32_t nrb = (na + 127u) / 128u;
-        uint32_t nz = (want + nrb - 1u) / nrb;
-        nz = nz < nsc ? nz : nsc;
-        hipLaunchKernelGGL((k_match_pk<4, 128>), dim3(nrb, 1, nz), dim3(256), 0, hs, da, norm_a, na, a_index_base, db, norm_b, nb, (uint32_t *)matches, redo,
-                           (const uint32_t *)nullptr, zp, noids, partial);
-        if (nz > 1)
-          hipLaunchKernelGGL(k_match_merge, dim3((na + 255u) / 256u), dim3(256), 0, hs, (const uint32_t *)partial, na, nz, a_index_base, (uint32_t *)matches, redo,
-                             (const uint32_t *)nullptr, 0u, 0xFFFFFFFFu, 0u, nb, 0u, 0u);
-      }
+        launch_pk_pieces<4, 128>(j, partial);
     }
     else if (na <= VKSIFT_HIP_MATCH_SMALL_NA && nb <= VKSIFT_HIP_MATCH_SMALL_NB)
-      hipLaunchKernelGGL(k_match_mfma_split, dim3((na + 15u) / 16u), dim3(256), 0, hs, da, norm_a, na, a_index_base, db, norm_b, nb, (uint32_t *)matches, redo,
-                         (const uint32_t *)nullptr, 0u, 0xFFFFFFFFu, z, noids);
-    else if (match_use_scan())
+      launch_split(j, dim3((na + 15u) / 16u), 0u, NA_ALL); /* a few hundred thousand distances: 16 A rows per workgroup, B split over its waves, one launch */
+    else if (match_use(MATCH_SCAN))
     {
       /* large reference sets: the branch-free cell scan, the exact finish from the descriptor bytes, the (rare) replay of tied rows.
        * Scratch: [row list: 1 + na][pad to 16 B][cell lists: 16 * na * VKSIFT_HIP_MATCH_CHUNKS] (VKSIFT_HIP_MATCH_SCRATCH_U32). */
@@ -1632,26 +1533,18 @@ extern "C"
       const bool r4 = vksift_hip_tune_get(VKSIFT_TUNE_SCAN_FORM) == 1;
       const uint32_t Gs = r4 ? 2u * device_cus() : device_cus(), brows = r4 ? 256u : 768u, trows = r4 ? 128u : 256u;
       if (r4)
-        hipLaunchKernelGGL((k_match_scan32<2, 4, 128, 0>), dim3(Gs), dim3(256), 0, hs, da, na, db, norm_b, nb, cells, list);
+        hipLaunchKernelGGL((k_match_scan32<2, 4, 128, 0>), dim3(Gs), dim3(256), 0, j.hs, j.desc_a, na, j.desc_b, norm_b, nb, cells, list);
       else
-        hipLaunchKernelGGL((k_match_scan32<3, 8, 256, 1>), dim3(Gs), dim3(512), 0, hs, da, na, db, norm_b, nb, cells, list);
-      hipLaunchKernelGGL(k_match_fix, dim3((na + 31u) / 32u), dim3(256), 0, hs, (const uint32_t *)cells, da, norm_a, na, a_index_base, db, norm_b, nb, Gs, trows, brows,
-                         (uint32_t *)matches, list);
-      hipLaunchKernelGGL(k_match_redo_rows, dim3(512), dim3(256), 0, hs, da, a_index_base, db, nb, (uint32_t *)matches, (const uint32_t *)list);
+        hipLaunchKernelGGL((k_match_scan32<3, 8, 256, 1>), dim3(Gs), dim3(512), 0, j.hs, j.desc_a, na, j.desc_b, norm_b, nb, cells, list);
+      hipLaunchKernelGGL(k_match_fix, dim3((na + 31u) / 32u), dim3(256), 0, j.hs, (const uint32_t *)cells, j.desc_a, norm_a, na, a_index_base, j.desc_b, norm_b, nb, Gs,
+                         trows, brows, j.matches, list);
+      hipLaunchKernelGGL(k_match_redo_rows, dim3(512), dim3(256), 0, j.hs, j.desc_a, a_index_base, j.desc_b, nb, j.matches, (const uint32_t *)list);
       return (int)hipGetLastError();
     }
     else
-    {
-      uint32_t *partial = redo + na;
-      const uint32_t G = 2u * device_cus();
-      hipLaunchKernelGGL((k_match_mfma<2, 8, 128>), dim3(G), dim3(512), 0, hs, da, norm_a, na, a_index_base, db, norm_b, nb, (uint32_t *)matches, redo,
-                         (const uint32_t *)nullptr, 0u, 0xFFFFFFFFu, z, partial, noids, 1u);
-      hipLaunchKernelGGL(k_match_merge, dim3((na + 255u) / 256u), dim3(256), 0, hs, (const uint32_t *)partial, na, (uint32_t)VKSIFT_HIP_MATCH_CHUNKS, a_index_base,
-                         (uint32_t *)matches, redo, (const uint32_t *)nullptr, 0u, 0xFFFFFFFFu, G, nb, 128u, 256u);
-    }
-    uint32_t rblocks = (na + 63u) / 64u;
-    hipLaunchKernelGGL(k_match_redo, dim3(rblocks > 1024u ? 1024u : rblocks), dim3(64), 0, hs, da, na, a_index_base, db, nb, (uint32_t *)matches,
-                       (const uint32_t *)redo, (const uint32_t *)nullptr, z, noids);
+      launch_stream(j, na, 0u, partial);
+    const uint32_t rblocks = (na + 63u) / 64u;
+    launch_redo(j, dim3(rblocks > 1024u ? 1024u : rblocks));
     return (int)hipGetLastError();
   }
 
@@ -1695,36 +1588,23 @@ extern "C"
     hipLaunchKernelGGL(k_slot_counts, dim3((nslots + 63u) / 64u), dim3(64), 0, (hipStream_t)s, cache_n, 1u, ids, nslots, n_dev, n_slot_stride);
     if (max_na == 0)
       return (int)hipGetLastError();
-    const uint8_t *desc_a = cache_desc, *desc_b = cache_desc;
-    const uint32_t *norm_a = cache_norm, *norm_b = cache_norm;
-    SlotStrides ss;
+    SlotStrides ss{};
     ss.desc_a = ss.desc_b = cache_desc_stride / 4;
     ss.norm_a = ss.norm_b = cache_norm_stride;
     ss.matches = match_slot_stride / 4;
     ss.n = n_slot_stride;
     ss.redo = redo_slot_stride;
-    ss.slot_fast = 0;
     ss.use_ids = 1;
-    ss.pk_nb_max = 0;
-    ss.nslots_loop = 0;
-    hipStream_t hs = (hipStream_t)s;
-    const uint32_t *da = (const uint32_t *)desc_a, *db = (const uint32_t *)desc_b;
+    MatchJob j{(hipStream_t)s, (const uint32_t *)cache_desc, cache_norm, (const uint32_t *)cache_desc, cache_norm, 0u, 0u, 0u, (uint32_t *)matches, redo, n_dev, ss, &ids};
     if (nslots == 1 && partial_scratch)
     {
       /* one pair: as vksift_hip_match_2nn_prenormed, but N_A is only known on the device — both kernels are launched, each
        * returns at once unless N_A falls in its range; the stream decomposition sizes its runs from the device-side counts */
       const uint32_t SS = VKSIFT_HIP_MATCH_SMALL_NA;
       const uint32_t n1 = max_na < SS ? max_na : SS;
-      hipLaunchKernelGGL(k_match_mfma_split, dim3((n1 + 15u) / 16u, 1), dim3(256), 0, hs, da, norm_a, 0u, 0u, db, norm_b, 0u, (uint32_t *)matches, redo, n_dev, 0u,
-                         SS, ss, ids);
+      launch_split(j, dim3((n1 + 15u) / 16u, 1), 0u, SS);
       if (max_na > SS)
-      {
-        const uint32_t G = 2u * device_cus();
-        hipLaunchKernelGGL((k_match_mfma<2, 8, 128>), dim3(G), dim3(512), 0, hs, da, norm_a, 0u, 0u, db, norm_b, 0u, (uint32_t *)matches, redo, n_dev, SS,
-                           0xFFFFFFFFu, ss, partial_scratch, ids, 1u);
-        hipLaunchKernelGGL(k_match_merge, dim3((max_na + 255u) / 256u), dim3(256), 0, hs, (const uint32_t *)partial_scratch, 0u,
-                           (uint32_t)VKSIFT_HIP_MATCH_CHUNKS, 0u, (uint32_t *)matches, redo, n_dev, SS, 0xFFFFFFFFu, G, 0u, 128u, 256u);
-      }
+        launch_stream(j, max_na, SS, partial_scratch);
     }
     else
     {
@@ -1741,59 +1621,56 @@ extern "C"
        * What is left for them in such a batch is the odd pair with a large reference set: one kernel for all N_A <= 32768 (the
        * B-split kernel is not launched) on a grid of 16 row blocks per slot — every launch of a mostly idle grid costs the batch
        * 4-5 us (4096 workgroups that only read their slot's counts) */
-      const bool pk = match_use_pk();
+      const bool pk = match_use(MATCH_PK);
       /* what is left for the pruning kernels: the slots beyond the packed-key range — if the host KNOWS there is one (nb_exact). A batch whose
        * counts are still on the device (the usual case: the matching is queued behind its detection) is served by the packed-key kernel alone,
        * whatever the N_B of a slot turns out to be: no grid is queued for slots that "could" exist (vksift_hip.h) */
       const bool prune = !pk || (max_nb > VKSIFT_HIP_MATCH_PK_NB && nb_exact != 0u);
       if (pk)
       {
-        ss.pk_nb_max = prune ? VKSIFT_HIP_MATCH_PK_NB : 0xFFFFFFFFu;
-        SlotStrides sp = ss;
-        sp.slot_fast = nslots > 1 ? 1u : 0u;
+        j.ss.pk_nb_max = prune ? VKSIFT_HIP_MATCH_PK_NB : 0xFFFFFFFFu;
+        MatchJob jp = j;
+        jp.ss.slot_fast = nslots > 1 ? 1u : 0u;
         /* (8 waves x 128-column tiles: swept against <4,128>, <4,64>, <8,64>, <16,128>, <2,64> on 512 self-matches of 1.9 k x 1.9 k:
          * 0.387 ms against 0.48 / 0.49 / 0.397 / 0.418 / 0.51-0.57 ms) */
         uint32_t gp = (max_na + 255u) / 256u;
         gp = gp < 16u ? gp : 16u;
-        hipLaunchKernelGGL((k_match_pk<8, 128>), sp.slot_fast ? dim3(nslots, gp) : dim3(gp, nslots), dim3(512), 0, hs, da, norm_a, 0u, 0u, db, norm_b, 0u,
-                           (uint32_t *)matches, redo, n_dev, sp, ids, (uint32_t *)nullptr);
+        hipLaunchKernelGGL((k_match_pk<8, 128>), jp.ss.slot_fast ? dim3(nslots, gp) : dim3(gp, nslots), dim3(512), 0, j.hs, j.desc_a, j.norm_a, 0u, 0u, j.desc_b, j.norm_b, 0u,
+                           j.matches, redo, n_dev, jp.ss, ids, (uint32_t *)nullptr);
         S1 = 0u;
         lim = nslots >= 8 ? 16u : lim;
       }
       auto bounded = [lim](uint32_t blocks) { return blocks < lim ? blocks : lim; };
       const uint32_t n1 = max_na < S1 ? max_na : S1;
       if (n1 > 0)
-        hipLaunchKernelGGL(k_match_mfma_split, dim3((n1 + 15u) / 16u, nslots), dim3(256), 0, hs, da, norm_a, 0u, 0u, db, norm_b, 0u, (uint32_t *)matches, redo, n_dev,
-                           0u, S1, ss, ids);
+        launch_split(j, dim3((n1 + 15u) / 16u, nslots), 0u, S1);
       /* What the packed-key kernel leaves (reference sets beyond 32 768 rows) and, without it, everything above S1: two size regimes
        * of the pruning kernel, (S1, 32768] with 16 rows per wave and above with 32 (B fragment reuse). With the packed-key kernel these
        * are the odd slots of a batch, usually none: at most 16 slot positions x 16 row-block positions = 256 workgroups per regime, every
        * one walking the slots of the call (ss.nslots_loop) and the row blocks of a slot that is its own. Without it they carry the
        * whole batch: one workgroup column per slot, slot index fastest so that the busy workgroups are contiguous in dispatch order. */
-      SlotStrides s2 = ss;
-      s2.slot_fast = nslots > 1 ? 1u : 0u;
+      MatchJob j2 = j;
+      j2.ss.slot_fast = nslots > 1 ? 1u : 0u;
       uint32_t gs = nslots;
       if (pk && nslots > 16u)
-        gs = 16u, s2.nslots_loop = nslots;
+        gs = 16u, j2.ss.nslots_loop = nslots;
       if (prune && max_na > S1)
       {
         const uint32_t n2 = max_na < S2 ? max_na : S2;
         const uint32_t gb = bounded((n2 + 63u) / 64u);
-        hipLaunchKernelGGL(k_match_mfma<1>, s2.slot_fast ? dim3(gs, gb) : dim3(gb, gs), dim3(256), 0, hs, da, norm_a, 0u, 0u, db, norm_b, 0u,
-                           (uint32_t *)matches, redo, n_dev, S1, S2, s2, (uint32_t *)nullptr, ids, 0u);
+        launch_prune<1>(j2, j2.ss.slot_fast ? dim3(gs, gb) : dim3(gb, gs), S1, S2);
       }
       if (prune && max_na > S2)
       {
         const uint32_t gb = bounded((max_na + 127u) / 128u);
-        hipLaunchKernelGGL(k_match_mfma<2>, s2.slot_fast ? dim3(gs, gb) : dim3(gb, gs), dim3(256), 0, hs, da, norm_a, 0u, 0u, db, norm_b, 0u,
-                           (uint32_t *)matches, redo, n_dev, S2, 0xFFFFFFFFu, s2, (uint32_t *)nullptr, ids, 0u);
+        launch_prune<2>(j2, j2.ss.slot_fast ? dim3(gs, gb) : dim3(gb, gs), S2, NA_ALL);
       }
     }
     uint32_t rblocks = (max_na + 63u) / 64u;
     const uint32_t rlim = nslots > 64u ? 16u : 64u; /* grid-stride over the rows: the flags are all zero for real descriptors */
     if (rblocks > rlim)
       rblocks = rlim;
-    hipLaunchKernelGGL(k_match_redo, dim3(rblocks, nslots), dim3(64), 0, hs, da, 0u, 0u, db, 0u, (uint32_t *)matches, (const uint32_t *)redo, n_dev, ss, ids);
+    launch_redo(j, dim3(rblocks, nslots));
     return (int)hipGetLastError();
   }
 }
