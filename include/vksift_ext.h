@@ -98,6 +98,37 @@ extern "C"
   /* Time (ms) of the last verification of either model (its three launches + the result posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getVerifyTime(vksift_Instance instance);
 
+  /* ---- GPU-side guided matching -----------------------------------------------------------------------------------------
+   * The step after a model is known: every feature of A is matched again against only those features of B that agree with the pair's model, so the ratio test
+   * compares the best candidate with the second best among the geometrically possible ones, not with a look-alike elsewhere in the image (repeated structure),
+   * for every pair of the last vksift_ext_matchFeaturesFiltered call, without downloading features or descriptors. With the model M (nine floats, row-major,
+   * pixel coordinates) (a, b) is admissible under a homography iff, with (u, v, d) = M (xa, ya, 1), d > 0 and (u - xb d)^2 + (v - yb d)^2 < (d d) t2; under a
+   * fundamental matrix iff, with l = M (xa, ya, 1), m = M^T (xb, yb, 1), r = (xb, yb, 1) l, r r < t2 ((l0 l0 + l1 l1) + (m0 m0 + m1 m1)); t2 = threshold_px^2;
+   * fp32, every operation rounded once, in this order (tests/np_guided.py restates the records bit for bit). Among the admissible b the nearest and the second
+   * nearest descriptor of a (exact integer distances, ties to the lowest index; padding rows are never candidates), and the same for every b over the admissible
+   * a (the same relation: the model is not inverted). (a, b1) is kept iff dist1 <= max_distance (+inf: no limit), dist1 / dist2 < ratio (true without a second
+   * candidate) and, with cross_check, b1's nearest admissible a is a and passes its own ratio test. Records in increasing idx_a; dist_a_b2 = +inf without a
+   * second candidate. A pair whose model is not valid has no guided matches.
+   * The test runs on the PUBLISHED model, so that a caller can reproduce it from public outputs and a supplied model means the same thing; the inlier masks
+   * come from the scaled internal model: it is NOT promised that a filtered match is admissible exactly when its mask byte is 1, to the last bit.
+   * models == NULL: the model of that kind verified for every pair of the last vksift_ext_matchFeaturesFiltered (an error if it has not been); otherwise 9
+   * floats per pair, the caller's own (e.g. refitted) models in the same convention, all finite; they are copied before the call returns.
+   * Contract of the verification entry points: asynchronous, queued behind the matching and the verification, the pairs' buffers stay busy, the accessors wait;
+   * results of its own (filtered matches, both models and their masks stay readable), replaced by the next run, invalidated by a new matching, plain or filtered.
+   * Precondition, as for the verification: the buffers of the pairs still hold the features that were matched. A detection or an upload into one of them after
+   * vksift_ext_matchFeaturesFiltered is not noticed: the row counts are the matching's, the rows the buffer's present ones, and the records are then
+   * meaningless (every read stays inside the buffers' storage). Match again first.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, earlier guided results untouched): no filtered matching, models == NULL for a model that has not been verified,
+   * an unknown kind, threshold_px not positive and finite, ratio or max_distance not greater than 0, a supplied model that is not finite, pair out of range. */
+#define VKSIFT_EXT_GUIDE_HOMOGRAPHY 0u
+#define VKSIFT_EXT_GUIDE_FUNDAMENTAL 1u
+  VKSIFT_EXPORT void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, const float *models, float threshold_px, float ratio,
+                                                    float max_distance, bool cross_check);
+  VKSIFT_EXPORT uint32_t vksift_ext_getGuidedMatchesNumber(vksift_Instance instance, uint32_t pair);
+  VKSIFT_EXPORT void vksift_ext_downloadGuidedMatches(vksift_Instance instance, uint32_t pair, vksift_ext_FilteredMatch *matches);
+  /* Time (ms) of the last guided matching (gather + sweeps + decision + the count posting), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getGuidedMatchTime(vksift_Instance instance);
+
   /* Deferred submission of vksift_detectFeatures (no counterpart in the reference, no change of its contract): consecutive plain
    * detect calls into consecutive SIFT buffers, with nothing asked in between, are staged and launched as ONE batched detection by
    * the first call that needs a result — any other entry point — or when 128 images (VKSIFT_DEFER_MAX) are staged, or 16 (VKSIFT_DEFER_CHUNK)

@@ -392,6 +392,37 @@ extern "C"
                                     uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
                                     uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
 
+  /* ------------------------------------------------------------------ guided matching (guided.hip; no counterpart in the reference) */
+#define VKSIFT_HIP_GUIDE_HOMOGRAPHY 0u
+#define VKSIFT_HIP_GUIDE_FUNDAMENTAL 1u
+  /* {x, y} of every stored row of both buffers of every slot, in download order: side t (0 = A, 1 = B) of slot i as dense float2 at
+   * xy + (2*i + t) * xy_side_stride * 2 floats (8-byte aligned; xy_side_stride >= max_n, rows [0, min(stored, max_n)) are written). slot_tab / layouts, the
+   * section walk and the counters as for vksift_hip_gather_correspondences. One launch whatever nslots. */
+  int vksift_hip_gather_xy(const uint8_t *feats_base, uint64_t buf_stride, const uint32_t *found_base, uint32_t found_buf_stride, const uint32_t *slot_tab,
+                           const uint32_t *layouts, uint32_t max_n, uint32_t nslots, float *xy, uint64_t xy_side_stride, vksift_hip_stream s);
+  /* Guided matching of nslots pairs in two or three launches (forward sweep, reverse sweep with cross_check, decision). Slot i: the features of A are the
+   * N_A = min(n_dev[i*n_stride], max_n) rows of cache entry slot_tab[i*slot_tab_stride] (dense 128-byte rows at cache_desc + entry*cache_desc_stride bytes, their
+   * shifted norms sum (byte - 128)^2 at cache_norm + entry*cache_norm_stride words: what vksift_hip_gather_sections / vksift_hip_shifted_norms write), the
+   * features of B the N_B = min(n_dev[i*n_stride + 1], max_n) rows of entry slot_tab[i*slot_tab_stride + 1]; their coordinates as vksift_hip_gather_xy lays them
+   * out; the model nine floats at models + i*model_stride (row-major, pixel coordinates, the convention of vksift_ext_getHomography / vksift_ext_getFundamental)
+   * and the word valid[i*valid_stride] (0: the slot yields no record). slot_tab, models and valid are read by the kernels (device or mapped pinned memory).
+   * (a, b) is admissible under a homography iff, with (u, v, d) = M (xa, ya, 1), d > 0 and (u - xb d)^2 + (v - yb d)^2 < (d d) t2; under a fundamental matrix
+   * iff, with l = M (xa, ya, 1), m = M^T (xb, yb, 1) and r = (xb, yb, 1) l, r r < t2 ((l0 l0 + l1 l1) + (m0 m0 + m1 m1)) — correctly rounded fp32 add / sub / mul
+   * in this order on unscaled pixels; t2 is the squared threshold in pixels. Forward record of a: the smallest and the second smallest key (d2 << 32 | b) over the
+   * admissible b (d2: the exact integer squared descriptor distance; ties to the lowest index; no padding rows, none of the plain matcher's quirks), dist =
+   * sqrtf(d2), dist2 = +inf with a single candidate; the reverse record of b likewise over the admissible a (the same relation, the model is not inverted).
+   * (a, b1(a)) is kept iff dist1 <= max_distance, dist1 / dist2 < ratio and, with cross_check, a1(b1(a)) == a and the reverse record passes its own ratio test.
+   * out + i*out_slot_stride (bytes): 16-byte records {idx_a, idx_b, dist1, dist2} in increasing idx_a, out_n[i] their number. tests/np_guided.py restates every
+   * record bit for bit. scratch: scratch_u32 >= vksift_hip_guided_scratch_u32(nslots, max_n) words, 8-byte aligned, need not be initialised.
+   * hipErrorInvalidValue, nothing launched: unknown model_kind, t2 not positive and finite, ratio or max_distance not greater than 0 (+inf is a max_distance),
+   * too little scratch, a stride below max_n rows (records, norms, coordinates, output), max_n above 2^24, nslots 0 or above 65535. */
+  size_t vksift_hip_guided_scratch_u32(uint32_t nslots, uint32_t max_n);
+  int vksift_hip_match_guided(const uint8_t *cache_desc, uint64_t cache_desc_stride, const uint32_t *cache_norm, uint64_t cache_norm_stride, const uint32_t *slot_tab,
+                              uint32_t slot_tab_stride, const float *xy, uint64_t xy_side_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n,
+                              const float *models, uint32_t model_stride, const uint32_t *valid, uint32_t valid_stride, uint32_t model_kind, float t2, float ratio,
+                              float max_distance, uint32_t cross_check, uint32_t nslots, uint8_t *out, uint64_t out_slot_stride, uint32_t *out_n, uint32_t *scratch,
+                              size_t scratch_u32, vksift_hip_stream s);
+
 #ifdef __cplusplus
 }
 #endif

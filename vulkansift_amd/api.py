@@ -141,6 +141,14 @@ def lib():
     L.vksift_ext_downloadFundamentalInlierMask.restype = None
     L.vksift_ext_getVerifyTime.argtypes = [inst]
     L.vksift_ext_getVerifyTime.restype = C.c_float
+    L.vksift_ext_matchFeaturesGuided.argtypes = [inst, u32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_bool]
+    L.vksift_ext_matchFeaturesGuided.restype = None
+    L.vksift_ext_getGuidedMatchesNumber.argtypes = [inst, u32]
+    L.vksift_ext_getGuidedMatchesNumber.restype = u32
+    L.vksift_ext_downloadGuidedMatches.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_downloadGuidedMatches.restype = None
+    L.vksift_ext_getGuidedMatchTime.argtypes = [inst]
+    L.vksift_ext_getGuidedMatchTime.restype = C.c_float
     L.vksift_ext_setProfiling.argtypes = [inst, C.c_bool]
     L.vksift_ext_getDetectTimings.argtypes = [inst, C.POINTER(vksift_ext_DetectTimings)]
     L.vksift_ext_getAccumulatedDetectTimings.argtypes = [inst, C.POINTER(vksift_ext_DetectTimings), C.POINTER(u32), C.c_bool]
@@ -200,6 +208,12 @@ def lib():
     L.vksift_hip_ransac_homography.restype = C.c_int
     L.vksift_hip_ransac_fundamental.argtypes = L.vksift_hip_ransac_homography.argtypes
     L.vksift_hip_ransac_fundamental.restype = C.c_int
+    L.vksift_hip_guided_scratch_u32.argtypes = [u32, u32]
+    L.vksift_hip_guided_scratch_u32.restype = C.c_size_t
+    L.vksift_hip_match_guided.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, C.c_uint64, C.c_void_p, u32, u32,
+                                          C.c_void_p, u32, C.c_void_p, u32, u32, C.c_float, C.c_float, C.c_float, u32, u32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]
+    L.vksift_hip_match_guided.restype = C.c_int
     _lib = L
     return L
 
@@ -316,6 +330,53 @@ def ransac_homography(corr, n, nb_hypotheses, threshold_px, seed, scratch_u32=No
 def ransac_fundamental(corr, n, nb_hypotheses, threshold_px, seed, scratch_u32=None):
     """vksift_hip_ransac_fundamental, as ransac_homography; the results are a FUNDAMENTAL_DTYPE array"""
     return _ransac(lib().vksift_hip_ransac_fundamental, 14, FUNDAMENTAL_DTYPE, corr, n, nb_hypotheses, threshold_px, seed, scratch_u32)
+
+
+GUIDE_HOMOGRAPHY, GUIDE_FUNDAMENTAL = 0, 1
+
+
+def guided_match(desc_a, xy_a, desc_b, xy_b, n, models, valid, model_kind, t2, ratio, max_distance, cross_check, scratch_u32=None, strides=None, buffers=None):
+    """vksift_hip_match_guided on torch tensors on the GPU: desc_a / desc_b uint8 [nslots, max_n, 128] (dense rows), xy_a / xy_b float32 [nslots, max_n, 2],
+    n int32 [nslots, 2] = {N_A, N_B}, models float32 [nslots, 9], valid int32 [nslots]; t2 is the squared threshold in pixels. The shifted norms of the rows are
+    formed here the way the matcher's cache holds them. Returns (error code, [FILTERED_MATCH_DTYPE array per slot]); on an error nothing was launched and the
+    list is None. scratch_u32: words of scratch to hand over instead of what vksift_hip_guided_scratch_u32 asks for; strides: overrides of the row strides
+    {"desc", "norm", "xy", "out"} in their own units; buffers: a dict that receives the tensors the launches write ("out", "out_n", "scratch"), each
+    filled with -1 beforehand (the refusal tests)."""
+    import torch
+
+    nslots, max_n = int(desc_a.shape[0]), int(desc_a.shape[1])
+    for d, xy in ((desc_a, xy_a), (desc_b, xy_b)):
+        assert d.is_cuda and d.dtype == torch.uint8 and d.shape == (nslots, max_n, 128) and xy.is_cuda and xy.dtype == torch.float32 and xy.shape == (nslots, max_n, 2)
+    assert n.is_cuda and n.dtype == torch.int32 and n.shape == (nslots, 2) and n.is_contiguous()
+    assert models.is_cuda and models.dtype == torch.float32 and models.shape == (nslots, 9) and models.is_contiguous()
+    assert valid.is_cuda and valid.dtype == torch.int32 and valid.shape == (nslots,) and valid.is_contiguous()
+    dev = desc_a.device
+    rows = max(max_n, 1)
+    # cache entry 2 i holds A of slot i, entry 2 i + 1 its B; the coordinates lie the same way
+    desc = torch.zeros((nslots, 2, rows, 128), dtype=torch.uint8, device=dev)
+    xy = torch.full((nslots, 2, rows, 2), float("nan"), dtype=torch.float32, device=dev)
+    desc[:, 0, :max_n], desc[:, 1, :max_n], xy[:, 0, :max_n], xy[:, 1, :max_n] = desc_a, desc_b, xy_a, xy_b
+    norm = ((desc.to(torch.int32) - 128) ** 2).sum(dim=3).to(torch.int32).contiguous()
+    tab = torch.arange(2 * nslots, dtype=torch.int32, device=dev)
+    need = int(lib().vksift_hip_guided_scratch_u32(nslots, max_n))
+    words = need if scratch_u32 is None else scratch_u32
+    # poisoned: the scratch needs no initialisation, the counts are written for every slot
+    scratch = torch.full((max(words, 2),), -1, dtype=torch.int32, device=dev)
+    out = torch.full((nslots, rows, 4), -1, dtype=torch.int32, device=dev)
+    out_n = torch.full((nslots,), -1, dtype=torch.int32, device=dev)
+    if buffers is not None:
+        buffers.update(out=out, out_n=out_n, scratch=scratch)
+    st = {"desc": rows * 128, "norm": rows, "xy": rows, "out": rows * 16}
+    st.update(strides or {})
+    err = lib().vksift_hip_match_guided(desc.data_ptr(), st["desc"], norm.data_ptr(), st["norm"], tab.data_ptr(), 2, xy.data_ptr(), st["xy"], n.data_ptr(), 2, max_n,
+                                        models.data_ptr(), 9, valid.data_ptr(), 1, model_kind, t2, ratio, max_distance, 1 if cross_check else 0, nslots,
+                                        out.data_ptr(), st["out"], out_n.data_ptr(), scratch.data_ptr(), words, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    if err:
+        return err, None
+    cnt = out_n.cpu().numpy()
+    rec = out.cpu().numpy()
+    return 0, [rec[i, :cnt[i]].copy().view(FILTERED_MATCH_DTYPE).reshape(-1) for i in range(nslots)]
 
 
 class Instance:
@@ -459,6 +520,28 @@ class Instance:
 
     def getVerifyTime(self):
         return lib().vksift_ext_getVerifyTime(self._h)
+
+    def matchFeaturesGuided(self, model, models=None, threshold_px=2.5, ratio=0.8, max_distance=float("inf"), cross_check=True):
+        """guided matching of every pair of the last matchFeaturesFiltered call under its verified model of kind `model` (GUIDE_HOMOGRAPHY /
+        GUIDE_FUNDAMENTAL), or under `models` (float32 [pairs, 9] or [pairs, 3, 3]) when given (vksift_ext_matchFeaturesGuided)"""
+        ptr = None
+        if models is not None:
+            models = np.ascontiguousarray(models, dtype=np.float32).reshape(-1, 9)
+            ptr = models.ctypes.data
+        lib().vksift_ext_matchFeaturesGuided(self._h, model, ptr, threshold_px, ratio, max_distance, cross_check)
+        _check_pending()
+
+    def downloadGuidedMatches(self, pair=0):
+        n = lib().vksift_ext_getGuidedMatchesNumber(self._h, pair)
+        _check_pending()
+        out = np.zeros(n, FILTERED_MATCH_DTYPE)
+        if n:
+            lib().vksift_ext_downloadGuidedMatches(self._h, pair, out.ctypes.data)
+            _check_pending()
+        return out
+
+    def getGuidedMatchTime(self):
+        return lib().vksift_ext_getGuidedMatchTime(self._h)
 
     def getMatchesNumberBatch(self, pair):
         n = lib().vksift_ext_getMatchesNumberBatch(self._h, pair)

@@ -15,6 +15,7 @@ void vksift_ext_setProfiling(vksift_Instance instance, bool enabled)
   instance->prof[0].accounted = instance->prof[1].accounted = false;
   instance->match_timing_valid = false;
   instance->verify_timing_valid = false;
+  instance->guided_timing_valid = false;
   memset(instance->acc_ms, 0, sizeof(instance->acc_ms));
   instance->acc_calls = 0;
   instance->acc_blur_launches = 0;

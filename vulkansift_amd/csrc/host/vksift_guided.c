@@ -1,0 +1,190 @@
+/*
+ * vksift_guided.c — guided matching of the pairs of the last filtered matching under their verified (or the caller's) models
+ * (vksift_ext_matchFeaturesGuided and its accessors). No counterpart in the reference: its callers download every feature and descriptor
+ * and loop on the CPU. Same contract as the verification it follows (vksift_verify.c): queued on the instance stream, the pairs' buffers
+ * busy, the accessors wait; results in storage of its own.
+ */
+#include "vksift_internal.h"
+
+#define GUIDED_FN "vksift_ext_matchFeaturesGuided()"
+
+/* words of h_gtab in front of the supplied models: the slot table and the section tables */
+static size_t gtab_models_at(const struct vksift_Instance_T *inst) { return (size_t)4u * inst->batch_cap + (size_t)VERIFY_LAYOUT_WORDS * 2u * inst->batch_cap; }
+
+/* coordinates, keys, records and counts of batch_cap pairs, allocated by the first guided matching */
+static bool ensure_guided_scratch(vksift_Instance inst)
+{
+  const uint32_t bc = inst->batch_cap, nb = inst->cfg.max_nb_sift_per_buffer;
+  inst->gxy_side_stride = nb;
+  inst->guided_slot_stride = (((uint64_t)nb * 16u) + 255u) & ~(uint64_t)255u;
+  inst->gkeys_u32 = vksift_hip_guided_scratch_u32(bc, nb);
+  const bool ok = mem_ensure(&inst->d_gxy, sizeof(float) * 2u * 2u * inst->gxy_side_stride * bc + 8u, MEM_DEVICE) &&
+                  mem_ensure(&inst->d_gkeys, sizeof(uint32_t) * inst->gkeys_u32 + 8u, MEM_DEVICE) && mem_ensure(&inst->d_guided, inst->guided_slot_stride * bc, MEM_DEVICE) &&
+                  mem_ensure(&inst->d_guided_n, sizeof(uint32_t) * bc, MEM_DEVICE) && mem_ensure(&inst->h_guided_n, sizeof(uint32_t) * bc, MEM_PINNED) &&
+                  mem_ensure(&inst->h_gtab, sizeof(uint32_t) * (gtab_models_at(inst) + (size_t)10u * bc), MEM_PINNED);
+  if (!inst->ev_gtab)
+    inst->ev_gtab = vksift_hip_event_create();
+  for (int i = 0; i < 2; i++)
+    if (!inst->ev_g[i])
+      inst->ev_g[i] = vksift_hip_event_create();
+  return ok && inst->ev_gtab && inst->ev_g[0] && inst->ev_g[1];
+}
+
+void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, const float *models, float threshold_px, float ratio, float max_distance,
+                                    bool cross_check)
+{
+  vksift_Instance inst = instance;
+  bool range_open = false;
+  vksift_hip_set_device(inst->device);
+  defer_sync(inst);
+  const uint32_t count = inst->filtered_slots_used;
+  /* the squared threshold in pixels, formed like the verification's (threshold_px 2^-13)^2 and brought back by the exact factor 2^26 */
+  const float ts = threshold_px * (1.0f / 8192.0f), t2 = (ts * ts) * 67108864.0f;
+  bool valid = count > 0 && model <= VKSIFT_EXT_GUIDE_FUNDAMENTAL && threshold_px > 0.f && isfinite(threshold_px) && t2 > 0.f && isfinite(t2) && ratio > 0.f &&
+               max_distance > 0.f;
+  if (valid && models == NULL)
+    valid = (model == VKSIFT_EXT_GUIDE_HOMOGRAPHY ? inst->verify_slots_used : inst->verify_f_slots_used) == count;
+  for (size_t i = 0; valid && models != NULL && i < (size_t)9u * count; i++)
+    valid = isfinite(models[i]);
+  if (!valid)
+  {
+    logError(LOG_TAG, GUIDED_FN " error: invalid input.");
+    inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
+    return;
+  }
+  if (!ensure_guided_scratch(inst))
+  {
+    logError(LOG_TAG, GUIDED_FN " error: out of device memory for the guided-matching scratch.");
+    goto gpu_error;
+  }
+  /* the tables are read by the launches out of pinned memory: the previous guided matching must be through with them */
+  if (inst->gtab_pending)
+  {
+    HIP_CHECK(vksift_hip_event_sync(inst->ev_gtab), "event synchronisation");
+    inst->gtab_pending = false;
+  }
+  uint32_t max_rows = 0;
+  {
+    uint32_t *layouts = inst->h_gtab + (size_t)4u * inst->batch_cap, nlay = 0;
+    (void)detect_running(inst); /* polls the detections in flight: rows_bound() uses the counts that have arrived */
+    for (uint32_t i = 0; i < count; i++)
+    {
+      const uint32_t a = inst->filt_ids[i], b = inst->filt_ids[inst->batch_cap + i];
+      uint32_t *t = inst->h_gtab + (size_t)4u * i;
+      t[0] = a, t[1] = b;
+      t[2] = layout_word(&inst->bufs[a], layouts, &nlay);
+      t[3] = layout_word(&inst->bufs[b], layouts, &nlay);
+      const uint32_t ra = rows_bound(inst, a), rb = rows_bound(inst, b);
+      max_rows = ra > max_rows ? ra : max_rows;
+      max_rows = rb > max_rows ? rb : max_rows;
+    }
+    if (max_rows > inst->cfg.max_nb_sift_per_buffer)
+      max_rows = inst->cfg.max_nb_sift_per_buffer;
+  }
+  uint32_t *h_models = inst->h_gtab + gtab_models_at(inst), *h_ones = h_models + (size_t)9u * inst->batch_cap;
+  const float *d_models;
+  const uint32_t *d_valid;
+  uint32_t model_stride, valid_stride;
+  if (models != NULL)
+  {
+    memcpy(h_models, models, sizeof(float) * 9u * count);
+    for (uint32_t i = 0; i < count; i++)
+      h_ones[i] = 1u;
+    d_models = (const float *)h_models, model_stride = 9u, d_valid = h_ones, valid_stride = 1u;
+  }
+  else if (model == VKSIFT_EXT_GUIDE_HOMOGRAPHY)
+    d_models = (const float *)inst->d_vres, model_stride = 13u, d_valid = inst->d_vres + 12u, valid_stride = 13u;
+  else
+    d_models = (const float *)inst->d_fres, model_stride = 14u, d_valid = inst->d_fres + 13u, valid_stride = 14u;
+  if (inst->profiling)
+    vksift_hip_event_record(inst->ev_g[0], inst->stream);
+  vksift_hip_range_push("Guided matching");
+  range_open = true;
+  /* the dense rows and norms: the matcher's cache, refreshed the way the matcher does it (a no-op while the buffers are unchanged) */
+  HIP_CHECK(refresh_match_cache(inst, inst->filt_ids, count), "descriptor gather");
+  HIP_CHECK(refresh_match_cache(inst, inst->filt_ids + inst->batch_cap, count), "descriptor gather");
+  HIP_CHECK(vksift_hip_gather_xy(inst->d_feats, inst->buf_stride, inst->d_found, VKSIFT_MAX_OCTAVES, inst->h_gtab, inst->h_gtab + (size_t)4u * inst->batch_cap, max_rows,
+                                 count, inst->d_gxy, inst->gxy_side_stride, inst->stream),
+            "coordinate gather");
+  /* {N_A, N_B} are the words the matching left in d_match_n, rows and coordinates the buffers' present ones: the same while the buffers hold the
+   * matched features, which the header asks for (as the verification does; nothing here notices a buffer refilled since). Strides are those of
+   * max_nb_sift_per_buffer rows, so the reads stay inside the storage either way. One launch sequence serves 65535 pairs. */
+  for (uint32_t r = 0; r < count; r += 65535u)
+  {
+    const uint32_t n = count - r < 65535u ? count - r : 65535u;
+    HIP_CHECK(vksift_hip_match_guided(inst->d_cache_desc, inst->desc_slot_stride, inst->d_cache_norm, inst->cache_norm_stride, inst->h_gtab + (size_t)4u * r, 4u,
+                                      inst->d_gxy + (size_t)4u * inst->gxy_side_stride * r, inst->gxy_side_stride, inst->d_match_n + (size_t)4u * r, 4u, max_rows,
+                                      d_models + (size_t)model_stride * r, model_stride, d_valid + (size_t)valid_stride * r, valid_stride, model, t2, ratio, max_distance,
+                                      cross_check ? 1u : 0u, n, inst->d_guided + inst->guided_slot_stride * r, inst->guided_slot_stride, inst->d_guided_n + r,
+                                      inst->d_gkeys, inst->gkeys_u32, inst->stream),
+              "guided matching");
+  }
+  HIP_CHECK(vksift_hip_event_record(inst->ev_gtab, inst->stream), "event record");
+  inst->gtab_pending = true;
+  HIP_CHECK(vksift_hip_post_words(inst->h_guided_n, inst->d_guided_n, count, inst->stream), "guided count read-back");
+  vksift_hip_range_pop();
+  range_open = false;
+  if (inst->profiling)
+  {
+    vksift_hip_event_record(inst->ev_g[1], inst->stream);
+    inst->guided_timing_valid = true;
+  }
+  /* same contract as the matching it follows: the accessors wait for ev_match, the pairs' buffers stay busy until it has passed */
+  (void)match_running(inst);
+  HIP_CHECK(vksift_hip_event_record(inst->ev_match, inst->stream), "event record");
+  inst->match_pending = true;
+  for (uint32_t i = 0; i < count; i++)
+    inst->match_busy[inst->filt_ids[i]] = inst->match_busy[inst->filt_ids[inst->batch_cap + i]] = true;
+  inst->guided_slots_used = count;
+  return;
+gpu_error:
+  if (range_open)
+    vksift_hip_range_pop();
+  logError(LOG_TAG, GUIDED_FN " error: Failed to start the guided-matching pipeline.");
+  inst->error_cb(VKSIFT_VULKAN_ERROR);
+}
+
+uint32_t vksift_ext_getGuidedMatchesNumber(vksift_Instance instance, uint32_t pair)
+{
+  wait_match(instance);
+  if (pair >= instance->guided_slots_used)
+  {
+    logError(LOG_TAG, "vksift_ext_getGuidedMatchesNumber() error: invalid input.");
+    instance->error_cb(VKSIFT_INVALID_INPUT_ERROR);
+    return 0;
+  }
+  return instance->h_guided_n[pair];
+}
+
+void vksift_ext_downloadGuidedMatches(vksift_Instance instance, uint32_t pair, vksift_ext_FilteredMatch *matches)
+{
+  vksift_Instance inst = instance;
+  wait_match(inst);
+  if (pair >= inst->guided_slots_used)
+  {
+    logError(LOG_TAG, "vksift_ext_downloadGuidedMatches() error: invalid input.");
+    inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
+    return;
+  }
+  const uint32_t n = inst->h_guided_n[pair];
+  if (n > 0)
+  {
+    HIP_CHECK(vksift_hip_memcpy_d2h(matches, inst->d_guided + (uint64_t)pair * inst->guided_slot_stride, (size_t)n * sizeof(vksift_ext_FilteredMatch), inst->dl_stream),
+              "guided match read-back");
+    HIP_CHECK(vksift_hip_stream_sync(inst->dl_stream), "guided match read-back");
+  }
+  return;
+gpu_error:
+  logError(LOG_TAG, "vksift_ext_downloadGuidedMatches() error when downloading the guided matches from GPU memory.");
+  inst->error_cb(VKSIFT_VULKAN_ERROR);
+}
+
+float vksift_ext_getGuidedMatchTime(vksift_Instance instance)
+{
+  defer_sync(instance);
+  if (!instance->profiling || !instance->guided_timing_valid)
+    return -1.f;
+  vksift_hip_set_device(instance->device);
+  wait_all(instance);
+  return vksift_hip_event_elapsed_ms(instance->ev_g[0], instance->ev_g[1]);
+}

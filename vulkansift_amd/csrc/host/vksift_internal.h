@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_guided.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -229,6 +229,19 @@ struct vksift_Instance_T
   uint32_t *d_fres, *h_fres;   /* 14 words (vksift_ext_Fundamental) per slot */
   uint32_t verify_f_slots_used;
   bool verify_timing_valid;
+  /* guided matching (vksift_ext_matchFeaturesGuided, vksift_guided.c): results of its own beside the filtered matches and the models; allocated on first use */
+  float *d_gxy;             /* per slot: 2 * gxy_side_stride float2, the coordinates of A's rows, then of B's */
+  uint64_t gxy_side_stride; /* float2 elements */
+  uint32_t *d_gkeys;        /* the sweeps' top-2 keys (vksift_hip_guided_scratch_u32) */
+  size_t gkeys_u32;
+  uint8_t *d_guided;        /* per slot: guided_slot_stride bytes of vksift_ext_FilteredMatch */
+  uint64_t guided_slot_stride;
+  uint32_t *d_guided_n, *h_guided_n;
+  uint32_t *h_gtab;         /* mapped pinned memory read by the launches: per slot {buffer A, buffer B, layout A, layout B}, the section tables (33 words each),
+                             * then 9 floats per slot of supplied models and a word 1 per slot */
+  bool gtab_pending;
+  uint32_t guided_slots_used;
+  bool guided_timing_valid;
 
   /* ---- download staging. Batched download: the first vksift_downloadFeatures() after a detection of VKSIFT_DL_BATCH_MIN images and more
    * packs the features of ALL its buffers on the device and fetches them with one copy into pinned memory; the downloads of the
@@ -277,6 +290,8 @@ struct vksift_Instance_T
   vksift_hip_event dl_ev[VKSIFT_DL_CHUNKS]; /* the packed copy arrives in pieces (created by the first one) */
   vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab (created, like ev_v, by the first verification) */
   vksift_hip_event ev_v[2];
+  vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created, like ev_g, by the first guided matching) */
+  vksift_hip_event ev_g[2];
   bool desc_start_valid, input_free_valid, staging_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];
   uint64_t det_seq, det_done; /* last detection issued / highest one known to have completed */
@@ -374,6 +389,12 @@ VKSIFT_INTERNAL uint32_t buffer_counts(vksift_Instance inst, uint32_t buf, uint3
 /* vksift_match.c */
 VKSIFT_INTERNAL MatchScratch fwd_scratch(vksift_Instance inst);
 VKSIFT_INTERNAL int refresh_match_cache(vksift_Instance inst, const uint32_t *ids, uint32_t count);
+VKSIFT_INTERNAL uint32_t rows_bound(vksift_Instance inst, uint32_t id);
 VKSIFT_INTERNAL void wait_match(vksift_Instance inst);
+
+/* vksift_verify.c: layout word of a buffer for the launches that resolve download-order rows on the device (vksift_hip_gather_correspondences,
+ * vksift_hip_gather_xy); its section table ({nsec, off[16], cap[16]}) is appended to `layouts` unless an equal one is there */
+#define VERIFY_LAYOUT_WORDS 33u
+VKSIFT_INTERNAL uint32_t layout_word(const BufferInfo *b, uint32_t *layouts, uint32_t *nlay);
 
 #endif

@@ -21,7 +21,7 @@ static bool same_layout(const BufferInfo *x, const BufferInfo *y)
 
 /* Launch bound on the number of stored rows of a buffer: the real total if its counters have reached the host, else the
  * sum of its section capacities. */
-static uint32_t rows_bound(vksift_Instance inst, uint32_t id)
+uint32_t rows_bound(vksift_Instance inst, uint32_t id)
 {
   const BufferInfo *b = &inst->bufs[id];
   if (b->nb_sections == 0)
@@ -188,6 +188,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
   inst->filtered_slots_used = 0;
   inst->verify_slots_used = 0;
   inst->verify_f_slots_used = 0;
+  inst->guided_slots_used = 0;
   inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
   if (filter)
   {

@@ -8,7 +8,6 @@
 
 #define VERIFY_RES_WORDS 13u   /* sizeof(vksift_ext_Homography) / 4 */
 #define VERIFY_F_RES_WORDS 14u /* sizeof(vksift_ext_Fundamental) / 4 */
-#define VERIFY_LAYOUT_WORDS 33u
 #define VERIFY_MAX_HYPOTHESES 65536u
 
 _Static_assert(sizeof(vksift_ext_Homography) == 4u * VERIFY_RES_WORDS, "vksift_ext_Homography is the kernel's 13-word result record");
@@ -61,7 +60,7 @@ static bool ensure_verify_scratch(vksift_Instance inst, const VerifyModel *m)
 }
 
 /* layout word of a buffer for vksift_hip_gather_correspondences: its section table is appended to `layouts` unless an equal one is there */
-static uint32_t layout_word(const BufferInfo *b, uint32_t *layouts, uint32_t *nlay)
+uint32_t layout_word(const BufferInfo *b, uint32_t *layouts, uint32_t *nlay)
 {
   if (b->nb_sections == 0)
     return 0x80000000u | b->nb_stored; /* uploaded: one dense run of records */
