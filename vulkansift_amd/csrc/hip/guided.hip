@@ -1,23 +1,24 @@
 // guided.hip — guided matching: every feature of a verified pair matched again against only those features of the other image that agree
 // with the pair's model (a homography or a fundamental matrix), so that the ratio test compares the best candidate with the second best
 // among the geometrically possible ones (no counterpart in the reference, whose callers loop over downloaded features on the CPU).
-//   k_gather_xy        {x, y} of every stored row of both buffers of every slot, download order, dense float2 (the layout-table walk of
-//                      k_gather_corr, verify.hip)
+//   k_gather_xy        {x, y} of every stored row of both buffers of every slot, download order, dense float2 (layout decode and walk:
+//                      records.h)
 //   k_guided_2nn<M, R> one workgroup per tile of 256 owner rows of a slot, a lane owns one row. The sweep over the other side is the
 //                      geometric test alone (about 8 VALU operations per pair: what depends on one side only is computed once, in the
 //                      owner's registers or while the other side is staged in LDS, read back as broadcasts). Admissible pairs are rare;
 //                      they are queued per wave in LDS as (owner lane, candidate) and drained one lane per entry whenever 64 wait: exact
 //                      integer distance from the matcher's cached rows and shifted norms, folded as a 64-bit key (d2 << 32 | candidate)
 //                      into the owner's two LDS slots (atomic min on the first; what loses there goes by atomic min into the second).
-//   k_guided_keep      per slot: max_distance, ratio test, cross-check; survivors in increasing idx_a (ballot + scan, no atomics)
-// The test is the expression of is_inlier / is_inlier_f (verify.hip) on unscaled pixel coordinates with the published model: correctly
-// rounded fp32 add / sub / mul in the order written (the tree is built with -ffp-contract=off), so tests/np_guided.py restates every
-// record bit for bit. Hoisting changes no bit: each hoisted value is the same fp32 expression.
+//   k_guided_keep      per slot: max_distance, ratio test, cross-check; survivors in increasing idx_a (ordered_keep, records.h)
+// The test is two_view.h's, the one the verification counted inliers with, here on unscaled pixel coordinates with the published model:
+// correctly rounded fp32 add / sub / mul in the order written, so tests/np_guided.py restates every record bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "vksift_hip.h"
+#include "hip/records.h"
+#include "hip/two_view.h"
 
 namespace
 {
@@ -28,107 +29,25 @@ constexpr uint32_t kWaveQueue = kChunk * 64u + 64u;   // fewer than 64 entries w
 constexpr unsigned long long kNoKey = ~0ull;
 
 // ---- stage 1 ---------------------------------------------------------------------------------------------------------------------------
-// Workgroup 2 * slot + side. slot_tab / layouts as for k_gather_corr: {buffer A, buffer B, layout A, layout B} per slot; a layout word with
-// bit 31 set names a buffer of that many dense rows, any other value a section table {nsec, off[16], cap[16]} whose stored counts
-// min(found, cap) are read on the device. Rows [0, min(total, max_n)) are written, nothing else.
+// Workgroup 2 * slot + side. slot_tab: {buffer A, buffer B, layout A, layout B} per slot, layouts: the section tables (records.h). Rows
+// [0, min(total, max_n)) are written, nothing else.
 __global__ void __launch_bounds__(256) k_gather_xy(const uint8_t *__restrict__ feats_base, uint64_t buf_stride, const uint32_t *__restrict__ found_base,
                                                    uint32_t found_buf_stride, const uint32_t *__restrict__ slot_tab, const uint32_t *__restrict__ layouts,
                                                    uint32_t max_n, float2 *__restrict__ xy, uint64_t xy_side_stride)
 {
-  __shared__ uint32_t s_off[16], s_cnt[16], s_total, s_buf;
-  const uint32_t slot = blockIdx.x >> 1, side = blockIdx.x & 1u;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t *tab = slot_tab + (size_t)slot * 4u;
-  if (tid < 16u)
-  {
-    const uint32_t o = tid;
-    const uint32_t bufi = tab[side], lay = tab[2u + side];
-    uint32_t off = 0, cnt = 0;
-    if (lay & 0x80000000u)
-      cnt = o == 0u ? (lay & 0x7fffffffu) : 0u;
-    else
-    {
-      const uint32_t *L = layouts + (size_t)lay * 33u;
-      if (o < L[0] && o < found_buf_stride)
-      {
-        const uint32_t f = found_base[(size_t)bufi * found_buf_stride + o], cap = L[17u + o];
-        off = L[1u + o];
-        cnt = f < cap ? f : cap;
-      }
-    }
-    s_off[o] = off, s_cnt[o] = cnt;
-    if (o == 0u)
-      s_buf = bufi; // (the table may live in mapped host memory: read once)
-  }
-  __syncthreads();
-  if (tid == 0u)
-  {
-    uint32_t t = 0;
-    for (uint32_t o = 0; o < 16u; o++)
-      t += s_cnt[o];
-    s_total = t;
-  }
-  __syncthreads();
-  const uint32_t n = s_total < max_n ? s_total : max_n;
+  __shared__ SideLayout L[1];
+  layout_decode(L, slot_tab + (size_t)(blockIdx.x >> 1) * 4u, blockIdx.x & 1u, layouts, found_base, found_buf_stride);
+  const uint32_t n = L[0].total < max_n ? L[0].total : max_n;
   float2 *out = xy + (size_t)blockIdx.x * xy_side_stride;
-  const uint8_t *feats = feats_base + (size_t)s_buf * buf_stride;
-  for (uint32_t row = tid; row < n; row += 256u)
+  const uint8_t *feats = feats_base + (size_t)L[0].buf * buf_stride;
+  for (uint32_t row = threadIdx.x; row < n; row += 256u)
   {
-    uint32_t base = 0, src_row = 0;
-#pragma unroll
-    for (uint32_t o = 0; o < 16u; o++)
-    {
-      const uint32_t c = s_cnt[o];
-      if (row >= base && row < base + c)
-        src_row = s_off[o] + (row - base);
-      base += c;
-    }
-    const float *f = (const float *)(feats + (size_t)src_row * 164u);
+    const float *f = (const float *)(feats + (size_t)section_row(L[0].cnt, L[0].off, row) * VKSIFT_RECORD_BYTES);
     out[row] = float2{f[0], f[1]};
   }
 }
 
 // ---- stage 2 ---------------------------------------------------------------------------------------------------------------------------
-// What the test needs of a feature of A alone / of B alone, four floats each.
-//   homography:   A {u, v, d, lim} with (u, v, d) = M (xa, ya, 1) and lim = (d d) t2 — replaced by -1 when d > 0 fails, so that
-//                 "d > 0 && e2 < lim" is the one comparison e2 < lim (e2 is a sum of squares or NaN) —, B {xb, yb}
-//   fundamental:  A {l0, l1, l2, l0 l0 + l1 l1} with l = M (xa, ya, 1), B {xb, yb, m0 m0 + m1 m1} with m = M^T (xb, yb, 1)
-// A NaN coordinate (rows a side does not hold) makes every value it enters NaN and the pair inadmissible.
-template <int MODEL> __device__ __forceinline__ float4 side_a(const float (&M)[9], float2 p, float t2)
-{
-  const float r0 = (M[0] * p.x + M[1] * p.y) + M[2];
-  const float r1 = (M[3] * p.x + M[4] * p.y) + M[5];
-  const float r2 = (M[6] * p.x + M[7] * p.y) + M[8];
-  if (MODEL == (int)VKSIFT_HIP_GUIDE_HOMOGRAPHY)
-  {
-    const float lim = (r2 * r2) * t2;
-    return float4{r0, r1, r2, r2 > 0.f ? lim : -1.f};
-  }
-  return float4{r0, r1, r2, r0 * r0 + r1 * r1};
-}
-
-template <int MODEL> __device__ __forceinline__ float4 side_b(const float (&M)[9], float2 p)
-{
-  if (MODEL == (int)VKSIFT_HIP_GUIDE_HOMOGRAPHY)
-    return float4{p.x, p.y, 0.f, 0.f};
-  const float m0 = (M[0] * p.x + M[3] * p.y) + M[6];
-  const float m1 = (M[1] * p.x + M[4] * p.y) + M[7];
-  return float4{p.x, p.y, m0 * m0 + m1 * m1, 0.f};
-}
-
-template <int MODEL> __device__ __forceinline__ bool admissible(float4 qa, float4 qb, float t2)
-{
-  if (MODEL == (int)VKSIFT_HIP_GUIDE_HOMOGRAPHY)
-  {
-    const float ru = qa.x - qb.x * qa.z, rv = qa.y - qb.y * qa.z;
-    const float e2 = ru * ru + rv * rv;
-    return e2 < qa.w;
-  }
-  const float r = (qb.x * qa.x + qb.y * qa.y) + qa.z;
-  const float g = qa.w + qb.z;
-  return r * r < t2 * g;
-}
-
 // lanes of one wave exchange data through LDS without a workgroup barrier: the wave's LDS operations complete in program order, the
 // fence keeps the compiler from moving them
 __device__ __forceinline__ void wave_sync()
@@ -266,9 +185,8 @@ __global__ void __launch_bounds__(256)
 // ---- stage 3 ---------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float key_dist(unsigned long long k) { return k == kNoKey ? __uint_as_float(0x7f800000u) : sqrtf((float)(uint32_t)(k >> 32)); }
 
-// One 1024-thread workgroup per slot, as k_filter_matches (records.hip): the match (a, idx(k1(a))) is kept iff dist1 <= max_distance,
-// dist1 / dist2 < ratio (true without a second candidate, false for 0 / 0) and, with cross_check, idx(k1_rev(b)) == a and the reverse
-// record passes its own ratio test. 16-byte records {idx_a, idx_b, dist1, dist2} in increasing idx_a, their number in out_n[slot].
+// One 1024-thread workgroup per slot: the match (a, idx(k1(a))) is kept iff dist1 <= max_distance, dist1 / dist2 < ratio (true without a
+// second candidate, false for 0 / 0) and, with cross_check, idx(k1_rev(b)) == a and the reverse record passes its own ratio test. 16-byte records {idx_a, idx_b, dist1, dist2} in increasing idx_a, their number in out_n[slot].
 __global__ void __launch_bounds__(1024)
     k_guided_keep(const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ n_dev, uint32_t n_stride, uint32_t max_n,
                   const uint32_t *__restrict__ valid, uint32_t valid_stride, float ratio, float max_distance, uint32_t cross_check, uint32_t *__restrict__ out,
@@ -283,7 +201,6 @@ __global__ void __launch_bounds__(1024)
   na = na < max_n ? na : max_n, nb = nb < max_n ? nb : max_n;
   if (valid[(size_t)slot * valid_stride] == 0u)
     na = 0u;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0)
     carry_s = 0;
   __syncthreads();
@@ -312,28 +229,9 @@ __global__ void __launch_bounds__(1024)
         }
       }
     }
-    const unsigned long long bal = __ballot(keep);
-    const uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0)
-      wave_tot[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t wave_base = 0, total = 0;
-    for (int wv = 0; wv < 16; wv++)
-    {
-      if (wv < wave)
-        wave_base += wave_tot[wv];
-      total += wave_tot[wv];
-    }
-    const uint32_t carry = carry_s;
+    uint32_t *o = out + (size_t)ordered_keep(keep, wave_tot, carry_s) * 4u;
     if (keep)
-    {
-      uint32_t *o = out + (size_t)(carry + wave_base + rank) * 4u;
       o[0] = i, o[1] = j, o[2] = __float_as_uint(d1), o[3] = __float_as_uint(d2);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-      carry_s = carry + total;
-    __syncthreads();
   }
   if (threadIdx.x == 0)
     out_n[slot] = carry_s;

@@ -2,12 +2,14 @@
 // sift_memory.c:957-1047: the gather pass that serves uploaded buffers and every buffer an instance matches before its cache exists; freshly
 // detected buffers get their rows from the descriptor launch, features.hip), sections -> dense 164-byte records for the batched
 // download, and the GPU-side cross-check + ratio filter over 2-NN records (src/examples/test_sift_match.cpp:90-107). Split off match.hip
-// in round 6: none of this is matcher arithmetic.
+// in round 6: none of this is matcher arithmetic. The steps these kernels share with each other and with verify.hip / guided.hip — the
+// section walk, the ordered append, the record constants — are defined once, in records.h.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <stdint.h>
 
 #include "vksift_hip.h"
+#include "hip/records.h"
 
 namespace
 {
@@ -18,7 +20,7 @@ __global__ void __launch_bounds__(256) k_gather_desc(const uint8_t *__restrict__
   if (i >= n * 32u)
     return;
   uint32_t row = i >> 5, j = i & 31u;
-  desc[i] = *(const uint32_t *)(feats + (size_t)row * 164 + 36 + 4 * j);
+  desc[i] = *(const uint32_t *)(feats + (size_t)row * VKSIFT_RECORD_BYTES + VKSIFT_RECORD_DESC_AT + 4 * j);
 }
 
 // Gather the descriptors of a (sectioned or packed) SIFT buffer into dense rows in download order AND compute
@@ -27,9 +29,9 @@ __global__ void __launch_bounds__(256) k_gather_desc(const uint8_t *__restrict__
 struct SectionTable
 {
   uint32_t nsec;
-  uint32_t off[16];   // first feature of each section inside the buffer
-  uint32_t cap[16];   // capacity (stored = min(found, cap))
-  uint32_t fixed[16]; // used instead of found[] when found == nullptr (uploaded / packed buffers)
+  uint32_t off[VKSIFT_MAX_SECTIONS];   // first feature of each section inside the buffer
+  uint32_t cap[VKSIFT_MAX_SECTIONS];   // capacity (stored = min(found, cap))
+  uint32_t fixed[VKSIFT_MAX_SECTIONS]; // used instead of found[] when found == nullptr (uploaded / packed buffers)
 };
 
 struct SlotMap
@@ -60,20 +62,8 @@ __global__ void __launch_bounds__(256) k_gather_sections(const uint8_t *__restri
 
   const uint32_t j = threadIdx.x & 7u; // 16 bytes of a row per lane: a wave moves 8 rows at a time, a workgroup 32
   // stored count of every section (uniform), then a grid-stride walk over the rows that exist
-  uint32_t cnt[16];
-  uint32_t total = 0;
-#pragma unroll
-  for (uint32_t o = 0; o < 16; o++)
-  {
-    uint32_t n = 0;
-    if (o < tab.nsec)
-    {
-      n = found ? found[o] : tab.fixed[o];
-      n = n < tab.cap[o] ? n : tab.cap[o];
-    }
-    cnt[o] = n;
-    total += n;
-  }
+  uint32_t cnt[VKSIFT_MAX_SECTIONS];
+  const uint32_t total = section_counts(tab.nsec, [&](uint32_t o) { return found ? found[o] : tab.fixed[o]; }, tab.cap, cnt);
   if (blockIdx.x == 0 && threadIdx.x == 0)
     *n_out = total;
   const uint32_t nrows = total > pad_rows_to ? total : pad_rows_to;
@@ -82,16 +72,8 @@ __global__ void __launch_bounds__(256) k_gather_sections(const uint8_t *__restri
     uint4 v = uint4{0u, 0u, 0u, 0u}; // rows in [total, pad_rows_to): quirk Q6 padding, all-zero descriptors
     if (row < total)
     {
-      uint32_t base = 0, src_row = 0;
-#pragma unroll
-      for (uint32_t o = 0; o < 16; o++)
-      {
-        if (row >= base && row < base + cnt[o])
-          src_row = tab.off[o] + (row - base);
-        base += cnt[o];
-      }
       // (records are 164 bytes, the descriptor starts at byte 36: dword-aligned 16-byte loads)
-      const uint32_t *p = (const uint32_t *)(feats + (size_t)src_row * 164 + 36 + 16 * j);
+      const uint32_t *p = (const uint32_t *)(feats + (size_t)section_row(cnt, tab.off, row) * VKSIFT_RECORD_BYTES + VKSIFT_RECORD_DESC_AT + 16 * j);
       v = uint4{p[0], p[1], p[2], p[3]};
     }
     *(uint4 *)(desc + (size_t)row * 32 + 4 * j) = v;
@@ -128,41 +110,21 @@ __global__ void __launch_bounds__(256) k_pack_features(const uint8_t *__restrict
   // feature posting: the buffer's counters go to the host mirror with the records (same layout as found_base, mapped pinned memory)
   if (found_post && blockIdx.x == 0 && threadIdx.x < found_buf_stride)
     found_post[(size_t)bufi * found_buf_stride + threadIdx.x] = found[threadIdx.x];
-  uint32_t cnt[16];
-  uint32_t total = 0;
-#pragma unroll
-  for (uint32_t o = 0; o < 16; o++)
-  {
-    uint32_t n = 0;
-    if (o < tab.nsec)
-    {
-      n = found[o];
-      n = n < tab.cap[o] ? n : tab.cap[o];
-    }
-    cnt[o] = n;
-    total += n;
-  }
-  uint32_t *dst = out + (size_t)offs.row[slot] * 41u;
-  const uint32_t ndw = total * 41u; // 164-byte records = 41 dwords
+  uint32_t cnt[VKSIFT_MAX_SECTIONS];
+  const uint32_t total = section_counts(tab.nsec, [&](uint32_t o) { return found[o]; }, tab.cap, cnt);
+  uint32_t *dst = out + (size_t)offs.row[slot] * VKSIFT_RECORD_WORDS;
+  const uint32_t ndw = total * VKSIFT_RECORD_WORDS;
   for (uint32_t d = blockIdx.x * 256u + threadIdx.x; d < ndw; d += gridDim.x * 256u)
   {
-    const uint32_t row = d / 41u, w = d - row * 41u;
-    uint32_t base = 0, src_row = 0;
-#pragma unroll
-    for (uint32_t o = 0; o < 16; o++)
-    {
-      if (row >= base && row < base + cnt[o])
-        src_row = tab.off[o] + (row - base);
-      base += cnt[o];
-    }
-    dst[d] = feats[(size_t)src_row * 41u + w];
+    const uint32_t row = d / VKSIFT_RECORD_WORDS, w = d - row * VKSIFT_RECORD_WORDS;
+    dst[d] = feats[(size_t)section_row(cnt, tab.off, row) * VKSIFT_RECORD_WORDS + w];
   }
 }
 
 // Cross-check + Lowe-ratio filter over the 2-NN records of a forward (A -> B) and, optionally, a reverse (B -> A)
 // matching — what every caller of the reference runs on the CPU after vksift_downloadMatches
 // (src/examples/test_sift_match.cpp:90-107, src/perf/perf_common.cpp:123-169). One 1024-thread workgroup per pair keeps
-// the survivors in increasing idx_a order (ballot + scan compaction, no atomics), 16 B per survivor.
+// the survivors in increasing idx_a order (ordered_keep: ballot + scan compaction, no atomics), 16 B per survivor.
 __global__ void __launch_bounds__(1024) k_filter_matches(const uint32_t *__restrict__ fwd, uint64_t fwd_slot_stride, const uint32_t *__restrict__ rev,
                                                          uint64_t rev_slot_stride, const uint32_t *__restrict__ n_fwd, uint32_t n_stride, float ratio,
                                                          uint32_t *__restrict__ out, uint64_t out_slot_stride, uint32_t *__restrict__ out_n)
@@ -175,7 +137,6 @@ __global__ void __launch_bounds__(1024) k_filter_matches(const uint32_t *__restr
     rev += (size_t)slot * rev_slot_stride;
   out += (size_t)slot * out_slot_stride;
   const uint32_t na = n_fwd[(size_t)slot * n_stride], nb = n_fwd[(size_t)slot * n_stride + 1];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0)
     carry_s = 0;
   __syncthreads();
@@ -199,28 +160,9 @@ __global__ void __launch_bounds__(1024) k_filter_matches(const uint32_t *__restr
         }
       }
     }
-    const unsigned long long bal = __ballot(keep);
-    const uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0)
-      wave_tot[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t wave_base = 0, total = 0;
-    for (int wv = 0; wv < 16; wv++)
-    {
-      if (wv < wave)
-        wave_base += wave_tot[wv];
-      total += wave_tot[wv];
-    }
-    const uint32_t carry = carry_s;
+    uint32_t *o = out + (size_t)ordered_keep(keep, wave_tot, carry_s) * 4;
     if (keep)
-    {
-      uint32_t *o = out + (size_t)(carry + wave_base + rank) * 4;
       o[0] = fwd[(size_t)i * 5], o[1] = j, o[2] = d1, o[3] = d2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-      carry_s = carry + total;
-    __syncthreads();
   }
   if (threadIdx.x == 0)
     out_n[slot] = carry_s;
@@ -290,7 +232,7 @@ extern "C"
     PackOffsets po;
     for (uint32_t i = 0; i < 64; i++)
       m.buf[i] = i < nslots ? buf_ids[i] : 0u, po.row[i] = i < nslots ? out_rows[i] : 0u;
-    uint32_t blocks = (uint32_t)(((uint64_t)max_rows * 41u + 1023u) / 1024u); /* four dwords per thread */
+    uint32_t blocks = (uint32_t)(((uint64_t)max_rows * VKSIFT_RECORD_WORDS + 1023u) / 1024u); /* four dwords per thread */
     blocks = blocks < 1u ? 1u : (blocks > 128u ? 128u : blocks);
     hipLaunchKernelGGL(k_pack_features, dim3(blocks, nslots), dim3(256), 0, (hipStream_t)s, feats_base, buf_stride, m, t, found_base, found_buf_stride,
                        (uint32_t *)out, po, found_post);

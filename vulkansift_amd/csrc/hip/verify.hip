@@ -2,18 +2,22 @@
 // matrix (no counterpart in the reference, whose callers run a CPU RANSAC after downloading matches and features; the reference's own
 // evaluation judges matches by a homography, src/perf/perf_matching.cpp:30-79). Three launches serve every pair (slot) of a call:
 //   k_gather_corr      filtered matches {idx_a, idx_b} (download-order rows) -> {xa, ya, xb, yb} read from the SIFT buffers' sections
-//   k_ransac_score_h   one lane per hypothesis: counter-based sample, closed-form four-point homography, inlier count over the slot's
-//                      correspondences staged through LDS (broadcast 16-byte reads), best (count, lowest index) per workgroup
-//   k_ransac_final_h   best hypothesis per slot, its model in pixel coordinates, the inlier mask (same test: popcount == count)
-//   k_ransac_score_f / k_ransac_final_f   the same pair for the fundamental matrix: seven-point samples, up to three models per lane
+//                      (layout decode and walk: records.h)
+//   k_ransac_score_*   one lane per hypothesis: counter-based sample, closed-form models, inlier counts over the slot's correspondences
+//                      staged through LDS (broadcast 16-byte reads), best (count, lowest model id) per workgroup
+//   k_ransac_final_*   best model per slot, recomputed and brought to pixel coordinates, the inlier mask (same test: popcount == count)
+// _h is the homography (four-point samples, one model per lane), _f the fundamental matrix (seven-point samples, up to three). Both are one
+// body, ransac_score<Model> / ransac_final<Model>: a model (ModelH, ModelF) is its sizes, its solver and how its winner is published; the
+// inlier test is two_view.h's, the gather, the sampler, the key reduction and the launch wrapper are model-free.
 // Everything is integer arithmetic or correctly rounded fp32 add / sub / mul / div / sqrt in a fixed order (the tree is built with
-// -ffp-contract=off and no fmaf is used here), so tests/np_verify.py and tests/np_verify_f.py restate it bit for bit. The gather, the
-// sampler, the key reduction and the launch wrapper are model-free.
+// -ffp-contract=off and no fmaf is used here), so tests/np_verify.py and tests/np_verify_f.py restate it bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "vksift_hip.h"
+#include "hip/records.h"
+#include "hip/two_view.h"
 
 namespace
 {
@@ -24,10 +28,21 @@ constexpr uint32_t kHypPerBlock = 256u; // lanes (= hypotheses) per workgroup of
 constexpr float kCoordScale = 1.0f / 8192.0f;
 constexpr float kCoordUnscale = 8192.0f;
 
-struct Hom
+// a model of either kind, row-major (wrapped in a struct: as a bare float[9] it costs k_ransac_final_h 12 VGPRs, NOTEBOOK.md section 15)
+struct Mat9
 {
-  float h0, h1, h2, h3, h4, h5, h6, h7, h8;
+  float f[9];
 };
+
+__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+
+// 2^(127 - e) for the exponent e of the largest magnitude `mbits`; ok: that magnitude is normal and below 2^127
+__device__ __forceinline__ float unit_scale(uint32_t mbits, bool &ok)
+{
+  const uint32_t e = mbits >> 23;
+  ok = e >= 1u && e <= 253u;
+  return __uint_as_float((254u - (ok ? e : 127u)) << 23);
+}
 
 __device__ __forceinline__ uint64_t splitmix64_next(uint64_t &state)
 {
@@ -71,7 +86,7 @@ __device__ __forceinline__ float4 scaled(float4 c) { return float4{c.x * kCoordS
 // adj(A) are lambda_j lambda_k (p_j x p_k), so the cross products are formed once. The result is scaled by the power of two that
 // brings its largest entry into [1, 2) (exact), negated if it maps the first sample point behind the plane; a sample whose largest entry is zero, subnormal, at or above 2^127, infinite or NaN
 // is degenerate and becomes all-NaN (no correspondence is an inlier of it).
-__device__ __forceinline__ Hom solve_h4(float4 c0, float4 c1, float4 c2, float4 c3)
+__device__ __forceinline__ void solve_h4(float4 c0, float4 c1, float4 c2, float4 c3, float (&H)[9])
 {
   // source side: rows of adj([p0 p1 p2]) and lambda
   const float ax = c1.y - c2.y, ay = c2.x - c1.x, az = c1.x * c2.y - c2.x * c1.y; // p1 x p2
@@ -87,53 +102,67 @@ __device__ __forceinline__ Hom solve_h4(float4 c0, float4 c1, float4 c2, float4 
   const float w0 = m0 * (l1 * l2), w1 = m1 * (l2 * l0), w2 = m2 * (l0 * l1);
   const float u0 = w0 * c0.z, u1 = w1 * c1.z, u2 = w2 * c2.z; // row 0 of B, times the weights of adj(A)'s rows
   const float v0 = w0 * c0.w, v1 = w1 * c1.w, v2 = w2 * c2.w; // row 1
-  Hom H;
-  H.h0 = (u0 * ax + u1 * bx) + u2 * gx;
-  H.h1 = (u0 * ay + u1 * by) + u2 * gy;
-  H.h2 = (u0 * az + u1 * bz) + u2 * gz;
-  H.h3 = (v0 * ax + v1 * bx) + v2 * gx;
-  H.h4 = (v0 * ay + v1 * by) + v2 * gy;
-  H.h5 = (v0 * az + v1 * bz) + v2 * gz;
-  H.h6 = (w0 * ax + w1 * bx) + w2 * gx;
-  H.h7 = (w0 * ay + w1 * by) + w2 * gy;
-  H.h8 = (w0 * az + w1 * bz) + w2 * gz;
-  // largest magnitude by its bit pattern (NaN and infinity sort above every finite value)
-  uint32_t m = __float_as_uint(H.h0) & 0x7fffffffu;
-  m = max(m, __float_as_uint(H.h1) & 0x7fffffffu);
-  m = max(m, __float_as_uint(H.h2) & 0x7fffffffu);
-  m = max(m, __float_as_uint(H.h3) & 0x7fffffffu);
-  m = max(m, __float_as_uint(H.h4) & 0x7fffffffu);
-  m = max(m, __float_as_uint(H.h5) & 0x7fffffffu);
-  m = max(m, __float_as_uint(H.h6) & 0x7fffffffu);
-  m = max(m, __float_as_uint(H.h7) & 0x7fffffffu);
-  m = max(m, __float_as_uint(H.h8) & 0x7fffffffu);
-  const uint32_t e = m >> 23;
-  const bool ok = e >= 1u && e <= 253u;
+  H[0] = (u0 * ax + u1 * bx) + u2 * gx;
+  H[1] = (u0 * ay + u1 * by) + u2 * gy;
+  H[2] = (u0 * az + u1 * bz) + u2 * gz;
+  H[3] = (v0 * ax + v1 * bx) + v2 * gx;
+  H[4] = (v0 * ay + v1 * by) + v2 * gy;
+  H[5] = (v0 * az + v1 * bz) + v2 * gz;
+  H[6] = (w0 * ax + w1 * bx) + w2 * gx;
+  H[7] = (w0 * ay + w1 * by) + w2 * gy;
+  H[8] = (w0 * az + w1 * bz) + w2 * gz;
+  uint32_t m = 0u; // largest magnitude by its bit pattern (NaN and infinity sort above every finite value)
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+    m = max(m, abs_bits(H[i]));
+  bool ok;
+  const float fa = unit_scale(m, ok);
   // the sign of B adj(A) follows the orientation of the sample: chosen so that the first sample point lies in front of the plane (d > 0)
-  const float d0 = (H.h6 * c0.x + H.h7 * c0.y) + H.h8;
-  const float fa = __uint_as_float((254u - (ok ? e : 127u)) << 23); // 2^(127 - e)
+  const float d0 = (H[6] * c0.x + H[7] * c0.y) + H[8];
   const float f = d0 < 0.f ? -fa : fa;
-  const float bad = __uint_as_float(0x7fc00000u);
-  H.h0 = ok ? H.h0 * f : bad, H.h1 = ok ? H.h1 * f : bad, H.h2 = ok ? H.h2 * f : bad;
-  H.h3 = ok ? H.h3 * f : bad, H.h4 = ok ? H.h4 * f : bad, H.h5 = ok ? H.h5 * f : bad;
-  H.h6 = ok ? H.h6 * f : bad, H.h7 = ok ? H.h7 * f : bad, H.h8 = ok ? H.h8 * f : bad;
-  return H;
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+    H[i] = ok ? H[i] * f : __uint_as_float(0x7fc00000u);
 }
 
-// Forward transfer error below the threshold, without a division: with (u, v, d) = H (xa, ya, 1), the correspondence is an inlier iff
-// d > 0 and (u - xb d)^2 + (v - yb d)^2 < t^2 d^2. A NaN anywhere fails both comparisons.
-__device__ __forceinline__ bool is_inlier(const Hom &H, float4 c, float t2)
+// What ransac_score / ransac_final need of a model: sample size, models per lane (a model's id is hypothesis << kRootBits | root; ids order
+// the ties), fewest inliers of a valid result, words of the result record ({M[9], nb_matches, nb_inliers, best_hypothesis, [best_root,]
+// valid}), the unroll factor of the scoring loop, solve (the models of hypothesis hyp's sample, absent ones all-NaN; returns how many
+// there are) and publish (the winner in pixel coordinates, and whether it can be given out).
+struct ModelH
 {
-  const float u = (H.h0 * c.x + H.h1 * c.y) + H.h2;
-  const float v = (H.h3 * c.x + H.h4 * c.y) + H.h5;
-  const float d = (H.h6 * c.x + H.h7 * c.y) + H.h8;
-  const float ru = u - c.z * d, rv = v - c.w * d;
-  const float e2 = ru * ru + rv * rv;
-  const float lim = (d * d) * t2;
-  return d > 0.f && e2 < lim;
+  static constexpr int kKind = (int)VKSIFT_HIP_GUIDE_HOMOGRAPHY;
+  static constexpr uint32_t kSample = 4u, kModels = 1u, kRootBits = 0u, kMinInliers = 4u, kResultWords = 13u, kUnroll = 4u;
+
+  static __device__ __forceinline__ uint32_t solve(const float4 *__restrict__ c, uint64_t seed_key, uint32_t slot, uint32_t hyp, uint32_t n, Mat9 (&M)[1])
+  {
+    uint32_t i4[4];
+    draw_sample<4>(seed_key, slot, hyp, n, i4);
+    solve_h4(scaled(c[i4[0]]), scaled(c[i4[1]]), scaled(c[i4[2]]), scaled(c[i4[3]]), M[0].f);
+    return 1u;
+  }
+
+  // back to pixel coordinates (powers of two) and divided by h22
+  static __device__ __forceinline__ void publish(const float (&H)[9], float (&o)[9], bool &valid)
+  {
+    const float p2 = H[2] * kCoordUnscale, p5 = H[5] * kCoordUnscale, p6 = H[6] * kCoordScale, p7 = H[7] * kCoordScale;
+    o[0] = H[0] / H[8], o[1] = H[1] / H[8], o[2] = p2 / H[8];
+    o[3] = H[3] / H[8], o[4] = H[4] / H[8], o[5] = p5 / H[8];
+    o[6] = p6 / H[8], o[7] = p7 / H[8], o[8] = H[8] / H[8];
+    valid = H[8] != 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+      valid = valid && ((__float_as_uint(o[i]) & 0x7f800000u) != 0x7f800000u);
+  }
+};
+
+template <class Model> __device__ __forceinline__ bool is_inlier(const float (&M)[9], float4 c, float t2)
+{
+  return admissible<Model::kKind>(side_a<Model::kKind>(M, float2{c.x, c.y}, t2), side_b<Model::kKind>(M, float2{c.z, c.w}), t2);
 }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
+// the largest key of a 256-thread workgroup, in every thread
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long k, unsigned long long (&wave_best)[4])
 {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1)
@@ -141,77 +170,41 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
     const unsigned long long o = __shfl_xor(k, off, 64);
     k = o > k ? o : k;
   }
+  if ((threadIdx.x & 63u) == 0u)
+    wave_best[threadIdx.x >> 6] = k;
+  __syncthreads();
+  k = wave_best[0];
+  for (int w = 1; w < 4; w++)
+    k = wave_best[w] > k ? wave_best[w] : k;
   return k;
 }
 
 // ---- stage 1 ---------------------------------------------------------------------------------------------------------------------------
-// One workgroup per slot. slot_tab: {buffer A, buffer B, layout A, layout B} per slot; a layout word with bit 31 set names a buffer
-// of that many dense rows (uploaded features), any other value a section table in `layouts` ({nsec, off[16], cap[16]}: the walk of
-// k_gather_sections / k_pack_features, records.hip, with the stored counts min(found, cap) read on the device). A match that names a
-// row the buffer does not hold yields a NaN correspondence (never an inlier); nothing is read out of bounds.
+// One workgroup per slot. slot_tab: {buffer A, buffer B, layout A, layout B} per slot, layouts: the section tables (records.h). A match
+// that names a row the buffer does not hold yields a NaN correspondence (never an inlier); nothing is read out of bounds.
 __global__ void __launch_bounds__(256) k_gather_corr(const uint8_t *__restrict__ feats_base, uint64_t buf_stride, const uint32_t *__restrict__ found_base,
                                                      uint32_t found_buf_stride, const uint32_t *__restrict__ slot_tab, const uint32_t *__restrict__ layouts,
                                                      const uint32_t *__restrict__ filtered, uint64_t filtered_slot_stride, const uint32_t *__restrict__ filtered_n,
                                                      uint32_t max_n, float4 *__restrict__ corr, uint64_t corr_slot_stride)
 {
-  __shared__ uint32_t s_off[2][16], s_cnt[2][16], s_total[2], s_buf[2];
+  __shared__ SideLayout L[2];
   const uint32_t slot = blockIdx.x;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t *tab = slot_tab + (size_t)slot * 4u;
-  if (tid < 32u)
-  {
-    const uint32_t side = tid >> 4, o = tid & 15u;
-    const uint32_t bufi = tab[side], lay = tab[2u + side];
-    uint32_t off = 0, cnt = 0;
-    if (lay & 0x80000000u)
-      cnt = o == 0u ? (lay & 0x7fffffffu) : 0u;
-    else
-    {
-      const uint32_t *L = layouts + (size_t)lay * 33u;
-      if (o < L[0] && o < found_buf_stride)
-      {
-        const uint32_t f = found_base[(size_t)bufi * found_buf_stride + o], cap = L[17u + o];
-        off = L[1u + o];
-        cnt = f < cap ? f : cap;
-      }
-    }
-    s_off[side][o] = off, s_cnt[side][o] = cnt;
-    if (o == 0u)
-      s_buf[side] = bufi; // (the table may live in mapped host memory: read once)
-  }
-  __syncthreads();
-  if (tid < 2u)
-  {
-    uint32_t t = 0;
-    for (uint32_t o = 0; o < 16u; o++)
-      t += s_cnt[tid][o];
-    s_total[tid] = t;
-  }
-  __syncthreads();
+  layout_decode(L, slot_tab + (size_t)slot * 4u, 0u, layouts, found_base, found_buf_stride);
   uint32_t n = filtered_n[slot];
   n = n < max_n ? n : max_n;
   const uint32_t *fm = filtered + (size_t)slot * filtered_slot_stride;
   float4 *out = corr + (size_t)slot * corr_slot_stride;
   const float bad = __uint_as_float(0x7fc00000u);
-  for (uint32_t k = tid; k < n; k += 256u)
+  for (uint32_t k = threadIdx.x; k < n; k += 256u)
   {
     float xy[4] = {bad, bad, bad, bad};
 #pragma unroll
     for (uint32_t side = 0; side < 2u; side++)
     {
       const uint32_t row = fm[(size_t)k * 4u + side];
-      if (row < s_total[side])
+      if (row < L[side].total)
       {
-        uint32_t base = 0, src_row = 0;
-#pragma unroll
-        for (uint32_t o = 0; o < 16u; o++)
-        {
-          const uint32_t c = s_cnt[side][o];
-          if (row >= base && row < base + c)
-            src_row = s_off[side][o] + (row - base);
-          base += c;
-        }
-        const float *f = (const float *)(feats_base + (size_t)s_buf[side] * buf_stride + (size_t)src_row * 164u);
+        const float *f = (const float *)(feats_base + (size_t)L[side].buf * buf_stride + (size_t)section_row(L[side].cnt, L[side].off, row) * VKSIFT_RECORD_BYTES);
         xy[2u * side] = f[0], xy[2u * side + 1u] = f[1];
       }
     }
@@ -221,10 +214,12 @@ __global__ void __launch_bounds__(256) k_gather_corr(const uint8_t *__restrict__
 
 // ---- stage 2 ---------------------------------------------------------------------------------------------------------------------------
 // Workgroup (slot, blk) scores hypotheses blk*256 .. blk*256+255 of its slot against all n correspondences and stores the largest
-// key (count << 32 | ~hypothesis) — most inliers, ties to the lowest hypothesis — as two words at keys[2 * (slot * nblk + blk)].
-__global__ void __launch_bounds__(256) k_ransac_score_h(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
-                                                        uint32_t n_stride, uint32_t max_n, uint32_t nb_hyp, uint32_t nblk, float t2, uint64_t seed_key,
-                                                        uint32_t *__restrict__ keys)
+// key (count << 32 | ~model id) — most inliers, ties to the lowest id — as two words at keys[2 * (slot * nblk + blk)]. With several
+// models per lane, roots 1 and 2 are scored only when some lane of the wave has them (a wave-uniform branch; an absent root is all-NaN
+// and counts nothing).
+template <class Model>
+__device__ __forceinline__ void ransac_score(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev, uint32_t n_stride,
+                                             uint32_t max_n, uint32_t nb_hyp, uint32_t nblk, float t2, uint64_t seed_key, uint32_t *__restrict__ keys)
 {
   __shared__ float4 tile[kHypPerBlock];
   __shared__ unsigned long long wave_best[4];
@@ -233,7 +228,7 @@ __global__ void __launch_bounds__(256) k_ransac_score_h(const float4 *__restrict
   uint32_t n = n_dev[(size_t)slot * n_stride];
   n = n < max_n ? n : max_n;
   uint32_t *kout = keys + 2u * (size_t)blockIdx.x;
-  if (n < 4u)
+  if (n < Model::kSample)
   {
     if (tid == 0)
       kout[0] = 0u, kout[1] = 0u;
@@ -242,10 +237,13 @@ __global__ void __launch_bounds__(256) k_ransac_score_h(const float4 *__restrict
   const float4 *c = corr + (size_t)slot * corr_slot_stride;
   const uint32_t hyp = blk * kHypPerBlock + tid;
   const bool active = hyp < nb_hyp;
-  uint32_t i4[4];
-  draw_sample<4>(seed_key, slot, active ? hyp : 0u, n, i4);
-  const Hom H = solve_h4(scaled(c[i4[0]]), scaled(c[i4[1]]), scaled(c[i4[2]]), scaled(c[i4[3]]));
-  uint32_t cnt = 0;
+  Mat9 M[Model::kModels];
+  const uint32_t nroots = Model::solve(c, seed_key, slot, active ? hyp : 0u, n, M);
+  bool any[Model::kModels];
+  uint32_t cnt[Model::kModels];
+#pragma unroll
+  for (uint32_t r = 0; r < Model::kModels; r++)
+    any[r] = r == 0u || __ballot(nroots > r) != 0ull, cnt[r] = 0u;
   for (uint32_t base = 0; base < n; base += kHypPerBlock)
   {
     __syncthreads();
@@ -253,31 +251,35 @@ __global__ void __launch_bounds__(256) k_ransac_score_h(const float4 *__restrict
       tile[tid] = scaled(c[base + tid]);
     __syncthreads();
     const uint32_t m = n - base < kHypPerBlock ? n - base : kHypPerBlock;
-#pragma unroll 4
+#pragma unroll Model::kUnroll
     for (uint32_t j = 0; j < m; j++)
-      cnt += is_inlier(H, tile[j], t2) ? 1u : 0u; // every lane reads the same 16 bytes: one broadcast LDS access
+    {
+      const float4 q = tile[j]; // every lane reads the same 16 bytes: one broadcast LDS access
+#pragma unroll
+      for (uint32_t r = 0; r < Model::kModels; r++)
+        if (any[r])
+          cnt[r] += is_inlier<Model>(M[r].f, q, t2) ? 1u : 0u;
+    }
   }
-  unsigned long long key = active ? (((unsigned long long)cnt << 32) | (unsigned long long)(~hyp)) : 0ull;
-  key = wave_max_u64(key);
-  if ((tid & 63u) == 0u)
-    wave_best[tid >> 6] = key;
-  __syncthreads();
-  if (tid == 0)
+  unsigned long long key = 0ull;
+#pragma unroll
+  for (uint32_t r = 0; r < Model::kModels; r++)
   {
-    for (int w = 1; w < 4; w++)
-      key = wave_best[w] > key ? wave_best[w] : key;
-    kout[0] = (uint32_t)key, kout[1] = (uint32_t)(key >> 32);
+    const unsigned long long k = ((unsigned long long)cnt[r] << 32) | (unsigned long long)(~((hyp << Model::kRootBits) + r));
+    key = k > key ? k : key;
   }
+  key = block_max_u64(active ? key : 0ull, wave_best);
+  if (tid == 0)
+    kout[0] = (uint32_t)key, kout[1] = (uint32_t)(key >> 32);
 }
 
 // ---- stage 3 ---------------------------------------------------------------------------------------------------------------------------
-// One workgroup per slot: the best key over the slot's nblk workgroups, the winner's model recomputed from its sample, brought back to
-// pixel coordinates (powers of two) and divided by h22; result record (13 words: H[9], nb_matches, nb_inliers, best_hypothesis, valid)
-// and one mask byte per correspondence.
-__global__ void __launch_bounds__(256) k_ransac_final_h(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
-                                                        uint32_t n_stride, uint32_t max_n, uint32_t nblk, float t2, uint64_t seed_key,
-                                                        const uint32_t *__restrict__ keys, uint32_t *__restrict__ results, uint8_t *__restrict__ masks,
-                                                        uint64_t mask_slot_stride)
+// One workgroup per slot: the best key over the slot's nblk workgroups, the winner's model recomputed from its sample and root and
+// published; the result record and one mask byte per correspondence.
+template <class Model>
+__device__ __forceinline__ void ransac_final(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev, uint32_t n_stride,
+                                             uint32_t max_n, uint32_t nblk, float t2, uint64_t seed_key, const uint32_t *__restrict__ keys,
+                                             uint32_t *__restrict__ results, uint8_t *__restrict__ masks, uint64_t mask_slot_stride)
 {
   __shared__ unsigned long long wave_best[4];
   const uint32_t slot = blockIdx.x, tid = threadIdx.x;
@@ -290,36 +292,27 @@ __global__ void __launch_bounds__(256) k_ransac_final_h(const float4 *__restrict
     const unsigned long long v = ((unsigned long long)k[1] << 32) | (unsigned long long)k[0];
     key = v > key ? v : key;
   }
-  key = wave_max_u64(key);
-  if ((tid & 63u) == 0u)
-    wave_best[tid >> 6] = key;
-  __syncthreads();
-  key = wave_best[0];
-  for (int w = 1; w < 4; w++)
-    key = wave_best[w] > key ? wave_best[w] : key;
-  const uint32_t cnt = (uint32_t)(key >> 32), hyp = ~(uint32_t)key;
+  key = block_max_u64(key, wave_best);
+  const uint32_t cnt = (uint32_t)(key >> 32), id = ~(uint32_t)key, hyp = id >> Model::kRootBits, rt = id & ((1u << Model::kRootBits) - 1u);
   const float4 *c = corr + (size_t)slot * corr_slot_stride;
   uint8_t *mask = masks + (size_t)slot * mask_slot_stride;
-  uint32_t *res = results + (size_t)slot * 13u;
-  bool valid = n >= 4u && cnt >= 4u;
-  Hom H = {};
+  uint32_t *res = results + (size_t)slot * Model::kResultWords;
+  bool valid = n >= Model::kSample && cnt >= Model::kMinInliers;
+  Mat9 W = {};
   float o[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (valid) // uniform over the workgroup
   {
-    uint32_t i4[4];
-    draw_sample<4>(seed_key, slot, hyp, n, i4);
-    H = solve_h4(scaled(c[i4[0]]), scaled(c[i4[1]]), scaled(c[i4[2]]), scaled(c[i4[3]]));
-    const float p2 = H.h2 * kCoordUnscale, p5 = H.h5 * kCoordUnscale, p6 = H.h6 * kCoordScale, p7 = H.h7 * kCoordScale;
-    o[0] = H.h0 / H.h8, o[1] = H.h1 / H.h8, o[2] = p2 / H.h8;
-    o[3] = H.h3 / H.h8, o[4] = H.h4 / H.h8, o[5] = p5 / H.h8;
-    o[6] = p6 / H.h8, o[7] = p7 / H.h8, o[8] = H.h8 / H.h8;
-    valid = H.h8 != 0.f;
+    Mat9 M[Model::kModels];
+    Model::solve(c, seed_key, slot, hyp, n, M);
 #pragma unroll
-    for (int i = 0; i < 9; i++)
-      valid = valid && ((__float_as_uint(o[i]) & 0x7f800000u) != 0x7f800000u);
+    for (uint32_t r = 0; r < Model::kModels; r++)
+#pragma unroll
+      for (int i = 0; i < 9; i++)
+        W.f[i] = (r == 0u || rt == r) ? M[r].f[i] : W.f[i];
+    Model::publish(W.f, o, valid);
   }
   for (uint32_t k = tid; k < n; k += 256u)
-    mask[k] = (valid && is_inlier(H, scaled(c[k]), t2)) ? 1u : 0u;
+    mask[k] = (valid && is_inlier<Model>(W.f, scaled(c[k]), t2)) ? 1u : 0u;
   if (tid == 0)
   {
 #pragma unroll
@@ -328,8 +321,25 @@ __global__ void __launch_bounds__(256) k_ransac_final_h(const float4 *__restrict
     res[9] = n;
     res[10] = valid ? cnt : 0u;
     res[11] = valid ? hyp : 0u;
-    res[12] = valid ? 1u : 0u;
+    if (Model::kRootBits)
+      res[12] = valid ? rt : 0u;
+    res[Model::kResultWords - 1u] = valid ? 1u : 0u;
   }
+}
+
+__global__ void __launch_bounds__(256) k_ransac_score_h(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
+                                                        uint32_t n_stride, uint32_t max_n, uint32_t nb_hyp, uint32_t nblk, float t2, uint64_t seed_key,
+                                                        uint32_t *__restrict__ keys)
+{
+  ransac_score<ModelH>(corr, corr_slot_stride, n_dev, n_stride, max_n, nb_hyp, nblk, t2, seed_key, keys);
+}
+
+__global__ void __launch_bounds__(256) k_ransac_final_h(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
+                                                        uint32_t n_stride, uint32_t max_n, uint32_t nblk, float t2, uint64_t seed_key,
+                                                        const uint32_t *__restrict__ keys, uint32_t *__restrict__ results, uint8_t *__restrict__ masks,
+                                                        uint64_t mask_slot_stride)
+{
+  ransac_final<ModelH>(corr, corr_slot_stride, n_dev, n_stride, max_n, nblk, t2, seed_key, keys, results, masks, mask_slot_stride);
 }
 
 // ---- the second model: fundamental matrix ----------------------------------------------------------------------------------------------
@@ -338,21 +348,6 @@ __global__ void __launch_bounds__(256) k_ransac_final_h(const float4 *__restrict
 // seven-point construction gives; no handling of the planar degeneracy (a caller runs both models on the same filtered matching and
 // compares the counts); no refit on the inliers.
 constexpr int kBisectSteps = 48; // halvings of a bracket no wider than 2 R: to the last bit of a root down to 2^-24 R
-
-struct Fund
-{
-  float f[9];
-};
-
-__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
-
-// 2^(127 - e) for the exponent e of the largest magnitude `mbits`; ok: that magnitude is normal and below 2^127
-__device__ __forceinline__ float unit_scale(uint32_t mbits, bool &ok)
-{
-  const uint32_t e = mbits >> 23;
-  ok = e >= 1u && e <= 253u;
-  return __uint_as_float((254u - (ok ? e : 127u)) << 23);
-}
 
 // One side of the sample: x, y become s (x - cx), s (y - cy) with the centroid (cx, cy) (fixed-order sum times 1.0f / 7.0f) and the power
 // of two s that brings the largest |deviation| into [1, 2); u = s cx, v = s cy. s is NaN (and with it the whole solve) when there is no such power.
@@ -431,7 +426,7 @@ __device__ __forceinline__ uint32_t cubic_roots(float c0, float c1, float c2, fl
 // registers. The free columns give F1 = (-a[.][7], 1, 0) and F2 = (-a[.][8], 0, 1); det(F1 + a F2) is expanded along the last row;
 // each real root gives F^ = F1 + a F2, taken back as T_b^T F^ T_a and scaled by the power of two that brings its largest entry into
 // [1, 2). A model that is absent or not finite is all-NaN (no correspondence is an inlier of it). Returns the number of roots.
-__device__ __forceinline__ uint32_t solve_f7(const float4 (&c)[7], Fund (&M)[3])
+__device__ __forceinline__ uint32_t solve_f7(const float4 (&c)[7], Mat9 (&M)[3])
 {
   float xa[7], ya[7], xb[7], yb[7];
 #pragma unroll
@@ -524,139 +519,30 @@ __device__ __forceinline__ uint32_t solve_f7(const float4 (&c)[7], Fund (&M)[3])
   return cnt;
 }
 
-// Sampson distance below the threshold, without a division: with l = F (xa, ya, 1), m = F^T (xb, yb, 1) and r = (xb, yb, 1) l, the
-// correspondence is an inlier iff r^2 < t^2 ((l0^2 + l1^2) + (m0^2 + m1^2)). A NaN anywhere fails the comparison.
-__device__ __forceinline__ bool is_inlier_f(const Fund &F, float4 c, float t2)
+struct ModelF
 {
-  const float l0 = (F.f[0] * c.x + F.f[1] * c.y) + F.f[2];
-  const float l1 = (F.f[3] * c.x + F.f[4] * c.y) + F.f[5];
-  const float l2 = (F.f[6] * c.x + F.f[7] * c.y) + F.f[8];
-  const float r = (c.z * l0 + c.w * l1) + l2;
-  const float m0 = (F.f[0] * c.z + F.f[3] * c.w) + F.f[6];
-  const float m1 = (F.f[1] * c.z + F.f[4] * c.w) + F.f[7];
-  const float g = (l0 * l0 + l1 * l1) + (m0 * m0 + m1 * m1);
-  return r * r < t2 * g;
-}
+  static constexpr int kKind = (int)VKSIFT_HIP_GUIDE_FUNDAMENTAL;
+  static constexpr uint32_t kSample = 7u, kModels = 3u, kRootBits = 2u, kMinInliers = 8u, kResultWords = 14u, kUnroll = 1u;
 
-__device__ __forceinline__ uint32_t solve_sample_f(const float4 *__restrict__ c, uint64_t seed_key, uint32_t slot, uint32_t hyp, uint32_t n, Fund (&M)[3])
-{
-  uint32_t idx[7];
-  draw_sample<7>(seed_key, slot, hyp, n, idx);
-  float4 sc[7];
+  static __device__ __forceinline__ uint32_t solve(const float4 *__restrict__ c, uint64_t seed_key, uint32_t slot, uint32_t hyp, uint32_t n, Mat9 (&M)[3])
+  {
+    uint32_t idx[7];
+    draw_sample<7>(seed_key, slot, hyp, n, idx);
+    float4 sc[7];
 #pragma unroll
-  for (int i = 0; i < 7; i++)
-    sc[i] = scaled(c[idx[i]]);
-  return solve_f7(sc, M);
-}
+    for (int i = 0; i < 7; i++)
+      sc[i] = scaled(c[idx[i]]);
+    return solve_f7(sc, M);
+  }
 
-// Stage 2 for the fundamental matrix: as k_ransac_score_h, three models per lane; key = count << 32 | ~(4 * hypothesis + root). Roots 1
-// and 2 are scored only when some lane of the wave has them (a wave-uniform branch; an absent root is all-NaN and counts nothing).
-__global__ void __launch_bounds__(256) k_ransac_score_f(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
-                                                        uint32_t n_stride, uint32_t max_n, uint32_t nb_hyp, uint32_t nblk, float t2, uint64_t seed_key,
-                                                        uint32_t *__restrict__ keys)
-{
-  __shared__ float4 tile[kHypPerBlock];
-  __shared__ unsigned long long wave_best[4];
-  const uint32_t slot = blockIdx.x / nblk, blk = blockIdx.x - slot * nblk;
-  const uint32_t tid = threadIdx.x;
-  uint32_t n = n_dev[(size_t)slot * n_stride];
-  n = n < max_n ? n : max_n;
-  uint32_t *kout = keys + 2u * (size_t)blockIdx.x;
-  if (n < 7u)
+  // pixel coordinates by powers of two (F_px = K F K with K = diag(2^-13, 2^-13, 1), times 2^26), scaled again so that the largest entry
+  // lies in [1, 2)
+  static __device__ __forceinline__ void publish(const float (&F)[9], float (&o)[9], bool &valid)
   {
-    if (tid == 0)
-      kout[0] = 0u, kout[1] = 0u;
-    return;
-  }
-  const float4 *c = corr + (size_t)slot * corr_slot_stride;
-  const uint32_t hyp = blk * kHypPerBlock + tid;
-  const bool active = hyp < nb_hyp;
-  Fund M[3];
-  const uint32_t nroots = solve_sample_f(c, seed_key, slot, active ? hyp : 0u, n, M);
-  const bool any1 = __ballot(nroots > 1u) != 0ull, any2 = __ballot(nroots > 2u) != 0ull;
-  uint32_t cnt0 = 0, cnt1 = 0, cnt2 = 0;
-  for (uint32_t base = 0; base < n; base += kHypPerBlock)
-  {
-    __syncthreads();
-    if (base + tid < n)
-      tile[tid] = scaled(c[base + tid]);
-    __syncthreads();
-    const uint32_t m = n - base < kHypPerBlock ? n - base : kHypPerBlock;
-    for (uint32_t j = 0; j < m; j++)
-    {
-      const float4 q = tile[j]; // every lane reads the same 16 bytes: one broadcast LDS access
-      cnt0 += is_inlier_f(M[0], q, t2) ? 1u : 0u;
-      if (any1)
-        cnt1 += is_inlier_f(M[1], q, t2) ? 1u : 0u;
-      if (any2)
-        cnt2 += is_inlier_f(M[2], q, t2) ? 1u : 0u;
-    }
-  }
-  const uint32_t id = hyp * 4u;
-  unsigned long long key = ((unsigned long long)cnt0 << 32) | (unsigned long long)(~id);
-  const unsigned long long k1 = ((unsigned long long)cnt1 << 32) | (unsigned long long)(~(id + 1u));
-  const unsigned long long k2 = ((unsigned long long)cnt2 << 32) | (unsigned long long)(~(id + 2u));
-  key = k1 > key ? k1 : key;
-  key = k2 > key ? k2 : key;
-  key = wave_max_u64(active ? key : 0ull);
-  if ((tid & 63u) == 0u)
-    wave_best[tid >> 6] = key;
-  __syncthreads();
-  if (tid == 0)
-  {
-    for (int w = 1; w < 4; w++)
-      key = wave_best[w] > key ? wave_best[w] : key;
-    kout[0] = (uint32_t)key, kout[1] = (uint32_t)(key >> 32);
-  }
-}
-
-// Stage 3 for the fundamental matrix: the best key of the slot, the winner's model recomputed from its sample and root, brought to pixel
-// coordinates (powers of two: F_px = K F K with K = diag(2^-13, 2^-13, 1), times 2^26) and scaled again so that its largest entry lies in
-// [1, 2); result record (14 words: F[9], nb_matches, nb_inliers, best_hypothesis, best_root, valid) and one mask byte per correspondence.
-__global__ void __launch_bounds__(256) k_ransac_final_f(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
-                                                        uint32_t n_stride, uint32_t max_n, uint32_t nblk, float t2, uint64_t seed_key,
-                                                        const uint32_t *__restrict__ keys, uint32_t *__restrict__ results, uint8_t *__restrict__ masks,
-                                                        uint64_t mask_slot_stride)
-{
-  __shared__ unsigned long long wave_best[4];
-  const uint32_t slot = blockIdx.x, tid = threadIdx.x;
-  uint32_t n = n_dev[(size_t)slot * n_stride];
-  n = n < max_n ? n : max_n;
-  unsigned long long key = 0ull;
-  for (uint32_t b = tid; b < nblk; b += 256u)
-  {
-    const uint32_t *k = keys + 2u * ((size_t)slot * nblk + b);
-    const unsigned long long v = ((unsigned long long)k[1] << 32) | (unsigned long long)k[0];
-    key = v > key ? v : key;
-  }
-  key = wave_max_u64(key);
-  if ((tid & 63u) == 0u)
-    wave_best[tid >> 6] = key;
-  __syncthreads();
-  key = wave_best[0];
-  for (int w = 1; w < 4; w++)
-    key = wave_best[w] > key ? wave_best[w] : key;
-  const uint32_t cnt = (uint32_t)(key >> 32), id = ~(uint32_t)key, hyp = id >> 2, rt = id & 3u;
-  const float4 *c = corr + (size_t)slot * corr_slot_stride;
-  uint8_t *mask = masks + (size_t)slot * mask_slot_stride;
-  uint32_t *res = results + (size_t)slot * 14u;
-  bool valid = n >= 7u && cnt >= 8u;
-  Fund F = {};
-  float o[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (valid) // uniform over the workgroup
-  {
-    Fund M[3];
-    solve_sample_f(c, seed_key, slot, hyp, n, M);
-    F = M[0];
-#pragma unroll
-    for (int k = 1; k < 3; k++)
-#pragma unroll
-      for (int i = 0; i < 9; i++)
-        F.f[i] = rt == (uint32_t)k ? M[k].f[i] : F.f[i];
     const float k1 = kCoordUnscale, k2 = kCoordUnscale * kCoordUnscale;
-    o[0] = F.f[0], o[1] = F.f[1], o[2] = F.f[2] * k1;
-    o[3] = F.f[3], o[4] = F.f[4], o[5] = F.f[5] * k1;
-    o[6] = F.f[6] * k1, o[7] = F.f[7] * k1, o[8] = F.f[8] * k2;
+    o[0] = F[0], o[1] = F[1], o[2] = F[2] * k1;
+    o[3] = F[3], o[4] = F[4], o[5] = F[5] * k1;
+    o[6] = F[6] * k1, o[7] = F[7] * k1, o[8] = F[8] * k2;
     uint32_t m = 0u;
 #pragma unroll
     for (int i = 0; i < 9; i++)
@@ -666,19 +552,21 @@ __global__ void __launch_bounds__(256) k_ransac_final_f(const float4 *__restrict
     for (int i = 0; i < 9; i++)
       o[i] = o[i] * f;
   }
-  for (uint32_t k = tid; k < n; k += 256u)
-    mask[k] = (valid && is_inlier_f(F, scaled(c[k]), t2)) ? 1u : 0u;
-  if (tid == 0)
-  {
-#pragma unroll
-    for (int i = 0; i < 9; i++)
-      res[i] = valid ? __float_as_uint(o[i]) : 0u;
-    res[9] = n;
-    res[10] = valid ? cnt : 0u;
-    res[11] = valid ? hyp : 0u;
-    res[12] = valid ? rt : 0u;
-    res[13] = valid ? 1u : 0u;
-  }
+};
+
+__global__ void __launch_bounds__(256) k_ransac_score_f(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
+                                                        uint32_t n_stride, uint32_t max_n, uint32_t nb_hyp, uint32_t nblk, float t2, uint64_t seed_key,
+                                                        uint32_t *__restrict__ keys)
+{
+  ransac_score<ModelF>(corr, corr_slot_stride, n_dev, n_stride, max_n, nb_hyp, nblk, t2, seed_key, keys);
+}
+
+__global__ void __launch_bounds__(256) k_ransac_final_f(const float4 *__restrict__ corr, uint64_t corr_slot_stride, const uint32_t *__restrict__ n_dev,
+                                                        uint32_t n_stride, uint32_t max_n, uint32_t nblk, float t2, uint64_t seed_key,
+                                                        const uint32_t *__restrict__ keys, uint32_t *__restrict__ results, uint8_t *__restrict__ masks,
+                                                        uint64_t mask_slot_stride)
+{
+  ransac_final<ModelF>(corr, corr_slot_stride, n_dev, n_stride, max_n, nblk, t2, seed_key, keys, results, masks, mask_slot_stride);
 }
 
 uint64_t seed_key_of(uint64_t seed)

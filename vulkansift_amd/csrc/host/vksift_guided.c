@@ -8,9 +8,6 @@
 
 #define GUIDED_FN "vksift_ext_matchFeaturesGuided()"
 
-/* words of h_gtab in front of the supplied models: the slot table and the section tables */
-static size_t gtab_models_at(const struct vksift_Instance_T *inst) { return (size_t)4u * inst->batch_cap + (size_t)VERIFY_LAYOUT_WORDS * 2u * inst->batch_cap; }
-
 /* coordinates, keys, records and counts of batch_cap pairs, allocated by the first guided matching */
 static bool ensure_guided_scratch(vksift_Instance inst)
 {
@@ -21,7 +18,7 @@ static bool ensure_guided_scratch(vksift_Instance inst)
   const bool ok = mem_ensure(&inst->d_gxy, sizeof(float) * 2u * 2u * inst->gxy_side_stride * bc + 8u, MEM_DEVICE) &&
                   mem_ensure(&inst->d_gkeys, sizeof(uint32_t) * inst->gkeys_u32 + 8u, MEM_DEVICE) && mem_ensure(&inst->d_guided, inst->guided_slot_stride * bc, MEM_DEVICE) &&
                   mem_ensure(&inst->d_guided_n, sizeof(uint32_t) * bc, MEM_DEVICE) && mem_ensure(&inst->h_guided_n, sizeof(uint32_t) * bc, MEM_PINNED) &&
-                  mem_ensure(&inst->h_gtab, sizeof(uint32_t) * (gtab_models_at(inst) + (size_t)10u * bc), MEM_PINNED);
+                  mem_ensure(&inst->h_gtab, sizeof(uint32_t) * (pair_table_words(inst) + (size_t)10u * bc), MEM_PINNED);
   if (!inst->ev_gtab)
     inst->ev_gtab = vksift_hip_event_create();
   for (int i = 0; i < 2; i++)
@@ -63,25 +60,9 @@ void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, co
     HIP_CHECK(vksift_hip_event_sync(inst->ev_gtab), "event synchronisation");
     inst->gtab_pending = false;
   }
-  uint32_t max_rows = 0;
-  {
-    uint32_t *layouts = inst->h_gtab + (size_t)4u * inst->batch_cap, nlay = 0;
-    (void)detect_running(inst); /* polls the detections in flight: rows_bound() uses the counts that have arrived */
-    for (uint32_t i = 0; i < count; i++)
-    {
-      const uint32_t a = inst->filt_ids[i], b = inst->filt_ids[inst->batch_cap + i];
-      uint32_t *t = inst->h_gtab + (size_t)4u * i;
-      t[0] = a, t[1] = b;
-      t[2] = layout_word(&inst->bufs[a], layouts, &nlay);
-      t[3] = layout_word(&inst->bufs[b], layouts, &nlay);
-      const uint32_t ra = rows_bound(inst, a), rb = rows_bound(inst, b);
-      max_rows = ra > max_rows ? ra : max_rows;
-      max_rows = rb > max_rows ? rb : max_rows;
-    }
-    if (max_rows > inst->cfg.max_nb_sift_per_buffer)
-      max_rows = inst->cfg.max_nb_sift_per_buffer;
-  }
-  uint32_t *h_models = inst->h_gtab + gtab_models_at(inst), *h_ones = h_models + (size_t)9u * inst->batch_cap;
+  uint32_t max_rows;
+  pair_tables(inst, inst->h_gtab, count, &max_rows);
+  uint32_t *h_models = inst->h_gtab + pair_table_words(inst), *h_ones = h_models + (size_t)9u * inst->batch_cap;
   const float *d_models;
   const uint32_t *d_valid;
   uint32_t model_stride, valid_stride;
@@ -103,7 +84,7 @@ void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, co
   /* the dense rows and norms: the matcher's cache, refreshed the way the matcher does it (a no-op while the buffers are unchanged) */
   HIP_CHECK(refresh_match_cache(inst, inst->filt_ids, count), "descriptor gather");
   HIP_CHECK(refresh_match_cache(inst, inst->filt_ids + inst->batch_cap, count), "descriptor gather");
-  HIP_CHECK(vksift_hip_gather_xy(inst->d_feats, inst->buf_stride, inst->d_found, VKSIFT_MAX_OCTAVES, inst->h_gtab, inst->h_gtab + (size_t)4u * inst->batch_cap, max_rows,
+  HIP_CHECK(vksift_hip_gather_xy(inst->d_feats, inst->buf_stride, inst->d_found, VKSIFT_MAX_OCTAVES, inst->h_gtab, pair_layouts(inst, inst->h_gtab), max_rows,
                                  count, inst->d_gxy, inst->gxy_side_stride, inst->stream),
             "coordinate gather");
   /* {N_A, N_B} are the words the matching left in d_match_n, rows and coordinates the buffers' present ones: the same while the buffers hold the
@@ -112,7 +93,7 @@ void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, co
   for (uint32_t r = 0; r < count; r += 65535u)
   {
     const uint32_t n = count - r < 65535u ? count - r : 65535u;
-    HIP_CHECK(vksift_hip_match_guided(inst->d_cache_desc, inst->desc_slot_stride, inst->d_cache_norm, inst->cache_norm_stride, inst->h_gtab + (size_t)4u * r, 4u,
+    HIP_CHECK(vksift_hip_match_guided(inst->d_cache_desc, inst->desc_slot_stride, inst->d_cache_norm, inst->cache_norm_stride, inst->h_gtab + (size_t)PAIR_SLOT_WORDS * r, PAIR_SLOT_WORDS,
                                       inst->d_gxy + (size_t)4u * inst->gxy_side_stride * r, inst->gxy_side_stride, inst->d_match_n + (size_t)4u * r, 4u, max_rows,
                                       d_models + (size_t)model_stride * r, model_stride, d_valid + (size_t)valid_stride * r, valid_stride, model, t2, ratio, max_distance,
                                       cross_check ? 1u : 0u, n, inst->d_guided + inst->guided_slot_stride * r, inst->guided_slot_stride, inst->d_guided_n + r,
@@ -129,12 +110,7 @@ void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, co
     vksift_hip_event_record(inst->ev_g[1], inst->stream);
     inst->guided_timing_valid = true;
   }
-  /* same contract as the matching it follows: the accessors wait for ev_match, the pairs' buffers stay busy until it has passed */
-  (void)match_running(inst);
-  HIP_CHECK(vksift_hip_event_record(inst->ev_match, inst->stream), "event record");
-  inst->match_pending = true;
-  for (uint32_t i = 0; i < count; i++)
-    inst->match_busy[inst->filt_ids[i]] = inst->match_busy[inst->filt_ids[inst->batch_cap + i]] = true;
+  HIP_CHECK(match_follow(inst, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
   inst->guided_slots_used = count;
   return;
 gpu_error:

@@ -8,6 +8,7 @@
 
 #include "vksift_ext.h"
 #include "vksift_hip.h"
+#include "hip/records.h" /* the record and section-table constants */
 #include "vksift_hostmath.h"
 #include "vksift_log.h"
 #include "vulkansift/vulkansift.h"
@@ -221,7 +222,7 @@ struct vksift_Instance_T
   uint32_t *d_vres, *h_vres; /* 13 words (vksift_ext_Homography) per slot; the host copy is posted like h_filtered_n */
   uint32_t *d_vscratch;
   size_t vscratch_u32;
-  uint32_t *h_vtab;         /* mapped pinned memory read by the gather launch: 4 words per slot, then the section tables (33 words each) */
+  uint32_t *h_vtab;         /* mapped pinned memory read by the gather launch: a pair table (pair_tables) */
   bool vtab_pending;
   uint32_t verify_slots_used;
   /* the second model (vksift_ext_verifyFundamental) keeps results and masks of its own, so that both can be read after one matching */
@@ -237,8 +238,8 @@ struct vksift_Instance_T
   uint8_t *d_guided;        /* per slot: guided_slot_stride bytes of vksift_ext_FilteredMatch */
   uint64_t guided_slot_stride;
   uint32_t *d_guided_n, *h_guided_n;
-  uint32_t *h_gtab;         /* mapped pinned memory read by the launches: per slot {buffer A, buffer B, layout A, layout B}, the section tables (33 words each),
-                             * then 9 floats per slot of supplied models and a word 1 per slot */
+  uint32_t *h_gtab;         /* mapped pinned memory read by the launches: a pair table (pair_tables), then 9 floats per slot of supplied models and
+                             * a word 1 per slot */
   bool gtab_pending;
   uint32_t guided_slots_used;
   bool guided_timing_valid;
@@ -391,10 +392,17 @@ VKSIFT_INTERNAL MatchScratch fwd_scratch(vksift_Instance inst);
 VKSIFT_INTERNAL int refresh_match_cache(vksift_Instance inst, const uint32_t *ids, uint32_t count);
 VKSIFT_INTERNAL uint32_t rows_bound(vksift_Instance inst, uint32_t id);
 VKSIFT_INTERNAL void wait_match(vksift_Instance inst);
+/* What every launch sequence queued on the matching's contract ends with (the matching itself, the verification, the guided matching): the
+ * accessors wait for ev_match, both buffers of every pair stay busy until it has passed. Returns the event record's error code. */
+VKSIFT_INTERNAL int match_follow(vksift_Instance inst, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count);
 
-/* vksift_verify.c: layout word of a buffer for the launches that resolve download-order rows on the device (vksift_hip_gather_correspondences,
- * vksift_hip_gather_xy); its section table ({nsec, off[16], cap[16]}) is appended to `layouts` unless an equal one is there */
-#define VERIFY_LAYOUT_WORDS 33u
-VKSIFT_INTERNAL uint32_t layout_word(const BufferInfo *b, uint32_t *layouts, uint32_t *nlay);
+/* The pair table of the launches that resolve download-order rows on the device (vksift_hip_gather_correspondences, vksift_hip_gather_xy;
+ * h_vtab, h_gtab): {buffer A, buffer B, layout A, layout B} per slot of batch_cap, then the section tables the layout words name (hip/records.h;
+ * at most one per buffer). pair_tables fills it for the `count` pairs of the last filtered matching; max_rows, unless NULL, receives the
+ * largest rows_bound() of their buffers, at most max_nb_sift_per_buffer. */
+#define PAIR_SLOT_WORDS 4u
+static inline uint32_t *pair_layouts(const struct vksift_Instance_T *inst, uint32_t *tab) { return tab + (size_t)PAIR_SLOT_WORDS * inst->batch_cap; }
+static inline size_t pair_table_words(const struct vksift_Instance_T *inst) { return ((size_t)PAIR_SLOT_WORDS + (size_t)VKSIFT_LAYOUT_WORDS * 2u) * inst->batch_cap; }
+VKSIFT_INTERNAL void pair_tables(vksift_Instance inst, uint32_t *tab, uint32_t count, uint32_t *max_rows);
 
 #endif

@@ -36,6 +36,40 @@ uint32_t rows_bound(vksift_Instance inst, uint32_t id)
   return counts_valid(inst, id) ? known : cap_sum;
 }
 
+/* layout word of a buffer in a pair table: its section table is appended to `layouts` unless an equal one is there */
+static uint32_t layout_word(const BufferInfo *b, uint32_t *layouts, uint32_t *nlay)
+{
+  if (b->nb_sections == 0)
+    return VKSIFT_LAYOUT_DENSE | b->nb_stored; /* uploaded: one dense run of records */
+  uint32_t t[VKSIFT_LAYOUT_WORDS] = {0};
+  t[0] = b->nb_sections;
+  for (uint32_t o = 0; o < b->nb_sections; o++)
+    t[VKSIFT_LAYOUT_OFF_AT + o] = b->sec_off[o], t[VKSIFT_LAYOUT_CAP_AT + o] = b->sec_cap[o];
+  for (uint32_t k = *nlay; k-- > 0;) /* the last one first: the buffers of a batched detection all share one */
+    if (memcmp(layouts + (size_t)k * VKSIFT_LAYOUT_WORDS, t, sizeof(t)) == 0)
+      return k;
+  memcpy(layouts + (size_t)*nlay * VKSIFT_LAYOUT_WORDS, t, sizeof(t));
+  return (*nlay)++;
+}
+
+void pair_tables(vksift_Instance inst, uint32_t *tab, uint32_t count, uint32_t *max_rows)
+{
+  uint32_t *layouts = pair_layouts(inst, tab), nlay = 0, rows = 0;
+  if (max_rows)
+    (void)detect_running(inst); /* polls the detections in flight: rows_bound() uses the counts that have arrived */
+  for (uint32_t i = 0; i < count; i++)
+    for (uint32_t side = 0; side < 2u; side++)
+    {
+      const uint32_t id = inst->filt_ids[side * inst->batch_cap + i];
+      tab[PAIR_SLOT_WORDS * i + side] = id;
+      tab[PAIR_SLOT_WORDS * i + 2u + side] = layout_word(&inst->bufs[id], layouts, &nlay);
+      if (max_rows && rows_bound(inst, id) > rows)
+        rows = rows_bound(inst, id);
+    }
+  if (max_rows)
+    *max_rows = rows < inst->cfg.max_nb_sift_per_buffer ? rows : inst->cfg.max_nb_sift_per_buffer;
+}
+
 /* The matcher's input of a SIFT buffer — dense 128-byte descriptor rows in download order, their shifted norms and the row
  * count — lives in a per-buffer cache entry, filled by ONE device-side gather the first time the buffer is matched after it
  * changed (detection, upload) and reused by every later matching: a self-match gathers once instead of twice, the two
@@ -222,12 +256,8 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
     vksift_hip_event_record(inst->ev_m[1], inst->stream);
     inst->match_timing_valid = true;
   }
-  (void)match_running(inst); /* an earlier matching that has completed releases its buffers; one still in flight keeps them */
-  HIP_CHECK(vksift_hip_event_record(inst->ev_match, inst->stream), "event record");
-  inst->match_pending = true;
+  HIP_CHECK(match_follow(inst, ids_a, ids_b, count), "event record");
   inst->match_slots_used = count;
-  for (uint32_t i = 0; i < count; i++)
-    inst->match_busy[ids_a[i]] = inst->match_busy[ids_b[i]] = true; /* every pair of a batched call (vksift_isBufferAvailable) */
   return;
 gpu_error:
   if (range_open)
@@ -256,6 +286,18 @@ void vksift_ext_matchFeaturesFiltered(vksift_Instance instance, uint32_t count, 
     return;
   }
   match_impl(instance, gpu_buffer_ids_A, gpu_buffer_ids_B, count, "vksift_ext_matchFeaturesFiltered()", true, ratio, cross_check);
+}
+
+int match_follow(vksift_Instance inst, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count)
+{
+  (void)match_running(inst); /* an earlier matching that has completed releases its buffers; one still in flight keeps them */
+  const int e = vksift_hip_event_record(inst->ev_match, inst->stream);
+  if (e)
+    return e;
+  inst->match_pending = true;
+  for (uint32_t i = 0; i < count; i++)
+    inst->match_busy[ids_a[i]] = inst->match_busy[ids_b[i]] = true; /* every pair of a batched call (vksift_isBufferAvailable) */
+  return 0;
 }
 
 void wait_match(vksift_Instance inst)

@@ -50,29 +50,13 @@ static bool ensure_verify_scratch(vksift_Instance inst, const VerifyModel *m)
                   mem_ensure(m->d_res, sizeof(uint32_t) * m->res_words * bc, MEM_DEVICE) &&
                   mem_ensure(&inst->d_vscratch, sizeof(uint32_t) * inst->vscratch_u32, MEM_DEVICE) &&
                   mem_ensure(m->h_res, sizeof(uint32_t) * m->res_words * bc, MEM_PINNED) &&
-                  mem_ensure(&inst->h_vtab, sizeof(uint32_t) * ((size_t)4u * bc + (size_t)VERIFY_LAYOUT_WORDS * 2u * bc), MEM_PINNED);
+                  mem_ensure(&inst->h_vtab, sizeof(uint32_t) * pair_table_words(inst), MEM_PINNED);
   if (!inst->ev_vtab)
     inst->ev_vtab = vksift_hip_event_create();
   for (int i = 0; i < 2; i++)
     if (!inst->ev_v[i])
       inst->ev_v[i] = vksift_hip_event_create();
   return ok && inst->ev_vtab && inst->ev_v[0] && inst->ev_v[1];
-}
-
-/* layout word of a buffer for vksift_hip_gather_correspondences: its section table is appended to `layouts` unless an equal one is there */
-uint32_t layout_word(const BufferInfo *b, uint32_t *layouts, uint32_t *nlay)
-{
-  if (b->nb_sections == 0)
-    return 0x80000000u | b->nb_stored; /* uploaded: one dense run of records */
-  uint32_t t[VERIFY_LAYOUT_WORDS] = {0};
-  t[0] = b->nb_sections;
-  for (uint32_t o = 0; o < b->nb_sections; o++)
-    t[1u + o] = b->sec_off[o], t[17u + o] = b->sec_cap[o];
-  for (uint32_t k = *nlay; k-- > 0;) /* the last one first: the buffers of a batched detection all share one */
-    if (memcmp(layouts + (size_t)k * VERIFY_LAYOUT_WORDS, t, sizeof(t)) == 0)
-      return k;
-  memcpy(layouts + (size_t)*nlay * VERIFY_LAYOUT_WORDS, t, sizeof(t));
-  return (*nlay)++;
 }
 
 static void verify(vksift_Instance inst, const VerifyModel *m, uint32_t nb_hypotheses, float threshold_px, uint64_t seed)
@@ -98,23 +82,13 @@ static void verify(vksift_Instance inst, const VerifyModel *m, uint32_t nb_hypot
     HIP_CHECK(vksift_hip_event_sync(inst->ev_vtab), "event synchronisation");
     inst->vtab_pending = false;
   }
-  {
-    uint32_t *layouts = inst->h_vtab + (size_t)4u * inst->batch_cap, nlay = 0;
-    for (uint32_t i = 0; i < count; i++)
-    {
-      const uint32_t a = inst->filt_ids[i], b = inst->filt_ids[inst->batch_cap + i];
-      uint32_t *t = inst->h_vtab + (size_t)4u * i;
-      t[0] = a, t[1] = b;
-      t[2] = layout_word(&inst->bufs[a], layouts, &nlay);
-      t[3] = layout_word(&inst->bufs[b], layouts, &nlay);
-    }
-  }
+  pair_tables(inst, inst->h_vtab, count, NULL);
   if (inst->profiling)
     vksift_hip_event_record(inst->ev_v[0], inst->stream);
   vksift_hip_range_push("Verification");
   range_open = true;
   HIP_CHECK(vksift_hip_gather_correspondences(inst->d_feats, inst->buf_stride, inst->d_found, VKSIFT_MAX_OCTAVES, inst->h_vtab,
-                                              inst->h_vtab + (size_t)4u * inst->batch_cap, inst->d_filtered, inst->filtered_slot_stride, inst->d_filtered_n,
+                                              pair_layouts(inst, inst->h_vtab), inst->d_filtered, inst->filtered_slot_stride, inst->d_filtered_n,
                                               inst->cfg.max_nb_sift_per_buffer, count, inst->d_corr, inst->filtered_slot_stride, inst->stream),
             "correspondence gather");
   HIP_CHECK(vksift_hip_event_record(inst->ev_vtab, inst->stream), "event record");
@@ -130,12 +104,7 @@ static void verify(vksift_Instance inst, const VerifyModel *m, uint32_t nb_hypot
     vksift_hip_event_record(inst->ev_v[1], inst->stream);
     inst->verify_timing_valid = true;
   }
-  /* same contract as the matching it follows: the accessors wait for ev_match, the pairs' buffers stay busy until it has passed */
-  (void)match_running(inst);
-  HIP_CHECK(vksift_hip_event_record(inst->ev_match, inst->stream), "event record");
-  inst->match_pending = true;
-  for (uint32_t i = 0; i < count; i++)
-    inst->match_busy[inst->filt_ids[i]] = inst->match_busy[inst->filt_ids[inst->batch_cap + i]] = true;
+  HIP_CHECK(match_follow(inst, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
   *m->slots_used = count;
   return;
 gpu_error:
