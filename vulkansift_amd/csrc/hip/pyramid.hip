@@ -337,15 +337,254 @@ __device__ __forceinline__ void unit_of_bytes(unsigned d, float t[4])
   t[0] = unit_of_byte<0>(d), t[1] = unit_of_byte<1>(d), t[2] = unit_of_byte<2>(d), t[3] = unit_of_byte<3>(d);
 }
 
-// Byte offset of the fp32 float4 that holds the virtual columns gx4 .. gx4+3 of a row of width W (a multiple of 4); rv is set when they
-// are mirrored: the four virtual columns then map to m3+3, m3+2, m3+1, m3 of that float4.
-__device__ __forceinline__ unsigned mirrored_col_off(int gx4, int W, bool &rv)
+// ---------------------------------------------------------------------------------------------
+// The steps the strip marches share (k_blur_lean / k_blur_lean_multi, k_blur_wide, k_blur_pair, k_blur_pair_wide), one definition each.
+// A march is: map the workgroup to its strip and segment, lane constants, prefetch the first group, then per group of NR source rows
+// stage -> H pass -> V pass -> slide (described at k_blur_lean). The kernels below read as that march; what a texel goes through is here.
+// Everything is force-inlined and every window / tap index is a compile-time constant once the loops are unrolled.
+// ---------------------------------------------------------------------------------------------
+constexpr int NR = 8; // source rows per group
+
+// XCD-aware work mapping: workgroup b is observed to run on XCD b % 8 (each XCD has its own L2). Give every XCD a contiguous range of the
+// (image, segment, strip) space, strips fastest, so that the workgroups that share halo columns and warm-up rows run on the same XCD at
+// about the same time and find them in its L2. rev: walk the work space back to front. (bx, by, bz) of the (gx, gy, gz) grid -> the
+// workgroup's strip, row segment and image; ALWAYS: divide even where the result is the block index itself (the pair kernels' form).
+struct Origin
+{
+  uint32_t strip, seg, img;
+};
+template <bool ALWAYS>
+__device__ __forceinline__ Origin march_origin(uint32_t bx, uint32_t by, uint32_t bz, uint32_t gx, uint32_t gy, uint32_t gz, int rev)
+{
+  Origin o{bx, by, bz};
+  const uint32_t total = gx * gy * gz;
+  const uint32_t b = bx + gx * (by + gy * bz);
+  uint32_t wi = b;
+  if ((total & 7u) == 0)
+  {
+    const uint32_t per = total >> 3, k = b >> 3;
+    wi = (b & 7u) * per + (rev ? per - 1u - k : k);
+  }
+  else if (rev)
+    wi = total - 1u - b;
+  if (ALWAYS || (total & 7u) == 0 || rev)
+  {
+    o.strip = wi % gx;
+    const uint32_t r = wi / gx;
+    o.seg = r % gy;
+    o.img = r / gy;
+  }
+  return o;
+}
+
+// The filter, stated once: N independent accumulator chains of blur_plane's expression, acc = c * k0; acc = fmaf(t(+i) + t(-i), k[i], acc)
+// for i ascending, the chains advanced side by side (dependent add -> fma pairs of one chain then need no wait states). t(c, d) is the
+// texel at distance d from the centre of chain c: a float, or a v4f whose four components are four chains of their own.
+template <typename V, int N>
+struct Chains
+{
+  V v[N];
+};
+__device__ __forceinline__ float fma_tap(float s, float k, float acc) { return fmaf(s, k, acc); }
+__device__ __forceinline__ v4f fma_tap(v4f s, float k, v4f acc) { return v4f{fmaf(s.x, k, acc.x), fmaf(s.y, k, acc.y), fmaf(s.z, k, acc.z), fmaf(s.w, k, acc.w)}; }
+template <int NT, int N, typename T>
+__device__ __forceinline__ auto sym_taps(const float *k, T t)
+{
+  Chains<decltype(t(0, 0)), N> o;
+#pragma unroll
+  for (int c = 0; c < N; c++)
+    o.v[c] = t(c, 0) * k[0];
+#pragma unroll
+  for (int i = 1; i < NT; i++)
+#pragma unroll
+    for (int c = 0; c < N; c++)
+      o.v[c] = fma_tap(t(c, i) + t(c, -i), k[i], o.v[c]);
+  return o;
+}
+
+// Byte offset (eb bytes per texel) of the four texels that hold the virtual columns gx4 .. gx4+3 of a row of width W (a multiple of 4); rv
+// is set when they are mirrored: the four virtual columns then map to m3+3, m3+2, m3+1, m3 of that group.
+__device__ __forceinline__ unsigned mirrored_col_off(int gx4, int W, unsigned eb, bool &rv)
 {
   if (gx4 >= 0 && gx4 + 3 < W)
-    return (unsigned)gx4 * 4u;
+    return (unsigned)gx4 * eb;
   rv = true;
-  return (unsigned)mirror_idx(gx4 + 3, W) * 4u;
+  return (unsigned)mirror_idx(gx4 + 3, W) * eb;
 }
+
+// Four-texel forms: a staged row is 64 + NX float4 wide (NX = RA / 2). The NX columns beyond the 64 that the lanes stage themselves, of all
+// NR rows of a group, are ONE load + ONE LDS write of the first NX * NR lanes: lane e takes float4 column 64 + e % NX of row e / NX.
+struct ExtraCol
+{
+  bool on, rev;      // this lane takes part; its column is mirrored
+  int row;           // e / NX
+  unsigned col, off; // byte offset of the column inside a row; ... of row `row` of a group that starts at the plane's first row
+  float *lds;        // where it goes in the staging buffer
+};
+template <int NX, int SW>
+__device__ __forceinline__ ExtraCol extra_col(float *s_grp, int lane, int gx0, int W, int pitch_bytes)
+{
+  static_assert(NX * NR <= 64, "the extra float4 columns of a group are staged by one instruction");
+  ExtraCol x;
+  x.on = lane < NX * NR, x.rev = false;
+  x.row = lane / NX;
+  const int xq = 64 + lane % NX;
+  x.col = BUF_OOB;
+  if (x.on)
+    x.col = mirrored_col_off(gx0 + 4 * xq, W, 4u, x.rev);
+  x.off = x.on ? x.col + (unsigned)(x.row * pitch_bytes) : BUF_OOB;
+  x.lds = s_grp + x.row * SW + 4 * xq;
+  return x;
+}
+
+// four texels of a source row: one 16-byte load (fp32) or one 8-byte load (fp16: .x, .y carry the four halves)
+template <bool F16>
+__device__ __forceinline__ u32x4 load4(__amdgpu_buffer_rsrc_t rs, unsigned off, int so)
+{
+  if (F16)
+  {
+    const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(rs, off, so, 0);
+    return u32x4{t.x, t.y, 0u, 0u};
+  }
+  return __builtin_amdgcn_raw_buffer_load_b128(rs, off, so, 0);
+}
+
+// The lane's four texels of the virtual rows r0 .. r0 + NR - 1 of a plane (X: and its extra column): in flight while the group before is
+// worked on. A group inside the plane is one row offset counted up; one that crosses the top or bottom edge has every row mirrored on its
+// own (the extra column's row is a lane value).
+struct Rows
+{
+  u32x4 v[NR], x;
+};
+template <bool F16, bool X>
+__device__ __forceinline__ Rows prefetch_rows(__amdgpu_buffer_rsrc_t rs, unsigned ld_off, const ExtraCol &xc, int r0, int H, int pitch_bytes)
+{
+  Rows p;
+  if (r0 >= 0 && r0 + NR <= H)
+  {
+    int so = r0 * pitch_bytes;
+    if (X)
+      p.x = __builtin_amdgcn_raw_buffer_load_b128(rs, xc.off, so, 0);
+#pragma unroll
+    for (int j = 0; j < NR; j++, so += pitch_bytes)
+      p.v[j] = load4<F16>(rs, ld_off, so);
+  }
+  else
+  {
+    if (X)
+    {
+      const unsigned ox = xc.on ? xc.col + (unsigned)(mirror_idx(r0 + xc.row, H) * pitch_bytes) : BUF_OOB;
+      p.x = __builtin_amdgcn_raw_buffer_load_b128(rs, ox, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < NR; j++)
+      p.v[j] = load4<F16>(rs, ld_off, mirror_idx(r0 + j, H) * pitch_bytes);
+  }
+  return p;
+}
+
+// A group into the staging buffer (rows of SW floats): texels(j) are the lane's four fp32 texels of row j, reversed when its column is mirrored.
+__device__ __forceinline__ u32x4 reversed_if(bool rev, u32x4 v) { return rev ? u32x4{v.w, v.z, v.y, v.x} : v; }
+template <int SW, typename T>
+__device__ __forceinline__ void stage_rows(float *s_grp, int lane, bool rev, T texels)
+{
+#pragma unroll
+  for (int j = 0; j < NR; j++)
+    *(u32x4 *)(s_grp + j * SW + 4 * lane) = reversed_if(rev, texels(j));
+}
+__device__ __forceinline__ void stage_extra(const ExtraCol &xc, u32x4 v)
+{
+  if (xc.on)
+    *(u32x4 *)xc.lds = reversed_if(xc.rev, v);
+}
+
+// Horizontal pass, two texels per lane (2 lane, 2 lane + 1 of the strip), rows j and j + 1 of the group: their chains are independent, so
+// the scheduler can alternate them (one row alone leaves an s_nop after almost every instruction). Texel x of the strip sits at float
+// START + x of an LDS row of SW floats; the lane reads the NP float2 that cover its window (OFS: parity fix so that the window starts on
+// an even float). F16: the pass's output is an image of the pyramid format too (the reference's blur temporary).
+struct RowPair
+{
+  float2 a, b;
+};
+template <int NT, int SW, int START, bool F16 = false>
+__device__ __forceinline__ RowPair hpass2(const float *s, int lane, const float *k, int j)
+{
+  constexpr int R = NT - 1, OFS = (START - R) & 1, NP = R + 1 + OFS, C0 = R + OFS;
+  static_assert(START >= R + OFS, "the window starts inside the LDS row");
+  const float *hb = s + (START - R - OFS) + 2 * lane;
+  const v2f *pa = (const v2f *)(hb + j * SW);
+  const v2f *pb = (const v2f *)(hb + (j + 1) * SW);
+  float v[2][2 * NP];
+#pragma unroll
+  for (int q = 0; q < NP; q++)
+  {
+    v2f ta = pa[q], tb = pb[q];
+    v[0][2 * q] = ta.x, v[0][2 * q + 1] = ta.y;
+    v[1][2 * q] = tb.x, v[1][2 * q + 1] = tb.y;
+  }
+  auto o = sym_taps<NT, 4>(k, [&](int c, int d) { return v[c >> 1][C0 + (c & 1) + d]; });
+  if (F16)
+  {
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+      o.v[c] = (float)to_h(o.v[c]);
+  }
+  return RowPair{make_float2(o.v[0], o.v[1]), make_float2(o.v[2], o.v[3])};
+}
+
+// Horizontal pass, four texels per lane (4 lane .. 4 lane + 3), row j: the 16-byte-aligned window [4 lane, 4 lane + 2 START + 4) of the LDS
+// row is START / 2 + 1 ds_read_b128 (START = the radius rounded up to 4), four chains.
+template <int NT, int SW, int START>
+__device__ __forceinline__ v4f hpass4(const float *s, int lane, const float *k, int j)
+{
+  constexpr int NQ = START / 2 + 1;
+  const v4f *hb = (const v4f *)(s + 4 * lane);
+  float v[4 * NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; q++)
+  {
+    const v4f t = hb[j * (SW / 4) + q];
+    v[4 * q] = t.x, v[4 * q + 1] = t.y, v[4 * q + 2] = t.z, v[4 * q + 3] = t.w;
+  }
+  const auto o = sym_taps<NT, 4>(k, [&](int c, int d) { return v[START + c + d]; });
+  return v4f{o.v[0], o.v[1], o.v[2], o.v[3]};
+}
+
+// Vertical pass from the register window: win(i) is window row i (the H rows of the lane's own columns, oldest first), output row j of the
+// group has its centre in window row R + j. The caller stores what comes back.
+template <int NT, typename W>
+__device__ __forceinline__ float2 vrow2(const float *k, W win, int j)
+{
+  const auto o = sym_taps<NT, 2>(k, [&](int c, int d) {
+    const float2 t = win(NT - 1 + j + d);
+    return c ? t.y : t.x;
+  });
+  return make_float2(o.v[0], o.v[1]);
+}
+template <int NT, typename W>
+__device__ __forceinline__ RowPair vrow2_pair(const float *k, W win, int j) // rows j and j + 1, side by side as in hpass2
+{
+  const auto o = sym_taps<NT, 4>(k, [&](int c, int d) {
+    const float2 t = win(NT - 1 + j + (c >> 1) + d);
+    return (c & 1) ? t.y : t.x;
+  });
+  return RowPair{make_float2(o.v[0], o.v[1]), make_float2(o.v[2], o.v[3])};
+}
+template <int NT, typename W>
+__device__ __forceinline__ v4f vrow4(const float *k, W win, int j)
+{
+  return sym_taps<NT, 1>(k, [&](int, int d) { return win(NT - 1 + j + d); }).v[0];
+}
+
+// the window moves on by a group: the 2R rows that stay, by copy (k_blur_wide renames instead)
+template <typename V, int NWIN>
+__device__ __forceinline__ void slide(V (&wv)[NWIN])
+{
+#pragma unroll
+  for (int i = 0; i < NWIN - NR; i++)
+    wv[i] = wv[i + NR];
+}
+__device__ __forceinline__ u32x4 bits_of(v4f v) { return u32x4{__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)}; }
 
 // (the body is shared by k_blur_lean — one plane set per launch, the launch grid is the work grid — and k_blur_lean_multi — several
 // octaves' planes in one flat launch, csrc/hip/multi.h: gx/gy/gz and bx/by/bz are then the octave's virtual grid)
@@ -354,71 +593,34 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
                                                const uint32_t gy_, const uint32_t gz_)
 {
   constexpr bool UPS = SRC == 1, U8 = SRC == 2;
-  constexpr int NR = 8;
   constexpr unsigned EB = F16 ? 2u : 4u; // bytes per texel
   constexpr int R = NT - 1;
   constexpr int RA = (R + 3) & ~3;
   constexpr int TW = 128;
   constexpr int SW = TW + 2 * RA;
-  constexpr int NV4 = SW / 4;       // float4 per staged row (<= 42 lanes stage, one float4 per row each)
-  constexpr int OFS = (RA - R) & 1; // parity fix so that the H-pass window starts on an even float
-  constexpr int NP = R + 1 + OFS;   // float2 pairs read per row in the H pass
-  constexpr int C0 = R + OFS;       // index of pixel 0's centre inside the window
+  constexpr int NV4 = SW / 4; // float4 per staged row (<= 42 lanes stage, one float4 per row each)
   constexpr int NWIN = 2 * R + NR;
   __shared__ __attribute__((aligned(16))) float s_grp[NR * SW];
 
   const int lane = threadIdx.x;
   const int W = a.w, H = a.h;
-  // XCD-aware work mapping: workgroup b is observed to run on XCD b % 8 (each XCD has its own L2). Give every XCD a
-  // contiguous range of the (image, segment, strip) space, strips fastest, so that the workgroups that share halo
-  // columns and warm-up rows run on the same XCD at about the same time and find them in its L2.
-  // (Written out in each strip-march kernel: as a shared __device__ function, every form tried changed the gfx950 code of k_blur_lean_multi,
-  // k_blur_wide and the pair kernels.)
-  uint32_t bs = bx_, bseg = by_, bimg = bz_;
-  {
-    const uint32_t total = gx_ * gy_ * gz_;
-    const uint32_t b = bx_ + gx_ * (by_ + gy_ * bz_);
-    uint32_t wi = b;
-    if ((total & 7u) == 0)
-    {
-      const uint32_t per = total >> 3, k = b >> 3;
-      wi = (b & 7u) * per + (a.rev ? per - 1u - k : k);
-    }
-    else if (a.rev)
-      wi = total - 1u - b;
-    if ((total & 7u) == 0 || a.rev)
-    {
-      bs = wi % gx_;
-      const uint32_t r = wi / gx_;
-      bseg = r % gy_;
-      bimg = r / gy_;
-    }
-  }
-  const int x0 = bs * TW;
-  const int y0 = bseg * a.seg;
+  const Origin og = march_origin<false>(bx_, by_, bz_, gx_, gy_, gz_, a.rev);
+  const int x0 = og.strip * TW;
+  const int y0 = og.seg * a.seg;
   const int y1 = min(y0 + a.seg, H);
   const __amdgpu_buffer_rsrc_t rs =
-      (UPS || U8) ? __builtin_amdgcn_make_buffer_rsrc((void *)((const uint8_t *)a.src + (size_t)bimg * a.src_img_stride), 0, a.spitch * (UPS ? H / 2 : H), 0x00020000)
-                  : plane_rsrc<F16>(a.src, (size_t)bimg * a.src_img_stride, a.spitch, H);
-  const __amdgpu_buffer_rsrc_t rd = plane_rsrc<F16>(a.dst, (size_t)bimg * a.dst_img_stride, a.dpitch, H);
+      (UPS || U8) ? __builtin_amdgcn_make_buffer_rsrc((void *)((const uint8_t *)a.src + (size_t)og.img * a.src_img_stride), 0, a.spitch * (UPS ? H / 2 : H), 0x00020000)
+                  : plane_rsrc<F16>(a.src, (size_t)og.img * a.src_img_stride, a.spitch, H);
+  const __amdgpu_buffer_rsrc_t rd = plane_rsrc<F16>(a.dst, (size_t)og.img * a.dst_img_stride, a.dpitch, H);
   const bool has_ds = SRC == 0 && a.ds != nullptr;
   const __amdgpu_buffer_rsrc_t rds =
-      plane_rsrc<F16>(has_ds ? a.ds : a.dst, has_ds ? (size_t)bimg * a.ds_img_stride : 0, has_ds ? a.ds_pitch : a.dpitch, has_ds ? H / 2 : H);
+      plane_rsrc<F16>(has_ds ? a.ds : a.dst, has_ds ? (size_t)og.img * a.ds_img_stride : 0, has_ds ? a.ds_pitch : a.dpitch, has_ds ? H / 2 : H);
 
   // ---- lane constants
-  const int gx4 = x0 - RA + 4 * lane;
   unsigned ld_off = BUF_OOB;
   bool rev = false;
   if (lane < NV4)
-  {
-    if (gx4 >= 0 && gx4 + 3 < W)
-      ld_off = (unsigned)gx4 * EB;
-    else
-    {
-      ld_off = (unsigned)mirror_idx(gx4 + 3, W) * EB; // the four virtual columns map to m3+3, m3+2, m3+1, m3
-      rev = true;
-    }
-  }
+    ld_off = mirrored_col_off(x0 - RA + 4 * lane, W, EB, rev);
   // UPS: the 4 output columns X..X+3 (X = real column of the float4 after mirroring) come from the source bytes
   // X/2-1 .. X/2+2, clamped to the row: one (byte-aligned) dword load + a lane-constant byte permutation
   unsigned perm_sel = 0x03020100u;
@@ -443,9 +645,8 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
   const int spitch4 = a.spitch * (int)EB, dpitch4 = a.dpitch * (int)EB; // row pitches in bytes
   const unsigned st_off_ds = px + 1 < W ? (unsigned)(px >> 1) * EB : BUF_OOB; // column px+1 (odd) -> column px/2 of the half-size plane
   const int dspitch4 = a.ds_pitch * (int)EB;
-  const float k0 = a.taps.k[0];
 
-  u32x4 pf[NR];
+  Rows pf;
   float vb[NR]; // UPS: vertical weight of the lower source row (wave-uniform)
   // UPS, group away from the top and bottom edges: output rows 2m+1 and 2m+2 interpolate between the SAME two source rows
   // (m, m+1) with weights 0.25 / 0.75, so the 8 rows of a group need 5 or 6 distinct source rows, not 16: each is loaded,
@@ -453,22 +654,13 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
   // Groups start on rows of the parity of R (segments start on multiples of 8).
   constexpr int UPS_PAR = R & 1, UPS_NSRC = UPS_PAR ? 5 : 6;
   auto ups_shared = [&](int r0) { return r0 >= 2 && r0 + NR + 2 <= H; };
-  // four texels of a source row: one 16-byte load (fp32) or one 8-byte load (fp16: .x, .y carry the four halves)
-  auto load4 = [&](int so) -> u32x4 {
-    if (F16)
-    {
-      const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(rs, ld_off, so, 0);
-      return u32x4{t.x, t.y, 0u, 0u};
-    }
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, ld_off, so, 0);
-  };
   auto prefetch = [&](int r0) {
     if (UPS && ups_shared(r0))
     {
       const int so0 = (UPS_PAR ? (r0 - 1) / 2 : r0 / 2 - 1) * a.spitch;
 #pragma unroll
       for (int s = 0; s < UPS_NSRC; s++)
-        pf[s].x = __builtin_amdgcn_raw_buffer_load_b32(rs, ld_off, so0 + s * a.spitch, 0);
+        pf.v[s].x = __builtin_amdgcn_raw_buffer_load_b32(rs, ld_off, so0 + s * a.spitch, 0);
     }
     else if (UPS)
     {
@@ -480,29 +672,18 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
         const int m = (ru & 1) ? (ru - 1) / 2 : ru / 2 - 1;
         vb[j] = (ru & 1) ? 0.25f : 0.75f;
         const int ya = m < 0 ? 0 : m, yb_ = m + 1 > sh - 1 ? sh - 1 : m + 1;
-        pf[j].x = __builtin_amdgcn_raw_buffer_load_b32(rs, ld_off, ya * sw, 0);
-        pf[j].y = __builtin_amdgcn_raw_buffer_load_b32(rs, ld_off, yb_ * sw, 0);
+        pf.v[j].x = __builtin_amdgcn_raw_buffer_load_b32(rs, ld_off, ya * sw, 0);
+        pf.v[j].y = __builtin_amdgcn_raw_buffer_load_b32(rs, ld_off, yb_ * sw, 0);
       }
     }
     else if (U8)
     {
 #pragma unroll
       for (int j = 0; j < NR; j++)
-        pf[j].x = __builtin_amdgcn_raw_buffer_load_b32(rs, ld_off, mirror_idx(r0 + j, H) * a.spitch, 0);
-    }
-    else if (r0 >= 0 && r0 + NR <= H)
-    {
-      int so = r0 * spitch4;
-#pragma unroll
-      for (int j = 0; j < NR; j++, so += spitch4)
-        pf[j] = load4(so);
+        pf.v[j].x = __builtin_amdgcn_raw_buffer_load_b32(rs, ld_off, mirror_idx(r0 + j, H) * a.spitch, 0);
     }
     else
-    {
-#pragma unroll
-      for (int j = 0; j < NR; j++)
-        pf[j] = load4(mirror_idx(r0 + j, H) * spitch4);
-    }
+      pf = prefetch_rows<F16, false>(rs, ld_off, ExtraCol{}, r0, H, spitch4);
   };
 
   int rg = y0 - R; // first virtual row of the current group
@@ -514,6 +695,7 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
 #pragma unroll
   for (int k = 0; k < NWIN; k++)
     wv[k] = make_float2(0.f, 0.f);
+  auto win = [&](int k) { return wv[k]; };
 
   for (; rg - R < y1; rg += NR)
   {
@@ -530,7 +712,7 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
       {
         float hr[UPS_NSRC][4];
         auto hrow = [&](int s) {
-          const unsigned d = __builtin_amdgcn_perm(pf[s].x, pf[s].x, perm_sel);
+          const unsigned d = __builtin_amdgcn_perm(pf.v[s].x, pf.v[s].x, perm_sel);
           float t[4];
           unit_of_bytes(d, t);
 #pragma unroll
@@ -563,9 +745,7 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
 #pragma unroll
           for (int k = 0; k < 4; k++)
             hrc[s][k] = hr[4 + s][k];
-#pragma unroll
-        for (int j = 0; j < NR; j++)
-        {
+        stage_rows<SW>(s_grp, lane, rev, [&](int j) {
           const int p = UPS_PAR ? j / 2 : (j + 1) / 2;           // rows (p, p+1) of hr
           const float b = ((j + UPS_PAR) & 1) ? 0.25f : 0.75f;   // odd output rows sit nearer the upper source row
           float res[4];
@@ -576,19 +756,14 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
             if (F16)
               res[k] = (float)to_h(res[k]);
           }
-          u32x4 v = u32x4{__float_as_uint(res[0]), __float_as_uint(res[1]), __float_as_uint(res[2]), __float_as_uint(res[3])};
-          if (rev)
-            v = u32x4{v.w, v.z, v.y, v.x};
-          *(u32x4 *)(s_grp + j * SW + 4 * lane) = v;
-        }
+          return u32x4{__float_as_uint(res[0]), __float_as_uint(res[1]), __float_as_uint(res[2]), __float_as_uint(res[3])};
+        });
       }
     }
     else if (lane < NV4)
     {
-#pragma unroll
-      for (int j = 0; j < NR; j++)
-      {
-        u32x4 v = pf[j];
+      stage_rows<SW>(s_grp, lane, rev, [&](int j) {
+        u32x4 v = pf.v[j];
         if (UPS)
         {
           const unsigned d0 = __builtin_amdgcn_perm(v.x, v.x, perm_sel), d1 = __builtin_amdgcn_perm(v.y, v.y, perm_sel);
@@ -628,48 +803,20 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
           unpack_h2(v.y, f2, f3);
           v = u32x4{__float_as_uint(f0), __float_as_uint(f1), __float_as_uint(f2), __float_as_uint(f3)};
         }
-        if (rev)
-          v = u32x4{v.w, v.z, v.y, v.x};
-        *(u32x4 *)(s_grp + j * SW + 4 * lane) = v;
-      }
+        return v;
+      });
     }
     prefetch(rg + NR);
     __syncthreads();
 
-    // ---- horizontal pass of the new rows, into the top of the register window. Two rows at a time: their accumulator
-    // chains are independent, so the scheduler can alternate them and the dependent v_pk_add -> v_pk_fma pairs need no
-    // wait states (one row alone leaves an s_nop after almost every packed instruction).
+    // ---- horizontal pass of the new rows, into the top of the register window
+#pragma unroll
+    for (int j = 0; j < NR; j += 2)
     {
-      const float *hb = s_grp + (RA - R - OFS) + 2 * lane;
-#pragma unroll
-      for (int j = 0; j < NR; j += 2)
-      {
-        const v2f *pa = (const v2f *)(hb + j * SW);
-        const v2f *pb = (const v2f *)(hb + (j + 1) * SW);
-        float va[2 * NP], vb2[2 * NP];
-#pragma unroll
-        for (int q = 0; q < NP; q++)
-        {
-          v2f ta = pa[q], tb = pb[q];
-          va[2 * q] = ta.x, va[2 * q + 1] = ta.y;
-          vb2[2 * q] = tb.x, vb2[2 * q + 1] = tb.y;
-        }
-        float a0 = va[C0] * k0, a1 = va[C0 + 1] * k0;
-        float b0 = vb2[C0] * k0, b1 = vb2[C0 + 1] * k0;
-#pragma unroll
-        for (int i = 1; i < NT; i++)
-        {
-          a0 = fmaf(va[C0 + i] + va[C0 - i], a.taps.k[i], a0);
-          a1 = fmaf(va[C0 + 1 + i] + va[C0 + 1 - i], a.taps.k[i], a1);
-          b0 = fmaf(vb2[C0 + i] + vb2[C0 - i], a.taps.k[i], b0);
-          b1 = fmaf(vb2[C0 + 1 + i] + vb2[C0 + 1 - i], a.taps.k[i], b1);
-        }
-        if (F16) // the horizontal pass's output is an image of the pyramid format too (the reference's blur temporary)
-          a0 = (float)to_h(a0), a1 = (float)to_h(a1), b0 = (float)to_h(b0), b1 = (float)to_h(b1);
-        wv[2 * R + j] = make_float2(a0, a1);
-        wv[2 * R + j + 1] = make_float2(b0, b1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      const RowPair o = hpass2<NT, SW, RA, F16>(s_grp, lane, a.taps.k, j);
+      wv[2 * R + j] = o.a;
+      wv[2 * R + j + 1] = o.b;
+      __builtin_amdgcn_sched_barrier(0);
     }
 
     // ---- vertical pass: output rows yb .. yb+NR-1
@@ -697,18 +844,9 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
 #pragma unroll
         for (int j = 0; j < NR; j += 2, so_d += 2 * dpitch4)
         {
-          float a0 = wv[R + j].x * k0, a1 = wv[R + j].y * k0;
-          float b0 = wv[R + j + 1].x * k0, b1 = wv[R + j + 1].y * k0;
-#pragma unroll
-          for (int i = 1; i < NT; i++)
-          {
-            a0 = fmaf(wv[R + j + i].x + wv[R + j - i].x, a.taps.k[i], a0);
-            a1 = fmaf(wv[R + j + i].y + wv[R + j - i].y, a.taps.k[i], a1);
-            b0 = fmaf(wv[R + j + 1 + i].x + wv[R + j + 1 - i].x, a.taps.k[i], b0);
-            b1 = fmaf(wv[R + j + 1 + i].y + wv[R + j + 1 - i].y, a.taps.k[i], b1);
-          }
-          emit(j, so_d, a0, a1);
-          emit(j + 1, so_d + dpitch4, b0, b1);
+          const RowPair o = vrow2_pair<NT>(a.taps.k, win, j);
+          emit(j, so_d, o.a.x, o.a.y);
+          emit(j + 1, so_d + dpitch4, o.b.x, o.b.y);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -720,22 +858,13 @@ __device__ __forceinline__ void blur_lean_body(const StreamArgs &a, const uint32
         {
           if (yb + j < y0 || yb + j >= y1)
             continue;
-          float acc0 = wv[R + j].x * k0, acc1 = wv[R + j].y * k0;
-#pragma unroll
-          for (int i = 1; i < NT; i++)
-          {
-            acc0 = fmaf(wv[R + j + i].x + wv[R + j - i].x, a.taps.k[i], acc0);
-            acc1 = fmaf(wv[R + j + i].y + wv[R + j - i].y, a.taps.k[i], acc1);
-          }
-          emit(j, so_d, acc0, acc1);
+          const float2 o = vrow2<NT>(a.taps.k, win, j);
+          emit(j, so_d, o.x, o.y);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
     }
-    // ---- slide the window
-#pragma unroll
-    for (int k = 0; k < 2 * R; k++)
-      wv[k] = wv[k + NR];
+    slide(wv);
   }
 }
 
@@ -774,89 +903,37 @@ __global__ void __launch_bounds__(64) k_blur_lean_multi(Multi<StreamArgs> m)
 template <int NT>
 __global__ void __launch_bounds__(64) k_blur_wide(StreamArgs a)
 {
-  constexpr int NR = 8;
   constexpr int R = NT - 1;
   constexpr int RA = (R + 3) & ~3;
   constexpr int TW = 256;
   constexpr int SW = TW + 2 * RA;
-  constexpr int NX = RA / 2;   // float4 columns of a staged row beyond the 64 that the lanes stage themselves
-  constexpr int NXT = NX * NR; // ... of a whole group: lane e < NXT stages float4 column 64 + e % NX of row e / NX
-  constexpr int NQ = RA / 2 + 1; // ds_read_b128 per row in the horizontal pass
   constexpr int NWIN = 2 * R + NR;
-  static_assert(NXT <= 64, "the extra float4 columns of a group are staged by one instruction");
   __shared__ __attribute__((aligned(16))) float s_grp[NR * SW];
 
   const int lane = threadIdx.x;
   const int W = a.w, H = a.h;
-  uint32_t bs = blockIdx.x, bseg = blockIdx.y, bimg = blockIdx.z;
-  {
-    // XCD-aware work mapping, as k_blur_lean (and written out for the same reason)
-    const uint32_t total = gridDim.x * gridDim.y * gridDim.z;
-    const uint32_t b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    uint32_t wi = b;
-    if ((total & 7u) == 0)
-    {
-      const uint32_t per = total >> 3, k = b >> 3;
-      wi = (b & 7u) * per + (a.rev ? per - 1u - k : k);
-    }
-    else if (a.rev)
-      wi = total - 1u - b;
-    if ((total & 7u) == 0 || a.rev)
-    {
-      bs = wi % gridDim.x;
-      const uint32_t r = wi / gridDim.x;
-      bseg = r % gridDim.y;
-      bimg = r / gridDim.y;
-    }
-  }
-  const int x0 = bs * TW;
-  const int y0 = bseg * a.seg;
+  const Origin og = march_origin<false>(blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z, a.rev);
+  const int x0 = og.strip * TW;
+  const int y0 = og.seg * a.seg;
   const int y1 = min(y0 + a.seg, H);
-  const __amdgpu_buffer_rsrc_t rs = plane_rsrc<false>(a.src, (size_t)bimg * a.src_img_stride, a.spitch, H);
-  const __amdgpu_buffer_rsrc_t rd = plane_rsrc<false>(a.dst, (size_t)bimg * a.dst_img_stride, a.dpitch, H);
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc<false>(a.src, (size_t)og.img * a.src_img_stride, a.spitch, H);
+  const __amdgpu_buffer_rsrc_t rd = plane_rsrc<false>(a.dst, (size_t)og.img * a.dst_img_stride, a.dpitch, H);
   const bool has_ds = a.ds != nullptr;
   const __amdgpu_buffer_rsrc_t rds =
-      plane_rsrc<false>(has_ds ? a.ds : a.dst, has_ds ? (size_t)bimg * a.ds_img_stride : 0, has_ds ? a.ds_pitch : a.dpitch, has_ds ? H / 2 : H);
+      plane_rsrc<false>(has_ds ? a.ds : a.dst, has_ds ? (size_t)og.img * a.ds_img_stride : 0, has_ds ? a.ds_pitch : a.dpitch, has_ds ? H / 2 : H);
   const int spitch4 = a.spitch * 4, dpitch4 = a.dpitch * 4, dspitch4 = a.ds_pitch * 4; // row pitches in bytes
 
   // ---- lane constants: the float4 column this lane stages in every row ...
-  bool rev = false, rev_x = false;
-  const unsigned ld_off = mirrored_col_off(x0 - RA + 4 * lane, W, rev);
+  bool rev = false;
+  const unsigned ld_off = mirrored_col_off(x0 - RA + 4 * lane, W, 4u, rev);
   // ... and the (row, column) beyond the 64th float4 it stages once per group
-  const int xr = lane / NX, xq = 64 + lane % NX;
-  unsigned ldx_col = BUF_OOB;
-  if (lane < NXT)
-    ldx_col = mirrored_col_off(x0 - RA + 4 * xq, W, rev_x);
-  const unsigned ldx_off = lane < NXT ? ldx_col + (unsigned)(xr * spitch4) : BUF_OOB;
-  float *const sx = s_grp + xr * SW + 4 * xq;
+  const ExtraCol xc = extra_col<RA / 2, SW>(s_grp, lane, x0 - RA, W, spitch4);
   const int px = x0 + 4 * lane;
   const unsigned st_off = px + 3 < W ? (unsigned)px * 4u : BUF_OOB;
   const unsigned st_off_ds = px + 3 < W ? (unsigned)(px >> 1) * 4u : BUF_OOB; // columns px+1, px+3 -> px/2, px/2+1 of the half-size plane
-  const float k0 = a.taps.k[0];
-
-  u32x4 pf[NR], pfx;
-  auto prefetch = [&](int r0) {
-    if (r0 >= 0 && r0 + NR <= H)
-    {
-      int so = r0 * spitch4;
-      pfx = __builtin_amdgcn_raw_buffer_load_b128(rs, ldx_off, so, 0);
-#pragma unroll
-      for (int j = 0; j < NR; j++, so += spitch4)
-        pf[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, ld_off, so, 0);
-    }
-    else
-    {
-      // a group that crosses the top or bottom edge: every row mirrored on its own (the extra column's row is a lane value)
-      const unsigned ox = lane < NXT ? ldx_col + (unsigned)(mirror_idx(r0 + xr, H) * spitch4) : BUF_OOB;
-      pfx = __builtin_amdgcn_raw_buffer_load_b128(rs, ox, 0, 0);
-#pragma unroll
-      for (int j = 0; j < NR; j++)
-        pf[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, ld_off, mirror_idx(r0 + j, H) * spitch4, 0);
-    }
-  };
 
   int rg = y0 - R; // first virtual row of the current group
-  prefetch(rg);
+  Rows pf = prefetch_rows<false, true>(rs, ld_off, xc, rg, H, spitch4);
 
   // The register window is a RING of NWP = NPH * NR rows: in phase P (the P-th group of a round) window row k lives in
   // wv[(k + P * NR) % NWP], so the window slides by renaming — the march loop is unrolled over the NPH phases and every index is a
@@ -872,51 +949,18 @@ __global__ void __launch_bounds__(64) k_blur_wide(StreamArgs a)
   auto group = [&](auto PH) {
     constexpr int P = decltype(PH)::value;
 #define WV(k) wv[((k) + P * NR) % NWP]
+    auto win = [&](int k) { return WV(k); };
     // ---- stage the prefetched group, then prefetch the next one
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NR; j++)
-    {
-      u32x4 v = pf[j];
-      if (rev)
-        v = u32x4{v.w, v.z, v.y, v.x};
-      *(u32x4 *)(s_grp + j * SW + 4 * lane) = v;
-    }
-    if (lane < NXT)
-    {
-      u32x4 v = pfx;
-      if (rev_x)
-        v = u32x4{v.w, v.z, v.y, v.x};
-      *(u32x4 *)sx = v;
-    }
-    prefetch(rg + NR);
+    stage_rows<SW>(s_grp, lane, rev, [&](int j) { return pf.v[j]; });
+    stage_extra(xc, pf.x);
+    pf = prefetch_rows<false, true>(rs, ld_off, xc, rg + NR, H, spitch4);
     __syncthreads();
 
-    // ---- horizontal pass of the new rows, into the top of the register window: four independent accumulator chains per row
-    {
-      const v4f *hb = (const v4f *)(s_grp + 4 * lane);
+    // ---- horizontal pass of the new rows, into the top of the register window
 #pragma unroll
-      for (int j = 0; j < NR; j++)
-      {
-        float va[4 * NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; q++)
-        {
-          const v4f t = hb[j * (SW / 4) + q];
-          va[4 * q] = t.x, va[4 * q + 1] = t.y, va[4 * q + 2] = t.z, va[4 * q + 3] = t.w;
-        }
-        float o[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          o[k] = va[RA + k] * k0;
-#pragma unroll
-        for (int i = 1; i < NT; i++)
-#pragma unroll
-          for (int k = 0; k < 4; k++)
-            o[k] = fmaf(va[RA + k + i] + va[RA + k - i], a.taps.k[i], o[k]);
-        WV(2 * R + j) = v4f{o[0], o[1], o[2], o[3]};
-      }
-    }
+    for (int j = 0; j < NR; j++)
+      WV(2 * R + j) = hpass4<NT, SW, RA>(s_grp, lane, a.taps.k, j);
 
     // ---- vertical pass: output rows yb .. yb+NR-1
     const int yb = rg - R;
@@ -924,17 +968,8 @@ __global__ void __launch_bounds__(64) k_blur_wide(StreamArgs a)
     {
       auto vrow = [&](auto J, int so_d) {
         constexpr int j = decltype(J)::value;
-        v4f acc = WV(R + j) * k0;
-#pragma unroll
-        for (int i = 1; i < NT; i++)
-        {
-          const v4f sm = WV(R + j + i) + WV(R + j - i);
-          acc.x = fmaf(sm.x, a.taps.k[i], acc.x);
-          acc.y = fmaf(sm.y, a.taps.k[i], acc.y);
-          acc.z = fmaf(sm.z, a.taps.k[i], acc.z);
-          acc.w = fmaf(sm.w, a.taps.k[i], acc.w);
-        }
-        store_b128_stream(u32x4{__float_as_uint(acc.x), __float_as_uint(acc.y), __float_as_uint(acc.z), __float_as_uint(acc.w)}, rd, st_off, so_d);
+        const v4f acc = vrow4<NT>(a.taps.k, win, j);
+        store_b128_stream(bits_of(acc), rd, st_off, so_d);
         // vkCmdBlitImage(NEAREST) into the next octave, exact 2:1: destination (x, y) takes source (2x+1, 2y+1); yb is even
         if (has_ds && (j & 1))
           __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(acc.y), __float_as_uint(acc.w)}, rds, st_off_ds, ((yb + j) >> 1) * dspitch4, ST_STREAM);
@@ -1002,87 +1037,40 @@ struct PairArgs
 template <int NT1, int NT2>
 __global__ void __launch_bounds__(64) k_blur_pair(PairArgs a)
 {
-  constexpr int NR = 8;
   constexpr int R1 = NT1 - 1, R2 = NT2 - 1;
   constexpr int RA1 = (R1 + 3) & ~3;
   constexpr int HC = (R2 + 3) & ~3;
   constexpr int TW = 128, OW = TW - 2 * HC;
   constexpr int SW = TW + 2 * RA1;
   constexpr int NV4 = SW / 4;
-  constexpr int OFS1 = (RA1 - R1) & 1, NP1 = R1 + 1 + OFS1, C01 = R1 + OFS1;
-  constexpr int OFS2 = R2 & 1, NP2 = R2 + 1 + OFS2, C02 = R2 + OFS2;
-  constexpr int PAD = (R2 + OFS2 + 3) & ~3; // floats of padding on both sides of a scale-s row in LDS
-  constexpr int G1S = TW + 2 * PAD;         // its row stride
-  static_assert(R2 + OFS2 <= PAD, "padding of the second stage's LDS rows");
+  constexpr int PAD = (R2 + (R2 & 1) + 3) & ~3; // floats of padding on both sides of a scale-s row in LDS: the H window of hpass2 fits
+  constexpr int G1S = TW + 2 * PAD;            // its row stride
   constexpr int NWIN1 = 2 * R1 + NR, NWIN2 = 2 * R2 + NR;
   __shared__ __attribute__((aligned(16))) float s_grp[NR * SW];
   __shared__ __attribute__((aligned(16))) float s_g1[NR * G1S];
 
   const int lane = threadIdx.x;
   const int W = a.w, H = a.h;
-  uint32_t bs = blockIdx.x, bseg = blockIdx.y, bimg = blockIdx.z;
-  { // XCD-aware work mapping as k_blur_lean's, unconditional form (written out there why)
-    const uint32_t total = gridDim.x * gridDim.y * gridDim.z;
-    const uint32_t b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    uint32_t wi = b;
-    if ((total & 7u) == 0)
-    {
-      const uint32_t per = total >> 3, k = b >> 3;
-      wi = (b & 7u) * per + (a.rev ? per - 1u - k : k);
-    }
-    else if (a.rev)
-      wi = total - 1u - b;
-    bs = wi % gridDim.x;
-    const uint32_t r = wi / gridDim.x;
-    bseg = r % gridDim.y;
-    bimg = r / gridDim.y;
-  }
-  const int x0 = (int)bs * OW - HC; // first computed column (virtual: negative on the first strip)
-  const int y0 = bseg * a.seg;
+  const Origin og = march_origin<true>(blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z, a.rev);
+  const int x0 = (int)og.strip * OW - HC; // first computed column (virtual: negative on the first strip)
+  const int y0 = og.seg * a.seg;
   const int y1 = min(y0 + a.seg, H);
-  const __amdgpu_buffer_rsrc_t rs = plane_rsrc<false>(a.src, (size_t)bimg * a.src_img_stride, a.spitch, H);
-  const __amdgpu_buffer_rsrc_t rd1 = plane_rsrc<false>(a.dst1, (size_t)bimg * a.dst1_img_stride, a.d1pitch, H);
-  const __amdgpu_buffer_rsrc_t rd2 = plane_rsrc<false>(a.dst2, (size_t)bimg * a.dst2_img_stride, a.d2pitch, H);
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc<false>(a.src, (size_t)og.img * a.src_img_stride, a.spitch, H);
+  const __amdgpu_buffer_rsrc_t rd1 = plane_rsrc<false>(a.dst1, (size_t)og.img * a.dst1_img_stride, a.d1pitch, H);
+  const __amdgpu_buffer_rsrc_t rd2 = plane_rsrc<false>(a.dst2, (size_t)og.img * a.dst2_img_stride, a.d2pitch, H);
 
   // ---- lane constants
-  const int gx4 = x0 - RA1 + 4 * lane;
   unsigned ld_off = BUF_OOB;
   bool rev = false;
   if (lane < NV4)
-  {
-    if (gx4 >= 0 && gx4 + 3 < W)
-      ld_off = (unsigned)gx4 * 4u;
-    else
-    {
-      ld_off = (unsigned)mirror_idx(gx4 + 3, W) * 4u; // the four virtual columns map to m3+3, m3+2, m3+1, m3
-      rev = true;
-    }
-  }
+    ld_off = mirrored_col_off(x0 - RA1 + 4 * lane, W, 4u, rev);
   const int px = x0 + 2 * lane;
   const bool own = 2 * lane >= HC && 2 * lane < TW - HC;
   const unsigned st_off = (own && px >= 0 && px + 1 < W) ? (unsigned)px * 4u : BUF_OOB;
   const int spitch4 = a.spitch * 4, d1pitch4 = a.d1pitch * 4, d2pitch4 = a.d2pitch * 4;
-  const float k10 = a.t1.k[0], k20 = a.t2.k[0];
-
-  u32x4 pf[NR];
-  auto prefetch = [&](int r0) {
-    if (r0 >= 0 && r0 + NR <= H)
-    {
-      int so = r0 * spitch4;
-#pragma unroll
-      for (int j = 0; j < NR; j++, so += spitch4)
-        pf[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, ld_off, so, 0);
-    }
-    else
-    {
-#pragma unroll
-      for (int j = 0; j < NR; j++)
-        pf[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, ld_off, mirror_idx(r0 + j, H) * spitch4, 0);
-    }
-  };
 
   int rg = y0 - R1 - R2; // first virtual source row of the current group
-  prefetch(rg);
+  Rows pf = prefetch_rows<false, false>(rs, ld_off, ExtraCol{}, rg, H, spitch4);
 
   float2 wv1[NWIN1], wv2[NWIN2];
 #pragma unroll
@@ -1091,55 +1079,26 @@ __global__ void __launch_bounds__(64) k_blur_pair(PairArgs a)
 #pragma unroll
   for (int k = 0; k < NWIN2; k++)
     wv2[k] = make_float2(0.f, 0.f);
+  auto win1 = [&](int k) { return wv1[k]; };
+  auto win2 = [&](int k) { return wv2[k]; };
 
   for (; rg - R1 - R2 < y1; rg += NR)
   {
     // ---- stage the prefetched group, then prefetch the next one
     __syncthreads();
     if (lane < NV4)
-    {
-#pragma unroll
-      for (int j = 0; j < NR; j++)
-      {
-        u32x4 v = pf[j];
-        if (rev)
-          v = u32x4{v.w, v.z, v.y, v.x};
-        *(u32x4 *)(s_grp + j * SW + 4 * lane) = v;
-      }
-    }
-    prefetch(rg + NR);
+      stage_rows<SW>(s_grp, lane, rev, [&](int j) { return pf.v[j]; });
+    pf = prefetch_rows<false, false>(rs, ld_off, ExtraCol{}, rg + NR, H, spitch4);
     __syncthreads();
 
-    // ---- first filter, horizontal: the new rows into the top of window 1 (two rows at a time, see k_blur_lean)
+    // ---- first filter, horizontal: the new rows into the top of window 1
+#pragma unroll
+    for (int j = 0; j < NR; j += 2)
     {
-      const float *hb = s_grp + (RA1 - R1 - OFS1) + 2 * lane;
-#pragma unroll
-      for (int j = 0; j < NR; j += 2)
-      {
-        const v2f *pa = (const v2f *)(hb + j * SW);
-        const v2f *pb = (const v2f *)(hb + (j + 1) * SW);
-        float va[2 * NP1], vb2[2 * NP1];
-#pragma unroll
-        for (int q = 0; q < NP1; q++)
-        {
-          v2f ta = pa[q], tb = pb[q];
-          va[2 * q] = ta.x, va[2 * q + 1] = ta.y;
-          vb2[2 * q] = tb.x, vb2[2 * q + 1] = tb.y;
-        }
-        float a0 = va[C01] * k10, a1 = va[C01 + 1] * k10;
-        float b0 = vb2[C01] * k10, b1 = vb2[C01 + 1] * k10;
-#pragma unroll
-        for (int i = 1; i < NT1; i++)
-        {
-          a0 = fmaf(va[C01 + i] + va[C01 - i], a.t1.k[i], a0);
-          a1 = fmaf(va[C01 + 1 + i] + va[C01 + 1 - i], a.t1.k[i], a1);
-          b0 = fmaf(vb2[C01 + i] + vb2[C01 - i], a.t1.k[i], b0);
-          b1 = fmaf(vb2[C01 + 1 + i] + vb2[C01 + 1 - i], a.t1.k[i], b1);
-        }
-        wv1[2 * R1 + j] = make_float2(a0, a1);
-        wv1[2 * R1 + j + 1] = make_float2(b0, b1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      const RowPair o = hpass2<NT1, SW, RA1>(s_grp, lane, a.t1.k, j);
+      wv1[2 * R1 + j] = o.a;
+      wv1[2 * R1 + j + 1] = o.b;
+      __builtin_amdgcn_sched_barrier(0);
     }
     // ---- first filter, vertical: rows yb1 .. yb1+7 of scale s (all 128 columns: the second filter's horizontal halo included)
     const int yb1 = rg - R1;
@@ -1148,62 +1107,29 @@ __global__ void __launch_bounds__(64) k_blur_pair(PairArgs a)
 #pragma unroll
       for (int j = 0; j < NR; j += 2, so_d += 2 * d1pitch4)
       {
-        float a0 = wv1[R1 + j].x * k10, a1 = wv1[R1 + j].y * k10;
-        float b0 = wv1[R1 + j + 1].x * k10, b1 = wv1[R1 + j + 1].y * k10;
-#pragma unroll
-        for (int i = 1; i < NT1; i++)
-        {
-          a0 = fmaf(wv1[R1 + j + i].x + wv1[R1 + j - i].x, a.t1.k[i], a0);
-          a1 = fmaf(wv1[R1 + j + i].y + wv1[R1 + j - i].y, a.t1.k[i], a1);
-          b0 = fmaf(wv1[R1 + j + 1 + i].x + wv1[R1 + j + 1 - i].x, a.t1.k[i], b0);
-          b1 = fmaf(wv1[R1 + j + 1 + i].y + wv1[R1 + j + 1 - i].y, a.t1.k[i], b1);
-        }
-        *(v2f *)(s_g1 + j * G1S + PAD + 2 * lane) = v2f{a0, a1};
-        *(v2f *)(s_g1 + (j + 1) * G1S + PAD + 2 * lane) = v2f{b0, b1};
+        const RowPair o = vrow2_pair<NT1>(a.t1.k, win1, j);
+        *(v2f *)(s_g1 + j * G1S + PAD + 2 * lane) = v2f{o.a.x, o.a.y};
+        *(v2f *)(s_g1 + (j + 1) * G1S + PAD + 2 * lane) = v2f{o.b.x, o.b.y};
         // the segment's own rows of scale s (wave-uniform tests)
         if (yb1 + j >= y0 && yb1 + j < y1)
-          __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(a0), __float_as_uint(a1)}, rd1, st_off, so_d, ST_STREAM);
+          __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(o.a.x), __float_as_uint(o.a.y)}, rd1, st_off, so_d, ST_STREAM);
         if (yb1 + j + 1 >= y0 && yb1 + j + 1 < y1)
-          __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(b0), __float_as_uint(b1)}, rd1, st_off, so_d + d1pitch4, ST_STREAM);
+          __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(o.b.x), __float_as_uint(o.b.y)}, rd1, st_off, so_d + d1pitch4, ST_STREAM);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#pragma unroll
-    for (int k = 0; k < 2 * R1; k++)
-      wv1[k] = wv1[k + NR];
+    slide(wv1);
     __syncthreads();
 
     // ---- second filter, horizontal, from the rows of scale s just written to LDS (lanes outside the owned columns read into the
     // padding: their results are never stored)
+#pragma unroll
+    for (int j = 0; j < NR; j += 2)
     {
-      const float *hb = s_g1 + (PAD - R2 - OFS2) + 2 * lane;
-#pragma unroll
-      for (int j = 0; j < NR; j += 2)
-      {
-        const v2f *pa = (const v2f *)(hb + j * G1S);
-        const v2f *pb = (const v2f *)(hb + (j + 1) * G1S);
-        float va[2 * NP2], vb2[2 * NP2];
-#pragma unroll
-        for (int q = 0; q < NP2; q++)
-        {
-          v2f ta = pa[q], tb = pb[q];
-          va[2 * q] = ta.x, va[2 * q + 1] = ta.y;
-          vb2[2 * q] = tb.x, vb2[2 * q + 1] = tb.y;
-        }
-        float a0 = va[C02] * k20, a1 = va[C02 + 1] * k20;
-        float b0 = vb2[C02] * k20, b1 = vb2[C02 + 1] * k20;
-#pragma unroll
-        for (int i = 1; i < NT2; i++)
-        {
-          a0 = fmaf(va[C02 + i] + va[C02 - i], a.t2.k[i], a0);
-          a1 = fmaf(va[C02 + 1 + i] + va[C02 + 1 - i], a.t2.k[i], a1);
-          b0 = fmaf(vb2[C02 + i] + vb2[C02 - i], a.t2.k[i], b0);
-          b1 = fmaf(vb2[C02 + 1 + i] + vb2[C02 + 1 - i], a.t2.k[i], b1);
-        }
-        wv2[2 * R2 + j] = make_float2(a0, a1);
-        wv2[2 * R2 + j + 1] = make_float2(b0, b1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      const RowPair o = hpass2<NT2, G1S, PAD>(s_g1, lane, a.t2.k, j);
+      wv2[2 * R2 + j] = o.a;
+      wv2[2 * R2 + j + 1] = o.b;
+      __builtin_amdgcn_sched_barrier(0);
     }
     // ---- second filter, vertical: rows yb2 .. yb2+7 of scale s+1
     const int yb2 = yb1 - R2;
@@ -1215,20 +1141,12 @@ __global__ void __launch_bounds__(64) k_blur_pair(PairArgs a)
       {
         if (yb2 + j < y0 || yb2 + j >= y1)
           continue;
-        float acc0 = wv2[R2 + j].x * k20, acc1 = wv2[R2 + j].y * k20;
-#pragma unroll
-        for (int i = 1; i < NT2; i++)
-        {
-          acc0 = fmaf(wv2[R2 + j + i].x + wv2[R2 + j - i].x, a.t2.k[i], acc0);
-          acc1 = fmaf(wv2[R2 + j + i].y + wv2[R2 + j - i].y, a.t2.k[i], acc1);
-        }
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(acc0), __float_as_uint(acc1)}, rd2, st_off, so_d, ST_STREAM);
+        const float2 o = vrow2<NT2>(a.t2.k, win2, j);
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(o.x), __float_as_uint(o.y)}, rd2, st_off, so_d, ST_STREAM);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#pragma unroll
-    for (int k = 0; k < 2 * R2; k++)
-      wv2[k] = wv2[k + NR];
+    slide(wv2);
   }
 }
 
@@ -1241,82 +1159,36 @@ __global__ void __launch_bounds__(64) k_blur_pair(PairArgs a)
 template <int NT1, int NT2>
 __global__ void __launch_bounds__(64) k_blur_pair_wide(PairArgs a)
 {
-  constexpr int NR = 8;
   constexpr int R1 = NT1 - 1, R2 = NT2 - 1;
   constexpr int RA1 = (R1 + 3) & ~3, RA2 = (R2 + 3) & ~3;
   constexpr int HC = RA2;
   constexpr int TW = 256, OW = TW - 2 * HC;
   constexpr int SW = TW + 2 * RA1;
-  constexpr int NX = RA1 / 2, NXT = NX * NR;
-  constexpr int NQ1 = RA1 / 2 + 1, NQ2 = RA2 / 2 + 1;
   constexpr int G1S = TW + 2 * RA2; // row stride of the scale-s rows in LDS: RA2 floats of padding on both sides
   constexpr int NWIN1 = 2 * R1 + NR, NWIN2 = 2 * R2 + NR;
-  static_assert(NXT <= 64, "the extra float4 columns of a group are staged by one instruction");
   __shared__ __attribute__((aligned(16))) float s_grp[NR * SW];
   __shared__ __attribute__((aligned(16))) float s_g1[NR * G1S];
 
   const int lane = threadIdx.x;
   const int W = a.w, H = a.h;
-  uint32_t bs = blockIdx.x, bseg = blockIdx.y, bimg = blockIdx.z;
-  { // XCD-aware work mapping as k_blur_lean's, unconditional form (written out there why)
-    const uint32_t total = gridDim.x * gridDim.y * gridDim.z;
-    const uint32_t b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    uint32_t wi = b;
-    if ((total & 7u) == 0)
-    {
-      const uint32_t per = total >> 3, k = b >> 3;
-      wi = (b & 7u) * per + (a.rev ? per - 1u - k : k);
-    }
-    else if (a.rev)
-      wi = total - 1u - b;
-    bs = wi % gridDim.x;
-    const uint32_t r = wi / gridDim.x;
-    bseg = r % gridDim.y;
-    bimg = r / gridDim.y;
-  }
-  const int x0 = (int)bs * OW - HC; // first computed column (virtual: negative on the first strip)
-  const int y0 = bseg * a.seg;
+  const Origin og = march_origin<true>(blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z, a.rev);
+  const int x0 = (int)og.strip * OW - HC; // first computed column (virtual: negative on the first strip)
+  const int y0 = og.seg * a.seg;
   const int y1 = min(y0 + a.seg, H);
-  const __amdgpu_buffer_rsrc_t rs = plane_rsrc<false>(a.src, (size_t)bimg * a.src_img_stride, a.spitch, H);
-  const __amdgpu_buffer_rsrc_t rd1 = plane_rsrc<false>(a.dst1, (size_t)bimg * a.dst1_img_stride, a.d1pitch, H);
-  const __amdgpu_buffer_rsrc_t rd2 = plane_rsrc<false>(a.dst2, (size_t)bimg * a.dst2_img_stride, a.d2pitch, H);
+  const __amdgpu_buffer_rsrc_t rs = plane_rsrc<false>(a.src, (size_t)og.img * a.src_img_stride, a.spitch, H);
+  const __amdgpu_buffer_rsrc_t rd1 = plane_rsrc<false>(a.dst1, (size_t)og.img * a.dst1_img_stride, a.d1pitch, H);
+  const __amdgpu_buffer_rsrc_t rd2 = plane_rsrc<false>(a.dst2, (size_t)og.img * a.dst2_img_stride, a.d2pitch, H);
   const int spitch4 = a.spitch * 4, d1pitch4 = a.d1pitch * 4, d2pitch4 = a.d2pitch * 4;
 
-  bool rev = false, rev_x = false;
-  const unsigned ld_off = mirrored_col_off(x0 - RA1 + 4 * lane, W, rev);
-  const int xr = lane / NX, xq = 64 + lane % NX;
-  unsigned ldx_col = BUF_OOB;
-  if (lane < NXT)
-    ldx_col = mirrored_col_off(x0 - RA1 + 4 * xq, W, rev_x);
-  const unsigned ldx_off = lane < NXT ? ldx_col + (unsigned)(xr * spitch4) : BUF_OOB;
-  float *const sx = s_grp + xr * SW + 4 * xq;
+  bool rev = false;
+  const unsigned ld_off = mirrored_col_off(x0 - RA1 + 4 * lane, W, 4u, rev);
+  const ExtraCol xc = extra_col<RA1 / 2, SW>(s_grp, lane, x0 - RA1, W, spitch4);
   const int px = x0 + 4 * lane;
   const bool own = 4 * lane >= HC && 4 * lane + 3 < TW - HC;
   const unsigned st_off = (own && px >= 0 && px + 3 < W) ? (unsigned)px * 4u : BUF_OOB;
-  const float k10 = a.t1.k[0], k20 = a.t2.k[0];
-
-  u32x4 pf[NR], pfx;
-  auto prefetch = [&](int r0) {
-    if (r0 >= 0 && r0 + NR <= H)
-    {
-      int so = r0 * spitch4;
-      pfx = __builtin_amdgcn_raw_buffer_load_b128(rs, ldx_off, so, 0);
-#pragma unroll
-      for (int j = 0; j < NR; j++, so += spitch4)
-        pf[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, ld_off, so, 0);
-    }
-    else
-    {
-      const unsigned ox = lane < NXT ? ldx_col + (unsigned)(mirror_idx(r0 + xr, H) * spitch4) : BUF_OOB;
-      pfx = __builtin_amdgcn_raw_buffer_load_b128(rs, ox, 0, 0);
-#pragma unroll
-      for (int j = 0; j < NR; j++)
-        pf[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, ld_off, mirror_idx(r0 + j, H) * spitch4, 0);
-    }
-  };
 
   int rg = y0 - R1 - R2; // first virtual source row of the current group
-  prefetch(rg);
+  Rows pf = prefetch_rows<false, true>(rs, ld_off, xc, rg, H, spitch4);
 
   v4f wv1[NWIN1], wv2[NWIN2];
 #pragma unroll
@@ -1325,54 +1197,22 @@ __global__ void __launch_bounds__(64) k_blur_pair_wide(PairArgs a)
 #pragma unroll
   for (int k = 0; k < NWIN2; k++)
     wv2[k] = v4f{0.f, 0.f, 0.f, 0.f};
+  auto win1 = [&](int k) { return wv1[k]; };
+  auto win2 = [&](int k) { return wv2[k]; };
 
   for (; rg - R1 - R2 < y1; rg += NR)
   {
     // ---- stage the prefetched group, then prefetch the next one
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NR; j++)
-    {
-      u32x4 v = pf[j];
-      if (rev)
-        v = u32x4{v.w, v.z, v.y, v.x};
-      *(u32x4 *)(s_grp + j * SW + 4 * lane) = v;
-    }
-    if (lane < NXT)
-    {
-      u32x4 v = pfx;
-      if (rev_x)
-        v = u32x4{v.w, v.z, v.y, v.x};
-      *(u32x4 *)sx = v;
-    }
-    prefetch(rg + NR);
+    stage_rows<SW>(s_grp, lane, rev, [&](int j) { return pf.v[j]; });
+    stage_extra(xc, pf.x);
+    pf = prefetch_rows<false, true>(rs, ld_off, xc, rg + NR, H, spitch4);
     __syncthreads();
 
     // ---- first filter, horizontal: the new rows into the top of window 1
-    {
-      const v4f *hb = (const v4f *)(s_grp + 4 * lane);
 #pragma unroll
-      for (int j = 0; j < NR; j++)
-      {
-        float va[4 * NQ1];
-#pragma unroll
-        for (int q = 0; q < NQ1; q++)
-        {
-          const v4f t = hb[j * (SW / 4) + q];
-          va[4 * q] = t.x, va[4 * q + 1] = t.y, va[4 * q + 2] = t.z, va[4 * q + 3] = t.w;
-        }
-        float o[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          o[k] = va[RA1 + k] * k10;
-#pragma unroll
-        for (int i = 1; i < NT1; i++)
-#pragma unroll
-          for (int k = 0; k < 4; k++)
-            o[k] = fmaf(va[RA1 + k + i] + va[RA1 + k - i], a.t1.k[i], o[k]);
-        wv1[2 * R1 + j] = v4f{o[0], o[1], o[2], o[3]};
-      }
-    }
+    for (int j = 0; j < NR; j++)
+      wv1[2 * R1 + j] = hpass4<NT1, SW, RA1>(s_grp, lane, a.t1.k, j);
     // ---- first filter, vertical: rows yb1 .. yb1+7 of scale s (all 256 columns: the second filter's horizontal halo included)
     const int yb1 = rg - R1;
     {
@@ -1380,53 +1220,21 @@ __global__ void __launch_bounds__(64) k_blur_pair_wide(PairArgs a)
 #pragma unroll
       for (int j = 0; j < NR; j++, so_d += d1pitch4)
       {
-        v4f acc = wv1[R1 + j] * k10;
-#pragma unroll
-        for (int i = 1; i < NT1; i++)
-        {
-          const v4f sm = wv1[R1 + j + i] + wv1[R1 + j - i];
-          acc.x = fmaf(sm.x, a.t1.k[i], acc.x);
-          acc.y = fmaf(sm.y, a.t1.k[i], acc.y);
-          acc.z = fmaf(sm.z, a.t1.k[i], acc.z);
-          acc.w = fmaf(sm.w, a.t1.k[i], acc.w);
-        }
+        const v4f acc = vrow4<NT1>(a.t1.k, win1, j);
         *(v4f *)(s_g1 + j * G1S + RA2 + 4 * lane) = acc;
         // the segment's own rows of scale s (wave-uniform test)
         if (yb1 + j >= y0 && yb1 + j < y1)
-          store_b128_stream(u32x4{__float_as_uint(acc.x), __float_as_uint(acc.y), __float_as_uint(acc.z), __float_as_uint(acc.w)}, rd1, st_off, so_d);
+          store_b128_stream(bits_of(acc), rd1, st_off, so_d);
       }
     }
-#pragma unroll
-    for (int k = 0; k < 2 * R1; k++)
-      wv1[k] = wv1[k + NR];
+    slide(wv1);
     __syncthreads();
 
     // ---- second filter, horizontal, from the rows of scale s just written to LDS (lanes outside the owned columns read into the
     // padding: their results are never stored)
-    {
-      const v4f *hb = (const v4f *)(s_g1 + 4 * lane);
 #pragma unroll
-      for (int j = 0; j < NR; j++)
-      {
-        float va[4 * NQ2];
-#pragma unroll
-        for (int q = 0; q < NQ2; q++)
-        {
-          const v4f t = hb[j * (G1S / 4) + q];
-          va[4 * q] = t.x, va[4 * q + 1] = t.y, va[4 * q + 2] = t.z, va[4 * q + 3] = t.w;
-        }
-        float o[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          o[k] = va[RA2 + k] * k20;
-#pragma unroll
-        for (int i = 1; i < NT2; i++)
-#pragma unroll
-          for (int k = 0; k < 4; k++)
-            o[k] = fmaf(va[RA2 + k + i] + va[RA2 + k - i], a.t2.k[i], o[k]);
-        wv2[2 * R2 + j] = v4f{o[0], o[1], o[2], o[3]};
-      }
-    }
+    for (int j = 0; j < NR; j++)
+      wv2[2 * R2 + j] = hpass4<NT2, G1S, RA2>(s_g1, lane, a.t2.k, j);
     // ---- second filter, vertical: rows yb2 .. yb2+7 of scale s+1
     const int yb2 = yb1 - R2;
     if (yb2 + NR > y0)
@@ -1437,22 +1245,10 @@ __global__ void __launch_bounds__(64) k_blur_pair_wide(PairArgs a)
       {
         if (yb2 + j < y0 || yb2 + j >= y1)
           continue;
-        v4f acc = wv2[R2 + j] * k20;
-#pragma unroll
-        for (int i = 1; i < NT2; i++)
-        {
-          const v4f sm = wv2[R2 + j + i] + wv2[R2 + j - i];
-          acc.x = fmaf(sm.x, a.t2.k[i], acc.x);
-          acc.y = fmaf(sm.y, a.t2.k[i], acc.y);
-          acc.z = fmaf(sm.z, a.t2.k[i], acc.z);
-          acc.w = fmaf(sm.w, a.t2.k[i], acc.w);
-        }
-        store_b128_stream(u32x4{__float_as_uint(acc.x), __float_as_uint(acc.y), __float_as_uint(acc.z), __float_as_uint(acc.w)}, rd2, st_off, so_d);
+        store_b128_stream(bits_of(vrow4<NT2>(a.t2.k, win2, j)), rd2, st_off, so_d);
       }
     }
-#pragma unroll
-    for (int k = 0; k < 2 * R2; k++)
-      wv2[k] = wv2[k + NR];
+    slide(wv2);
   }
 }
 
@@ -1848,8 +1644,17 @@ PairArgs pair_args(const vksift_hip_Plane &src, const vksift_hip_Plane &dst1, co
   return a;
 }
 
-// One tap-count switch for k_blur_lean<N, SRC, F16> (host side): 2..20 taps for a plane source (SRC 0), 2..12 for the two seed forms.
-// -1 (nothing launched) for a tap count without an instantiation.
+// The one tap-count switch of the launchers: f(std::integral_constant<int, N>) for the N of the list that equals ntaps, and what it
+// returns; -1 (nothing launched) for a count outside the list. The lists are the sets of instantiations.
+template <int... Ns, typename F>
+int dispatch_taps(uint32_t ntaps, F f)
+{
+  int r = -1;
+  (void)((ntaps == (uint32_t)Ns && (r = f(std::integral_constant<int, Ns>{}), true)) || ...);
+  return r;
+}
+
+// k_blur_lean<N, SRC, F16>: 2..20 taps for a plane source (SRC 0), 2..12 for the two seed forms
 template <int SRC, int N>
 int launch_lean(dim3 grid, const StreamArgs &a, bool f16, hipStream_t s)
 {
@@ -1868,18 +1673,8 @@ int launch_lean(dim3 grid, const StreamArgs &a, bool f16, hipStream_t s)
 template <int SRC>
 int blur_lean_launch(uint32_t ntaps, dim3 grid, const StreamArgs &a, bool f16, hipStream_t s)
 {
-  switch (ntaps)
-  {
-#define VKSIFT_CASE(N) \
-  case N:              \
-    return launch_lean<SRC, N>(grid, a, f16, s);
-    VKSIFT_CASE(2) VKSIFT_CASE(3) VKSIFT_CASE(4) VKSIFT_CASE(5) VKSIFT_CASE(6) VKSIFT_CASE(7) VKSIFT_CASE(8) VKSIFT_CASE(9) VKSIFT_CASE(10)
-    VKSIFT_CASE(11) VKSIFT_CASE(12) VKSIFT_CASE(13) VKSIFT_CASE(14) VKSIFT_CASE(15) VKSIFT_CASE(16) VKSIFT_CASE(17) VKSIFT_CASE(18)
-    VKSIFT_CASE(19) VKSIFT_CASE(20)
-#undef VKSIFT_CASE
-  default:
-    return -1;
-  }
+  return dispatch_taps<2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20>(
+      ntaps, [&](auto N) { return launch_lean<SRC, decltype(N)::value>(grid, a, f16, s); });
 }
 
 } // namespace
@@ -1960,17 +1755,12 @@ extern "C"
     {
       /* (from 11 taps on half as many, twice as long marches: 512 x 1280x960, tools/blur_ab.py: 11 taps 928 -> 905 us, 13 taps 988 -> 939 us) */
       const dim3 wgrid = march_grid(march_strips(src.w, ntaps, 256u), src.h, batch, ntaps >= 11u ? 5120u : 10240u, true, &a.seg);
-      switch (ntaps)
-      {
-#define VKSIFT_CASE(N)                                              \
-  case N:                                                           \
-    hipLaunchKernelGGL((k_blur_wide<N>), wgrid, dim3(64), 0, hs, a); \
-    return (int)hipGetLastError();
-        VKSIFT_CASE(5) VKSIFT_CASE(7) VKSIFT_CASE(9) VKSIFT_CASE(11) VKSIFT_CASE(13)
-#undef VKSIFT_CASE
-      default: /* (a VKSIFT_TUNE_WIDE_MASK bit without a four-texel instantiation: the two-texel form) */
-        break;
-      }
+      const int e = dispatch_taps<5, 7, 9, 11, 13>(ntaps, [&](auto N) {
+        hipLaunchKernelGGL((k_blur_wide<decltype(N)::value>), wgrid, dim3(64), 0, hs, a);
+        return (int)hipGetLastError();
+      });
+      if (e != -1) /* (-1: a VKSIFT_TUNE_WIDE_MASK bit without a four-texel instantiation takes the two-texel form) */
+        return e;
     }
     const dim3 grid = march_grid(march_strips(src.w, ntaps, 128u), src.h, batch, lean_wg_target(ntaps), true, &a.seg);
     return blur_lean_launch<0>(ntaps, grid, a, src.fp16 != 0, hs);
@@ -1998,21 +1788,13 @@ extern "C"
     }
     const dim3 grid(m.start[m.n]);
     const bool f16 = src[0].fp16 != 0;
-    switch (ntaps)
-    {
-#define VKSIFT_CASE(N)                                                                      \
-  case N:                                                                                   \
-    if (f16)                                                                                \
-      hipLaunchKernelGGL((k_blur_lean_multi<N, true>), grid, dim3(64), 0, (hipStream_t)s, m);  \
-    else                                                                                    \
-      hipLaunchKernelGGL((k_blur_lean_multi<N, false>), grid, dim3(64), 0, (hipStream_t)s, m); \
-    break;
-      VKSIFT_CASE(9) VKSIFT_CASE(11) VKSIFT_CASE(13) VKSIFT_CASE(15)
-#undef VKSIFT_CASE
-    default:
-      return -1;
-    }
-    return (int)hipGetLastError();
+    return dispatch_taps<9, 11, 13, 15>(ntaps, [&](auto N) {
+      if (f16)
+        hipLaunchKernelGGL((k_blur_lean_multi<decltype(N)::value, true>), grid, dim3(64), 0, (hipStream_t)s, m);
+      else
+        hipLaunchKernelGGL((k_blur_lean_multi<decltype(N)::value, false>), grid, dim3(64), 0, (hipStream_t)s, m);
+      return (int)hipGetLastError();
+    });
   }
 
   int vksift_hip_blur_pair(vksift_hip_Plane src, vksift_hip_Plane dst1, vksift_hip_Plane dst2, const float *taps1, uint32_t ntaps1, const float *taps2,
