@@ -271,9 +271,23 @@ extern "C"
    * scan_done (may be NULL): recorded right after the streaming scan kernel, the one bandwidth-bound launch of the stage. */
   int vksift_hip_extract_keypoints(const vksift_hip_OctaveJob *job, uint32_t batch, vksift_hip_stream s, vksift_hip_event scan_done);
   /* ComputeOrientation.comp (sift_detector.c:1191-1241): main orientation written in place, extra
-   * orientations appended in (keypoint, bin) order; found[] updated. */
+   * orientations appended in (keypoint, bin) order; found[] updated.
+   * Contract of the records (both launchers; tests/test_gpu_feature_launchers.py sweeps it). READ: for every image the first min(found, cap)
+   * records of the section hold what vksift_hip_extract_keypoints can emit: 0 <= scale_x < w and 0 <= scale_y < h, scale_idx <= S + 1, a
+   * finite sigma > 0 with sigma / 2^octave_idx from 0.02 to 29 (orientation windows of radius 0 .. 130, descriptor windows of radius 1 .. 257
+   * texels; octave_idx -1 .. 6); the descriptor launcher also reads orientation, in [0, 2 pi]. No other field is interpreted. A window may be
+   * larger than the plane and the planes may be as small as 3 x 3. WRITTEN by the orientation launcher, per image: word 7 (orientation) of
+   * those records that have a histogram peak (a record without one keeps its word: quirk Q4); for every further peak of a record — up to
+   * max_ori per record, 0 = all — a copy of its 9 header words with that angle at record found, found + 1, .. in (keypoint, bin) order,
+   * dropped at and beyond cap; found itself, raised by the number of copies whether stored or dropped (un-clamped); and the scratch rows
+   * ori_ang / ori_cnt of the first min(found, cap) records. Nothing else: not the descriptor bytes of any record, not a record at or beyond
+   * cap, not the counter of another section. */
   int vksift_hip_orientations(const vksift_hip_OctaveJob *job, uint32_t batch, vksift_hip_stream s);
-  /* ComputeDescriptors.comp (sift_detector.c:1243-1259). */
+  /* ComputeDescriptors.comp (sift_detector.c:1243-1259).
+   * READ: as above (found as the orientation launcher left it), and desc_fp_tab[min(R / 2, desc_fp_tab_len - 1)]. WRITTEN, per image: bytes
+   * 36..163 (descriptor) of the first min(found, cap) records — all zero for a window without a texel of the image interior or without a
+   * gradient — and, through vksift_hip_descriptors_multi_dense, the dense rows, norms, n and the posting that vksift_hip_DenseRows describes.
+   * Nothing else. */
   int vksift_hip_descriptors(const vksift_hip_OctaveJob *job, uint32_t batch, vksift_hip_stream s);
   /* The same three stages for SEVERAL octaves of one detection in one chain of launches: the reference records the dispatches of
    * all octaves of a stage into one command buffer (sift_detector.c:1106-1259); here the workgroups of all octaves share one flat

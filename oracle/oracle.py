@@ -87,6 +87,8 @@ def lib():
         L.orc_effective_taps.argtypes = [cfgp, f32p, u32p]
         L.orc_pyramid_build.argtypes = [cfgp, C.c_void_p, C.c_uint32, C.c_uint32]
         L.orc_pyramid_build.restype = C.c_void_p
+        L.orc_pyramid_from_planes.argtypes = [cfgp, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.orc_pyramid_from_planes.restype = C.c_void_p
         L.orc_pyramid_free.argtypes = [C.c_void_p]
         L.orc_pyramid_nb_octaves.argtypes = [C.c_void_p]
         L.orc_pyramid_nb_octaves.restype = C.c_uint32
@@ -225,6 +227,19 @@ class Pyramid:
         self.S = cfg.nb_scales_per_octave
         self._p = lib().orc_pyramid_build(C.byref(cfg), img.ctypes.data, img.shape[1], img.shape[0])
         self.nb_octaves = lib().orc_pyramid_nb_octaves(self._p)
+
+    @classmethod
+    def from_planes(cls, cfg, planes):
+        """One octave whose S+3 Gaussian layers are the given (S+3, h, w) float32 planes; the DoG layers are formed from them as in a built
+        pyramid (orc_pyramid_from_planes). Everything that takes an octave index works on octave 0 of the result."""
+        planes = np.ascontiguousarray(planes, dtype=np.float32)
+        assert planes.ndim == 3 and planes.shape[0] == cfg.nb_scales_per_octave + 3 and planes.size > 0
+        self = cls.__new__(cls)
+        self.cfg = cfg
+        self.S = cfg.nb_scales_per_octave
+        self._p = lib().orc_pyramid_from_planes(C.byref(cfg), planes.ctypes.data, planes.shape[2], planes.shape[1])
+        self.nb_octaves = 1
+        return self
 
     def resolution(self, o):
         w, h = C.c_uint32(), C.c_uint32()

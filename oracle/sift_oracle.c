@@ -442,6 +442,19 @@ void orc_blit_nearest(const float *src, uint32_t sw, uint32_t sh, float *dst, ui
 }
 void orc_store_f16(float *plane, size_t n) { store_as_f16(plane, n); }
 
+/* DifferenceOfGaussian.comp:13-17: the S+2 DoG planes of octave o from its Gaussian planes (binary16 texels in fp16 mode) */
+static void form_dog(orc_Pyramid *p, uint32_t o, int fp16)
+{
+  const uint32_t S = p->S;
+  const size_t px = (size_t)p->w[o] * p->h[o];
+  const float *g = p->gauss[o];
+  for (uint32_t s = 0; s < S + 2; s++)
+    for (size_t i = 0; i < px; i++)
+      p->dog[o][s * px + i] = g[(s + 1) * px + i] - g[s * px + i];
+  if (fp16)
+    store_as_f16(p->dog[o], px * (S + 2));
+}
+
 orc_Pyramid *orc_pyramid_build(const orc_Config *cfg, const uint8_t *img, uint32_t w, uint32_t h)
 {
   orc_Pyramid *p = (orc_Pyramid *)calloc(1, sizeof(orc_Pyramid));
@@ -488,14 +501,25 @@ orc_Pyramid *orc_pyramid_build(const orc_Config *cfg, const uint8_t *img, uint32
       else
         blur_plane(g + (s - 1) * px, g + s * px, tmp, (int)p->w[o], (int)p->h[o], &taps[s * ORC_MAX_KERNEL], (int)ntaps[s], cfg->pyramid_fp16);
     }
-    /* DifferenceOfGaussian.comp:13-17 */
-    for (uint32_t s = 0; s < S + 2; s++)
-      for (size_t i = 0; i < px; i++)
-        p->dog[o][s * px + i] = g[(s + 1) * px + i] - g[s * px + i];
-    if (cfg->pyramid_fp16)
-      store_as_f16(p->dog[o], px * (S + 2));
+    form_dog(p, o, cfg->pyramid_fp16);
   }
   free(tmp);
+  return p;
+}
+
+orc_Pyramid *orc_pyramid_from_planes(const orc_Config *cfg, const float *planes, uint32_t w, uint32_t h)
+{
+  orc_Pyramid *p = (orc_Pyramid *)calloc(1, sizeof(orc_Pyramid));
+  uint32_t S = (uint32_t)cfg->nb_scales_per_octave;
+  p->S = S;
+  p->ups = cfg->use_input_upsampling;
+  p->nb_octaves = 1;
+  p->w[0] = w, p->h[0] = h;
+  size_t px = (size_t)w * h;
+  p->gauss[0] = (float *)malloc(sizeof(float) * px * (S + 3));
+  p->dog[0] = (float *)malloc(sizeof(float) * px * (S + 2));
+  memcpy(p->gauss[0], planes, sizeof(float) * px * (S + 3));
+  form_dog(p, 0, cfg->pyramid_fp16);
   return p;
 }
 
@@ -776,7 +800,9 @@ void orc_descriptor(const orc_Config *cfg, const orc_Pyramid *p, uint32_t o, orc
     for (int j = i + 1; j < R / 2; j++)
       max_elem_val += m.exp_(es * (float)((i * i) + (j * j))) * sqrtf(2.f) * 2;
   }
-  float fp = (float)(1u << (uint32_t)(16 - m.ceil_log2_(max_elem_val)));
+  /* R / 2 == 0 (R = 1: sigma below 0.142 texels of the octave) leaves the sum at 0 and the shader's shift undefined: int(ceil(log2(0)))
+   * saturates to INT_MIN on the GPUs this build targets and a shift takes its count modulo 32, which makes the shift 16. Defined so here. */
+  float fp = (float)(1u << (uint32_t)(max_elem_val > 0.f ? 16 - m.ceil_log2_(max_elem_val) : 16));
 
   float rsx = roundf(kp->scale_x), rsy = roundf(kp->scale_y);
   int box = 2 * R + 1;

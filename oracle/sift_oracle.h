@@ -94,6 +94,11 @@ extern "C"
   /* ---- pyramid ---- */
   typedef struct orc_Pyramid orc_Pyramid;
   orc_Pyramid *orc_pyramid_build(const orc_Config *cfg, const uint8_t *img, uint32_t w, uint32_t h);
+  /* ONE octave from given planes: the S+3 Gaussian layers are copied from `planes` ((S+3) dense w x h fp32 planes, layer 0 first), the DoG
+   * layers are formed from them exactly as orc_pyramid_build forms them (rounded through binary16 under cfg->pyramid_fp16; the planes are
+   * then expected to hold binary16 values already: orc_store_f16). Octave 0 of the result has octave_idx = -1 under
+   * cfg->use_input_upsampling, like octave 0 of a built pyramid. */
+  orc_Pyramid *orc_pyramid_from_planes(const orc_Config *cfg, const float *planes, uint32_t w, uint32_t h);
   void orc_pyramid_free(orc_Pyramid *p);
   uint32_t orc_pyramid_nb_octaves(const orc_Pyramid *p);
   void orc_pyramid_resolution(const orc_Pyramid *p, uint32_t o, uint32_t *w, uint32_t *h);

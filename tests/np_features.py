@@ -253,7 +253,7 @@ def descriptor(plane, kp, theta, vlfeat=False):
     e = np.exp(es * (jj[:, None] ** 2 + jj[None, :] ** 2).astype(np.float64))
     # the shader walks the upper triangle with the off-diagonal doubled = the full symmetric sum
     M = float(e.sum() * np.sqrt(2.0)) if half > 0 else 0.0
-    fp = f32(1 << (16 - _ceil_log2(M))) if M > 0 else f32(np.inf)
+    fp = f32(1 << (16 - _ceil_log2(M))) if M > 0 else f32(1 << 16)     # R = 1: the shader's shift is undefined; the build defines it as 16
 
     cx = f32(_round_half_away(kp["scale_x"]))
     cy = f32(_round_half_away(kp["scale_y"]))

@@ -132,7 +132,9 @@ uint32_t vksift_hm_desc_fp_table(const vksift_Config *cfg, float *tab, uint32_t 
       for (uint32_t j = i + 1; j < n; j++)
         m += dm_expf(es * (float)((i * i) + (j * j))) * sqrtf(2.f) * 2;
     }
-    /* n == 0 cannot occur for a real keypoint (radius >= 1); keep the table total */
+    /* n == 0 is R = 1 (relative sigma below 0.142): the sum is empty and the shader's shift 16 - int(ceil(log2(0))) is undefined.
+     * Exponent 0, i.e. shift 16, is the defined behaviour: it is what the shader's arithmetic gives on the hardware this build
+     * targets (the conversion of -inf saturates, a shift takes its count modulo 32), and the oracle and the numpy restatement agree */
     int e = m > 0.f ? dm_ceil_log2f(m) : 0;
     int sh = 16 - e;
     if (sh < 0)
