@@ -105,7 +105,8 @@ extern "C"
     VKSIFT_TUNE_DENSE_ROWS = 7, /* 1: the descriptor launch does not write the matcher's dense rows (the gather pass of the first matching does, as
                                  * for uploaded buffers); A/B and the bit-identity matrix */
     VKSIFT_TUNE_SEED_WG = 8,    /* waves aimed at by the fused up-sampling + seed launch (0 = built-in) */
-    VKSIFT_TUNE_SCAN_BAND = 9,  /* rows per wave of the streaming extrema scan (0 = built-in: 32 on large octaves, 16 on small ones) */
+    VKSIFT_TUNE_SCAN_BAND = 9,  /* rows per wave of the streaming extrema scan on octaves of more than 256 rows (0 = built-in: 48 there, and 16 when
+                                 * the whole launch has fewer than 2048 waves; octaves of up to 256 rows always take 16) */
     VKSIFT_TUNE_TAIL_MULTI = 10, /* 1: no multi-octave launches for scales S+1, S+2 (batches queue every octave in full; forked detections one launch per
                                   * octave and scale) */
     VKSIFT_TUNE_ZERO_COPY = 11,  /* 1: a single host image is copied into device memory in front of the seed launch (default: the launch reads the pinned
@@ -268,7 +269,27 @@ extern "C"
   /* ExtractKeypoints.comp (sift_detector.c:1106-1189) as a deterministic, atomic-free pipeline: streaming
    * 26-neighbour test -> per-64-pixel-segment candidate ballots -> exclusive scan -> compact candidate list ->
    * dense refinement -> per-image scan + emit in raster order. found[] receives the un-clamped keypoint count.
-   * scan_done (may be NULL): recorded right after the streaming scan kernel, the one bandwidth-bound launch of the stage. */
+   * scan_done (may be NULL): recorded right after the streaming scan kernel, the one bandwidth-bound launch of the stage.
+   * Contract (all three entry points; tests/test_gpu_extract_launcher.py sweeps it). READ: for every image b < batch the S + 3 Gaussian layers
+   * at gauss + b * img_stride + l * plane_stride texels, rows pitch texels apart; the w x h texels of every layer are finite, whatever lies
+   * in the pitch padding, between layers or between images is never interpreted. Served: sides 1 .. VKSIFT_HIP_MAX_OCTAVE_SIDE (planes below
+   * 3 x 3 have no interior texel and yield nothing), S = 1 .. 13, planes (pitch * h texels) below 2 GiB, pitch >= w, plane_stride >= pitch * h
+   * (layers and images may be laid out in either order and with gaps). fp32 texels: any such pitch and strides, gauss 4-byte aligned. binary16
+   * texels: the scan loads the texel pair (x, x + 1), x even, as one dword, so pitch, plane_stride and img_stride must be EVEN and gauss
+   * 4-byte aligned. Scratch: seg_img_stride == S * h * ceil(w / 64), both for seg_mask (u64) and seg_off (u32) — the chunk counts the emit stage
+   * keeps in seg_off, one word per 256 candidates, always fit: an image has at most 64 candidates per segment —; cand_cap >=
+   * ceil(S * h * ceil(w / 64) / 4096) (the scan's chunk totals live in cand_flag for a while); cand_img_stride >= cand_cap. An image with more
+   * candidates than cand_cap keeps the first cand_cap of them in raster order (scale, y, x) and the rest is dropped without a word: records and
+   * found are then those of the kept candidates alone (S * 2 * ((w - 1) / 2) * ((h - 1) / 2) candidates are the most an octave can have).
+   * WRITTEN, per image: words 0..8 of the first min(found, cap) records of the section, in raster order (scale, y, x) of the candidate texel
+   * they were refined from, orientation = 0; found[b * found_img_stride], un-clamped, also when the image has no candidate at all. The scratch
+   * arrays are left with unspecified contents, every write inside the first seg_img_stride * batch elements of seg_mask / seg_off, the first
+   * cand_cap elements of every image's cand_xy / cand_flag and the batch words of cand_n. Nothing else: not bytes 36..163 of any record, not a
+   * record at or beyond cap, not the counter of another section, not ori_ang / ori_cnt.
+   * hipErrorInvalidValue and NOTHING launched (no mask is cleared either, and no job of a multi-octave call runs): a side of 0 or above
+   * VKSIFT_HIP_MAX_OCTAVE_SIDE, S = 0 or S > 13, pitch < w, plane_stride < pitch * h, a plane of 2 GiB or more, a gauss pointer that is not
+   * 4-byte aligned, an odd pitch, plane_stride or img_stride with binary16 texels, seg_img_stride != S * h * ceil(w / 64), cand_cap below the
+   * chunk count, cand_img_stride < cand_cap. */
   int vksift_hip_extract_keypoints(const vksift_hip_OctaveJob *job, uint32_t batch, vksift_hip_stream s, vksift_hip_event scan_done);
   /* ComputeOrientation.comp (sift_detector.c:1191-1241): main orientation written in place, extra
    * orientations appended in (keypoint, bin) order; found[] updated.
@@ -292,10 +313,13 @@ extern "C"
   /* The same three stages for SEVERAL octaves of one detection in one chain of launches: the reference records the dispatches of
    * all octaves of a stage into one command buffer (sift_detector.c:1106-1259); here the workgroups of all octaves share one flat
    * grid per kernel (csrc/hip/multi.h), so a stage costs 1-8 launches whatever the number of octaves, and the small octaves' work
-   * fills the gaps of the large one's instead of trickling through launches of their own. jobs[0..n_jobs): same S, same texel
-   * type, same batch; results are identical to calling the single-octave form once per job. scan_done as above (all octaves). */
+   * fills the gaps of the large one's instead of trickling through launches of their own. jobs[0..n_jobs): same batch; results are
+   * identical to calling the single-octave form once per job. Any number of jobs: the list is cut into runs of at most 8 (VKSIFT_TUNE_MULTI_MAX)
+   * consecutive jobs of the same S and texel type, one chain of launches per run. scan_done as above (recorded behind the last run's scan). */
   int vksift_hip_extract_keypoints_multi(const vksift_hip_OctaveJob *jobs, uint32_t n_jobs, uint32_t batch, vksift_hip_stream s, vksift_hip_event scan_done);
-  /* the clear of the candidate-ballot masks that vksift_hip_extract_keypoints_multi starts with, on its own (see masks_cleared) */
+  /* the clear of the candidate-ballot masks that vksift_hip_extract_keypoints_multi starts with, on its own (see masks_cleared): zeroes the
+   * seg_img_stride * batch words of every job's seg_mask and nothing else (one fill per run of jobs whose regions follow each other, never
+   * the bytes between regions that do not); at most 16 jobs. A launch only skips its own clear when EVERY job of its run has masks_cleared set. */
   int vksift_hip_clear_segment_masks(const vksift_hip_OctaveJob *jobs, uint32_t n_jobs, uint32_t batch, vksift_hip_stream s);
   /* test entry (tests/test_gpu_descriptor_ranges.py): the in-range forms of sqrtf, '/' and x / 2 pi that the orientation and descriptor kernels
    * use (features.hip: sqrt_inrange, div_inrange, div_2pi_inrange) against the compiler's general forms on n pseudo-random operands

@@ -1,4 +1,4 @@
-"""Direct access to the keypoint-stage launchers of include/vksift_hip.h (orientation, descriptor) for tests: plain module, no fixtures.
+"""Direct access to the keypoint-stage launchers of include/vksift_hip.h (extraction, orientation, descriptor) for tests: plain module, no fixtures.
 
   * OctaveJob / DenseRows / bind(): the ctypes vksift_hip_OctaveJob and vksift_hip_DenseRows (tests/test_abi_hip.py compares every offset
     with the header) and the argtypes of vksift_hip_orientations(_multi) and vksift_hip_descriptors(_multi)(_dense)
@@ -18,7 +18,12 @@
   * expected_orientation() / expected_descriptor(): the arena as the contract of the header says it must look after a launch, computed with
     orc_orientations / orc_descriptor; check(): byte comparison of the whole arena that names the first differing block, image and record
 
-What a launch may change (include/vksift_hip.h): orientation — word 7 of the first min(found, cap) records, 9-word copies appended at found..
+  * scratch=True adds what vksift_hip_extract_keypoints needs: seg_mask, seg_off, cand_xy, cand_flag, cand_n, each a block between guards,
+    poisoned with 0xA5 (a launcher that relies on a cleared mask without clearing it reads set bits everywhere); expected_extraction(): the arena
+    as the extraction contract says it must look, from orc_extract_keypoints (tests/extract_planes.py builds the planes of those cases)
+
+What a launch may change (include/vksift_hip.h): extraction — words 0..8 of the first min(found, cap) records, found, and its scratch blocks
+(seg_mask / seg_off: seg_img_stride * batch elements, cand_xy / cand_flag: cand_cap elements per image, cand_n: batch words); orientation — word 7 of the first min(found, cap) records, 9-word copies appended at found..
 (clipped at cap), found, and its scratch rows of those records; descriptor — bytes 36..163 of the first min(found, cap) records and the dense
 rows / norms / n / posting when asked for. Every other byte of the arena must come back as it went in.
 """
@@ -33,6 +38,9 @@ REC = 164
 HIP_ERROR_INVALID_VALUE = 1
 POISON_BYTE = 0xA5
 GUARD = 1024  # bytes on either side of every block
+POISON_WORD = 0xA5A5A5A5
+TUNE_MULTI_MAX, TUNE_REFINE_PTR, TUNE_SCAN_BAND = 2, 3, 9  # VKSIFT_TUNE_* of the header
+SEG_CHUNK, CAND_CHUNK = 4096, 256  # extrema.hip: segments per scan chunk, candidates per refinement chunk
 FEATURE_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("scale_x", "<f4"), ("scale_y", "<f4"), ("scale_idx", "<u4"), ("octave_idx", "<i4"),
                           ("sigma", "<f4"), ("orientation", "<f4"), ("intensity", "<f4"), ("descriptor", "u1", (128,))])
 assert FEATURE_DTYPE.itemsize == REC
@@ -68,6 +76,11 @@ def bind(L):
         "vksift_hip_orientations_multi": [jp, u32, u32, vp],
         "vksift_hip_descriptors_multi": [jp, u32, u32, vp],
         "vksift_hip_descriptors_multi_dense": [jp, u32, u32, dp, vp],
+        "vksift_hip_extract_keypoints": [jp, u32, vp, vp],
+        "vksift_hip_extract_keypoints_multi": [jp, u32, u32, vp, vp],
+        "vksift_hip_clear_segment_masks": [jp, u32, u32, vp],
+        "vksift_hip_tune": [C.c_int, C.c_int],
+        "vksift_hip_tune_get": [C.c_int],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
@@ -190,19 +203,26 @@ class Block:
 class FeatureArena:
     def __init__(self, planes, recs, found, cap, *, fp16=False, pitch=None, layer_gap=0, img_gap=0, image_major=False, base_offset=0,
                  feat_gap=0, found_img_stride=None, ori_img_stride=None, sec_index=0, front=None, nsec=None, tab=None,
-                 dense=None, post=False, dense_strides=(0, 0, 0, 0), device="cuda"):
+                 dense=None, post=False, dense_strides=(0, 0, 0, 0), device="cuda", scratch=False, cand_cap=None, cand_img_stride=None,
+                 seg_extra=0):
         """planes: (batch, S + 3, h, w) float32 (binary16 values when fp16); recs: per image, the valid records (min(found, cap) of them);
         found: per image, the counter on entry; front: per image, the sec_index counters in front of it (and the counters behind it up to
-        nsec); dense: None or a list of sec_cap (nsec entries): dense rows, norms and n are laid out; post: a posting block as well."""
+        nsec); dense: None or a list of sec_cap (nsec entries): dense rows, norms and n are laid out; post: a posting block as well.
+        scratch: the extraction stage's scratch blocks as well (cand_cap: candidates per image, default the most an octave can have + 64;
+        cand_img_stride >= cand_cap; seg_extra: elements behind the batch's seg_mask / seg_off regions, which a launch must leave alone).
+        found=None (extraction: the counter is an output): the counter holds poison on entry and the section no record."""
         planes = np.asarray(planes, f32)
         self.batch, self.layers, self.h, self.w = planes.shape
+        self.found_is_output = found is None
+        if found is None:
+            found, recs = [POISON_WORD] * self.batch, [np.zeros(0, FEATURE_DTYPE)] * self.batch
         self.S = self.layers - 3
         self.fp16, self.cap, self.sec_index = bool(fp16), int(cap), int(sec_index)
         self.found0 = [int(v) for v in found]
         self.recs = [np.array(r, FEATURE_DTYPE) for r in recs]
         assert len(self.found0) == self.batch and len(self.recs) == self.batch
         for r, f in zip(self.recs, self.found0):
-            assert len(r) == min(f, self.cap), (len(r), f, self.cap)
+            assert self.found_is_output or len(r) == min(f, self.cap), (len(r), f, self.cap)
         self.arena = HP.Arena(device)
         kind = "f16" if fp16 else "f32"
         pitch = int(pitch or self.w)
@@ -253,6 +273,23 @@ class FeatureArena:
         self.tab_block = Block("fixed-point table", self.tab)
 
         self.blocks = [self.feats, self.found, self.ori_ang, self.ori_cnt, self.tab_block]
+        self.scratch = bool(scratch)
+        if scratch:
+            self.nseg = (self.w + 63) // 64
+            self.nsegs = self.S * self.h * self.nseg          # seg_img_stride: the contract fixes it
+            self.nchunks = -(-self.nsegs // SEG_CHUNK)
+            self.seg_extra = int(seg_extra)
+            most = self.S * 2 * ((self.w - 1) // 2) * ((self.h - 1) // 2)   # tests/test_extraction_limits.py
+            self.cand_cap = int(cand_cap) if cand_cap is not None else max(most + 64, self.nchunks)
+            self.cand_img_stride = int(cand_img_stride) if cand_img_stride is not None else self.cand_cap
+            nseg_words = self.nsegs * self.batch + self.seg_extra
+            ncand = (self.batch - 1) * self.cand_img_stride + self.cand_cap
+            self.seg_mask = Block("seg_mask", np.full(nseg_words, 0xA5A5A5A5A5A5A5A5, np.uint64))
+            self.seg_off = Block("seg_off", np.full(nseg_words, POISON_WORD, np.uint32))
+            self.cand_xy = Block("cand_xy", np.full(ncand, POISON_WORD, np.uint32))
+            self.cand_flag = Block("cand_flag", np.full(ncand, POISON_WORD, np.uint32))
+            self.cand_n = Block("cand_n", np.full(self.batch, POISON_WORD, np.uint32))
+            self.blocks += [self.seg_mask, self.seg_off, self.cand_xy, self.cand_flag, self.cand_n]
         self.dense_caps = None
         self.post = bool(post)
         if dense is not None or post:
@@ -286,15 +323,23 @@ class FeatureArena:
         self.host = self.arena.host
 
     # ------------------------------------------------------------------------------------------------------------ the job
-    def job(self, *, max_ori=4, use_vlfeat=0, octave_idx=0):
+    def job(self, *, max_ori=4, use_vlfeat=0, octave_idx=0, seed_sigma=1.6, dog_threshold=None, edge_limit=12.1, scan_reverse=0, masks_cleared=0,
+            cap=None):
+        """dog_threshold: default intensity_threshold 0.04 / S; cap: a section capacity below the arena's (the records behind it are poison)"""
         j = OctaveJob()
         j.gauss = self.layer_refs[0].ptr
         j.fp16 = 1 if self.fp16 else 0
         j.w, j.h, j.pitch = self.w, self.h, self.pitch
         j.plane_stride, j.img_stride = self.plane_stride, self.img_stride
         j.S, j.octave_idx = self.S, octave_idx
-        j.seed_sigma, j.dog_threshold, j.edge_limit = 1.6, 0.04 / self.S, 12.1
-        j.feats, j.feat_img_stride, j.cap = self.feats.ptr, self.feat_img_stride, self.cap
+        j.seed_sigma, j.dog_threshold, j.edge_limit = seed_sigma, (0.04 / self.S if dog_threshold is None else dog_threshold), edge_limit
+        j.feats, j.feat_img_stride, j.cap = self.feats.ptr, self.feat_img_stride, (self.cap if cap is None else cap)
+        assert j.cap <= self.cap
+        j.scan_reverse, j.masks_cleared = scan_reverse, masks_cleared
+        if self.scratch:
+            j.seg_mask, j.seg_off, j.seg_img_stride = self.seg_mask.ptr, self.seg_off.ptr, self.nsegs
+            j.cand_xy, j.cand_flag, j.cand_n = self.cand_xy.ptr, self.cand_flag.ptr, self.cand_n.ptr
+            j.cand_img_stride, j.cand_cap = self.cand_img_stride, self.cand_cap
         j.found, j.found_img_stride = self.found.ptr + 4 * self.sec_index, self.found_img_stride
         j.ori_ang, j.ori_cnt, j.ori_img_stride = self.ori_ang.ptr, self.ori_cnt.ptr, self.ori_img_stride
         j.max_ori, j.use_vlfeat = max_ori, use_vlfeat
@@ -358,6 +403,44 @@ class FeatureArena:
             free[self.ori_cnt.off + 4 * k0:self.ori_cnt.off + 4 * (k0 + n0)] = True
             angles.append(per)
         return exp, free, angles
+
+    def expected_extraction(self, pyramids, *, octave_idx=0, cap=None, keep=None, seg_free=()):
+        """(arena bytes after vksift_hip_extract_keypoints, mask of the scratch bytes the launch may change, per image the un-clamped count).
+        Records and count: orc_extract_keypoints in det math mode on pyramids[b] (Pyramid.from_planes, octave index 0); for another octave_idx
+        the oracle's x, y and sigma are scaled by 2^octave_idx, which is exact in fp32 (tests/test_extract_reference.py compares it with the
+        oracle's own octave -1). Words 0..8 of the first min(found, cap) records over the poison, nothing else of the section.
+        keep: per image, how many of the oracle's keypoints the candidate list holds (cand_cap below the candidate count: the contract keeps
+        the first cand_cap candidates in raster order, so the first `keep` keypoints); seg_free: further (lo, hi) element ranges of the seg
+        blocks that belong to other jobs of the call (their regions inside this arena's seg blocks)."""
+        assert self.scratch
+        cap = self.cap if cap is None else cap
+        exp = self.host.copy()
+        free = np.zeros(len(exp), bool)
+        counts = []
+        for b in range(self.batch):
+            recs, n = pyramids[b].extract_keypoints(0, cap=max(cap, 1) if keep is None else 1 << 20)
+            if keep is not None:
+                n = int(keep[b])
+                recs = recs[:n]
+            recs = recs[:min(n, cap)].copy()
+            assert (recs["octave_idx"] == 0).all() and (recs["orientation"] == 0).all()
+            sf = f32(2.0 ** octave_idx)
+            recs["x"], recs["y"], recs["sigma"] = recs["x"] * sf, recs["y"] * sf, recs["sigma"] * sf
+            recs["octave_idx"] = octave_idx
+            dst = self.records(exp, b, len(recs)).view(np.uint8).reshape(-1, REC)
+            dst[:, :36] = recs.view(np.uint8).reshape(-1, REC)[:, :36]
+            self.words(exp, self.found)[b * self.found_img_stride + self.sec_index] = n
+            counts.append(n)
+            for blk in (self.cand_xy, self.cand_flag):
+                lo = blk.off + 4 * b * self.cand_img_stride
+                free[lo:lo + 4 * self.cand_cap] = True
+        free[self.seg_mask.off:self.seg_mask.off + 8 * self.nsegs * self.batch] = True
+        free[self.seg_off.off:self.seg_off.off + 4 * self.nsegs * self.batch] = True
+        for lo, hi in seg_free:
+            free[self.seg_mask.off + 8 * lo:self.seg_mask.off + 8 * hi] = True
+            free[self.seg_off.off + 4 * lo:self.seg_off.off + 4 * hi] = True
+        free[self.cand_n.off:self.cand_n.off + 4 * self.batch] = True
+        return exp, free, counts
 
     def expected_descriptor(self, pyramids, dense=False, post=False):
         exp = self.host.copy()

@@ -40,9 +40,11 @@ def _round_half_away(v):
 # ------------------------------------------------------------------------------------------------------------------
 # K4 — ExtractKeypoints.comp
 # ------------------------------------------------------------------------------------------------------------------
-def extract_keypoints(dog, S, octave_idx, seed_sigma=1.6, intensity_threshold=0.04, edge_threshold=10.0):
+def extract_keypoints(dog, S, octave_idx, seed_sigma=1.6, intensity_threshold=0.04, edge_threshold=10.0, strict=True):
     """dog: (S+2, H, W) float32 DoG planes of one octave. Returns KP_DTYPE records in raster (s, y, x) order
-    (the reference's order is whatever its atomics produce; the build defines raster order)."""
+    (the reference's order is whatever its atomics produce; the build defines raster order).
+    strict=False: a WRONG 26-neighbour test on purpose — a centre that merely ties with the largest (smallest) value of its cube passes.
+    tests/test_extract_reference.py uses it to prove that its plateau cases tell `>` from `>=`."""
     dog = np.asarray(dog, dtype=f32)
     nl, H, W = dog.shape
     assert nl == S + 2
@@ -55,7 +57,7 @@ def extract_keypoints(dog, S, octave_idx, seed_sigma=1.6, intensity_threshold=0.
     cmax = cubes.max(axis=(3, 4, 5))
     cmin = cubes.min(axis=(3, 4, 5))
     n_eq = (cubes == centre[..., None, None, None]).sum(axis=(3, 4, 5))  # how many cube texels carry the centre's value
-    is_ext = ((centre == cmax) | (centre == cmin)) & (n_eq == 1) & (np.abs(centre) > pre)
+    is_ext = ((centre == cmax) | (centre == cmin)) & ((n_eq == 1) | (not strict)) & (np.abs(centre) > pre)
     ss, yy, xx = np.nonzero(is_ext)
     s = (ss + 1).astype(np.int64)
     y = (yy + 1).astype(np.int64)

@@ -394,7 +394,9 @@ __global__ void __launch_bounds__(256, 4) k_extrema_lean(Multi<ExtremaArgs> m, i
 #pragma unroll
   for (int l = 0; l <= NL; l++)
     rs[l] = __builtin_amdgcn_make_buffer_rsrc((void *)(img + (size_t)l * a.plane_stride * EB), 0, a.pitch * a.h * EB, 0x00020000);
-  // the pitch is a multiple of 64 texels, x is even: the pair (x, x+1) is inside the row or entirely outside
+  // x is even: the pair (x, x+1) starts inside the row or is left out. With an odd pitch (fp32 only) the pair at x = pitch - 1 takes its second
+  // texel from the next row (zero behind the last one): columns at and beyond w only ever reach the tests of columns >= w - 1, which colA / colB
+  // remove. A binary16 pair is one dword: make_extrema_args admits even pitches and strides on a 4-byte-aligned base only
   const unsigned off2 = x < a.pitch ? (unsigned)x * (unsigned)EB : EXT_OOB;
   const int hx = lane == 0 ? x0 - 1 : x0 + 128;
   const unsigned offh = ((lane == 0 || lane == 63) && hx >= 0 && hx < a.pitch) ? (unsigned)hx * (unsigned)EB : EXT_OOB;
@@ -773,10 +775,20 @@ __global__ void __launch_bounds__(256) k_cand_emit(Multi<ExtremaArgs> m)
 
 } // namespace
 
+/* Everything the contract of vksift_hip_extract_keypoints (include/vksift_hip.h) excludes is refused here, before anything is launched. */
 static int make_extrema_args(const vksift_hip_OctaveJob *job, ExtremaArgs *out)
 {
-  if (job->w > VKSIFT_HIP_MAX_OCTAVE_SIDE || job->h > VKSIFT_HIP_MAX_OCTAVE_SIDE || job->S > 14u)
-    return (int)hipErrorInvalidValue; /* candidate coordinates are packed 14 + 14 + 4 bits */
+  if (job->w == 0u || job->h == 0u || job->w > VKSIFT_HIP_MAX_OCTAVE_SIDE || job->h > VKSIFT_HIP_MAX_OCTAVE_SIDE || job->S == 0u || job->S > 13u)
+    return (int)hipErrorInvalidValue; /* candidate coordinates are packed 14 + 14 + 4 bits; k_extrema_lean is instantiated for S = 1 .. 13 */
+  const uint64_t eb = job->fp16 ? 2u : 4u;
+  /* rows inside their pitch, layers that do not overlap (the buffer form of the refinement sees an image's octave as (S + 3) * plane_stride
+   * texels), planes below 2 GiB (the scan addresses a plane with 32-bit byte offsets) */
+  if (job->pitch < job->w || job->plane_stride < (uint64_t)job->pitch * job->h || (uint64_t)job->pitch * job->h * eb >= 0x80000000ull)
+    return (int)hipErrorInvalidValue;
+  /* texels at their natural alignment; the scan loads the binary16 pair (x, x + 1), x even, as ONE dword: every row of every layer of every
+   * image has to start on a 4-byte boundary */
+  if (((uintptr_t)job->gauss & 3u) != 0u || (job->fp16 && ((job->pitch | job->plane_stride | job->img_stride) & 1u) != 0u))
+    return (int)hipErrorInvalidValue;
   ExtremaArgs a;
   a.gauss = job->gauss;
   a.fp16 = (int)job->fp16;
@@ -798,8 +810,9 @@ static int make_extrema_args(const vksift_hip_OctaveJob *job, ExtremaArgs *out)
     a.band = vksift_hip_tune_get(VKSIFT_TUNE_SCAN_BAND);
   a.nsegs = job->S * job->h * (uint32_t)a.nseg;
   a.nchunks = (a.nsegs + SEG_CHUNK - 1u) / SEG_CHUNK;
-  /* the per-image mask regions are contiguous (the clear below is one fill per octave), the chunk bases fit the flag array */
-  if (job->seg_img_stride != a.nsegs || a.nchunks > a.cand_cap)
+  /* the per-image mask regions are contiguous (the clear below is one fill per octave), the chunk bases fit the flag array, the candidate
+   * lists of consecutive images do not overlap */
+  if (job->seg_img_stride != a.nsegs || a.nchunks > a.cand_cap || job->cand_img_stride < job->cand_cap)
     return (int)hipErrorInvalidValue;
   *out = a;
   return 0;
@@ -950,6 +963,14 @@ extern "C" int vksift_hip_extract_keypoints_multi(const vksift_hip_OctaveJob *jo
 {
   if (n_jobs == 0 || batch == 0)
     return 0;
+  /* a job the contract excludes refuses the whole call before the first run is launched */
+  for (uint32_t i = 0; i < n_jobs; i++)
+  {
+    ExtremaArgs a;
+    const int e = make_extrema_args(&jobs[i], &a);
+    if (e)
+      return e;
+  }
   /* runs of octaves that one launch can serve: same S and texel type (always the case inside one detection), at most MULTI_MAX */
   for (uint32_t i0 = 0; i0 < n_jobs;)
   {
