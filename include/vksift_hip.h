@@ -333,8 +333,12 @@ extern "C"
                                          vksift_hip_stream s);
 
   /* ------------------------------------------------------------------ matcher */
-  /* vksift_Feature records (stride 164 B) -> dense 128-byte descriptor rows (16-byte aligned). Replaces the
-   * section packing of sift_memory.c:957-1047 as the matcher's input preparation. */
+  /* vksift_Feature records (stride 164 B) -> dense 128-byte descriptor rows. Replaces the section packing of sift_memory.c:957-1047 as the
+   * matcher's input preparation.
+   * Contract of the record-moving launches (this one, vksift_hip_shifted_norms, _gather_sections, _pack_features, _filter_matches,
+   * _gather_correspondences, _gather_xy; tests/test_gpu_record_launchers.py sweeps it against tests/np_records.py, byte for byte).
+   * READ: bytes 36..163 of the n records at feats (4-byte aligned; a record base need not be 16-byte aligned). WRITTEN: the n * 128 bytes at
+   * desc (4-byte aligned; the matcher wants 16). Nothing else; n == 0 returns 0 and launches nothing. */
   int vksift_hip_gather_descriptors(const uint8_t *feats, uint32_t n, uint8_t *desc, vksift_hip_stream s);
   /* Get2NearestNeighbors.comp (sift_matcher.c:246-279) on dense descriptor matrices in HBM, as an exact int8
    * MFMA contraction with a fused top-2 epilogue. desc_a: na rows, desc_b: nb >= 2 rows (callers pad, quirk Q6).
@@ -349,7 +353,9 @@ extern "C"
                                 size_t scratch_u32, uint8_t *matches, vksift_hip_stream s);
   /* The two halves of vksift_hip_match_2nn_desc, for callers that overlap the pre-pass of A with the arrival of B (the sharded
    * matcher: RCCL all-gather of B): norms[i] = sum over the 128 bytes of (byte - 128)^2; scratch:
-   * scratch_u32 >= vksift_hip_match_scratch_u32(na, nb) - 2*na - nb words (checked like above). */
+   * scratch_u32 >= vksift_hip_match_scratch_u32(na, nb) - 2*na - nb words (checked like above).
+   * vksift_hip_shifted_norms — READ: the n rows of 128 bytes at desc (16-byte aligned: rows are loaded 16 bytes at a time). WRITTEN: norms[0..n),
+   * exact (0 for a row of 128s, 128^3 for a row of zeros). Nothing else; n == 0 returns 0 and launches nothing. */
   int vksift_hip_shifted_norms(const uint8_t *desc, uint32_t n, uint32_t *norms, vksift_hip_stream s);
   int vksift_hip_match_2nn_prenormed(const uint8_t *desc_a, const uint32_t *norm_a, uint32_t na, uint32_t a_index_base, const uint8_t *desc_b,
                                      const uint32_t *norm_b, uint32_t nb, uint32_t *scratch, size_t scratch_u32, uint8_t *matches, vksift_hip_stream s);
@@ -358,7 +364,17 @@ extern "C"
    * src/examples/test_sift_match.cpp:90-107 / src/perf/perf_common.cpp:123-169: keep record i iff d1/d2 < ratio and (with
    * rev) rev[idx_b1].idx_b1 == i and its own d1/d2 < ratio. n_fwd[slot*n_stride + {0,1}] = {N_A, N_B} on the device.
    * out: per slot 16-byte records {idx_a, idx_b, dist_a_b1, dist_a_b2} in increasing idx_a order, out_n[slot] their number.
-   * Strides in bytes. */
+   * Strides in bytes.
+   * READ, per slot: {N_A, N_B} at n_fwd[slot * n_stride + 0..1]; the N_A forward records (20 bytes {idx_a, idx_b1, idx_b2, dist1, dist2}) at
+   * fwd + slot * fwd_slot_stride; with rev, record idx_b1 of the reverse table at rev + slot * rev_slot_stride for every forward record that
+   * passed its own test and has idx_b1 < N_B — never a reverse record at or beyond N_B. The quotient is the correctly rounded fp32 division of
+   * the two stored distances, compared with `<`: a NaN quotient (0 / 0, inf / inf, a NaN distance) or an infinite one (x / 0) drops the record,
+   * 0 / x keeps it, subnormal distances divide like any others. Record i of a table is row i: "rev[idx_b1].idx_b1 == i" compares with the
+   * position, the output carries the stored idx_a. WRITTEN, per slot: the kept records {fwd[i].idx_a, idx_b1, dist1 bits, dist2 bits} in
+   * increasing i at out + slot * out_slot_stride, and out_n[slot]. Nothing else: not a record at or beyond out_n[slot]. Every forward record
+   * may survive: the CALLER provides out_slot_stride >= 16 * N_A for every slot (N_A lives on the device; the launcher cannot check it).
+   * hipErrorInvalidValue, nothing launched: nslots 0; fwd, rev (when given) or out not 4-byte aligned; fwd_slot_stride, rev_slot_stride (with
+   * rev) or out_slot_stride not a multiple of 4. */
   int vksift_hip_filter_matches(const uint8_t *fwd, uint64_t fwd_slot_stride, const uint8_t *rev, uint64_t rev_slot_stride, const uint32_t *n_fwd,
                                 uint32_t n_stride, float ratio, uint32_t nslots, uint8_t *out, uint64_t out_slot_stride, uint32_t *out_n, vksift_hip_stream s);
 
@@ -368,7 +384,18 @@ extern "C"
    * id*buf_stride, counters found_base + id*found_buf_stride; all buffers of one call share the section table): walks up
    * to 16 sections whose stored counts are min(found[o], sec_cap[o]) (or fixed_counts[o] when found_base is NULL), writes
    * the dense descriptor rows in download order to desc + id*desc_stride, their shifted norms to norms + id*norm_stride and
-   * the row total to n_out_dev[id*n_stride]; rows below pad_rows_to are zero-filled (quirk Q6). max_rows bounds the launch.
+   * the row total to n_out_dev[id*n_stride]; rows below pad_rows_to are zero-filled (quirk Q6). max_rows sizes the grid and nothing else:
+   * the kernel strides over the total it reads on the device, so the results do not depend on max_rows (0 and values far above the total
+   * included).
+   * READ, per named buffer id: found_base[id * found_buf_stride + o] for o < nsec (found_buf_stride >= nsec is the caller's to provide: the
+   * launch reads nsec counters whatever the stride; no counter at or beyond nsec, no entry of sec_off / sec_cap / fixed_counts at or beyond
+   * nsec), and bytes 36..163 of the stored records. WRITTEN, per named buffer — addressed by the BUFFER's id, not by the slot that names it —:
+   * max(total, pad_rows_to) rows of 128 bytes at desc + id * desc_stride (rows total .. pad_rows_to - 1 all zero), as many norms at norms +
+   * id * norm_stride (128^3 for a zero row), and n_out_dev[id * n_stride] = total. Nothing else: not the entry of a buffer that is not named,
+   * not a row at or beyond that count, not the padding of a stride. A buffer named twice is written twice with the same bytes. nsec == 0: every
+   * buffer is empty. Alignment: feats_base and buf_stride multiples of 4 (records are loaded as dwords), desc and desc_stride multiples of 16
+   * (rows are stored 16 bytes at a time). hipErrorInvalidValue, nothing launched: nslots 0 or above VKSIFT_HIP_GATHER_SLOTS, nsec above 16, a
+   * misaligned feats_base, buf_stride, desc or desc_stride.
    * match_2nn_async (nslots <= VKSIFT_HIP_MATCH_SLOTS): slot i matches cache entry ids_a[i] against ids_b[i]; it first writes {N_A, N_B} of every slot to
    * n_dev[i*n_slot_stride + 0..1] (read by the kernels, the filter and the host). Strides in bytes for desc/matches and in
    * u32 elements for norms/redo/n. partial_scratch (may be NULL): 5*max_na*VKSIFT_HIP_MATCH_CHUNKS u32 used by the
@@ -382,7 +409,13 @@ extern "C"
    * slot i copies the stored records of buffer buf_ids[i] — sections in order, min(found, capacity) each, the order
    * vksift_downloadFeatures returns (sift_memory.c:957-1047, 1160-1196) — as dense 164-byte records to out + out_rows[i] * 164.
    * The host then reads every buffer of the detection with one device-to-host copy instead of one per section and buffer.
-   * found_post (or NULL): a host-mapped mirror of found_base; the counters of the packed buffers are stored there as well. */
+   * found_post (or NULL): a host-mapped mirror of found_base; the counters of the packed buffers are stored there as well.
+   * READ, per slot: the nsec counters and the stored records of buffer buf_ids[i], as vksift_hip_gather_sections reads them (found_buf_stride
+   * >= nsec is the caller's to provide). WRITTEN: the total_i stored records at out + out_rows[i] * 164 — out_rows in any order, with or
+   * without room between the slots' runs, which stays untouched — and, with found_post, found_post[id * found_buf_stride + k] =
+   * found_base[id * found_buf_stride + k] for all k < found_buf_stride of the NAMED buffers only. Nothing else. max_rows sizes the grid and
+   * nothing else (an understated value, 0 included, gives the same bytes). hipErrorInvalidValue, nothing launched: nslots 0 or above 64, nsec
+   * above 16, found_post with found_buf_stride above 256, feats_base, buf_stride or out not a multiple of 4. */
   int vksift_hip_pack_features(const uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, const uint32_t *out_rows, uint32_t nslots, uint32_t nsec,
                                const uint32_t *sec_off, const uint32_t *sec_cap, const uint32_t *found_base, uint32_t found_buf_stride, uint8_t *out,
                                uint32_t max_rows, uint32_t *found_post, vksift_hip_stream s);
@@ -402,7 +435,11 @@ extern "C"
    * with bit 31 set names a buffer of (word & 0x7fffffff) dense records (uploaded features), any other value entry `word` of layouts[], 33 words each
    * {nsec, off[16], cap[16]}, whose stored counts min(found, cap) are read on the device (found_base + buffer*found_buf_stride) like vksift_hip_gather_sections
    * does. slot_tab / layouts are read by the kernel (device or mapped pinned memory). A record naming a row its buffer does not hold gives a NaN
-   * correspondence. One launch whatever nslots. */
+   * correspondence. One launch whatever nslots.
+   * Sections of a table at or beyond found_buf_stride count as empty and their counters are not read (a found_buf_stride below nsec cuts the
+   * table). A row >= the buffer's total makes THAT side's two floats the quiet NaN 0x7fc00000; the other side is gathered as usual. WRITTEN:
+   * records 0 .. min(filtered_n[i], max_n) - 1 of every slot, nothing else. hipErrorInvalidValue, nothing launched: nslots 0,
+   * filtered_slot_stride not a multiple of 4, corr_slot_stride not a multiple of 16, corr not 16-byte aligned. */
   int vksift_hip_gather_correspondences(const uint8_t *feats_base, uint64_t buf_stride, const uint32_t *found_base, uint32_t found_buf_stride,
                                         const uint32_t *slot_tab, const uint32_t *layouts, const uint8_t *filtered, uint64_t filtered_slot_stride,
                                         const uint32_t *filtered_n, uint32_t max_n, uint32_t nslots, float *corr, uint64_t corr_slot_stride, vksift_hip_stream s);
@@ -435,7 +472,9 @@ extern "C"
 #define VKSIFT_HIP_GUIDE_FUNDAMENTAL 1u
   /* {x, y} of every stored row of both buffers of every slot, in download order: side t (0 = A, 1 = B) of slot i as dense float2 at
    * xy + (2*i + t) * xy_side_stride * 2 floats (8-byte aligned; xy_side_stride >= max_n, rows [0, min(stored, max_n)) are written). slot_tab / layouts, the
-   * section walk and the counters as for vksift_hip_gather_correspondences. One launch whatever nslots. */
+   * section walk and the counters as for vksift_hip_gather_correspondences. One launch whatever nslots. WRITTEN: those rows, nothing else (not
+   * the rows of a side from min(stored, max_n) to xy_side_stride). hipErrorInvalidValue, nothing launched: nslots 0, xy_side_stride < max_n,
+   * xy not 8-byte aligned. */
   int vksift_hip_gather_xy(const uint8_t *feats_base, uint64_t buf_stride, const uint32_t *found_base, uint32_t found_buf_stride, const uint32_t *slot_tab,
                            const uint32_t *layouts, uint32_t max_n, uint32_t nslots, float *xy, uint64_t xy_side_stride, vksift_hip_stream s);
   /* Guided matching of nslots pairs in two or three launches (forward sweep, reverse sweep with cross_check, decision). Slot i: the features of A are the

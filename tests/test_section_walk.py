@@ -2,7 +2,7 @@
 section_row, used by k_gather_sections, k_pack_features, k_gather_corr and k_gather_xy). The header is compiled into a host program
 (tests/native/section_probe.cpp) and compared, for every row of every table, with the numpy statement: the stored rows of a buffer in
 download order are concatenate(arange(off[o], off[o] + min(found[o], cap[o]))) over its sections. (The kernels themselves are compared
-with the numpy restatements by the -m gpu tests.)"""
+with the numpy restatements of tests/np_records.py, which import stored_rows and TABLES from here, by tests/test_gpu_record_launchers.py.)"""
 import os
 import subprocess
 

@@ -188,6 +188,9 @@ extern "C"
   {
     if (nsec > 16 || nslots < 1 || nslots > VKSIFT_HIP_GATHER_SLOTS)
       return (int)hipErrorInvalidValue;
+    /* the kernel loads dwords from the records and stores 16-byte row pieces; the byte stride of the rows is handed to it in dwords */
+    if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || ((uintptr_t)desc & 15u) || (desc_slot_stride & 15u))
+      return (int)hipErrorInvalidValue;
     SectionTable t;
     t.nsec = nsec;
     for (uint32_t o = 0; o < 16; o++)
@@ -220,6 +223,8 @@ extern "C"
   {
     if (nslots < 1 || nslots > 64 || nsec > 16 || (found_post && found_buf_stride > 256u))
       return (int)hipErrorInvalidValue;
+    if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || ((uintptr_t)out & 3u)) /* records are copied dword by dword */
+      return (int)hipErrorInvalidValue;
     SectionTable t;
     t.nsec = nsec;
     for (uint32_t o = 0; o < 16; o++)
@@ -243,6 +248,10 @@ extern "C"
                                 uint32_t n_stride, float ratio, uint32_t nslots, uint8_t *out, uint64_t out_slot_stride, uint32_t *out_n, vksift_hip_stream s)
   {
     if (nslots < 1)
+      return (int)hipErrorInvalidValue;
+    /* records are read and written dword by dword; the byte strides are handed to the kernel in dwords */
+    if (((uintptr_t)fwd & 3u) || (fwd_slot_stride & 3u) || ((uintptr_t)out & 3u) || (out_slot_stride & 3u) ||
+        (rev && (((uintptr_t)rev & 3u) || (rev_slot_stride & 3u))))
       return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_filter_matches, dim3(nslots), dim3(1024), 0, (hipStream_t)s, (const uint32_t *)fwd, fwd_slot_stride / 4, (const uint32_t *)rev,
                        rev_slot_stride / 4, n_fwd, n_stride, ratio, (uint32_t *)out, out_slot_stride / 4, out_n);
