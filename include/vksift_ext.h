@@ -59,7 +59,8 @@ extern "C"
    * three launches, without downloading matches or features. nb_hypotheses (1 .. 65536) four-point samples per pair, drawn from a counter-based generator
    * keyed by (seed, pair, hypothesis); a match is an inlier when the forward transfer error of its A keypoint is below threshold_px (and it is not mapped
    * behind the plane); the model with the most inliers wins, ties to the lowest hypothesis. Deterministic: the same inputs give the same bytes on every run
-   * (tests/np_verify.py restates the estimator bit for bit). No refit on the inliers: the mask is what a caller's own least-squares refinement needs.
+   * (tests/np_verify.py restates the estimator bit for bit). No refit on the inliers in this call (H is the four-point model of the winning sample):
+   * vksift_ext_refineHomography (below) refits it on the GPU; the mask is also what a caller's own least-squares refinement needs.
    * Asynchronous like the matching entry points: queued behind the matching, the pairs' buffers stay busy (vksift_isBufferAvailable), the accessors wait. The
    * SIFT buffers of the pairs must still hold the features that were matched. A new matching invalidates the results like it invalidates the filtered matches.
    * VKSIFT_INVALID_INPUT_ERROR (nothing queued): no filtered matching to verify, nb_hypotheses 0 or above 65536, threshold_px not a positive finite number,
@@ -82,7 +83,8 @@ extern "C"
    * tests/np_verify_f.py. Contract, busy buffers, errors and invalidation as for vksift_ext_verifyHomography. The two models keep separate results and masks:
    * after one vksift_ext_matchFeaturesFiltered both may be run and both read (each accessor is an error until its own model has been verified) — comparing the
    * two inlier counts is how a caller recognises a planar scene or a pure rotation, which this estimator does not handle (seven coplanar points do not
-   * determine F). No rank or orientation test beyond the seven-point construction, no refit on the inliers. */
+   * determine F). No rank or orientation test beyond the seven-point construction, no refit on the inliers (vksift_ext_refineHomography serves the
+   * homography only). */
   typedef struct
   {
     float F[9];            /* row-major, pixel coordinates: (xb, yb, 1) F (xa, ya, 1)^T = 0; largest |entry| in [1, 2) */
@@ -98,6 +100,35 @@ extern "C"
   /* Time (ms) of the last verification of either model (its three launches + the result posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getVerifyTime(vksift_Instance instance);
 
+  /* ---- GPU-side refit of the verified homographies on their inliers -----------------------------------------------------
+   * The step between verification and guided matching: for every pair of the last vksift_ext_verifyHomography, nb_rounds (1 .. 8) locally optimised rounds in
+   * one launch, without downloading matches, features or masks. A round fits a least-squares homography to the matches the current mask marks (conditioned
+   * coordinates, a linear start, two Gauss-Newton steps on the forward transfer error, the error the inlier test measures) and scores all matches of the pair
+   * again under the published model with the test of vksift_ext_matchFeaturesGuided at threshold_px; round r starts from the mask of round r - 1, the first from
+   * the RANSAC mask. A round is accepted iff it can be computed and has at least as many inliers as the result kept so far; the first one that is not ends the
+   * loop, so nb_inliers never falls below the verification's. rounds == 0: H, nb_inliers and the mask are the verification's (the mask byte for byte). A pair whose verification is not
+   * valid: everything zero. Deterministic: every sum has a fixed order, tests/np_refine.py restates the estimator bit for bit.
+   * Contract of guided matching: asynchronous, queued behind the matching and the verification, the pairs' buffers stay busy, the accessors wait; results of
+   * its own (filtered matches, both verified models, their masks and the guided matches stay readable and unchanged), replaced by the next run, invalidated
+   * by a new matching, plain or filtered, and by a new vksift_ext_verifyHomography (not by vksift_ext_verifyFundamental).
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, earlier refined results untouched): no verified homography, nb_rounds 0 or above 8, threshold_px not a
+   * positive finite number or one whose square (threshold_px 2^-13)^2 2^26, the fp32 value the test compares with, is zero or not finite (below about 1e-19,
+   * above about 1e19), pair out of range, out == NULL. */
+  typedef struct
+  {
+    float H[9];            /* row-major, pixel coordinates of A -> B, H[8] == 1 */
+    uint32_t nb_matches;   /* filtered matches of the pair */
+    uint32_t nb_inliers;   /* >= the verification's */
+    uint32_t rounds;       /* the last accepted round; 0: the verification's model, count and mask */
+    uint32_t valid;        /* 0: the pair's verification is not valid; everything else is zero then */
+  } vksift_ext_RefinedHomography; /* 52 bytes */
+  VKSIFT_EXPORT void vksift_ext_refineHomography(vksift_Instance instance, uint32_t nb_rounds, float threshold_px);
+  VKSIFT_EXPORT void vksift_ext_getRefinedHomography(vksift_Instance instance, uint32_t pair, vksift_ext_RefinedHomography *out);
+  /* vksift_ext_getFilteredMatchesNumber(pair) bytes, in the order of the filtered matches: 1 = admissible under the refined model */
+  VKSIFT_EXPORT void vksift_ext_downloadRefinedInlierMask(vksift_Instance instance, uint32_t pair, uint8_t *mask);
+  /* Time (ms) of the last refinement (its launch + the result posting), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getRefineTime(vksift_Instance instance);
+
   /* ---- GPU-side guided matching -----------------------------------------------------------------------------------------
    * The step after a model is known: every feature of A is matched again against only those features of B that agree with the pair's model, so the ratio test
    * compares the best candidate with the second best among the geometrically possible ones, not with a look-alike elsewhere in the image (repeated structure),
@@ -112,7 +143,9 @@ extern "C"
    * The test runs on the PUBLISHED model, so that a caller can reproduce it from public outputs and a supplied model means the same thing; the inlier masks
    * come from the scaled internal model: it is NOT promised that a filtered match is admissible exactly when its mask byte is 1, to the last bit.
    * models == NULL: the model of that kind verified for every pair of the last vksift_ext_matchFeaturesFiltered (an error if it has not been); otherwise 9
-   * floats per pair, the caller's own (e.g. refitted) models in the same convention, all finite; they are copied before the call returns.
+   * floats per pair, the caller's own models in the same convention, all finite; they are copied before the call returns. The refined homographies of
+   * vksift_ext_refineHomography are handed over this way (the H[9] of vksift_ext_getRefinedHomography, pair by pair): their refined masks are exactly the
+   * admissibility of the filtered matches under them.
    * Contract of the verification entry points: asynchronous, queued behind the matching and the verification, the pairs' buffers stay busy, the accessors wait;
    * results of its own (filtered matches, both models and their masks stay readable), replaced by the next run, invalidated by a new matching, plain or filtered.
    * Precondition, as for the verification: the buffers of the pairs still hold the features that were matched. A detection or an upload into one of them after

@@ -449,7 +449,8 @@ extern "C"
    * correspondences with d > 0 and forward transfer error below threshold_px; the best is the largest count, ties to the lowest j. results + 52*i: float H[9]
    * (row-major, pixel coordinates, H[8] == 1), uint32 nb_matches (= n), nb_inliers, best_hypothesis, valid; masks + i*mask_slot_stride: n bytes, 1 = inlier of
    * H by the same test (their sum is nb_inliers). n < 4, a best count below 4, h22 == 0 or a non-finite entry: valid = 0 and H, nb_inliers, best_hypothesis and
-   * the mask are zero. No refinement on the inliers (a least-squares refit cannot be pinned bit for bit; the mask is what a caller's own refit needs).
+   * the mask are zero. No refinement on the inliers here: H is the four-point model of the winning sample. vksift_hip_refit_homography (below) refits it
+   * on its inliers, bit for bit reproducible because every sum has a fixed order; the mask is also what a caller's own refit needs.
    * tests/np_verify.py restates every output bit for bit. scratch: scratch_u32 >= vksift_hip_ransac_scratch_u32(nslots, nb_hypotheses) words, need not be
    * initialised. hipErrorInvalidValue, nothing launched: nb_hypotheses 0 or above 65536, threshold_px not positive and finite, too little scratch, strides below
    * max_n records. */
@@ -462,10 +463,35 @@ extern "C"
    * the best is the largest count, ties to the lowest model id. results + 56*i: float F[9] (row-major, pixel coordinates, (xb, yb, 1) F (xa, ya, 1)^T = 0, largest
    * |entry| in [1, 2)), uint32 nb_matches (= n), nb_inliers, best_hypothesis, best_root, valid; masks as above. n < 7, a best count below 8 (the seven sample
    * points fit their own model) or a non-finite model: valid = 0 and everything else zero. No rank or orientation test beyond the seven-point construction, no
-   * handling of the planar degeneracy, no refit. tests/np_verify_f.py restates every output bit for bit. */
+   * handling of the planar degeneracy, no refit on the inliers (vksift_hip_refit_homography serves the homography only; its reductions and conditioning
+   * are model-free). tests/np_verify_f.py restates every output bit for bit. */
   int vksift_hip_ransac_fundamental(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
                                     uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
                                     uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
+
+  /* ------------------------------------------------------------------ refit on the inliers (refine.hip; no counterpart in the reference) */
+  /* Locally optimised refit of nslots verified homographies in one launch, one workgroup per slot, all rounds inside it. Slot i: n = min(n_dev[i*n_stride],
+   * max_n) correspondences at corr + i*corr_slot_stride (as for vksift_hip_ransac_homography), the 13-word RANSAC record at start_results + 52*i and its mask
+   * at start_masks + i*mask_slot_stride. A round takes the correspondences whose mask byte is 1 (fewer than four: it fails) through: conditioning of each side
+   * (centroid; the power of two that brings the largest |deviation| into [1, 2), none: it fails); the inhomogeneous least-squares homography with h8 = 1 in
+   * conditioned coordinates; two Gauss-Newton steps on the forward transfer error (u/d - xb)^2 + (v/d - yb)^2; each 8x8 normal system by Gauss-Jordan with the
+   * pivoting of the seven-point solve (a pivot that is zero, subnormal or not finite, or a solution that is not finite: it fails); back to pixels and divided
+   * by h22 (h22 == 0 or an entry not finite: it fails); all n correspondences re-scored under the PUBLISHED model in pixel coordinates with the test and the
+   * threshold of vksift_hip_match_guided (t2 = (threshold_px 2^-13)^2 2^26): the refined mask is exactly what guided matching would admit for that model, and
+   * reproducible from public outputs. Round r starts from the mask of round r - 1 (the first from start_masks); it is accepted iff it did not fail and counts
+   * at least as many inliers as the result kept so far (the RANSAC record at first); the first round that is not accepted ends the loop. results + 52*i: float
+   * H[9] (row-major, pixels, H[8] == 1), uint32 nb_matches (= n), nb_inliers, rounds (the last accepted round; 0: H and nb_inliers are the start record's and
+   * the mask is the start mask byte for byte, so its ones sum to nb_inliers only if the start record was consistent with its mask; after an accepted round
+   * the bytes are 0 / 1 and sum to nb_inliers), valid; nb_inliers is never below the start record's. A start record with valid == 0: the whole record and the mask are zero.
+   * Every sum over correspondences has one order (thread t of 256 adds its elements t, t + 256, ... in increasing index, a fixed butterfly over the 64 lanes,
+   * the four waves in order), everything is correctly rounded fp32 add / sub / mul / div, coordinates up to VKSIFT_HIP_MAX_OCTAVE_SIDE: the same inputs give the
+   * same bytes on every run, tests/np_refine.py restates every output bit for bit. WRITTEN: the nslots records and bytes 0 .. n-1 of every slot of masks_out,
+   * nothing else (start_results, start_masks and corr are only read; no scratch). hipErrorInvalidValue, nothing launched: nslots 0, nb_rounds 0 or above 8,
+   * threshold_px not positive and finite or t2 zero or not finite, corr not 16-byte aligned or corr_slot_stride not a multiple of 16, results or start_results not 4-byte aligned,
+   * strides below max_n records (nslots > 1), masks_out overlapping start_masks. */
+  int vksift_hip_refit_homography(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
+                                  const uint8_t *start_results /* the 13-word RANSAC records */, const uint8_t *start_masks, uint64_t mask_slot_stride,
+                                  uint32_t nb_rounds, float threshold_px, uint8_t *results, uint8_t *masks_out, vksift_hip_stream s);
 
   /* ------------------------------------------------------------------ guided matching (guided.hip; no counterpart in the reference) */
 #define VKSIFT_HIP_GUIDE_HOMOGRAPHY 0u

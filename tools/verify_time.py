@@ -1,9 +1,12 @@
 """Time vksift_ext_verifyHomography (--model h, the default) or vksift_ext_verifyFundamental (--model f) on the benchmark workload: B frames
 640x480, consecutive pairs, matchFeaturesFiltered(0.8, True), then the verification (nb_hypotheses, 2.5) timed by HIP events
 (vksift_ext_getVerifyTime): warm-ups, then repetitions; median and spread. The only other RANSAC on the box is the numpy restatement
-(tests/np_verify.py, tests/np_verify_f.py), timed on a few of the same pairs for scale.
+(tests/np_verify.py, tests/np_verify_f.py), timed on a few of the same pairs for scale. With --refine ROUNDS (model h) every verification is
+followed by vksift_ext_refineHomography(ROUNDS, 2.5), timed by its own events (vksift_ext_getRefineTime). In every mode the host wall time
+from the verify call to the first record read back (the verified one, or the refined one with --refine) is reported as
+wall_ms_to_first_record_median: each iteration reads record 0, a host wait, before it asks for the event times, which that wait does not change.
 
-usage: verify_time.py [B=512] [nb_hypotheses=1024] [repeats=20] [warmups=3] [--model h|f] [--json out.json] [--once]
+usage: verify_time.py [B=512] [nb_hypotheses=1024] [repeats=20] [warmups=3] [--model h|f] [--refine ROUNDS] [--json out.json] [--once]
        (--once: one verification, for a kernel trace)"""
 import json
 import os
@@ -18,14 +21,18 @@ import numpy as np
 from vulkansift_amd import api
 
 MODEL = "h"
+REFINE = 0
 argv = []
 for i, arg in enumerate(sys.argv[1:], 1):
-    if sys.argv[i - 1] in ("--model", "--json"):
+    if sys.argv[i - 1] in ("--model", "--json", "--refine"):
         if sys.argv[i - 1] == "--model":
             MODEL = arg
+        if sys.argv[i - 1] == "--refine":
+            REFINE = int(arg)
         continue
     argv.append(arg)
 assert MODEL in ("h", "f"), "--model h|f"
+assert REFINE == 0 or MODEL == "h", "--refine needs --model h"
 args = [a for a in argv if not a.startswith("--")]
 B = int(args[0]) if len(args) > 0 else 512
 NH = int(args[1]) if len(args) > 1 else 1024
@@ -44,16 +51,34 @@ with api.Instance(cfg, batch_capacity=B) as inst:
     inst.detectFeaturesBatch(list(frames), 0)
     inst.matchFeaturesFiltered(a, b, 0.8, True)
     n_f = np.array([len(inst.downloadFilteredMatches(k)) for k in range(B)])
-    ms = []
+    ms, rms, wall = [], [], []
     for it in range(1 if once else WARM + REP):
+        t0 = time.perf_counter()
         (inst.verifyFundamental if MODEL == "f" else inst.verifyHomography)(NH, 2.5, it)
+        if REFINE:
+            inst.refineHomography(REFINE, 2.5)
+            inst.getRefinedHomography(0)
+        else:
+            (inst.getFundamental if MODEL == "f" else inst.getHomography)(0)
+        t1 = time.perf_counter()
         t = inst.getVerifyTime()
         if once or it >= WARM:
             ms.append(t)
+            wall.append((t1 - t0) * 1e3)
+            if REFINE:
+                rms.append(inst.getRefineTime())
     valid = sum(int((inst.getFundamental if MODEL == "f" else inst.getHomography)(k)["valid"]) for k in range(B))
     out = {"model": MODEL, "pairs": B, "nb_hypotheses": NH, "threshold_px": 2.5, "repeats": len(ms), "verify_ms_median": float(np.median(ms)), "verify_ms_min": float(np.min(ms)),
            "verify_ms_max": float(np.max(ms)), "filtered_matches_per_pair_mean": float(n_f.mean()), "filtered_matches_per_pair_min": int(n_f.min()),
-           "filtered_matches_per_pair_max": int(n_f.max()), "valid_pairs": valid, "match_ms": float(inst.getMatchTime())}
+           "filtered_matches_per_pair_max": int(n_f.max()), "valid_pairs": valid, "match_ms": float(inst.getMatchTime()),
+           "wall_ms_to_first_record_median": float(np.median(wall))}
+    if REFINE:
+        ref = [inst.getRefinedHomography(k) for k in range(B)]
+        hom = [inst.getHomography(k) for k in range(B)]
+        out.update({"refine_rounds": REFINE, "refine_ms_median": float(np.median(rms)), "refine_ms_min": float(np.min(rms)), "refine_ms_max": float(np.max(rms)),
+                    "pairs_with_an_accepted_round": sum(int(r["rounds"]) > 0 for r in ref),
+                    "inliers_per_pair_mean_ransac": float(np.mean([int(h["nb_inliers"]) for h in hom])),
+                    "inliers_per_pair_mean_refined": float(np.mean([int(r["nb_inliers"]) for r in ref]))})
     if not once:
         if MODEL == "f":
             import np_verify_f as V

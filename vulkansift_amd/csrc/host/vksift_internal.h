@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_guided.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -230,6 +230,12 @@ struct vksift_Instance_T
   uint32_t *d_fres, *h_fres;   /* 14 words (vksift_ext_Fundamental) per slot */
   uint32_t verify_f_slots_used;
   bool verify_timing_valid;
+  /* refit of the verified homographies on their inliers (vksift_ext_refineHomography, vksift_refine.c): results of its own, read from d_corr, d_vres and
+   * d_vmask; allocated on first use */
+  uint8_t *d_rmask;            /* per slot: vmask_slot_stride bytes */
+  uint32_t *d_rres, *h_rres;   /* 13 words (vksift_ext_RefinedHomography) per slot; the host copy is posted like h_vres */
+  uint32_t refine_slots_used;  /* pairs with refined results: zero again after a new matching or a new vksift_ext_verifyHomography */
+  bool refine_timing_valid;
   /* guided matching (vksift_ext_matchFeaturesGuided, vksift_guided.c): results of its own beside the filtered matches and the models; allocated on first use */
   float *d_gxy;             /* per slot: 2 * gxy_side_stride float2, the coordinates of A's rows, then of B's */
   uint64_t gxy_side_stride; /* float2 elements */
@@ -293,6 +299,7 @@ struct vksift_Instance_T
   vksift_hip_event ev_v[2];
   vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created, like ev_g, by the first guided matching) */
   vksift_hip_event ev_g[2];
+  vksift_hip_event ev_r[2]; /* profiling: the refinement interval (created by the first refinement) */
   bool desc_start_valid, input_free_valid, staging_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];
   uint64_t det_seq, det_done; /* last detection issued / highest one known to have completed */
