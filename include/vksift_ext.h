@@ -83,8 +83,8 @@ extern "C"
    * tests/np_verify_f.py. Contract, busy buffers, errors and invalidation as for vksift_ext_verifyHomography. The two models keep separate results and masks:
    * after one vksift_ext_matchFeaturesFiltered both may be run and both read (each accessor is an error until its own model has been verified) — comparing the
    * two inlier counts is how a caller recognises a planar scene or a pure rotation, which this estimator does not handle (seven coplanar points do not
-   * determine F). No rank or orientation test beyond the seven-point construction, no refit on the inliers (vksift_ext_refineHomography serves the
-   * homography only). */
+   * determine F). No rank or orientation test beyond the seven-point construction, no refit on the inliers in this call (F is the seven-point model of the
+   * winning sample): vksift_ext_refineFundamental (below) refits it on the GPU. */
   typedef struct
   {
     float F[9];            /* row-major, pixel coordinates: (xb, yb, 1) F (xa, ya, 1)^T = 0; largest |entry| in [1, 2) */
@@ -126,8 +126,33 @@ extern "C"
   VKSIFT_EXPORT void vksift_ext_getRefinedHomography(vksift_Instance instance, uint32_t pair, vksift_ext_RefinedHomography *out);
   /* vksift_ext_getFilteredMatchesNumber(pair) bytes, in the order of the filtered matches: 1 = admissible under the refined model */
   VKSIFT_EXPORT void vksift_ext_downloadRefinedInlierMask(vksift_Instance instance, uint32_t pair, uint8_t *mask);
-  /* Time (ms) of the last refinement (its launch + the result posting), HIP events; needs profiling on. -1 when there is none. */
+  /* Time (ms) of the last vksift_ext_refineHomography (its launch + the result posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getRefineTime(vksift_Instance instance);
+  /* The same for the fundamental matrices of the last vksift_ext_verifyFundamental: nb_rounds (1 .. 8) locally optimised rounds per pair in one launch. A
+   * round needs at least eight marked matches and fits a least-squares F to them: conditioned coordinates, the entry of F that is largest in the model the
+   * round starts from fixed to 1, a linear start, two steps reweighted by the Sampson denominator (so that the error minimised is the one the inlier test
+   * measures), two Newton steps on the determinant for rank 2, published in the convention of vksift_ext_Fundamental; then all matches of the pair are scored
+   * again under the published model with the test of vksift_ext_matchFeaturesGuided at threshold_px. Round r starts from the mask and the model of round r - 1,
+   * the first from the verification's. Acceptance, rounds == 0, invalid pairs, determinism (tests/np_refine_f.py restates the estimator bit for bit), contract
+   * and errors as for vksift_ext_refineHomography, with "no verified fundamental matrix" in place of "no verified homography". The two models keep separate
+   * refined results: these are invalidated by a new matching, plain or filtered, and by a new vksift_ext_verifyFundamental, not by
+   * vksift_ext_verifyHomography or vksift_ext_refineHomography, and vksift_ext_refineFundamental leaves the refined homographies alone.
+   * Not attempted: no chirality test; no handling of the planar degeneracy (coplanar inliers give a near-singular system, and whatever model comes out is
+   * subject to the acceptance rule like any other). */
+  typedef struct
+  {
+    float F[9];            /* row-major, pixel coordinates: (xb, yb, 1) F (xa, ya, 1)^T = 0; largest |entry| in [1, 2) */
+    uint32_t nb_matches;   /* filtered matches of the pair */
+    uint32_t nb_inliers;   /* >= the verification's */
+    uint32_t rounds;       /* the last accepted round; 0: the verification's model, count and mask */
+    uint32_t valid;        /* 0: the pair's verification is not valid; everything else is zero then */
+  } vksift_ext_RefinedFundamental; /* 52 bytes */
+  VKSIFT_EXPORT void vksift_ext_refineFundamental(vksift_Instance instance, uint32_t nb_rounds, float threshold_px);
+  VKSIFT_EXPORT void vksift_ext_getRefinedFundamental(vksift_Instance instance, uint32_t pair, vksift_ext_RefinedFundamental *out);
+  /* vksift_ext_getFilteredMatchesNumber(pair) bytes, in the order of the filtered matches: 1 = admissible under the refined model */
+  VKSIFT_EXPORT void vksift_ext_downloadRefinedFundamentalInlierMask(vksift_Instance instance, uint32_t pair, uint8_t *mask);
+  /* Time (ms) of the last vksift_ext_refineFundamental (vksift_ext_getRefineTime reports the homography's only). -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getRefineFundamentalTime(vksift_Instance instance);
 
   /* ---- GPU-side guided matching -----------------------------------------------------------------------------------------
    * The step after a model is known: every feature of A is matched again against only those features of B that agree with the pair's model, so the ratio test
@@ -145,7 +170,8 @@ extern "C"
    * models == NULL: the model of that kind verified for every pair of the last vksift_ext_matchFeaturesFiltered (an error if it has not been); otherwise 9
    * floats per pair, the caller's own models in the same convention, all finite; they are copied before the call returns. The refined homographies of
    * vksift_ext_refineHomography are handed over this way (the H[9] of vksift_ext_getRefinedHomography, pair by pair): their refined masks are exactly the
-   * admissibility of the filtered matches under them.
+   * admissibility of the filtered matches under them. The refined fundamental matrices of vksift_ext_refineFundamental likewise (the F[9] of
+   * vksift_ext_getRefinedFundamental with VKSIFT_EXT_GUIDE_FUNDAMENTAL), with the same guarantee.
    * Contract of the verification entry points: asynchronous, queued behind the matching and the verification, the pairs' buffers stay busy, the accessors wait;
    * results of its own (filtered matches, both models and their masks stay readable), replaced by the next run, invalidated by a new matching, plain or filtered.
    * Precondition, as for the verification: the buffers of the pairs still hold the features that were matched. A detection or an upload into one of them after

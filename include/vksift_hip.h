@@ -463,13 +463,13 @@ extern "C"
    * the best is the largest count, ties to the lowest model id. results + 56*i: float F[9] (row-major, pixel coordinates, (xb, yb, 1) F (xa, ya, 1)^T = 0, largest
    * |entry| in [1, 2)), uint32 nb_matches (= n), nb_inliers, best_hypothesis, best_root, valid; masks as above. n < 7, a best count below 8 (the seven sample
    * points fit their own model) or a non-finite model: valid = 0 and everything else zero. No rank or orientation test beyond the seven-point construction, no
-   * handling of the planar degeneracy, no refit on the inliers (vksift_hip_refit_homography serves the homography only; its reductions and conditioning
-   * are model-free). tests/np_verify_f.py restates every output bit for bit. */
+   * handling of the planar degeneracy, no refit on the inliers here: F is the seven-point model of the winning sample, vksift_hip_refit_fundamental
+   * (below) refits it on its inliers. tests/np_verify_f.py restates every output bit for bit. */
   int vksift_hip_ransac_fundamental(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
                                     uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
                                     uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
 
-  /* ------------------------------------------------------------------ refit on the inliers (refine.hip; no counterpart in the reference) */
+  /* ------------------------------------------------------------------ refit on the inliers (refine.hip, refine_f.hip; no counterpart in the reference) */
   /* Locally optimised refit of nslots verified homographies in one launch, one workgroup per slot, all rounds inside it. Slot i: n = min(n_dev[i*n_stride],
    * max_n) correspondences at corr + i*corr_slot_stride (as for vksift_hip_ransac_homography), the 13-word RANSAC record at start_results + 52*i and its mask
    * at start_masks + i*mask_slot_stride. A round takes the correspondences whose mask byte is 1 (fewer than four: it fails) through: conditioning of each side
@@ -492,6 +492,19 @@ extern "C"
   int vksift_hip_refit_homography(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
                                   const uint8_t *start_results /* the 13-word RANSAC records */, const uint8_t *start_masks, uint64_t mask_slot_stride,
                                   uint32_t nb_rounds, float threshold_px, uint8_t *results, uint8_t *masks_out, vksift_hip_stream s);
+  /* The same for nslots verified fundamental matrices (refine_f.hip, kernel k_refit_f): the same arguments, chain, acceptance rule, mask handling, WRITTEN
+   * set and refusals; the start record is the 14-word record of vksift_hip_ransac_fundamental at start_results + 56*i, the result at results + 52*i is float
+   * F[9] (row-major, pixels, largest |entry| in [1, 2)), uint32 nb_matches, nb_inliers, rounds, valid. A round takes the correspondences whose mask byte is 1
+   * (fewer than eight: it fails) through: the same conditioning; the gauge f_j = 1 at the largest |entry| (bit pattern, ties to the lowest index) of the model
+   * the round starts from (the kept one: the RANSAC F at first) brought into the conditioned frame; the linear least-squares F over the monomials (X x, X y, X,
+   * Y x, Y y, Y, x, y, 1); two steps reweighted by 1 / g, g the Sampson denominator of the step before (zero, subnormal or not finite on a marked
+   * correspondence: it fails); each step one accumulation of 44 sums and one 8x8 Gauss-Jordan as above; two Newton steps on the determinant along the cofactor
+   * matrix (rank 2 without an SVD; |C|^2 zero, subnormal or not finite: it fails); back to pixels and times the power of two that brings the largest |entry|
+   * into [1, 2) (none: it fails); the re-scoring under the published model with the Sampson test and threshold of vksift_hip_match_guided. No chirality test,
+   * no handling of the planar degeneracy. tests/np_refine_f.py restates every output bit for bit. */
+  int vksift_hip_refit_fundamental(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
+                                   const uint8_t *start_results /* the 14-word RANSAC records */, const uint8_t *start_masks, uint64_t mask_slot_stride,
+                                   uint32_t nb_rounds, float threshold_px, uint8_t *results, uint8_t *masks_out, vksift_hip_stream s);
 
   /* ------------------------------------------------------------------ guided matching (guided.hip; no counterpart in the reference) */
 #define VKSIFT_HIP_GUIDE_HOMOGRAPHY 0u

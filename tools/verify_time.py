@@ -1,8 +1,9 @@
 """Time vksift_ext_verifyHomography (--model h, the default) or vksift_ext_verifyFundamental (--model f) on the benchmark workload: B frames
 640x480, consecutive pairs, matchFeaturesFiltered(0.8, True), then the verification (nb_hypotheses, 2.5) timed by HIP events
 (vksift_ext_getVerifyTime): warm-ups, then repetitions; median and spread. The only other RANSAC on the box is the numpy restatement
-(tests/np_verify.py, tests/np_verify_f.py), timed on a few of the same pairs for scale. With --refine ROUNDS (model h) every verification is
-followed by vksift_ext_refineHomography(ROUNDS, 2.5), timed by its own events (vksift_ext_getRefineTime). In every mode the host wall time
+(tests/np_verify.py, tests/np_verify_f.py), timed on a few of the same pairs for scale. With --refine ROUNDS every verification is
+followed by vksift_ext_refineHomography(ROUNDS, 2.5) or, with --model f, vksift_ext_refineFundamental(ROUNDS, 2.5), timed by its own events
+(vksift_ext_getRefineTime, vksift_ext_getRefineFundamentalTime). In every mode the host wall time
 from the verify call to the first record read back (the verified one, or the refined one with --refine) is reported as
 wall_ms_to_first_record_median: each iteration reads record 0, a host wait, before it asks for the event times, which that wait does not change.
 
@@ -32,7 +33,6 @@ for i, arg in enumerate(sys.argv[1:], 1):
         continue
     argv.append(arg)
 assert MODEL in ("h", "f"), "--model h|f"
-assert REFINE == 0 or MODEL == "h", "--refine needs --model h"
 args = [a for a in argv if not a.startswith("--")]
 B = int(args[0]) if len(args) > 0 else 512
 NH = int(args[1]) if len(args) > 1 else 1024
@@ -47,6 +47,9 @@ cfg = api.default_config(sift_buffer_count=B, gpu_device_index=0, input_image_ma
 a = list(range(B))
 b = [(i + 1) % B for i in a]
 with api.Instance(cfg, batch_capacity=B) as inst:
+    verify, get = (inst.verifyFundamental, inst.getFundamental) if MODEL == "f" else (inst.verifyHomography, inst.getHomography)
+    refine, get_refined, refine_time = ((inst.refineFundamental, inst.getRefinedFundamental, inst.getRefineFundamentalTime) if MODEL == "f" else
+                                        (inst.refineHomography, inst.getRefinedHomography, inst.getRefineTime))
     inst.setProfiling(True)
     inst.detectFeaturesBatch(list(frames), 0)
     inst.matchFeaturesFiltered(a, b, 0.8, True)
@@ -54,27 +57,27 @@ with api.Instance(cfg, batch_capacity=B) as inst:
     ms, rms, wall = [], [], []
     for it in range(1 if once else WARM + REP):
         t0 = time.perf_counter()
-        (inst.verifyFundamental if MODEL == "f" else inst.verifyHomography)(NH, 2.5, it)
+        verify(NH, 2.5, it)
         if REFINE:
-            inst.refineHomography(REFINE, 2.5)
-            inst.getRefinedHomography(0)
+            refine(REFINE, 2.5)
+            get_refined(0)
         else:
-            (inst.getFundamental if MODEL == "f" else inst.getHomography)(0)
+            get(0)
         t1 = time.perf_counter()
         t = inst.getVerifyTime()
         if once or it >= WARM:
             ms.append(t)
             wall.append((t1 - t0) * 1e3)
             if REFINE:
-                rms.append(inst.getRefineTime())
-    valid = sum(int((inst.getFundamental if MODEL == "f" else inst.getHomography)(k)["valid"]) for k in range(B))
+                rms.append(refine_time())
+    valid = sum(int(get(k)["valid"]) for k in range(B))
     out = {"model": MODEL, "pairs": B, "nb_hypotheses": NH, "threshold_px": 2.5, "repeats": len(ms), "verify_ms_median": float(np.median(ms)), "verify_ms_min": float(np.min(ms)),
            "verify_ms_max": float(np.max(ms)), "filtered_matches_per_pair_mean": float(n_f.mean()), "filtered_matches_per_pair_min": int(n_f.min()),
            "filtered_matches_per_pair_max": int(n_f.max()), "valid_pairs": valid, "match_ms": float(inst.getMatchTime()),
            "wall_ms_to_first_record_median": float(np.median(wall))}
     if REFINE:
-        ref = [inst.getRefinedHomography(k) for k in range(B)]
-        hom = [inst.getHomography(k) for k in range(B)]
+        ref = [get_refined(k) for k in range(B)]
+        hom = [get(k) for k in range(B)]
         out.update({"refine_rounds": REFINE, "refine_ms_median": float(np.median(rms)), "refine_ms_min": float(np.min(rms)), "refine_ms_max": float(np.max(rms)),
                     "pairs_with_an_accepted_round": sum(int(r["rounds"]) > 0 for r in ref),
                     "inliers_per_pair_mean_ransac": float(np.mean([int(h["nb_inliers"]) for h in hom])),

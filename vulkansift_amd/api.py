@@ -75,7 +75,8 @@ FILTERED_MATCH_DTYPE = np.dtype([("idx_a", "<u4"), ("idx_b", "<u4"), ("dist_a_b1
 HOMOGRAPHY_DTYPE = np.dtype([("H", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("best_hypothesis", "<u4"), ("valid", "<u4")])
 FUNDAMENTAL_DTYPE = np.dtype([("F", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("best_hypothesis", "<u4"), ("best_root", "<u4"), ("valid", "<u4")])
 REFINED_HOMOGRAPHY_DTYPE = np.dtype([("H", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("rounds", "<u4"), ("valid", "<u4")])
-assert FUNDAMENTAL_DTYPE.itemsize == 56 and REFINED_HOMOGRAPHY_DTYPE.itemsize == 52
+REFINED_FUNDAMENTAL_DTYPE = np.dtype([("F", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("rounds", "<u4"), ("valid", "<u4")])
+assert FUNDAMENTAL_DTYPE.itemsize == 56 and REFINED_HOMOGRAPHY_DTYPE.itemsize == 52 and REFINED_FUNDAMENTAL_DTYPE.itemsize == 52
 assert FEATURE_DTYPE.itemsize == 164 and MATCH_DTYPE.itemsize == 20 and FILTERED_MATCH_DTYPE.itemsize == 16 and HOMOGRAPHY_DTYPE.itemsize == 52
 
 _lib = None
@@ -150,6 +151,14 @@ def lib():
     L.vksift_ext_downloadRefinedInlierMask.restype = None
     L.vksift_ext_getRefineTime.argtypes = [inst]
     L.vksift_ext_getRefineTime.restype = C.c_float
+    L.vksift_ext_refineFundamental.argtypes = [inst, u32, C.c_float]
+    L.vksift_ext_refineFundamental.restype = None
+    L.vksift_ext_getRefinedFundamental.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_getRefinedFundamental.restype = None
+    L.vksift_ext_downloadRefinedFundamentalInlierMask.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_downloadRefinedFundamentalInlierMask.restype = None
+    L.vksift_ext_getRefineFundamentalTime.argtypes = [inst]
+    L.vksift_ext_getRefineFundamentalTime.restype = C.c_float
     L.vksift_ext_matchFeaturesGuided.argtypes = [inst, u32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_bool]
     L.vksift_ext_matchFeaturesGuided.restype = None
     L.vksift_ext_getGuidedMatchesNumber.argtypes = [inst, u32]
@@ -220,6 +229,8 @@ def lib():
     L.vksift_hip_refit_homography.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, u32, u32, u32, C.c_void_p, C.c_void_p, C.c_uint64, u32, C.c_float, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
     L.vksift_hip_refit_homography.restype = C.c_int
+    L.vksift_hip_refit_fundamental.argtypes = L.vksift_hip_refit_homography.argtypes
+    L.vksift_hip_refit_fundamental.restype = C.c_int
     L.vksift_hip_guided_scratch_u32.argtypes = [u32, u32]
     L.vksift_hip_guided_scratch_u32.restype = C.c_size_t
     L.vksift_hip_match_guided.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, C.c_uint64, C.c_void_p, u32, u32,
@@ -344,32 +355,41 @@ def ransac_fundamental(corr, n, nb_hypotheses, threshold_px, seed, scratch_u32=N
     return _ransac(lib().vksift_hip_ransac_fundamental, 14, FUNDAMENTAL_DTYPE, corr, n, nb_hypotheses, threshold_px, seed, scratch_u32)
 
 
-def refit_homography(d_corr, d_n, start_results, start_masks, nb_rounds, threshold_px, overrides=None, buffers=None):
-    """vksift_hip_refit_homography on torch tensors on the GPU: d_corr float32 [nslots, max_n, 4], d_n int32 [nslots], start_results int32 [nslots, 13] (the
-    RANSAC records as words), start_masks uint8 [nslots, max_n]. Returns (error code, records as a REFINED_HOMOGRAPHY_DTYPE array, masks uint8 [nslots, max_n]);
-    on an error nothing was launched and the other two are None. overrides: arguments to hand over instead {"corr", "corr_stride", "mask_stride", "nslots",
-    "masks_out"} (pointers as integers, strides in bytes); buffers: a dict that receives the tensors the launch writes ("results", "masks"), poisoned
-    beforehand (the refusal tests)."""
+def _refit(entry, start_words, dtype, d_corr, d_n, start_results, start_masks, nb_rounds, threshold_px, overrides, buffers):
     import torch
 
     assert d_corr.is_cuda and d_corr.dtype == torch.float32 and d_corr.is_contiguous() and d_corr.dim() == 3 and d_corr.shape[2] == 4
     nslots, max_n = int(d_corr.shape[0]), int(d_corr.shape[1])
     rows = max(max_n, 1)
     assert d_n.is_cuda and d_n.dtype == torch.int32 and d_n.is_contiguous() and d_n.numel() == nslots
-    assert start_results.is_cuda and start_results.dtype == torch.int32 and start_results.is_contiguous() and start_results.shape == (nslots, 13)
+    assert start_results.is_cuda and start_results.dtype == torch.int32 and start_results.is_contiguous() and start_results.shape == (nslots, start_words)
     assert start_masks.is_cuda and start_masks.dtype == torch.uint8 and start_masks.is_contiguous() and start_masks.shape == (nslots, rows)
     results = torch.full((nslots, 13), -1, dtype=torch.int32, device=d_corr.device)
     masks = torch.full((nslots, rows), 0x55, dtype=torch.uint8, device=d_corr.device)
     if buffers is not None:
         buffers.update(results=results, masks=masks)
-    a = {"corr": d_corr.data_ptr(), "corr_stride": max_n * 16, "mask_stride": rows, "nslots": nslots, "masks_out": masks.data_ptr()}
+    a = {"corr": d_corr.data_ptr(), "corr_stride": max_n * 16, "mask_stride": rows, "nslots": nslots, "masks_out": masks.data_ptr(), "max_n": max_n}
     a.update(overrides or {})
-    err = lib().vksift_hip_refit_homography(a["corr"], a["corr_stride"], d_n.data_ptr(), 1, max_n, a["nslots"], start_results.data_ptr(), start_masks.data_ptr(),
-                                            a["mask_stride"], nb_rounds, threshold_px, results.data_ptr(), a["masks_out"], torch.cuda.current_stream().cuda_stream)
+    err = entry(a["corr"], a["corr_stride"], d_n.data_ptr(), 1, a["max_n"], a["nslots"], start_results.data_ptr(), start_masks.data_ptr(),
+                a["mask_stride"], nb_rounds, threshold_px, results.data_ptr(), a["masks_out"], torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     if err:
         return err, None, None
-    return 0, results.cpu().numpy().view(np.uint8).reshape(nslots, 52).copy().view(REFINED_HOMOGRAPHY_DTYPE).reshape(nslots), masks.cpu().numpy()
+    return 0, results.cpu().numpy().view(np.uint8).reshape(nslots, 52).copy().view(dtype).reshape(nslots), masks.cpu().numpy()
+
+
+def refit_homography(d_corr, d_n, start_results, start_masks, nb_rounds, threshold_px, overrides=None, buffers=None):
+    """vksift_hip_refit_homography on torch tensors on the GPU: d_corr float32 [nslots, max_n, 4], d_n int32 [nslots], start_results int32 [nslots, 13] (the
+    RANSAC records as words), start_masks uint8 [nslots, max_n]. Returns (error code, records as a REFINED_HOMOGRAPHY_DTYPE array, masks uint8 [nslots, max_n]);
+    on an error nothing was launched and the other two are None. overrides: arguments to hand over instead {"corr", "corr_stride", "mask_stride", "nslots",
+    "masks_out", "max_n"} (pointers as integers, strides in bytes); buffers: a dict that receives the tensors the launch writes ("results", "masks"), poisoned
+    beforehand (the refusal tests)."""
+    return _refit(lib().vksift_hip_refit_homography, 13, REFINED_HOMOGRAPHY_DTYPE, d_corr, d_n, start_results, start_masks, nb_rounds, threshold_px, overrides, buffers)
+
+
+def refit_fundamental(d_corr, d_n, start_results, start_masks, nb_rounds, threshold_px, overrides=None, buffers=None):
+    """vksift_hip_refit_fundamental, as refit_homography; start_results int32 [nslots, 14], the records are a REFINED_FUNDAMENTAL_DTYPE array"""
+    return _refit(lib().vksift_hip_refit_fundamental, 14, REFINED_FUNDAMENTAL_DTYPE, d_corr, d_n, start_results, start_masks, nb_rounds, threshold_px, overrides, buffers)
 
 
 GUIDE_HOMOGRAPHY, GUIDE_FUNDAMENTAL = 0, 1
@@ -584,6 +604,30 @@ class Instance:
 
     def getRefineTime(self):
         return lib().vksift_ext_getRefineTime(self._h)
+
+    def refineFundamental(self, nb_rounds=3, threshold_px=2.5):
+        """locally optimised refit of every pair's verified fundamental matrix on its inliers, on the GPU (vksift_ext_refineFundamental); its results are
+        kept beside the verification's and the refined homographies, not in their place."""
+        lib().vksift_ext_refineFundamental(self._h, nb_rounds, threshold_px)
+        _check_pending()
+
+    def getRefinedFundamental(self, pair=0):
+        """structured scalar (REFINED_FUNDAMENTAL_DTYPE): F 3x3 float32 (pixels, largest |entry| in [1, 2)), nb_matches, nb_inliers, rounds, valid"""
+        out = np.zeros(1, REFINED_FUNDAMENTAL_DTYPE)
+        lib().vksift_ext_getRefinedFundamental(self._h, pair, out.ctypes.data)
+        _check_pending()
+        return out[0]
+
+    def downloadRefinedFundamentalInlierMask(self, pair=0):
+        n = lib().vksift_ext_getFilteredMatchesNumber(self._h, pair)
+        _check_pending()
+        out = np.zeros(n, np.uint8)
+        lib().vksift_ext_downloadRefinedFundamentalInlierMask(self._h, pair, out.ctypes.data)
+        _check_pending()
+        return out.astype(bool)
+
+    def getRefineFundamentalTime(self):
+        return lib().vksift_ext_getRefineFundamentalTime(self._h)
 
     def matchFeaturesGuided(self, model, models=None, threshold_px=2.5, ratio=0.8, max_distance=float("inf"), cross_check=True):
         """guided matching of every pair of the last matchFeaturesFiltered call under its verified model of kind `model` (GUIDE_HOMOGRAPHY /

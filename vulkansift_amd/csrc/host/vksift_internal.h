@@ -236,6 +236,11 @@ struct vksift_Instance_T
   uint32_t *d_rres, *h_rres;   /* 13 words (vksift_ext_RefinedHomography) per slot; the host copy is posted like h_vres */
   uint32_t refine_slots_used;  /* pairs with refined results: zero again after a new matching or a new vksift_ext_verifyHomography */
   bool refine_timing_valid;
+  /* the same for the verified fundamental matrices (vksift_ext_refineFundamental): read from d_corr, d_fres and d_fmask */
+  uint8_t *d_rfmask;             /* per slot: vmask_slot_stride bytes */
+  uint32_t *d_rfres, *h_rfres;   /* 13 words (vksift_ext_RefinedFundamental) per slot */
+  uint32_t refine_f_slots_used;  /* zero again after a new matching or a new vksift_ext_verifyFundamental */
+  bool refine_f_timing_valid;
   /* guided matching (vksift_ext_matchFeaturesGuided, vksift_guided.c): results of its own beside the filtered matches and the models; allocated on first use */
   float *d_gxy;             /* per slot: 2 * gxy_side_stride float2, the coordinates of A's rows, then of B's */
   uint64_t gxy_side_stride; /* float2 elements */
@@ -300,6 +305,7 @@ struct vksift_Instance_T
   vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created, like ev_g, by the first guided matching) */
   vksift_hip_event ev_g[2];
   vksift_hip_event ev_r[2]; /* profiling: the refinement interval (created by the first refinement) */
+  vksift_hip_event ev_rf[2]; /* the same for the fundamental matrices' refinement */
   bool desc_start_valid, input_free_valid, staging_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];
   uint64_t det_seq, det_done; /* last detection issued / highest one known to have completed */

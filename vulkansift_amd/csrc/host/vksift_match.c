@@ -224,6 +224,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
   inst->verify_f_slots_used = 0;
   inst->guided_slots_used = 0;
   inst->refine_slots_used = 0;
+  inst->refine_f_slots_used = 0;
   inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
   if (filter)
   {

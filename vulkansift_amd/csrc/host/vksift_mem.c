@@ -110,6 +110,7 @@ static const Block blocks[] = {
     LAZY(d_corr, MEM_DEVICE), LAZY(d_vmask, MEM_DEVICE), LAZY(d_vres, MEM_DEVICE), LAZY(d_vscratch, MEM_DEVICE), LAZY(h_vres, MEM_PINNED), LAZY(h_vtab, MEM_PINNED),
     LAZY(d_fmask, MEM_DEVICE), LAZY(d_fres, MEM_DEVICE), LAZY(h_fres, MEM_PINNED),
     LAZY(d_rmask, MEM_DEVICE), LAZY(d_rres, MEM_DEVICE), LAZY(h_rres, MEM_PINNED),
+    LAZY(d_rfmask, MEM_DEVICE), LAZY(d_rfres, MEM_DEVICE), LAZY(h_rfres, MEM_PINNED),
     LAZY(d_gxy, MEM_DEVICE), LAZY(d_gkeys, MEM_DEVICE), LAZY(d_guided, MEM_DEVICE), LAZY(d_guided_n, MEM_DEVICE), LAZY(h_guided_n, MEM_PINNED), LAZY(h_gtab, MEM_PINNED),
     LAZY(d_dl, MEM_DEVICE), LAZY(h_dl, MEM_PINNED), LAZY(dl_row, MEM_HEAP), LAZY(h_post[0], MEM_PINNED), LAZY(h_post[1], MEM_PINNED),
 };
@@ -210,6 +211,7 @@ static const Handle handles[] = {
     EVENTS(prof[0].ev_scan, 2, sizeof(ProfSet), false), EVENTS(ev_m, 2, sizeof(vksift_hip_event), false),
     EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_v, 2, sizeof(vksift_hip_event), true),
     EVENTS(ev_gtab, 1, 0, true), EVENTS(ev_g, 2, sizeof(vksift_hip_event), true), EVENTS(ev_r, 2, sizeof(vksift_hip_event), true),
+    EVENTS(ev_rf, 2, sizeof(vksift_hip_event), true),
 };
 #define N_HANDLES (sizeof(handles) / sizeof(handles[0]))
 

@@ -25,7 +25,7 @@ typedef struct
   uint8_t **d_mask;
   uint32_t **d_res, **h_res;
   uint32_t *slots_used;
-  uint32_t *derived_slots_used; /* results computed from this model's records and masks, no longer theirs once it is verified again (NULL: none) */
+  uint32_t *derived_slots_used; /* results computed from this model's records and masks, no longer theirs once it is verified again */
 } VerifyModel;
 
 static VerifyModel model_h(vksift_Instance inst)
@@ -37,7 +37,7 @@ static VerifyModel model_h(vksift_Instance inst)
 static VerifyModel model_f(vksift_Instance inst)
 {
   return (VerifyModel){"vksift_ext_verifyFundamental", "vksift_ext_getFundamental", "vksift_ext_downloadFundamentalInlierMask", vksift_hip_ransac_fundamental,
-                       VERIFY_F_RES_WORDS, &inst->d_fmask, &inst->d_fres, &inst->h_fres, &inst->verify_f_slots_used, NULL};
+                       VERIFY_F_RES_WORDS, &inst->d_fmask, &inst->d_fres, &inst->h_fres, &inst->verify_f_slots_used, &inst->refine_f_slots_used};
 }
 
 /* correspondences, reduction keys and pair tables of batch_cap pairs, and the masks and results of the model asked for; allocated by the
@@ -94,8 +94,7 @@ static void verify(vksift_Instance inst, const VerifyModel *m, uint32_t nb_hypot
             "correspondence gather");
   HIP_CHECK(vksift_hip_event_record(inst->ev_vtab, inst->stream), "event record");
   inst->vtab_pending = true;
-  if (m->derived_slots_used)
-    *m->derived_slots_used = 0; /* the launch below replaces the records and masks the refinement (vksift_refine.c) was computed from */
+  *m->derived_slots_used = 0; /* the launch below replaces the records and masks the refinement (vksift_refine.c) was computed from */
   HIP_CHECK(m->ransac(inst->d_corr, inst->filtered_slot_stride, inst->d_filtered_n, 1, inst->cfg.max_nb_sift_per_buffer, count, nb_hypotheses, threshold_px, seed,
                       (uint8_t *)*m->d_res, *m->d_mask, inst->vmask_slot_stride, inst->d_vscratch, inst->vscratch_u32, inst->stream),
             "RANSAC");
