@@ -175,8 +175,15 @@ def test_layouts_and_batches(L, oracle, batch, fp16):
 
 @pytest.mark.parametrize("fp16", [False, True], ids=["fp32", "fp16"])
 def test_pointer_refinement(L, oracle, fp16):
-    """VKSIFT_TUNE_REFINE_PTR = 1: k_refine_flags / k_cand_emit in the form that octaves beyond 2 GiB take, on a subset of the cases above"""
+    """VKSIFT_TUNE_REFINE_PTR = 1: k_refine_flags / k_cand_emit in the form that octaves beyond 2 GiB take, on a subset of the cases above;
+    the edge test on both sides of its limit; the steps of moves_case leave the same arena bytes as the buffer form does"""
+    _, buf_bytes, _ = run(L, oracle, EP.moves_case(fp16), "buf moves")
     with tuned(L, HF.TUNE_REFINE_PTR, 1):
+        _, ptr_bytes, _ = run(L, oracle, EP.moves_case(fp16), "ptr moves")
+        assert np.array_equal(ptr_bytes, buf_bytes)
+        if not fp16:
+            assert run(L, oracle, EP.edge_case(False), "ptr edge 10")[2] == [1]
+            assert run(L, oracle, EP.edge_case(True), "ptr edge inf")[2] == [3]
         for S in (1, 3, 13):
             run(L, oracle, EP.scales_case(S, fp16), f"ptr S={S}", octave_idx=S % 3 - 1, pitch=116, img_gap=10)
         run(L, oracle, EP.columns_case(130, fp16), "ptr columns", pitch=130)

@@ -13,15 +13,19 @@
 //   k_refine_flags   : one thread per CANDIDATE (dense waves: no lane idles while a neighbour refines) -> accept flag
 //   k_cand_emit      : second level of the scan of the accept counts, accepted candidates recompute their record and store it
 //                      at their rank (clamped to the section capacity); the un-clamped count goes to found[]
-// The arithmetic of refine_texel() is kept operation-for-operation identical to
-// oracle/sift_oracle.c:extract_one (fp32, no contraction) so results are bit-exact.
+// The refinement is a LOADER, which fetches the 19 DoG values around a position (PtrLoader: 64-bit pointers, any octave size;
+// BufLoader: one buffer resource per image's octave), and refine_core(), everything else, written once. The arithmetic of
+// refine_core() is kept operation-for-operation identical to oracle/sift_oracle.c:extract_one (fp32, no contraction) so
+// results are bit-exact.
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include <vector>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "../detmath.h"
 #include "multi.h"
+#include "records.h"
 #include "vksift_hip.h"
 
 namespace
@@ -33,12 +37,12 @@ struct DogView
   int w, h, pitch;
   size_t plane; // texels between layers
   int S;
-  int fp16;     // binary16 texels (VKSIFT_PYRAMID_PRECISION_FLOAT16): widened exactly; the DoG image of such a pyramid is binary16 too
 };
 
 // imageLoad of the DoG image with robust out-of-bounds behaviour on the layer axis (quirk Q1): layer S+2 reads 0.
-// F16 (binary16 texels) is a template parameter of everything that refines: a run-time flag inside this function was
-// miscompiled (fp32 results of images >= 1 of a batch changed with unrelated edits of the callers).
+// F16 (binary16 texels: widened exactly; the DoG image of such a pyramid is binary16 too) is a template parameter of everything
+// that refines: a run-time flag inside this function was miscompiled (fp32 results of images >= 1 of a batch changed with
+// unrelated edits of the callers).
 template <bool F16>
 __device__ __forceinline__ float ld(const DogView &d, int s, int x, int y)
 {
@@ -61,106 +65,66 @@ struct KpRecord
   float sigma, orientation, intensity;
 };
 
-// Refinement + acceptance tests (ExtractKeypoints.comp:121-224).
-template <bool F16>
-__device__ bool refine_texel(const DogView &d, int x, int y, int s, float dog_threshold, float edge_limit, float seed_sigma, int octave_idx, KpRecord *kp)
+// The 19 DoG values a refinement step reads around (x, y, s): the centre, its neighbours along each axis, and the four
+// diagonal neighbours in each of the planes (s, x), (s, y) and (x, y). Named by the axis and sign of their offsets.
+struct Dog19
 {
-  const int W = d.w, H = d.h, S = d.S;
-  float oX = 0.f, oY = 0.f, oS = 0.f, gX = 0.f, gY = 0.f, gS = 0.f;
-  int rx = x, ry = y, rs = s;
-  for (int step = 0; step < 5; step++)
+  float c;
+  float sp, sm, xp, xm, yp, ym;
+  float sp_xp, sp_xm, sm_xp, sm_xm;
+  float sp_yp, sp_ym, sm_yp, sm_ym;
+  float xp_yp, xp_ym, xm_yp, xm_ym;
+};
+
+// 19 imageLoads through 64-bit pointers: serves octaves of any size. Each costs two 64-bit multiply-adds and an exec-mask branch
+// for the layer test (300 of the 700 VALU instructions of a step are addressing), so the step loop stays rolled.
+template <bool F16>
+struct PtrLoader
+{
+  static constexpr int UNROLL_STEPS = 1;
+  const DogView &d;
+  __device__ __forceinline__ Dog19 operator()(int x, int y, int s) const
   {
-    float vc = ld<F16>(d, rs, rx, ry);
-    float sp = ld<F16>(d, rs + 1, rx, ry), sm = ld<F16>(d, rs - 1, rx, ry);
-    float xp = ld<F16>(d, rs, rx + 1, ry), xm = ld<F16>(d, rs, rx - 1, ry);
-    float yp = ld<F16>(d, rs, rx, ry + 1), ym = ld<F16>(d, rs, rx, ry - 1);
-    gS = 0.5f * (sp - sm);
-    gX = 0.5f * (xp - xm);
-    gY = 0.5f * (yp - ym);
-    float h11 = sp + sm - 2.f * vc;
-    float h22 = xp + xm - 2.f * vc;
-    float h33 = yp + ym - 2.f * vc;
-    float h12 = 0.25f * (ld<F16>(d, rs + 1, rx + 1, ry) - ld<F16>(d, rs + 1, rx - 1, ry) - ld<F16>(d, rs - 1, rx + 1, ry) + ld<F16>(d, rs - 1, rx - 1, ry));
-    float h13 = 0.25f * (ld<F16>(d, rs + 1, rx, ry + 1) - ld<F16>(d, rs + 1, rx, ry - 1) - ld<F16>(d, rs - 1, rx, ry + 1) + ld<F16>(d, rs - 1, rx, ry - 1));
-    float h23 = 0.25f * (ld<F16>(d, rs, rx + 1, ry + 1) - ld<F16>(d, rs, rx + 1, ry - 1) - ld<F16>(d, rs, rx - 1, ry + 1) + ld<F16>(d, rs, rx - 1, ry - 1));
-
-    float det = h11 * ((h22 * h33) - (h23 * h23)) - h12 * ((h12 * h33) - (h13 * h23)) + h13 * ((h12 * h23) - (h13 * h22));
-    if (det == 0.0f)
-      return false;
-    float i11 = ((h22 * h33) - (h23 * h23)) / det;
-    float i12 = -1.f * ((h12 * h33) - (h13 * h23)) / det;
-    float i13 = ((h12 * h23) - (h13 * h22)) / det;
-    float i22 = ((h11 * h33) - (h13 * h13)) / det;
-    float i23 = -1.f * ((h11 * h23) - (h13 * h12)) / det;
-    float i33 = ((h11 * h22) - (h12 * h12)) / det;
-    oS = -i11 * gS - i12 * gX - i13 * gY;
-    oX = -i12 * gS - i22 * gX - i23 * gY;
-    oY = -i13 * gS - i23 * gX - i33 * gY;
-
-    if (fabsf(oX) < 0.6f && fabsf(oY) < 0.6f && fabsf(oS) < 0.6f)
-      break;
-    else if (step < 4)
-    {
-      rx += ((oX >= 0.6f && rx < (W - 2)) ? 1 : 0) + ((oX <= -0.6f && rx > 1) ? -1 : 0);
-      ry += ((oY >= 0.6f && ry < (H - 2)) ? 1 : 0) + ((oY <= -0.6f && ry > 1) ? -1 : 0);
-      rs += ((oS >= 0.6f && rs < (S + 1)) ? 1 : 0) + ((oS <= -0.6f && rs > 1) ? -1 : 0);
-    }
+    Dog19 v;
+    v.c = ld<F16>(d, s, x, y);
+    v.sp = ld<F16>(d, s + 1, x, y), v.sm = ld<F16>(d, s - 1, x, y);
+    v.xp = ld<F16>(d, s, x + 1, y), v.xm = ld<F16>(d, s, x - 1, y);
+    v.yp = ld<F16>(d, s, x, y + 1), v.ym = ld<F16>(d, s, x, y - 1);
+    v.sp_xp = ld<F16>(d, s + 1, x + 1, y), v.sp_xm = ld<F16>(d, s + 1, x - 1, y), v.sm_xp = ld<F16>(d, s - 1, x + 1, y), v.sm_xm = ld<F16>(d, s - 1, x - 1, y);
+    v.sp_yp = ld<F16>(d, s + 1, x, y + 1), v.sp_ym = ld<F16>(d, s + 1, x, y - 1), v.sm_yp = ld<F16>(d, s - 1, x, y + 1), v.sm_ym = ld<F16>(d, s - 1, x, y - 1);
+    v.xp_yp = ld<F16>(d, s, x + 1, y + 1), v.xp_ym = ld<F16>(d, s, x + 1, y - 1), v.xm_yp = ld<F16>(d, s, x - 1, y + 1), v.xm_ym = ld<F16>(d, s, x - 1, y - 1);
+    return v;
   }
-  float sx = (float)rx + oX, sy = (float)ry + oY, ss = (float)rs + oS;
-  float vc = ld<F16>(d, rs, rx, ry);
-  float nv = vc + 0.5f * (gX * oX + gY * oY + gS * oS);
-  if (!(fabsf(nv) > dog_threshold && fabsf(oX) < 1.5f && fabsf(oY) < 1.5f && fabsf(oS) < 1.5f && sx >= 0 && sx < (float)W && sy >= 0 && sy < (float)H &&
-        ss >= 0 && ss <= (float)(S + 1)))
-    return false;
-  float e11 = ld<F16>(d, rs, rx + 1, ry) + ld<F16>(d, rs, rx - 1, ry) - 2.f * vc;
-  float e22 = ld<F16>(d, rs, rx, ry + 1) + ld<F16>(d, rs, rx, ry - 1) - 2.f * vc;
-  float e12 = 0.25f * (ld<F16>(d, rs, rx + 1, ry + 1) - ld<F16>(d, rs, rx + 1, ry - 1) - ld<F16>(d, rs, rx - 1, ry + 1) + ld<F16>(d, rs, rx - 1, ry - 1));
-  float edgeness = ((e11 + e22) * (e11 + e22)) / ((e11 * e22) - (e12 * e12));
-  if (!((edgeness < edge_limit) && (edgeness >= 0)))
-    return false;
+};
 
-  float scale_factor = octave_idx >= 0 ? dm_pow2i(octave_idx) : 1.f / dm_pow2i(-octave_idx);
-  kp->scale_x = sx;
-  kp->scale_y = sy;
-  kp->scale_idx = (uint32_t)roundf(ss);
-  kp->octave_idx = octave_idx;
-  kp->sigma = seed_sigma * dm_exp2f(ss / (float)S) * scale_factor;
-  kp->orientation = 0.f;
-  kp->intensity = nv;
-  kp->x = sx * scale_factor;
-  kp->y = sy * scale_factor;
-  return true;
-}
-
-// The same refinement through a BUFFER RESOURCE over the octave of one image (32-bit byte offsets, the rows as scalar offsets, the
-// columns as immediates): refine_texel() above addresses every DoG value with two 64-bit multiply-adds and an exec-mask branch for
-// the layer test — 300 of its 700 VALU instructions and 38 branches per iteration are addressing. Here an iteration loads the 28
-// GAUSSIAN texels of its neighbourhood once (5 + 9 + 9 + 5 over the four layers; the pointer form loads 38 + 38) and forms the 19
-// DoG values from them with the same subtraction; the acceptance tests reuse the last iteration's values (the position does not
-// move after the last loads). Same operations on the same operands in the same order: bit-identical. The caller guarantees
-// (S + 3) * plane * texel bytes < 2^31.
+// The same values through a BUFFER RESOURCE over the octave of one image (32-bit byte offsets, the rows as scalar offsets, the
+// columns as immediates): no address arithmetic and no branch per value. A step loads the 28 GAUSSIAN texels of its neighbourhood
+// once (5 + 9 + 9 + 5 over the four layers; the pointer form loads 38 + 38) and forms the 19 DoG values from them with the same
+// subtraction: bit-identical. The step loop is unrolled. The caller guarantees (S + 3) * plane * texel bytes < 2^31.
 template <bool F16>
-__device__ bool refine_texel_buf(const __amdgpu_buffer_rsrc_t rsrc, int W, int H, int pitch, unsigned plane, int S, int x, int y, int s, float dog_threshold,
-                                 float edge_limit, float seed_sigma, int octave_idx, KpRecord *kp)
+struct BufLoader
 {
-  constexpr unsigned EB = F16 ? 2u : 4u;
-  const int pitch_b = pitch * (int)EB;
-  const unsigned plane_b = plane * EB;
-  auto tex = [&](unsigned base, int row_off) -> float {
+  static constexpr int UNROLL_STEPS = 5;
+  static constexpr unsigned EB = F16 ? 2u : 4u;
+  const __amdgpu_buffer_rsrc_t rsrc;
+  const int pitch;
+  const unsigned plane;
+  const int S;
+  __device__ __forceinline__ float tex(unsigned base, int row_off) const
+  {
     if (F16)
       return (float)__builtin_bit_cast(_Float16, (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, base, row_off, 0));
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, base, row_off, 0));
-  };
-  auto dog = [&](float hi, float lo) -> float { return F16 ? (float)(_Float16)(hi - lo) : hi - lo; };
-  float oX = 0.f, oY = 0.f, oS = 0.f, gX = 0.f, gY = 0.f, gS = 0.f;
-  float vc = 0.f, xp = 0.f, xm = 0.f, yp = 0.f, ym = 0.f, h23 = 0.f;
-  int rx = x, ry = y, rs = s;
-  for (int step = 0; step < 5; step++)
+  }
+  static __device__ __forceinline__ float dog(float hi, float lo) { return F16 ? (float)(_Float16)(hi - lo) : hi - lo; }
+  __device__ __forceinline__ Dog19 operator()(int x, int y, int s) const
   {
-    // byte offset of Gaussian texel (rx - 1, ry - 1) of layer rs; rs >= 1, rx >= 1, ry >= 1 always
-    const unsigned b0 = ((unsigned)rs * plane + (unsigned)(ry - 1) * (unsigned)pitch + (unsigned)(rx - 1)) * EB;
-    const unsigned bm = b0 - plane_b, b1 = b0 + plane_b, b2 = b1 + plane_b; // layers rs - 1, rs + 1, rs + 2 (past the last layer: reads 0)
-    // Gaussian texels: the full 3x3 of layers rs and rs + 1, the cross of layers rs - 1 and rs + 2
+    const int pitch_b = pitch * (int)EB;
+    const unsigned plane_b = plane * EB;
+    // byte offset of Gaussian texel (x - 1, y - 1) of layer s; s >= 1, x >= 1, y >= 1 always
+    const unsigned b0 = ((unsigned)s * plane + (unsigned)(y - 1) * (unsigned)pitch + (unsigned)(x - 1)) * EB;
+    const unsigned bm = b0 - plane_b, b1 = b0 + plane_b, b2 = b1 + plane_b; // layers s - 1, s + 1, s + 2 (past the last layer: reads 0)
+    // Gaussian texels: the full 3x3 of layers s and s + 1, the cross of layers s - 1 and s + 2
     float g0[3][3], g1[3][3];
 #pragma unroll
     for (int j = 0; j < 3; j++)
@@ -172,29 +136,49 @@ __device__ bool refine_texel_buf(const __amdgpu_buffer_rsrc_t rsrc, int W, int H
       }
     const float gm_c = tex(bm + EB, pitch_b), gm_xm = tex(bm, pitch_b), gm_xp = tex(bm + 2u * EB, pitch_b), gm_ym = tex(bm + EB, 0), gm_yp = tex(bm + EB, 2 * pitch_b);
     const float g2_c = tex(b2 + EB, pitch_b), g2_xm = tex(b2, pitch_b), g2_xp = tex(b2 + 2u * EB, pitch_b), g2_ym = tex(b2 + EB, 0), g2_yp = tex(b2 + EB, 2 * pitch_b);
-    // DoG layer rs + 1 exists up to S + 1 (quirk Q1: beyond it the reference's image load returns 0)
-    const bool up = rs + 1 <= S + 1;
-    const float sp = up ? dog(g2_c, g1[1][1]) : 0.f, sm = dog(g0[1][1], gm_c);
-    const float p_xp = up ? dog(g2_xp, g1[1][2]) : 0.f, p_xm = up ? dog(g2_xm, g1[1][0]) : 0.f;
-    const float p_yp = up ? dog(g2_yp, g1[2][1]) : 0.f, p_ym = up ? dog(g2_ym, g1[0][1]) : 0.f;
-    const float m_xp = dog(g0[1][2], gm_xp), m_xm = dog(g0[1][0], gm_xm), m_yp = dog(g0[2][1], gm_yp), m_ym = dog(g0[0][1], gm_ym);
+    // DoG layer s + 1 exists up to S + 1 (quirk Q1: beyond it the reference's image load returns 0)
+    const bool up = s + 1 <= S + 1;
+    Dog19 v;
+    v.sp = up ? dog(g2_c, g1[1][1]) : 0.f, v.sm = dog(g0[1][1], gm_c);
+    v.sp_xp = up ? dog(g2_xp, g1[1][2]) : 0.f, v.sp_xm = up ? dog(g2_xm, g1[1][0]) : 0.f;
+    v.sp_yp = up ? dog(g2_yp, g1[2][1]) : 0.f, v.sp_ym = up ? dog(g2_ym, g1[0][1]) : 0.f;
+    v.sm_xp = dog(g0[1][2], gm_xp), v.sm_xm = dog(g0[1][0], gm_xm), v.sm_yp = dog(g0[2][1], gm_yp), v.sm_ym = dog(g0[0][1], gm_ym);
     float d0[3][3];
 #pragma unroll
     for (int j = 0; j < 3; j++)
 #pragma unroll
       for (int i = 0; i < 3; i++)
         d0[j][i] = dog(g1[j][i], g0[j][i]);
-    vc = d0[1][1];
-    xp = d0[1][2], xm = d0[1][0], yp = d0[2][1], ym = d0[0][1];
-    gS = 0.5f * (sp - sm);
+    v.c = d0[1][1];
+    v.xp = d0[1][2], v.xm = d0[1][0], v.yp = d0[2][1], v.ym = d0[0][1];
+    v.xp_yp = d0[2][2], v.xp_ym = d0[0][2], v.xm_yp = d0[2][0], v.xm_ym = d0[0][0];
+    return v;
+  }
+};
+
+// Refinement + acceptance tests (ExtractKeypoints.comp:121-224) of the candidate at (x, y, s) of a W x H octave with S scales.
+template <class Load>
+__device__ bool refine_core(const Load &load, int W, int H, int S, int x, int y, int s, float dog_threshold, float edge_limit, float seed_sigma, int octave_idx,
+                            KpRecord *kp)
+{
+  float oX = 0.f, oY = 0.f, oS = 0.f, gX = 0.f, gY = 0.f, gS = 0.f;
+  float vc = 0.f, xp = 0.f, xm = 0.f, yp = 0.f, ym = 0.f, h23 = 0.f;
+  int rx = x, ry = y, rs = s;
+#pragma unroll Load::UNROLL_STEPS
+  for (int step = 0; step < 5; step++)
+  {
+    const Dog19 v = load(rx, ry, rs);
+    vc = v.c;
+    xp = v.xp, xm = v.xm, yp = v.yp, ym = v.ym;
+    gS = 0.5f * (v.sp - v.sm);
     gX = 0.5f * (xp - xm);
     gY = 0.5f * (yp - ym);
-    float h11 = sp + sm - 2.f * vc;
+    float h11 = v.sp + v.sm - 2.f * vc;
     float h22 = xp + xm - 2.f * vc;
     float h33 = yp + ym - 2.f * vc;
-    float h12 = 0.25f * (p_xp - p_xm - m_xp + m_xm);
-    float h13 = 0.25f * (p_yp - p_ym - m_yp + m_ym);
-    h23 = 0.25f * (d0[2][2] - d0[0][2] - d0[2][0] + d0[0][0]);
+    float h12 = 0.25f * (v.sp_xp - v.sp_xm - v.sm_xp + v.sm_xm);
+    float h13 = 0.25f * (v.sp_yp - v.sp_ym - v.sm_yp + v.sm_ym);
+    h23 = 0.25f * (v.xp_yp - v.xp_ym - v.xm_yp + v.xm_ym);
 
     float det = h11 * ((h22 * h33) - (h23 * h23)) - h12 * ((h12 * h33) - (h13 * h23)) + h13 * ((h12 * h23) - (h13 * h22));
     if (det == 0.0f)
@@ -218,7 +202,8 @@ __device__ bool refine_texel_buf(const __amdgpu_buffer_rsrc_t rsrc, int W, int H
       rs += ((oS >= 0.6f && rs < (S + 1)) ? 1 : 0) + ((oS <= -0.6f && rs > 1) ? -1 : 0);
     }
   }
-  // (rx, ry, rs) is where the last neighbourhood was loaded: vc, the axis neighbours and h23's diagonal differences are current
+  // (rx, ry, rs) is where the last neighbourhood was loaded (the position does not move after the last loads): vc, the axis
+  // neighbours and h23's diagonal differences are the values the acceptance and edge tests read
   float sx = (float)rx + oX, sy = (float)ry + oY, ss = (float)rs + oS;
   float nv = vc + 0.5f * (gX * oX + gY * oY + gS * oS);
   if (!(fabsf(nv) > dog_threshold && fabsf(oX) < 1.5f && fabsf(oY) < 1.5f && fabsf(oS) < 1.5f && sx >= 0 && sx < (float)W && sy >= 0 && sy < (float)H &&
@@ -242,6 +227,20 @@ __device__ bool refine_texel_buf(const __amdgpu_buffer_rsrc_t rsrc, int W, int H
   kp->x = sx * scale_factor;
   kp->y = sy * scale_factor;
   return true;
+}
+
+__device__ __forceinline__ void store_record(uint32_t *rec, const KpRecord &kp)
+{
+  static_assert(sizeof(KpRecord) == VKSIFT_RECORD_HEAD_WORDS * 4u, "the header words of a stored record");
+  rec[0] = __float_as_uint(kp.x);
+  rec[1] = __float_as_uint(kp.y);
+  rec[2] = __float_as_uint(kp.scale_x);
+  rec[3] = __float_as_uint(kp.scale_y);
+  rec[4] = kp.scale_idx;
+  rec[5] = (uint32_t)kp.octave_idx;
+  rec[6] = __float_as_uint(kp.sigma);
+  rec[7] = __float_as_uint(kp.orientation);
+  rec[8] = __float_as_uint(kp.intensity);
 }
 
 struct ExtremaArgs
@@ -316,6 +315,15 @@ __device__ __forceinline__ float fmin3(float a, float b, float c)
   return r;
 }
 
+// sum over the lanes of a wave, in every lane (xor butterfly)
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
+{
+#pragma unroll
+  for (int dlt = 32; dlt >= 1; dlt >>= 1)
+    v += __shfl_xor(v, dlt, 64);
+  return v;
+}
+
 // spread the low 32 bits of x to the even bit positions of a 64-bit word
 __device__ __forceinline__ unsigned long long spread32(unsigned long long x)
 {
@@ -329,11 +337,8 @@ __device__ __forceinline__ unsigned long long spread32(unsigned long long x)
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_extrema_lean — the streaming 26-neighbour test (a generic form of it, k_extrema_stream, was the fallback until round 5: planes
-// stay below 2 GiB — sides of 16384 and more are refused — so nothing ever took it), built around what bounds it. The pass is a pure stream (20 B per octave pixel at S = 3, no reuse beyond a 3-row window), so
-// its speed is the number of bytes a CU keeps in flight: the generic kernel holds the horizontal 3-max AND 3-min of three
-// rows per layer and column (~100 live registers of window state, one row of loads in flight, and ~700 issued
-// instructions per row — 64-bit per-lane address arithmetic, exec-mask branches around every load, window moves).
+// k_extrema_lean — the streaming 26-neighbour test, built around what bounds it. The pass is a pure stream (20 B per octave pixel
+// at S = 3, no reuse beyond a 3-row window), so its speed is the number of bytes a CU keeps in flight:
 //   * the window holds the RAW texels (3 rows x (2 columns + 1 halo) per layer — they serve max and min alike); the
 //     vertical 3-max / 3-min of a column is formed first, its left / right neighbours then come from ONE lane shift per
 //     side, layer and sign. 60-75 registers of state: 4 waves per SIMD with two rows of loads in flight each.
@@ -636,9 +641,7 @@ __global__ void __launch_bounds__(256) k_cand_list(Multi<ExtremaArgs> mu)
   uint32_t base = 0;
   for (uint32_t c = threadIdx.x & 63u, nc = (vb.x * 256u) / SEG_CHUNK; c < nc; c += 64u)
     base += chunk_tot[c];
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1)
-    base += __shfl_xor(base, dlt, 64);
+  base = wave_sum_u32(base);
   if (m == 0ull)
     return;
   uint32_t pos = a.seg_off[seg + (size_t)b * a.seg_img_stride] + base;
@@ -656,45 +659,67 @@ __global__ void __launch_bounds__(256) k_cand_list(Multi<ExtremaArgs> mu)
   }
 }
 
+// What both refinement kernels derive from their octave and image: the candidate list and its (clamped) length, the image's octave as
+// a view and as one buffer resource (BUF: the launcher has checked that it stays below 2 GiB), the accept flags and per-chunk accept counts
+// (in the segment-offset array, free again after k_cand_list).
+struct RefineCtx
+{
+  const ExtremaArgs &a;
+  uint32_t n, nch; // candidates, chunks of 256
+  DogView d;
+  __amdgpu_buffer_rsrc_t rsrc;
+  const uint32_t *xy;
+  uint32_t *flag, *chunk_sum;
+};
+
+template <bool F16>
+__device__ __forceinline__ RefineCtx refine_ctx(const ExtremaArgs &a, int b)
+{
+  constexpr unsigned EB = F16 ? 2u : 4u;
+  const uint32_t found = a.cand_n[b], n = found < a.cand_cap ? found : a.cand_cap;
+  const DogView d{(const float *)((const uint8_t *)a.gauss + (size_t)b * a.img_stride * EB), a.w, a.h, a.pitch, (size_t)a.plane_stride, a.S};
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)d.base, 0, (int)((unsigned)(a.S + 3) * (unsigned)a.plane_stride * EB), 0x00020000);
+  const size_t at = (size_t)b * a.cand_img_stride;
+  return RefineCtx{a, n, (n + 255u) / 256u, d, rsrc, a.cand_xy + at, a.cand_flag + at, a.seg_off + (size_t)b * a.seg_img_stride};
+}
+
+// refine the candidate packed as x | y << 14 | scale << 28 (k_cand_list)
+template <bool F16, bool BUF>
+__device__ __forceinline__ bool refine_candidate(const RefineCtx &c, uint32_t packed, KpRecord *kp)
+{
+  const ExtremaArgs &a = c.a;
+  const int x = (int)(packed & 0x3fffu), y = (int)((packed >> 14) & 0x3fffu), s = (int)(packed >> 28);
+  if constexpr (BUF)
+    return refine_core(BufLoader<F16>{c.rsrc, a.pitch, (unsigned)a.plane_stride, a.S}, a.w, a.h, a.S, x, y, s, a.dog_threshold, a.edge_limit, a.seed_sigma, a.octave_idx, kp);
+  else
+    return refine_core(PtrLoader<F16>{c.d}, a.w, a.h, a.S, x, y, s, a.dog_threshold, a.edge_limit, a.seed_sigma, a.octave_idx, kp);
+}
+
 // Dense refinement: thread t of a 256-candidate chunk refines candidate chunk*256 + t (count read from HBM, workgroups
-// stride over the chunks). Besides the accept flags every chunk publishes its number of accepted candidates (into the
-// segment-offset array, free again after k_cand_list) for the second scan level inside k_cand_emit.
+// stride over the chunks). Besides the accept flags every chunk publishes its number of accepted candidates for the second
+// scan level inside k_cand_emit.
 template <bool F16, bool BUF>
 __global__ void __launch_bounds__(256) k_refine_flags(Multi<ExtremaArgs> m)
 {
   __shared__ uint32_t s_cnt[4];
   const VBlock vb = vblock(m); // virtual grid (images, chunks)
-  const ExtremaArgs &a = m.oct[vb.o];
-  const int b = (int)vb.x; // image index fastest: see the launch
-  uint32_t n = a.cand_n[b];
-  n = n < a.cand_cap ? n : a.cand_cap;
-  const uint32_t nch = (n + 255u) / 256u;
-  DogView d{(const float *)((const uint8_t *)a.gauss + (size_t)b * a.img_stride * (a.fp16 ? 2u : 4u)), a.w, a.h, a.pitch, (size_t)a.plane_stride, a.S, a.fp16};
-  // the octave of this image as one buffer (BUF: the launcher has checked that it stays below 2 GiB)
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void *)d.base, 0, (int)((unsigned)(a.S + 3) * (unsigned)a.plane_stride * (F16 ? 2u : 4u)), 0x00020000);
-  const uint32_t *xy = a.cand_xy + (size_t)b * a.cand_img_stride;
-  uint32_t *flag = a.cand_flag + (size_t)b * a.cand_img_stride;
-  uint32_t *chunk_sum = a.seg_off + (size_t)b * a.seg_img_stride;
-  for (uint32_t chunk = vb.y; chunk < nch; chunk += vb.gy)
+  const RefineCtx c = refine_ctx<F16>(m.oct[vb.o], (int)vb.x); // image index fastest: see the launch
+  for (uint32_t chunk = vb.y; chunk < c.nch; chunk += vb.gy)
   {
     const uint32_t i = chunk * 256u + threadIdx.x;
     bool ok = false;
-    if (i < n)
+    if (i < c.n)
     {
-      const uint32_t c = xy[i];
       KpRecord kp;
-      const int cx = (int)(c & 0x3fffu), cy = (int)((c >> 14) & 0x3fffu), cs = (int)(c >> 28);
-      ok = BUF ? refine_texel_buf<F16>(rsrc, a.w, a.h, a.pitch, (unsigned)a.plane_stride, a.S, cx, cy, cs, a.dog_threshold, a.edge_limit, a.seed_sigma, a.octave_idx, &kp)
-               : refine_texel<F16>(d, cx, cy, cs, a.dog_threshold, a.edge_limit, a.seed_sigma, a.octave_idx, &kp);
-      flag[i] = ok ? 1u : 0u;
+      ok = refine_candidate<F16, BUF>(c, c.xy[i], &kp);
+      c.flag[i] = ok ? 1u : 0u;
     }
     const unsigned long long bal = __ballot(ok);
     if ((threadIdx.x & 63) == 0)
       s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(bal);
     __syncthreads();
     if (threadIdx.x == 0)
-      chunk_sum[chunk] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+      c.chunk_sum[chunk] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     __syncthreads();
   }
 }
@@ -712,28 +737,17 @@ __global__ void __launch_bounds__(256) k_cand_emit(Multi<ExtremaArgs> m)
   const ExtremaArgs &a = m.oct[vb.o];
   const int b = (int)vb.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t n = a.cand_n[b];
-  n = n < a.cand_cap ? n : a.cand_cap;
-  const uint32_t nch = (n + 255u) / 256u;
-  DogView d{(const float *)((const uint8_t *)a.gauss + (size_t)b * a.img_stride * (a.fp16 ? 2u : 4u)), a.w, a.h, a.pitch, (size_t)a.plane_stride, a.S, a.fp16};
-  // the octave of this image as one buffer (BUF: the launcher has checked that it stays below 2 GiB)
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void *)d.base, 0, (int)((unsigned)(a.S + 3) * (unsigned)a.plane_stride * (F16 ? 2u : 4u)), 0x00020000);
-  const uint32_t *xy = a.cand_xy + (size_t)b * a.cand_img_stride;
-  const uint32_t *flag = a.cand_flag + (size_t)b * a.cand_img_stride;
-  const uint32_t *chunk_sum = a.seg_off + (size_t)b * a.seg_img_stride; // accepted candidates per chunk (k_refine_flags)
-  for (uint32_t chunk = vb.y; chunk < nch; chunk += vb.gy)
+  const RefineCtx c = refine_ctx<F16>(a, b);
+  for (uint32_t chunk = vb.y; chunk < c.nch; chunk += vb.gy)
   {
     // records of the chunks in front of this one (raster order is preserved): partial sums of their accept counts ride on the barrier
     // the rank computation needs anyway; the image's last chunk posts the keypoint count
     uint32_t part = 0;
-    for (uint32_t c = threadIdx.x; c < chunk; c += 256u)
-      part += chunk_sum[c];
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-      part += __shfl_xor(part, dlt, 64);
+    for (uint32_t k = threadIdx.x; k < chunk; k += 256u)
+      part += c.chunk_sum[k];
+    part = wave_sum_u32(part);
     const uint32_t i = chunk * 256u + threadIdx.x;
-    const bool v = i < n && flag[i] != 0u;
+    const bool v = i < c.n && c.flag[i] != 0u;
     const unsigned long long bal = __ballot(v);
     if (lane == 0)
       s_cnt[wave] = (uint32_t)__popcll(bal), s_red[wave] = part;
@@ -744,30 +758,16 @@ __global__ void __launch_bounds__(256) k_cand_emit(Multi<ExtremaArgs> m)
       rank += s_cnt[wv];
     const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     if (v)
-      s_list[rank] = xy[i];
+      s_list[rank] = c.xy[i];
     __syncthreads();
     const uint32_t idx = cbase + threadIdx.x;
-    if (chunk + 1u == nch && threadIdx.x == 0)
+    if (chunk + 1u == c.nch && threadIdx.x == 0)
       a.found[(size_t)b * a.found_img_stride] = cbase + total; // un-clamped, like nb_elem (0 candidates: the counter reset's 0 stays)
     if (threadIdx.x < total && idx < a.cap)
     {
-      const uint32_t c = s_list[threadIdx.x];
       KpRecord kp;
-      const int cx = (int)(c & 0x3fffu), cy = (int)((c >> 14) & 0x3fffu), cs = (int)(c >> 28);
-      if (BUF)
-        refine_texel_buf<F16>(rsrc, a.w, a.h, a.pitch, (unsigned)a.plane_stride, a.S, cx, cy, cs, a.dog_threshold, a.edge_limit, a.seed_sigma, a.octave_idx, &kp);
-      else
-        refine_texel<F16>(d, cx, cy, cs, a.dog_threshold, a.edge_limit, a.seed_sigma, a.octave_idx, &kp);
-      uint32_t *rec = (uint32_t *)(a.feats + (size_t)b * a.feat_img_stride + (size_t)idx * 164);
-      rec[0] = __float_as_uint(kp.x);
-      rec[1] = __float_as_uint(kp.y);
-      rec[2] = __float_as_uint(kp.scale_x);
-      rec[3] = __float_as_uint(kp.scale_y);
-      rec[4] = kp.scale_idx;
-      rec[5] = (uint32_t)kp.octave_idx;
-      rec[6] = __float_as_uint(kp.sigma);
-      rec[7] = __float_as_uint(kp.orientation);
-      rec[8] = __float_as_uint(kp.intensity);
+      refine_candidate<F16, BUF>(c, s_list[threadIdx.x], &kp);
+      store_record((uint32_t *)(a.feats + (size_t)b * a.feat_img_stride + (size_t)idx * VKSIFT_RECORD_BYTES), kp);
     }
     __syncthreads();
   }
@@ -835,16 +835,9 @@ static int clear_masks(const ExtremaArgs *args, uint32_t n, uint32_t batch, hipS
   return 0;
 }
 
-/* the launches of one run of at most MULTI_MAX octaves (same S, same texel type) */
-static int extract_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t batch, hipStream_t hs, hipEvent_t scan_done)
+/* the launches of one run of at most MULTI_MAX octaves (same S, same texel type); args: the jobs' validated arguments (make_extrema_args) */
+static int extract_run(const vksift_hip_OctaveJob *jobs, ExtremaArgs *args, uint32_t n, uint32_t batch, hipStream_t hs, hipEvent_t scan_done)
 {
-  ExtremaArgs args[MULTI_MAX];
-  for (uint32_t i = 0; i < n; i++)
-  {
-    const int e = make_extrema_args(&jobs[i], &args[i]);
-    if (e)
-      return e;
-  }
   const bool f16 = args[0].fp16 != 0;
   const int S = args[0].S;
   {
@@ -871,12 +864,6 @@ static int extract_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t ba
   }
   /* bit 0: the 4 waves of a block take adjacent strips (-5 % against adjacent bands), bit 1: XCD-contiguous block order (-3 %) */
   const int sm = 3;
-  /* window slots: fp32 texels 4 (one row of loads in flight; two rows spill registers since the slots receive S+3 Gaussian
-   * texels), binary16 texels 5 (a row in flight costs half the registers) */
-  /* the kernel addresses a plane with 32-bit byte offsets: planes stay below 2 GiB (sides of 16384 and more are refused above) */
-  for (uint32_t i = 0; i < n; i++)
-    if ((uint64_t)jobs[i].pitch * jobs[i].h * (f16 ? 2u : 4u) >= 0x80000000ull)
-      return (int)hipErrorInvalidValue;
 
 #define VKSIFT_MULTI(M, GX, GY, GZ)                              \
   Multi<ExtremaArgs> M;                                           \
@@ -891,36 +878,32 @@ static int extract_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t ba
   {
     VKSIFT_MULTI(ms, (uint32_t)(a.nseg + 1) / 2u, ((a.h + a.band - 1) / a.band + 3u) / 4u, batch)
     const dim3 sgrid(ms.start[ms.n]);
-    switch (S)
-    {
-#define VKSIFT_CASE(N)                                                                \
-  case N:                                                                             \
-    if (f16)                                                                          \
-      hipLaunchKernelGGL((k_extrema_lean<N, 5, true>), sgrid, dim3(256), 0, hs, ms, sm);  \
-    else                                                                              \
-      hipLaunchKernelGGL((k_extrema_lean<N, 4, false>), sgrid, dim3(256), 0, hs, ms, sm); \
-    break;
-      VKSIFT_CASE(1) VKSIFT_CASE(2) VKSIFT_CASE(3) VKSIFT_CASE(4) VKSIFT_CASE(5) VKSIFT_CASE(6) VKSIFT_CASE(7) VKSIFT_CASE(8) VKSIFT_CASE(9)
-      VKSIFT_CASE(10) VKSIFT_CASE(11) VKSIFT_CASE(12) VKSIFT_CASE(13)
-#undef VKSIFT_CASE
-    default:
+    /* window slots: fp32 texels 4 (one row of loads in flight; two rows spill registers since the slots receive S+3 Gaussian
+     * texels), binary16 texels 5 (a row in flight costs half the registers) */
+    const bool known = with_scales(S, [&](auto NS) {
+      with_bool(f16, [&](auto F16) {
+        constexpr bool h = decltype(F16)::value;
+        hipLaunchKernelGGL((k_extrema_lean<decltype(NS)::value, h ? 5 : 4, h>), sgrid, dim3(256), 0, hs, ms, sm);
+      });
+    });
+    if (!known)
       return (int)hipErrorInvalidValue;
-    }
   }
   if (scan_done)
     (void)hipEventRecord(scan_done, hs);
-  /* 2. offsets + candidate count: chunk-local scan, then the (short) scan of the chunk totals; the totals/bases live at
+  /* 2. offsets + candidate count: chunk-local scan (the scan of the chunk totals happens in the consumer); the totals live at
    * the start of the flag array until the refinement overwrites it */
   {
     VKSIFT_MULTI(m2, a.nchunks, batch, 1u)
     hipLaunchKernelGGL(k_segment_scan, dim3(m2.start[m2.n]), dim3(1024), 0, hs, m2);
   }
-  /* 3. compact list, 4. dense refinement (+ per-chunk accept counts), 5. scan of those counts, 6. accepted -> records */
+  /* 3. compact list */
   {
     VKSIFT_MULTI(m3, (a.nsegs + 255u) / 256u, batch, 1u)
     hipLaunchKernelGGL(k_cand_list, dim3(m3.start[m3.n]), dim3(256), 0, hs, m3);
   }
-  /* virtual grid = (image, chunk): the busy workgroups (chunk < candidates / 256, a small and unknown part of the grid) are then
+  /* 4. dense refinement (+ per-chunk accept counts), 5. accepted -> records.
+   * virtual grid = (image, chunk): the busy workgroups (chunk < candidates / 256, a small and unknown part of the grid) are then
    * contiguous in dispatch order. With the chunk index fastest they formed a short run at the start of every image's row of
    * 512 workgroups, which the dispatcher's round-robin maps onto the same half of the shader engines of every XCD:
    * measured 221 us instead of 70 us for this launch (and 137 instead of 51 us for k_cand_emit). */
@@ -932,30 +915,33 @@ static int extract_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t ba
 #define VKSIFT_REFINE_CHUNKS(a) (((uint64_t)(a).S * (uint32_t)(a).w * (uint32_t)(a).h / 4u + 64u + 255u) / 256u)
   VKSIFT_MULTI(mr, batch, VKSIFT_REFINE_CHUNKS(a) > rcap ? rcap : (uint32_t)VKSIFT_REFINE_CHUNKS(a), 1u)
 #undef VKSIFT_REFINE_CHUNKS
+#undef VKSIFT_MULTI
   const dim3 rgrid(mr.start[mr.n]);
   /* the refinement addresses an image's octave through one buffer resource with 32-bit offsets where it fits (always, short of
    * 4096 x 4096 octaves with many scales); the pointer form serves the rest */
   bool buf = vksift_hip_tune_get(VKSIFT_TUNE_REFINE_PTR) == 0;
   for (uint32_t i = 0; i < n; i++)
     buf = buf && (uint64_t)(args[i].S + 3) * args[i].plane_stride * (f16 ? 2u : 4u) < 0x7FFF0000ull;
-  if (f16 && buf)
-    hipLaunchKernelGGL((k_refine_flags<true, true>), rgrid, dim3(256), 0, hs, mr);
-  else if (f16)
-    hipLaunchKernelGGL((k_refine_flags<true, false>), rgrid, dim3(256), 0, hs, mr);
-  else if (buf)
-    hipLaunchKernelGGL((k_refine_flags<false, true>), rgrid, dim3(256), 0, hs, mr);
-  else
-    hipLaunchKernelGGL((k_refine_flags<false, false>), rgrid, dim3(256), 0, hs, mr);
-  if (f16 && buf)
-    hipLaunchKernelGGL((k_cand_emit<true, true>), rgrid, dim3(256), 0, hs, mr);
-  else if (f16)
-    hipLaunchKernelGGL((k_cand_emit<true, false>), rgrid, dim3(256), 0, hs, mr);
-  else if (buf)
-    hipLaunchKernelGGL((k_cand_emit<false, true>), rgrid, dim3(256), 0, hs, mr);
-  else
-    hipLaunchKernelGGL((k_cand_emit<false, false>), rgrid, dim3(256), 0, hs, mr);
-#undef VKSIFT_MULTI
+  with_bool(f16, [&](auto F16) {
+    with_bool(buf, [&](auto BUF) {
+      hipLaunchKernelGGL((k_refine_flags<decltype(F16)::value, decltype(BUF)::value>), rgrid, dim3(256), 0, hs, mr);
+      hipLaunchKernelGGL((k_cand_emit<decltype(F16)::value, decltype(BUF)::value>), rgrid, dim3(256), 0, hs, mr);
+    });
+  });
   return (int)hipGetLastError();
+}
+
+/* the validated arguments of every job, or the error of the first one the contract excludes */
+static int make_all_extrema_args(const vksift_hip_OctaveJob *jobs, uint32_t n_jobs, std::vector<ExtremaArgs> &args)
+{
+  args.resize(n_jobs);
+  for (uint32_t i = 0; i < n_jobs; i++)
+  {
+    const int e = make_extrema_args(&jobs[i], &args[i]);
+    if (e)
+      return e;
+  }
+  return 0;
 }
 
 extern "C" int vksift_hip_extract_keypoints_multi(const vksift_hip_OctaveJob *jobs, uint32_t n_jobs, uint32_t batch, vksift_hip_stream s,
@@ -964,20 +950,17 @@ extern "C" int vksift_hip_extract_keypoints_multi(const vksift_hip_OctaveJob *jo
   if (n_jobs == 0 || batch == 0)
     return 0;
   /* a job the contract excludes refuses the whole call before the first run is launched */
-  for (uint32_t i = 0; i < n_jobs; i++)
-  {
-    ExtremaArgs a;
-    const int e = make_extrema_args(&jobs[i], &a);
-    if (e)
-      return e;
-  }
+  std::vector<ExtremaArgs> args;
+  const int bad = make_all_extrema_args(jobs, n_jobs, args);
+  if (bad)
+    return bad;
   /* runs of octaves that one launch can serve: same S and texel type (always the case inside one detection), at most MULTI_MAX */
   for (uint32_t i0 = 0; i0 < n_jobs;)
   {
     uint32_t i1 = i0 + 1;
     while (i1 < n_jobs && i1 - i0 < multi_run_max() && jobs[i1].S == jobs[i0].S && jobs[i1].fp16 == jobs[i0].fp16)
       i1++;
-    const int e = extract_run(jobs + i0, i1 - i0, batch, (hipStream_t)s, i1 == n_jobs ? (hipEvent_t)scan_done : nullptr);
+    const int e = extract_run(jobs + i0, args.data() + i0, i1 - i0, batch, (hipStream_t)s, i1 == n_jobs ? (hipEvent_t)scan_done : nullptr);
     if (e)
       return e;
     i0 = i1;
@@ -991,14 +974,9 @@ extern "C" int vksift_hip_clear_segment_masks(const vksift_hip_OctaveJob *jobs, 
     return 0;
   if (n_jobs > 16)
     return (int)hipErrorInvalidValue;
-  ExtremaArgs args[16];
-  for (uint32_t i = 0; i < n_jobs; i++)
-  {
-    const int e = make_extrema_args(&jobs[i], &args[i]);
-    if (e)
-      return e;
-  }
-  return clear_masks(args, n_jobs, batch, (hipStream_t)s);
+  std::vector<ExtremaArgs> args;
+  const int bad = make_all_extrema_args(jobs, n_jobs, args);
+  return bad ? bad : clear_masks(args.data(), n_jobs, batch, (hipStream_t)s);
 }
 
 extern "C" int vksift_hip_extract_keypoints(const vksift_hip_OctaveJob *job, uint32_t batch, vksift_hip_stream s, vksift_hip_event scan_done)

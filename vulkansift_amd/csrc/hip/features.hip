@@ -18,6 +18,7 @@
 
 #include "../detmath.h"
 #include "multi.h"
+#include "records.h"
 #include "vksift_hip.h"
 
 namespace
@@ -47,14 +48,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t layer_rsrc(const float *gauss,
 {
   const void *p = f16 ? (const void *)((const _Float16 *)gauss + texel_off) : (const void *)(gauss + texel_off);
   return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, pitch * h * (f16 ? 2 : 4), 0x00020000);
-}
-
-// imageLoad with robust out-of-bounds behaviour (returns 0) — quirk Q2 relies on it.
-__device__ __forceinline__ float ldg(const GaussView &g, const float *layer, int x, int y)
-{
-  if ((unsigned)x >= (unsigned)g.w || (unsigned)y >= (unsigned)g.h)
-    return 0.f;
-  return layer[(size_t)y * g.pitch + x];
 }
 
 struct FeatArgs
@@ -183,7 +176,7 @@ __global__ void __launch_bounds__(256) k_orientation(Multi<FeatArgs> m)
     __builtin_amdgcn_wave_barrier();
     float fp = 0.f;
     {
-      const float *rec = (const float *)(feats + (size_t)k * 164);
+      const float *rec = (const float *)(feats + (size_t)k * VKSIFT_RECORD_BYTES);
       const float scale_x = rec[2], scale_y = rec[3];
       const uint32_t scale_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)((const uint32_t *)rec)[4]); // one keypoint per wave
       const int octave_idx = ((const int *)rec)[5];
@@ -384,16 +377,16 @@ __global__ void __launch_bounds__(1024) k_orientation_finalize(Multi<FeatArgs> m
     uint32_t excl = carry + wave_base + incl - v;
     if (k < n0 && c >= 1)
     {
-      uint32_t *rec = (uint32_t *)(feats + (size_t)k * 164);
+      uint32_t *rec = (uint32_t *)(feats + (size_t)k * VKSIFT_RECORD_BYTES);
       rec[7] = __float_as_uint(ang[(size_t)k * VKSIFT_HIP_MAX_ORI]);
       for (uint32_t j = 1; j < c; j++)
       {
         uint32_t idx = found + excl + (j - 1);
         if (idx < a.cap)
         {
-          uint32_t *dst = (uint32_t *)(feats + (size_t)idx * 164);
+          uint32_t *dst = (uint32_t *)(feats + (size_t)idx * VKSIFT_RECORD_BYTES);
 #pragma unroll
-          for (int q = 0; q < 9; q++)
+          for (int q = 0; q < (int)VKSIFT_RECORD_HEAD_WORDS; q++)
             dst[q] = rec[q];
           dst[7] = __float_as_uint(ang[(size_t)k * VKSIFT_HIP_MAX_ORI + j]);
         }
@@ -624,7 +617,7 @@ k_descriptor(Multi<FeatArgs> m, vksift_hip_DenseRows dr)
     for (int i = tid; i < 256; i += NT_)
       s_work[desc_cell_word(i >> 4) + (i & 15)] = 0; // the 16 grid cells; made visible by the barrier behind the row-span pass below
 
-    const float *rec = (const float *)(feats + (size_t)k * 164);
+    const float *rec = (const float *)(feats + (size_t)k * VKSIFT_RECORD_BYTES);
     const uint32_t scale_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)((const uint32_t *)rec)[4]); // uniform: keeps the resource in SGPRs
     const int octave_idx = ((const int *)rec)[5];
     const float sigma = rec[6];
@@ -844,20 +837,20 @@ k_descriptor(Multi<FeatArgs> m, vksift_hip_DenseRows dr)
       p1 |= __shfl_xor(p1, 2, 64);
       if ((ln & 3) == 0)
       {
-        uint32_t *desc = (uint32_t *)(feats + (size_t)k * 164 + 36);
+        uint32_t *desc = (uint32_t *)(feats + (size_t)k * VKSIFT_RECORD_BYTES + VKSIFT_RECORD_DESC_AT);
         desc[ln >> 2] = p0;
         desc[16 + (ln >> 2)] = p1;
       }
       if (CAN_POST && dr.post)
       {
-        // the posted record: 9 header words from the section record (written by the extraction and orientation launches), the
+        // the posted record: its header words from the section record (written by the extraction and orientation launches), the
         // descriptor's 32 words from the registers of the lanes that hold them
         const uint32_t j = (uint32_t)ln & 15u;
         const uint32_t d0 = __shfl(p0, (int)(4u * j), 64), d1 = __shfl(p1, (int)(4u * j), 64);
-        uint32_t *out = (uint32_t *)(dr.post + (size_t)b * dr.post_img_stride) + (size_t)(s_row0 + k) * 41u;
+        uint32_t *out = (uint32_t *)(dr.post + (size_t)b * dr.post_img_stride) + (size_t)(s_row0 + k) * VKSIFT_RECORD_WORDS;
         if (ln < 32)
-          out[9 + ln] = ln < 16 ? d0 : d1;
-        else if (ln < 41)
+          out[(int)VKSIFT_RECORD_HEAD_WORDS + ln] = ln < 16 ? d0 : d1;
+        else if (ln < (int)VKSIFT_RECORD_WORDS)
           out[ln - 32] = ((const uint32_t *)rec)[ln - 32];
       }
       if (dr.desc)
@@ -914,27 +907,18 @@ FeatArgs make_args(const vksift_hip_OctaveJob *job)
 // planes in one L2). grid.y is limited to 65535.
 bool img_fast(uint32_t batch, bool descriptor)
 {
-  static int mode = -1;
-  if (mode < 0)
-  {
-    /* bit 0: orientation kernel, bit 1: descriptor kernel. Measured (128 x 640x480): orientation -5 %, descriptor +3 %
-     * (its grid is mostly busy and the keypoint-fastest order spreads the long coarse-scale windows better): default 1 */
-    mode = 1;
-  }
-  return batch > 1 && ((mode >> (descriptor ? 1 : 0)) & 1);
+  /* Measured (128 x 640x480): orientation -5 %, descriptor +3 % (its grid is mostly busy and the keypoint-fastest order spreads the long
+   * coarse-scale windows better): the orientation kernel only */
+  return batch > 1 && !descriptor;
 }
 
 // grid sizing only (the kernels stride over the real, device-side count): a generous estimate of the keypoints of an octave
 uint32_t expected_keypoints(const vksift_hip_OctaveJob *job, uint32_t batch)
 {
-  static int div = -1;
-  if (div < 0)
-  {
-    div = 512; /* pixels per expected keypoint */
-  }
-  if (div <= 0 || batch < 8u) /* a handful of images: idle workgroups cost nothing, keep the full parallelism */
+  const uint32_t pixels_per_keypoint = 512;
+  if (batch < 8u) /* a handful of images: idle workgroups cost nothing, keep the full parallelism */
     return 0xFFFFFFFFu;
-  const uint64_t n = (uint64_t)job->w * job->h / (uint32_t)div;
+  const uint64_t n = (uint64_t)job->w * job->h / pixels_per_keypoint;
   return n < 32u ? 32u : (n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n);
 }
 
@@ -967,20 +951,9 @@ static int orientation_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_
   }
   const bool f16 = mo.oct[0].fp16 != 0;
   const dim3 grid(mo.start[mo.n]);
-  if (f)
-  {
-    if (f16)
-      hipLaunchKernelGGL((k_orientation<true, true>), grid, dim3(256), 0, hs, mo);
-    else
-      hipLaunchKernelGGL((k_orientation<true, false>), grid, dim3(256), 0, hs, mo);
-  }
-  else
-  {
-    if (f16)
-      hipLaunchKernelGGL((k_orientation<false, true>), grid, dim3(256), 0, hs, mo);
-    else
-      hipLaunchKernelGGL((k_orientation<false, false>), grid, dim3(256), 0, hs, mo);
-  }
+  with_bool(f, [&](auto IMG_FAST) {
+    with_bool(f16, [&](auto F16) { hipLaunchKernelGGL((k_orientation<decltype(IMG_FAST)::value, decltype(F16)::value>), grid, dim3(256), 0, hs, mo); });
+  });
   hipLaunchKernelGGL(k_orientation_finalize, dim3(mf.start[mf.n]), dim3(1024), 0, hs, mf);
   return (int)hipGetLastError();
 }
@@ -1002,37 +975,21 @@ static int descriptor_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t
     if (!multi_add(md, a, f ? batch : blocks, f ? blocks : batch, 1u))
       return (int)hipErrorInvalidValue;
   }
-  /* waves per keypoint: 4 keep the critical path of a single image short; a batch has keypoints to spare and runs
-   * 3-4 % faster with 2 (less redundant per-keypoint work, measured under the overlapped batch schedule) */
-  /* waves per keypoint: 4 for single images (latency), 2 for batches (1 wave: 55 % slower, 8: no faster than 4; measured round 2) */
-  const int nwv = batch >= 8u ? 2 : 4;
-  if (dr.post && nwv != 4)
+  /* waves per keypoint: 4 keep the critical path of a single image short (1 wave: 55 % slower, 8: no faster than 4); a batch has keypoints
+   * to spare and runs 3-4 % faster with 2 (less redundant per-keypoint work, measured under the overlapped batch schedule) */
+  const bool two_waves = batch >= 8u;
+  if (dr.post && two_waves)
     return (int)hipErrorInvalidValue; /* posting is compiled into the four-wave form only */
   const bool f16 = md.oct[0].fp16 != 0;
   const dim3 grid(md.start[md.n]);
-#define VKSIFT_DESC(N)                                                                  \
-  do                                                                                    \
-  {                                                                                     \
-    if (f)                                                                              \
-    {                                                                                   \
-      if (f16)                                                                          \
-        hipLaunchKernelGGL((k_descriptor<N, true, true>), grid, dim3(64 * N), 0, hs, md, dr);  \
-      else                                                                              \
-        hipLaunchKernelGGL((k_descriptor<N, true, false>), grid, dim3(64 * N), 0, hs, md, dr); \
-    }                                                                                   \
-    else                                                                                \
-    {                                                                                   \
-      if (f16)                                                                          \
-        hipLaunchKernelGGL((k_descriptor<N, false, true>), grid, dim3(64 * N), 0, hs, md, dr); \
-      else                                                                              \
-        hipLaunchKernelGGL((k_descriptor<N, false, false>), grid, dim3(64 * N), 0, hs, md, dr); \
-    }                                                                                   \
-  } while (0)
-  if (nwv == 2)
-    VKSIFT_DESC(2);
-  else
-    VKSIFT_DESC(4);
-#undef VKSIFT_DESC
+  with_bool(two_waves, [&](auto TWO) {
+    constexpr int NWV = decltype(TWO)::value ? 2 : 4;
+    with_bool(f, [&](auto IMG_FAST) {
+      with_bool(f16, [&](auto F16) {
+        hipLaunchKernelGGL((k_descriptor<NWV, decltype(IMG_FAST)::value, decltype(F16)::value>), grid, dim3(64 * NWV), 0, hs, md, dr);
+      });
+    });
+  });
   return (int)hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "vksift_hip.h"
 
@@ -73,4 +74,30 @@ static inline bool multi_add(Multi<A> &m, const A &a, uint32_t gx, uint32_t gy, 
   m.start[m.n + 1] = (uint32_t)end;
   m.n++;
   return true;
+}
+
+// host side: a run-time value as a compile-time argument of a generic lambda, so that a launcher names its kernel once:
+//   with_bool(f16, [&](auto F16) { hipLaunchKernelGGL((k<decltype(F16)::value>), ...); });
+template <class F>
+static inline void with_bool(bool v, F &&f)
+{
+  if (v)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
+// the same for the number of scales per octave, 1 .. 13 (what the extraction is instantiated for); false for any other S
+template <int N = 1, class F>
+static inline bool with_scales(int S, F &&f)
+{
+  if constexpr (N > 13)
+    return false;
+  else
+  {
+    if (S != N)
+      return with_scales<N + 1>(S, f);
+    f(std::integral_constant<int, N>{});
+    return true;
+  }
 }

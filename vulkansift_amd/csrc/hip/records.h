@@ -10,6 +10,7 @@
 
 #define VKSIFT_RECORD_BYTES 164u /* a stored feature: {x, y, ...} from byte 0, the 128 descriptor bytes from VKSIFT_RECORD_DESC_AT */
 #define VKSIFT_RECORD_WORDS 41u
+#define VKSIFT_RECORD_HEAD_WORDS 9u /* {x, y, scale_x, scale_y, scale_idx, octave_idx, sigma, orientation, intensity} */
 #define VKSIFT_RECORD_DESC_AT 36u
 #define VKSIFT_MAX_SECTIONS 16u /* one section per octave */
 /* A pair table names each buffer's layout by one word: VKSIFT_LAYOUT_DENSE | n for n dense records (uploaded features), else the index
