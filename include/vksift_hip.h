@@ -112,6 +112,9 @@ extern "C"
     VKSIFT_TUNE_ZERO_COPY = 11,  /* 1: a single host image is copied into device memory in front of the seed launch (default: the launch reads the pinned
                                   * staging buffer itself) */
     VKSIFT_TUNE_MIN_MARCH = 12,  /* output rows per wave of the smallest strip-march launches (a single image's): 0 = built-in */
+    VKSIFT_TUNE_TAIL_FUSED = 13, /* tail of the keypoint extraction (ballots -> records): 0 = built-in (batches of 64 images and more take one launch with one
+                                  * workgroup per image and octave, smaller calls the four sparse launches), 1: always the four launches, 2: always the one, 3: as 2 with the 512-thread workgroups that launches
+                                  * of 512 workgroups and more take (tests of that form at small sizes) */
     VKSIFT_TUNE_COUNT = 16
   };
   int vksift_hip_tune(int knob, int value);
