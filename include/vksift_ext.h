@@ -188,6 +188,29 @@ extern "C"
   /* Time (ms) of the last guided matching (gather + sweeps + decision + the count posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getGuidedMatchTime(vksift_Instance instance);
 
+  /* ---- GPU-side feature budget ------------------------------------------------------------------------------------------
+   * Every SIFT buffer of [first_gpu_buffer_id, first_gpu_buffer_id + count) keeps its max_features strongest features (OpenCV's nfeatures, SiftGPU's -tc,
+   * PopSift's --filter-max-extrema), selected and compacted on the device: no download, host sort and upload. The capacity max_nb_sift_per_buffer drops the
+   * tail of a full section in raster order, wherever the features sit in the image; this call chooses by strength. Everything behind it is priced by the row
+   * count (the matcher is N_A x N_B, the guided sweep visits all pairs, a download moves every stored record), so it goes between detection and matching.
+   * With rows numbered in download order, key(row) is the 32 bits of the feature's `intensity` field with the sign bit cleared, compared as an unsigned integer:
+   * |DoG response| for every finite value, and a total order on every bit pattern (-0 equals +0, infinities rank above finite values, NaN patterns above
+   * those). The first min(n, max_features) rows by (key descending, row ascending) are kept, in download order: vksift_getFeaturesNumber becomes min(n,
+   * max_features), vksift_downloadFeatures returns the kept records as they were, and a matching sees those rows. Deterministic. The orientations of one
+   * keypoint are separate features with equal keys: a tie at the threshold is broken by row, so the budget may keep some of them and not the others.
+   * A buffer that holds at most max_features features is not touched at all; selecting again with the same budget changes nothing. A detected buffer stays
+   * laid out in its octave sections (the kept features of an octave stay in it), an uploaded one stays one dense run.
+   * Contract of vksift_detectFeatures: asynchronous, queued on the instance stream behind every detection and matching already queued (staged plain
+   * detections are launched first); the buffers are busy (vksift_isBufferAvailable false) until it has run, and every accessor of them waits for it.
+   * Precondition on earlier results, as for the guided matching: filtered matches, verified or refined models and guided matches of an earlier matching
+   * index the buffers' old rows. The selection is not noticed by them: the row counts are the matching's, the rows the buffer's present ones, and the
+   * records are then meaningless (every read stays inside the buffers' storage). Match again first.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, nothing changed): count 0 or above 512, a range outside sift_buffer_count, max_features 0. A launch failure
+   * is VKSIFT_VULKAN_ERROR. */
+  VKSIFT_EXPORT void vksift_ext_keepStrongestFeatures(vksift_Instance instance, uint32_t first_gpu_buffer_id, uint32_t count, uint32_t max_features);
+  /* Time (ms) of the last vksift_ext_keepStrongestFeatures (its launches), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getKeepStrongestTime(vksift_Instance instance);
+
   /* Deferred submission of vksift_detectFeatures (no counterpart in the reference, no change of its contract): consecutive plain
    * detect calls into consecutive SIFT buffers, with nothing asked in between, are staged and launched as ONE batched detection by
    * the first call that needs a result — any other entry point — or when 128 images (VKSIFT_DEFER_MAX) are staged, or 16 (VKSIFT_DEFER_CHUNK)

@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 6u      /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version) */
+#define VKSIFT_HIP_ABI_VERSION 7u      /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version) */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -426,6 +426,30 @@ extern "C"
                                  const uint32_t *sec_off, const uint32_t *sec_cap, const uint32_t *fixed_counts, const uint32_t *found_base,
                                  uint32_t found_buf_stride, uint32_t max_rows, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride,
                                  uint32_t *norms, uint64_t norm_stride, uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s);
+  /* The feature budget (strongest.hip): every SIFT buffer buf_ids[0..nslots), nslots <= VKSIFT_HIP_GATHER_SLOTS, keeps its max_features strongest
+   * records, in place; one launch, one 1024-thread workgroup per buffer, all buffers of the call share the section table (named as for
+   * vksift_hip_gather_sections: the counters are found_base + id*found_buf_stride, or fixed_counts for uploaded buffers — exactly one of the two).
+   * Rows are numbered in download order. key(row) = the record's intensity word (byte 32) with the sign bit cleared, compared as an unsigned
+   * integer (|DoG response| for every finite value; -0 equals +0, infinities rank above finite values, NaN patterns above those; no float
+   * comparison). The first min(total, max_features) rows by (key descending, row ascending) are kept; they stay in their section, keep their
+   * order and move to its front: section o then holds its kept[o] rows from record sec_off[o] on. The orientations of one keypoint are
+   * separate records with equal keys: a tie at the threshold is broken by row, so the budget may keep some of them and not the others.
+   * READ, per named buffer id: its nsec counters (or fixed_counts[o], o < nsec) and its stored records. WRITTEN, per named buffer whose total
+   * exceeds max_features: records sec_off[o] .. sec_off[o] + kept[o] - 1 of every section (the kept records); found_base[id*found_buf_stride +
+   * o] = kept[o] for o < nsec, and the same words of found_post (or NULL: a host-mapped mirror of found_base, stored by the kernel itself)
+   * when counters are given; with desc != NULL the buffer's matcher-cache entry as vksift_hip_gather_sections would write it for the selected
+   * buffer (max(max_features, pad_rows_to) rows at desc + id*desc_stride, as many norms at norms + id*norm_stride words, n_out_dev[id*n_stride] =
+   * max_features). The records of a section from its new count up to its old stored count hold unspecified bytes afterwards (old records or
+   * kept ones). Nothing else; of a buffer whose total is at most max_features NOTHING is written: not its records, not a counter (one above
+   * its capacity stays), not its cache entry. With fixed_counts no counter is written: the caller knows the new total, min(total, max_features).
+   * A buffer must not be named twice. Alignment: feats_base and buf_stride multiples of 4, desc and desc_stride multiples of 16.
+   * hipErrorInvalidValue, nothing launched: nslots 0 or above VKSIFT_HIP_GATHER_SLOTS, nsec above 16, max_features 0, a misaligned feats_base,
+   * buf_stride, desc or desc_stride, desc without norms or n_out_dev, found_post with found_buf_stride above 256 or without found_base,
+   * fixed_counts and found_base both given or both NULL. */
+  int vksift_hip_keep_strongest(uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, uint32_t nslots, uint32_t nsec, const uint32_t *sec_off,
+                                const uint32_t *sec_cap, const uint32_t *fixed_counts, uint32_t *found_base, uint32_t found_buf_stride, uint32_t *found_post,
+                                uint32_t max_features, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms, uint64_t norm_stride,
+                                uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s);
   int vksift_hip_match_2nn_async(const uint8_t *cache_desc, const uint32_t *cache_norm, const uint32_t *cache_n, const uint32_t *ids_a, const uint32_t *ids_b,
                                  uint32_t max_na, uint32_t max_nb, uint32_t nb_exact, uint32_t *redo, uint32_t *n_dev, uint8_t *matches, uint32_t nslots, uint64_t cache_desc_stride,
                                  uint64_t cache_norm_stride, uint64_t redo_slot_stride, uint64_t match_slot_stride, uint32_t n_slot_stride,

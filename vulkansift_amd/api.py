@@ -167,6 +167,10 @@ def lib():
     L.vksift_ext_downloadGuidedMatches.restype = None
     L.vksift_ext_getGuidedMatchTime.argtypes = [inst]
     L.vksift_ext_getGuidedMatchTime.restype = C.c_float
+    L.vksift_ext_keepStrongestFeatures.argtypes = [inst, u32, u32, u32]
+    L.vksift_ext_keepStrongestFeatures.restype = None
+    L.vksift_ext_getKeepStrongestTime.argtypes = [inst]
+    L.vksift_ext_getKeepStrongestTime.restype = C.c_float
     L.vksift_ext_setProfiling.argtypes = [inst, C.c_bool]
     L.vksift_ext_getDetectTimings.argtypes = [inst, C.POINTER(vksift_ext_DetectTimings)]
     L.vksift_ext_getAccumulatedDetectTimings.argtypes = [inst, C.POINTER(vksift_ext_DetectTimings), C.POINTER(u32), C.c_bool]
@@ -650,6 +654,15 @@ class Instance:
 
     def getGuidedMatchTime(self):
         return lib().vksift_ext_getGuidedMatchTime(self._h)
+
+    def keepStrongestFeatures(self, first_buffer, count, max_features):
+        """every SIFT buffer of [first_buffer, first_buffer + count) keeps its max_features strongest features (|DoG response|, ties by download
+        order), selected and compacted on the GPU (vksift_ext_keepStrongestFeatures); asynchronous like detectFeatures"""
+        lib().vksift_ext_keepStrongestFeatures(self._h, first_buffer, count, max_features)
+        _check_pending()
+
+    def getKeepStrongestTime(self):
+        return lib().vksift_ext_getKeepStrongestTime(self._h)
 
     def getMatchesNumberBatch(self, pair):
         n = lib().vksift_ext_getMatchesNumberBatch(self._h, pair)

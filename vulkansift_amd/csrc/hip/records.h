@@ -1,6 +1,6 @@
 /* records.h — the steps every launch that moves or addresses SIFT records shares (hip/records.hip, hip/verify.hip, hip/guided.hip), each
  * defined once: the record and section-table constants, the walk from a download-order row to a stored row, the decode of a pair table's
- * layout word, and the ordered append of a 1024-thread workgroup. The constants compile as C (host/vksift_internal.h takes them from
+ * layout word, the by-value launch arguments, and the ordered append of a 1024-thread workgroup. The constants compile as C (host/vksift_internal.h takes them from
  * here), the walk as host C++ too: plain integer arithmetic, checked row by row by tests/test_section_walk.py, which compiles this header
  * with the host compiler. The rest is device code. */
 #ifndef VKSIFT_RECORDS_H
@@ -65,6 +65,48 @@ template <class Cnt, class Off> static inline VKSIFT_HD uint32_t section_row(con
 }
 
 #if defined(__HIPCC__)
+
+#include "vksift_hip.h" /* VKSIFT_HIP_GATHER_SLOTS */
+
+/* ---- launch arguments -----------------------------------------------------------------------------------------------------------------
+ * What the launches over sectioned buffers take by value (vksift_hip_gather_sections, vksift_hip_pack_features, vksift_hip_keep_strongest): the
+ * section table every buffer of the launch shares, and the buffer each slot serves. */
+struct SectionTable
+{
+  uint32_t nsec;
+  uint32_t off[VKSIFT_MAX_SECTIONS];   // first feature of each section inside the buffer
+  uint32_t cap[VKSIFT_MAX_SECTIONS];   // capacity (stored = min(found, cap))
+  uint32_t fixed[VKSIFT_MAX_SECTIONS]; // used instead of found[] when found == nullptr (uploaded / packed buffers)
+};
+
+/* entries at and beyond nsec are zero; fixed_counts may be NULL (all zero) */
+static inline SectionTable section_table(uint32_t nsec, const uint32_t *sec_off, const uint32_t *sec_cap, const uint32_t *fixed_counts)
+{
+  SectionTable t;
+  t.nsec = nsec;
+  for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
+  {
+    t.off[o] = o < nsec ? sec_off[o] : 0u;
+    t.cap[o] = o < nsec ? sec_cap[o] : 0u;
+    t.fixed[o] = (o < nsec && fixed_counts) ? fixed_counts[o] : 0u;
+  }
+  return t;
+}
+
+// (all buffers of a batched detection in ONE launch: 512 buffers = 8 launches of 64 slots x 256 blocks until round 5 — 25 us each alone,
+// 330 us each queued behind the next detection's blur launches, 16 384 mostly idle workgroups per launch)
+struct GatherMap
+{
+  uint32_t buf[VKSIFT_HIP_GATHER_SLOTS]; // SIFT buffer index handled by the slot's workgroup(s)
+};
+
+static inline GatherMap gather_map(const uint32_t *buf_ids, uint32_t nslots)
+{
+  GatherMap m;
+  for (uint32_t i = 0; i < VKSIFT_HIP_GATHER_SLOTS; i++)
+    m.buf[i] = i < nslots ? buf_ids[i] : 0u;
+  return m;
+}
 
 /* ---- layout decode --------------------------------------------------------------------------------------------------------------------
  * One side of a pair-table slot, resolved into LDS: what section_row needs, the total and the buffer. */

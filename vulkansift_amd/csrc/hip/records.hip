@@ -26,24 +26,9 @@ __global__ void __launch_bounds__(256) k_gather_desc(const uint8_t *__restrict__
 // Gather the descriptors of a (sectioned or packed) SIFT buffer into dense rows in download order AND compute
 // their shifted norms, with the per-section feature counts read on the device (no host round trip):
 // row -> section by scanning the <= 16 section counts; eight lanes per row, 16 bytes per lane.
-struct SectionTable
-{
-  uint32_t nsec;
-  uint32_t off[VKSIFT_MAX_SECTIONS];   // first feature of each section inside the buffer
-  uint32_t cap[VKSIFT_MAX_SECTIONS];   // capacity (stored = min(found, cap))
-  uint32_t fixed[VKSIFT_MAX_SECTIONS]; // used instead of found[] when found == nullptr (uploaded / packed buffers)
-};
-
 struct SlotMap
 {
   uint32_t buf[64]; // SIFT buffer index handled by slot blockIdx.y
-};
-
-// (all buffers of a batched detection in ONE launch: 512 buffers = 8 launches of 64 slots x 256 blocks until round 5 — 25 us each alone,
-// 330 us each queued behind the next detection's blur launches, 16 384 mostly idle workgroups per launch)
-struct GatherMap
-{
-  uint32_t buf[VKSIFT_HIP_GATHER_SLOTS]; // SIFT buffer index handled by slot blockIdx.y
 };
 
 __global__ void __launch_bounds__(256) k_gather_sections(const uint8_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
@@ -191,17 +176,8 @@ extern "C"
     /* the kernel loads dwords from the records and stores 16-byte row pieces; the byte stride of the rows is handed to it in dwords */
     if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || ((uintptr_t)desc & 15u) || (desc_slot_stride & 15u))
       return (int)hipErrorInvalidValue;
-    SectionTable t;
-    t.nsec = nsec;
-    for (uint32_t o = 0; o < 16; o++)
-    {
-      t.off[o] = o < nsec ? sec_off[o] : 0u;
-      t.cap[o] = o < nsec ? sec_cap[o] : 0u;
-      t.fixed[o] = (o < nsec && fixed_counts) ? fixed_counts[o] : 0u;
-    }
-    GatherMap m;
-    for (uint32_t i = 0; i < VKSIFT_HIP_GATHER_SLOTS; i++)
-      m.buf[i] = i < nslots ? buf_ids[i] : 0u;
+    const SectionTable t = section_table(nsec, sec_off, sec_cap, fixed_counts);
+    const GatherMap m = gather_map(buf_ids, nslots);
     if (max_rows < pad_rows_to)
       max_rows = pad_rows_to;
     /* grid-stride over the rows that actually exist (count read on the device): ~4096 workgroups per launch whatever the batch — a
@@ -225,14 +201,7 @@ extern "C"
       return (int)hipErrorInvalidValue;
     if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || ((uintptr_t)out & 3u)) /* records are copied dword by dword */
       return (int)hipErrorInvalidValue;
-    SectionTable t;
-    t.nsec = nsec;
-    for (uint32_t o = 0; o < 16; o++)
-    {
-      t.off[o] = o < nsec ? sec_off[o] : 0u;
-      t.cap[o] = o < nsec ? sec_cap[o] : 0u;
-      t.fixed[o] = 0u;
-    }
+    const SectionTable t = section_table(nsec, sec_off, sec_cap, nullptr);
     SlotMap m;
     PackOffsets po;
     for (uint32_t i = 0; i < 64; i++)

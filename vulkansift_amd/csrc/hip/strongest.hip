@@ -1,0 +1,241 @@
+// strongest.hip — the feature budget (vksift_ext_keepStrongestFeatures; OpenCV's nfeatures, SiftGPU's -tc, PopSift's --filter-max-extrema; no
+// counterpart in the reference, whose only limit is the capacity of a section): every named SIFT buffer keeps its max_features strongest
+// records, in place and in download order, and with cache pointers the same launch leaves the matcher's view of the selected buffer.
+// One 1024-thread workgroup per buffer: the compaction is ordered, so it takes no atomics on global memory, and the section walk and the
+// ordered append are those of records.h.
+//
+//   key(row)   the record's intensity word (|DoG response|) with the sign bit cleared, compared as an unsigned integer: a total order on
+//              every bit pattern (-0 == +0 < denormals < normals < inf < NaN patterns); no float comparison takes place
+//   kept       the first min(total, max_features) rows by (key descending, download row ascending)
+//
+// 1. section table and counters -> LDS; total <= max_features: the workgroup returns, nothing of the buffer is written
+// 2. threshold key: radix select, most significant byte first, four passes over the keys with a 256-bin LDS histogram each (one dword per
+//    record and pass; the keys of the first STRONGEST_LDS_KEYS rows are held in LDS after the first pass)
+// 3. the select leaves how many rows AT the threshold are kept (the tie quota): max_features less the rows above it
+// 4. one ordered pass in rounds of 1024 rows: keep = above, or at the threshold with a tie rank below the quota; a kept row's place is its
+//    section's start plus the kept rows of that section in front of it. Every kept record of the round is loaded into registers, a barrier
+//    is passed, then it is stored: a destination never lies beyond its source (the kept rows in front of a row are at most the rows in
+//    front of it) and never beyond the round (it is the old place of a row at or in front of the source), and rounds run in order — so a
+//    store can only land on a record of an earlier round, already consumed, or of this round, already in registers.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vksift_hip.h"
+#include "hip/records.h"
+
+#define STRONGEST_LDS_KEYS 8192u
+#define STRONGEST_KEY_WORD 8u /* intensity: word 8 of the record's head */
+
+namespace
+{
+
+struct CacheEntry // the matcher's cache block (vksift_hip_gather_sections); rows == nullptr: none
+{
+  uint32_t *rows, *norms, *n;
+  uint64_t row_stride, norm_stride; // dwords per buffer
+  uint32_t n_stride, pad_rows_to;
+};
+
+__global__ void __launch_bounds__(1024) k_keep_strongest(uint8_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
+                                                         uint32_t *__restrict__ found_base, uint32_t found_buf_stride, uint32_t *__restrict__ found_post,
+                                                         uint32_t max_features, CacheEntry cache)
+{
+  __shared__ uint32_t off_s[VKSIFT_MAX_SECTIONS], cnt_s[VKSIFT_MAX_SECTIONS], kept_s[VKSIFT_MAX_SECTIONS];
+  __shared__ uint32_t hist[256], keys_s[STRONGEST_LDS_KEYS];
+  __shared__ uint32_t wave_tot[16], tie_carry, keep_carry, sel_s[2];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t bufi = map.buf[blockIdx.x];
+  uint32_t *feats = (uint32_t *)(feats_base + (size_t)bufi * buf_stride);
+  uint32_t *found = found_base ? found_base + (size_t)bufi * found_buf_stride : nullptr;
+
+  // ---- 1
+  if (tid < VKSIFT_MAX_SECTIONS)
+  {
+    const uint32_t raw = tid < tab.nsec ? (found ? found[tid] : tab.fixed[tid]) : 0u;
+    off_s[tid] = tab.off[tid];
+    cnt_s[tid] = section_stored(raw, tab.cap[tid]); // (cap is zero from nsec on)
+    kept_s[tid] = 0;
+  }
+  if (tid == 0)
+    tie_carry = 0, keep_carry = 0;
+  __syncthreads();
+  uint32_t cnt[VKSIFT_MAX_SECTIONS];
+  const uint32_t total = section_counts(VKSIFT_MAX_SECTIONS, [&](uint32_t o) { return cnt_s[o]; }, cnt_s, cnt);
+  if (total <= max_features)
+    return;
+
+  auto key_at = [&](uint32_t row) { return feats[(size_t)section_row(cnt, off_s, row) * VKSIFT_RECORD_WORDS + STRONGEST_KEY_WORD] & 0x7FFFFFFFu; };
+
+  // ---- 2, 3
+  uint32_t prefix = 0, want = max_features; // the want-th largest of the keys that start with `prefix`
+  for (uint32_t pass = 0; pass < 4u; pass++)
+  {
+    const uint32_t shift = 24u - 8u * pass, decided = pass ? 0xFFFFFFFFu << (shift + 8u) : 0u;
+    if (tid < 256u)
+      hist[tid] = 0;
+    __syncthreads();
+    for (uint32_t row = tid; row < total; row += 1024u)
+    {
+      uint32_t key;
+      if (pass == 0u)
+      {
+        key = key_at(row);
+        if (row < STRONGEST_LDS_KEYS)
+          keys_s[row] = key;
+      }
+      else
+        key = row < STRONGEST_LDS_KEYS ? keys_s[row] : key_at(row);
+      if ((key & decided) == prefix)
+        atomicAdd(&hist[(key >> shift) & 255u], 1u); // LDS
+    }
+    __syncthreads();
+    if (tid < 64u)
+    {
+      // lane l owns bins 255 - 4l .. 252 - 4l: an inclusive scan over the lanes counts the keys from the top bin down
+      uint32_t h[4], sum = 0;
+      for (uint32_t i = 0; i < 4u; i++)
+        h[i] = hist[255u - 4u * tid - i], sum += h[i];
+      uint32_t incl = sum;
+      for (uint32_t d = 1; d < 64u; d <<= 1)
+      {
+        const uint32_t below = __shfl_up(incl, d, 64);
+        if (lane >= d)
+          incl += below;
+      }
+      uint32_t above = incl - sum;
+      if (above < want && want <= incl) // one lane: the keys that start with `prefix` are at least `want`
+      {
+        uint32_t bin = 255u - 4u * tid;
+        for (uint32_t i = 0; i < 3u && want > above + h[i]; i++)
+          above += h[i], bin--;
+        sel_s[0] = bin, sel_s[1] = want - above;
+      }
+    }
+    __syncthreads();
+    prefix |= sel_s[0] << shift;
+    want = sel_s[1];
+  }
+  const uint32_t threshold = prefix, quota = want; // `quota` of the rows at the threshold are kept, max_features - quota rows lie above it
+
+  // ---- 4
+  uint32_t *c_rows = nullptr, *c_norms = nullptr;
+  if (cache.rows)
+  {
+    c_rows = cache.rows + (size_t)bufi * cache.row_stride;
+    c_norms = cache.norms + (size_t)bufi * cache.norm_stride;
+  }
+  for (uint32_t base = 0; base < total; base += 1024u)
+  {
+    const uint32_t row = base + tid;
+    uint32_t key = 0, sec = 0, src_row = 0;
+    const bool valid = row < total;
+    if (valid)
+    {
+      key = row < STRONGEST_LDS_KEYS ? keys_s[row] : key_at(row);
+      src_row = section_row(cnt, off_s, row);
+      uint32_t first = 0;
+      VKSIFT_UNROLL
+      for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
+      {
+        if (row >= first && row < first + cnt[o])
+          sec = o;
+        first += cnt[o];
+      }
+    }
+    const bool tie = valid && key == threshold;
+    const uint32_t tie_rank = ordered_keep(tie, wave_tot, tie_carry);
+    const bool keep = valid && (key > threshold || (tie && tie_rank < quota));
+    const uint32_t out_row = ordered_keep(keep, wave_tot, keep_carry); // its download-order row afterwards
+    // kept rows of every section, this round's included: those of the sections in front of a row's own are complete when it is placed
+    VKSIFT_UNROLL
+    for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
+    {
+      const unsigned long long bal = __ballot(keep && sec == o);
+      if (lane == 0u && bal)
+        atomicAdd(&kept_s[o], (uint32_t)__popcll(bal)); // LDS
+    }
+    __syncthreads();
+    uint32_t rec[VKSIFT_RECORD_WORDS], dst_row = 0;
+    if (keep)
+    {
+      uint32_t in_front = 0;
+      VKSIFT_UNROLL
+      for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
+        in_front += o < sec ? kept_s[o] : 0u;
+      dst_row = off_s[sec] + (out_row - in_front);
+      const uint32_t *src = feats + (size_t)src_row * VKSIFT_RECORD_WORDS;
+      VKSIFT_UNROLL
+      for (uint32_t w = 0; w < VKSIFT_RECORD_WORDS; w++)
+        rec[w] = src[w];
+    }
+    __builtin_amdgcn_s_waitcnt(0); // every record of the round is in registers ...
+    __syncthreads();               // ... in every wave, before any is overwritten
+    if (keep)
+    {
+      if (dst_row != src_row)
+      {
+        uint32_t *dst = feats + (size_t)dst_row * VKSIFT_RECORD_WORDS;
+        VKSIFT_UNROLL
+        for (uint32_t w = 0; w < VKSIFT_RECORD_WORDS; w++)
+          dst[w] = rec[w];
+      }
+      if (c_rows && out_row < max_features) // (always: max_features rows are kept; the entry holds no more)
+      {
+        // the bytes k_gather_sections writes for the selected buffer: the 128 descriptor bytes and their shifted norm
+        uint32_t s2 = 0, s1 = 0;
+        VKSIFT_UNROLL
+        for (uint32_t q = 0; q < 8u; q++)
+        {
+          const uint32_t *d = rec + VKSIFT_RECORD_HEAD_WORDS + 4u * q;
+          *(uint4 *)(c_rows + (size_t)out_row * 32u + 4u * q) = uint4{d[0], d[1], d[2], d[3]};
+          VKSIFT_UNROLL
+          for (uint32_t k = 0; k < 4u; k++)
+            s2 = __builtin_amdgcn_udot4(d[k], d[k], s2, false), s1 = __builtin_amdgcn_udot4(d[k], 0x01010101u, s1, false);
+        }
+        c_norms[out_row] = s2 - 256u * s1 + 128u * 128u * 128u;
+      }
+    }
+  }
+  // the counters: on the device, and posted to the host mirror by this launch (mapped pinned memory; no dependent copy)
+  if (tid < tab.nsec)
+  {
+    if (found)
+      found[tid] = kept_s[tid];
+    if (found_post)
+      found_post[(size_t)bufi * found_buf_stride + tid] = kept_s[tid];
+  }
+  if (c_rows)
+  {
+    if (tid == 0)
+      cache.n[(size_t)bufi * cache.n_stride] = max_features;
+    // quirk Q6: all-zero rows from the row count up to pad_rows_to
+    for (uint32_t i = max_features * 32u + tid; i < cache.pad_rows_to * 32u && max_features < cache.pad_rows_to; i += 1024u)
+    {
+      c_rows[i] = 0u;
+      if ((i & 31u) == 0u)
+        c_norms[i >> 5] = 128u * 128u * 128u;
+    }
+  }
+}
+
+} // namespace
+
+extern "C" int vksift_hip_keep_strongest(uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, uint32_t nslots, uint32_t nsec, const uint32_t *sec_off,
+                                         const uint32_t *sec_cap, const uint32_t *fixed_counts, uint32_t *found_base, uint32_t found_buf_stride,
+                                         uint32_t *found_post, uint32_t max_features, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms,
+                                         uint64_t norm_stride, uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s)
+{
+  if (nslots < 1 || nslots > VKSIFT_HIP_GATHER_SLOTS || nsec > VKSIFT_MAX_SECTIONS || max_features < 1 || (found_post && found_buf_stride > 256u) ||
+      (fixed_counts != nullptr) == (found_base != nullptr))
+    return (int)hipErrorInvalidValue;
+  /* records move dword by dword; cache rows are stored 16 bytes at a time, the byte stride of the rows is handed to the kernel in dwords */
+  if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || (desc && (((uintptr_t)desc & 15u) || (desc_stride & 15u) || !norms || !n_out_dev)))
+    return (int)hipErrorInvalidValue;
+  /* (the mirror without device counters has nothing to mirror) */
+  if (found_post && !found_base)
+    return (int)hipErrorInvalidValue;
+  const CacheEntry cache = {(uint32_t *)desc, desc ? norms : nullptr, desc ? n_out_dev : nullptr, desc_stride / 4u, norm_stride, n_stride, pad_rows_to};
+  hipLaunchKernelGGL(k_keep_strongest, dim3(nslots), dim3(1024), 0, (hipStream_t)s, feats_base, buf_stride, gather_map(buf_ids, nslots),
+                     section_table(nsec, sec_off, sec_cap, fixed_counts), found_base, found_buf_stride, found_post, max_features, cache);
+  return (int)hipGetLastError();
+}

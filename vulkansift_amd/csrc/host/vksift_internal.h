@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -306,6 +306,7 @@ struct vksift_Instance_T
   vksift_hip_event ev_g[2];
   vksift_hip_event ev_r[2]; /* profiling: the refinement interval (created by the first refinement) */
   vksift_hip_event ev_rf[2]; /* the same for the fundamental matrices' refinement */
+  vksift_hip_event ev_ks[2]; /* profiling: the feature selection's interval (vksift_strongest.c; created by the first one that is timed) */
   bool desc_start_valid, input_free_valid, staging_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];
   uint64_t det_seq, det_done; /* last detection issued / highest one known to have completed */
@@ -315,6 +316,7 @@ struct vksift_Instance_T
   ProfSet prof[2]; /* two event sets: the host may enqueue one detection ahead of the one being timed */
   int prof_cur;
   bool match_timing_valid;
+  bool ks_timing_valid;
   double acc_ms[8]; /* upload, pyramid (octave 0), extrema stage, orientation, descriptor, total, extrema scan kernel alone, pyramid (all octaves) */
   uint32_t acc_calls;
   uint64_t acc_blur_launches, acc_blur_launches_all, acc_alg_bytes, acc_scan_bytes;
@@ -401,6 +403,8 @@ VKSIFT_INTERNAL void wait_for_buffer(vksift_Instance inst, uint32_t buf);
 VKSIFT_INTERNAL uint32_t buffer_counts(vksift_Instance inst, uint32_t buf, uint32_t *cnt, bool log_lost);
 
 /* vksift_match.c */
+/* the same section layout (so one kernel launch can serve both buffers)? */
+VKSIFT_INTERNAL bool same_layout(const BufferInfo *x, const BufferInfo *y);
 VKSIFT_INTERNAL MatchScratch fwd_scratch(vksift_Instance inst);
 VKSIFT_INTERNAL int refresh_match_cache(vksift_Instance inst, const uint32_t *ids, uint32_t count);
 VKSIFT_INTERNAL uint32_t rows_bound(vksift_Instance inst, uint32_t id);

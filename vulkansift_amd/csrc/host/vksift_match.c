@@ -6,8 +6,7 @@
 /* ------------------------------------------------------------------------------------------------ */
 /* matching (vulkansift.c:417-462, sift_memory.c:957-1058, sift_matcher.c:408-486)                  */
 /* ------------------------------------------------------------------------------------------------ */
-/* Same section layout (so one kernel launch can serve both buffers)? */
-static bool same_layout(const BufferInfo *x, const BufferInfo *y)
+bool same_layout(const BufferInfo *x, const BufferInfo *y)
 {
   if (x->nb_sections != y->nb_sections)
     return false;

@@ -195,7 +195,7 @@ typedef struct
 {
   size_t field;
   uint16_t count, step;
-  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_refine.c), destroyed here */
+  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_refine.c, vksift_strongest.c), destroyed here */
 } Handle;
 #define EVENTS(f, n, step, lazy) {FIELD(f), n, step, false, lazy}
 #define STREAM(f) {FIELD(f), 1, 0, true, false}
@@ -211,7 +211,7 @@ static const Handle handles[] = {
     EVENTS(prof[0].ev_scan, 2, sizeof(ProfSet), false), EVENTS(ev_m, 2, sizeof(vksift_hip_event), false),
     EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_v, 2, sizeof(vksift_hip_event), true),
     EVENTS(ev_gtab, 1, 0, true), EVENTS(ev_g, 2, sizeof(vksift_hip_event), true), EVENTS(ev_r, 2, sizeof(vksift_hip_event), true),
-    EVENTS(ev_rf, 2, sizeof(vksift_hip_event), true),
+    EVENTS(ev_rf, 2, sizeof(vksift_hip_event), true), EVENTS(ev_ks, 2, sizeof(vksift_hip_event), true),
 };
 #define N_HANDLES (sizeof(handles) / sizeof(handles[0]))
 
