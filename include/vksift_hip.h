@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 7u      /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version) */
+#define VKSIFT_HIP_ABI_VERSION 8u      /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version) */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -356,7 +356,14 @@ extern "C"
                                 size_t scratch_u32, uint8_t *matches, vksift_hip_stream s);
   /* The two halves of vksift_hip_match_2nn_desc, for callers that overlap the pre-pass of A with the arrival of B (the sharded
    * matcher: RCCL all-gather of B): norms[i] = sum over the 128 bytes of (byte - 128)^2; scratch:
-   * scratch_u32 >= vksift_hip_match_scratch_u32(na, nb) - 2*na - nb words (checked like above).
+   * scratch_u32 >= vksift_hip_match_scratch_u32(na, nb) - na - nb words (= 72 + 513 na; checked like above. Up to ABI version 7 the figure was one
+   * na smaller, and the cell scan wrote past it: its row list takes up to na + 4 words in front of the 512 na words of the rows' lists).
+   * vksift_hip_match_2nn_prenormed (tests/test_gpu_match_launchers.py sweeps the three matcher entries against tests/np_match.py, byte for byte) —
+   * READ: the na rows of 128 bytes at desc_a and the nb >= 2 rows at desc_b (16-byte aligned), norm_a[0..na), norm_b[0..nb). WRITTEN: the na records
+   * of 20 bytes at matches (4-byte aligned), idx_a = a_index_base + row modulo 2^32; scratch[0..scratch_u32) holds unspecified values afterwards
+   * (16-byte aligned; it needs no initialisation). Nothing else: not a record at or beyond na, not a word of scratch at or beyond scratch_u32.
+   * vksift_hip_match_2nn_desc — the same, the norms being computed into the first na + nb words of its scratch. na == 0: both return 0 and launch
+   * nothing. hipErrorInvalidValue, nothing launched: nb < 2, scratch NULL, scratch_u32 below the figure.
    * vksift_hip_shifted_norms — READ: the n rows of 128 bytes at desc (16-byte aligned: rows are loaded 16 bytes at a time). WRITTEN: norms[0..n),
    * exact (0 for a row of 128s, 128^3 for a row of zeros). Nothing else; n == 0 returns 0 and launches nothing. */
   int vksift_hip_shifted_norms(const uint8_t *desc, uint32_t n, uint32_t *norms, vksift_hip_stream s);
@@ -407,7 +414,17 @@ extern "C"
    * packed-key kernel's range launches that kernel only — the pruning kernels' grids for larger reference sets are not queued at all. nb_exact: max_nb
    * is the largest N_B itself (every count has reached the host), not a capacity bound: only then are the pruning kernels queued for the slots
    * beyond the packed-key range; with a mere bound the packed-key kernel serves every slot of the batch whatever its N_B (exact for any size: it
-   * walks B in super-chunks of 4096 columns; beyond 32 768 rows the pruning kernel is the faster one, which is all the regime was for). */
+   * walks B in super-chunks of 4096 columns; beyond 32 768 rows the pruning kernel is the faster one, which is all the regime was for).
+   * READ, per slot i: cache_n[ids_a[i]], cache_n[ids_b[i]] (cache_n is dense: one word per entry); rows [0, N_A) of entry ids_a[i] and rows [0, max(N_B, 2))
+   * of entry ids_b[i] (at cache_desc + id * cache_desc_stride, 16-byte aligned, stride a multiple of 16) with their norms (cache_norm + id *
+   * cache_norm_stride words): an entry of fewer than two rows holds zero rows with norm 128^3 up to row 2, as vksift_hip_gather_sections leaves it
+   * (quirk Q6). Never a row or a norm at or beyond that, whatever it holds; entries in any order, one entry as A and B, one entry in several slots.
+   * WRITTEN, per slot: n_dev[i * n_slot_stride + 0..1] = {N_A, N_B} — the counts as stored, N_B not raised to two —, and, unless max_na is 0, the N_A
+   * records at matches + i * match_slot_stride (a multiple of 4) as vksift_hip_match_2nn_prenormed writes them with a_index_base 0. redo[i *
+   * redo_slot_stride + 0 .. max_na) and partial_scratch[0 .. 5 * max_na * VKSIFT_HIP_MATCH_CHUNKS) hold unspecified values afterwards. Nothing else: not a
+   * record at or beyond N_A, not the padding of a stride, not the other words of an n_slot_stride. max_na >= every N_A is the CALLER's to provide (the
+   * grids and the scratch are sized by it); a larger value gives the same bytes; max_na == 0 writes the count words only. hipErrorInvalidValue, nothing
+   * launched: nslots 0 or above VKSIFT_HIP_MATCH_SLOTS. */
   /* Download packing for a batch of up to 64 SIFT buffers that share one section table (the buffers of one batched detection):
    * slot i copies the stored records of buffer buf_ids[i] — sections in order, min(found, capacity) each, the order
    * vksift_downloadFeatures returns (sift_memory.c:957-1047, 1160-1196) — as dense 164-byte records to out + out_rows[i] * 164.

@@ -150,13 +150,16 @@ def test_match_float_collisions(vk, oracle):
                                           (33000, 5000, True), (40000, 300, False), (70001, 130, True), (2600, 2500, False),
                                           (1536, 4096, True), (1537, 4096, True), (1536, 4097, True), (4096, 15625, True), (4097, 15622, True)])
 def test_match_ties_in_every_kernel_regime(vk, oracle, na, nb, via_ptr):
-    """quirk Q7 (d(b0) == d(b1): index 1 first), duplicate B rows (earlier index first) and exact zero distances in the one-launch
-    small kernel and in the stream-decomposed kernel — few row blocks with the piece count at its cap (300 x 33000), runs that
-    end one row block and start the next, more workgroups than tiles (70001 x 130) — through the instance (device-side counts)
-    and through the device-pointer entry. The last five cases sit on the planner's branch boundaries of the device-pointer entry:
-    the last shape of the one-launch small kernel (1536 x 4096) and the first two past it (stream decomposition), exactly
-    64 000 000 distances (4096 x 15625: the first shape of k_match_pk<2,64>, several pieces of B + merge) and the first shape of
-    k_match_pk<4,128> (4097 x 15622)"""
+    """quirk Q7 (d(b0) == d(b1): index 1 first), duplicate B rows (earlier index first) and exact zero distances in every kernel the two
+    entries reach. Through the instance (device-side counts, via_ptr False): the one-launch small kernel up to 1536 query rows and the
+    stream-decomposed kernel above — runs that end one row block and start the next, more workgroups than tiles (40000 x 300). Through
+    the device-pointer entry (via_ptr True), whose planner tests the packed-key case, then the small case, and sends EVERYTHING else to
+    the cell scan (hip/match.hip; the stream decomposition serves this entry only under VKSIFT_MATCH_SCAN=0, which
+    tests/test_gpu_match_launchers.py runs in a child process): the small kernel (1200 x 900, and its last shape 1536 x 4096), the cell
+    scan — the first two shapes past the small kernel (1537 x 4096, 1536 x 4097), few row blocks with the piece count at its cap
+    (300 x 33000), more workgroups than tiles (70001 x 130), 1500 x 5000, 20000 x 2100 —, exactly 64 000 000 distances (4096 x 15625:
+    the first shape of k_match_pk<2,64>, several pieces of B + merge), the first shape of k_match_pk<4,128> (4097 x 15622) and
+    33000 x 5000 in the same kernel"""
     rng = np.random.default_rng(na + nb)
     a = vk.gen_synthetic_descriptors(na, na)
     b = vk.gen_synthetic_descriptors(nb, nb)

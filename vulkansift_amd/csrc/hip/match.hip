@@ -30,15 +30,20 @@
 //   entry                                   problem                                   kernels
 //   ---------------------------------------------------------------------------------------------------------------------------------
 //   vksift_hip_match_2nn_async, n pairs     every slot with N_B <= 32 768             k_match_pk<8,128> (packed keys, branch free) + k_match_redo
-//   (vksift_ext_matchFeaturesBatch,         a slot with N_B > 32 768 (the host's      + k_match_mfma<1,4,64> (N_A <= 32 768) / <2,4,64> (above): the pruning
-//    the frames of a batched detection)     bound max_nb says whether one can exist)    kernel on grids that walk the slots; not queued when max_nb <= 32 768
+//   (vksift_ext_matchFeaturesBatch,         a slot with N_B > 32 768 that the host    + k_match_mfma<1,4,64> (N_A <= 32 768) / <2,4,64> (above): the pruning
+//    the frames of a batched detection)     KNOWS of (nb_exact and max_nb > 32 768;     kernel on grids that walk the slots; under a mere bound it is not queued
+//                                           VKSIFT_MATCH_PK=0: every slot)              and k_match_pk serves every slot whatever its N_B
 //   vksift_hip_match_2nn_async, 1 pair      N_A <= 1 536 (count on the device)        k_match_mfma_split (one launch, B split over the waves)
 //   (vksift_matchFeatures)                  N_A >  1 536                              k_match_mfma<2,8,128> stream decomposition + k_match_merge
 //                                                                                     (both are queued: the count decides on the device) + k_match_redo
-//   vksift_hip_match_2nn_desc / _prenormed  N_A x N_B >= 64 M and N_B <= 32 768        k_match_pk on row blocks x strided pieces of B (+ k_match_merge)
-//   (device pointers: the sharded matcher,  N_A <= 1 536 and N_B <= 4 096             k_match_mfma_split
-//    vksift_ext_matchSharded)               N_B > 32 768 (BASELINE config 4)          k_match_scan32<3,8,256> -> k_match_fix -> k_match_redo_rows
-//                                           anything else                             k_match_mfma<2,8,128> stream decomposition + k_match_merge
+//   vksift_hip_match_2nn_desc / _prenormed  tested in this order (counts on the host):
+//   (device pointers: the sharded matcher,  1. N_A x N_B >= 64 M and N_B <= 32 768    k_match_pk<2,64> (N_A <= 4 096) / <4,128> on row blocks x strided pieces of B
+//    vksift_ext_matchSharded)                                                         (+ k_match_merge) + k_match_redo
+//                                           2. N_A <= 1 536 and N_B <= 4 096          k_match_mfma_split + k_match_redo
+//                                           3. anything else (1 537 x 2, 1 x 4 097,   k_match_scan32<3,8,256> -> k_match_fix -> k_match_redo_rows: the cell scan
+//                                              1 953 x 32 768, BASELINE config 4)     (VKSIFT_TUNE_SCAN_FORM = 1: <2,4,128>)
+//                                              ... with VKSIFT_MATCH_SCAN=0           k_match_mfma<2,8,128> stream decomposition + k_match_merge + k_match_redo;
+//                                                                                     by default NO shape reaches the stream decomposition through these entries
 //
 //   k_match_redo / k_match_redo_rows replay the reference's float loop for the rows a kernel flagged (a distance >= 2^22, a packed key that
 //   failed its verification, a tie the cell scan cannot order): zero rows for real descriptors.
@@ -1501,7 +1506,9 @@ extern "C"
       return 0;
     if (nb < 2)
       return (int)hipErrorInvalidValue; /* callers pad B to two rows (quirk Q6) */
-    if (scratch == nullptr || scratch_u32 < vksift_hip_match_scratch_u32(na, nb) - 2u * (size_t)na - (size_t)nb)
+    /* what the cell scan lays out below: up to na + 4 words of row list and padding, then 16 words for each of the 32 pieces of a row
+     * (72 + 512 na, the figure up to ABI version 7, was overrun by its last row block from 30 pieces on: 200 x 7 680 wrote 100 words past it) */
+    if (scratch == nullptr || scratch_u32 < vksift_hip_match_scratch_u32(na, nb) - (size_t)na - (size_t)nb)
       return (int)hipErrorInvalidValue; /* a buffer sized by an older formula: nothing is launched */
     const SlotIds noids{};
     uint32_t *redo = scratch, *partial = redo + na; /* scratch of the kernels that flag rows: redo[na], then the partial lists */
@@ -1520,7 +1527,8 @@ extern "C"
     else if (match_use(MATCH_SCAN))
     {
       /* large reference sets: the branch-free cell scan, the exact finish from the descriptor bytes, the (rare) replay of tied rows.
-       * Scratch: [row list: 1 + na][pad to 16 B][cell lists: 16 * na * VKSIFT_HIP_MATCH_CHUNKS] (VKSIFT_HIP_MATCH_SCRATCH_U32). */
+       * Scratch: [row list: 1 + na][pad to 16 B][cell lists: 16 * na * VKSIFT_HIP_MATCH_CHUNKS]: at most na + 4 + 512 na words, inside the
+       * 72 + 513 na checked above. */
       uint32_t *list = scratch;
       uint32_t *cells = (uint32_t *)(((uintptr_t)(scratch + na + 1u) + 15u) & ~(uintptr_t)15u); /* 16 words per (row, piece) */
       /* Eight waves per workgroup, one workgroup per CU (the two waves of a SIMD share the staged tile: half the staging per MFMA of
