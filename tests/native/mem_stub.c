@@ -182,9 +182,9 @@ int main(int argc, char **argv)
     {
       /* every block and event that somebody else allocates on first use (the ELSEWHERE rows of blocks[], the lazy rows of handles[]) */
       const Named lazy[] = {NAMED(d_cache_desc, MEM_DEVICE), NAMED(d_cache_norm, MEM_DEVICE), NAMED(d_match_partial, MEM_DEVICE), NAMED(h_matches, MEM_PINNED),
-                            NAMED(rev.matches, MEM_DEVICE),  NAMED(rev.redo, MEM_DEVICE),     NAMED(rev.match_n, MEM_DEVICE),     NAMED(d_filtered, MEM_DEVICE),
-                            NAMED(d_filtered_n, MEM_DEVICE), NAMED(h_filtered_n, MEM_PINNED), NAMED(filt_ids, MEM_HEAP),          NAMED(d_corr, MEM_DEVICE),
-                            NAMED(d_vmask, MEM_DEVICE),      NAMED(d_vres, MEM_DEVICE),       NAMED(d_vscratch, MEM_DEVICE),      NAMED(h_vres, MEM_PINNED),
+                            NAMED(rev.matches, MEM_DEVICE),  NAMED(rev.redo, MEM_DEVICE),     NAMED(rev.match_n, MEM_DEVICE),     NAMED(res[PR_FILTERED].d_payload, MEM_DEVICE),
+                            NAMED(res[PR_FILTERED].d_words, MEM_DEVICE), NAMED(res[PR_FILTERED].h_words, MEM_PINNED), NAMED(filt_ids, MEM_HEAP), NAMED(d_corr, MEM_DEVICE),
+                            NAMED(res[PR_VERIFY_H].d_payload, MEM_DEVICE), NAMED(res[PR_VERIFY_H].d_words, MEM_DEVICE), NAMED(d_vscratch, MEM_DEVICE), NAMED(res[PR_VERIFY_H].h_words, MEM_PINNED),
                             NAMED(h_vtab, MEM_PINNED),       NAMED(dl_row, MEM_HEAP),         NAMED(h_post[0], MEM_PINNED),       NAMED(h_post[1], MEM_PINNED)};
       const size_t n = sizeof(lazy) / sizeof(lazy[0]);
       if (!strcmp(cmd, "lazy"))
@@ -194,7 +194,7 @@ int main(int argc, char **argv)
           ok = mem_ensure(lazy[i].field, 64 + i, lazy[i].kind) && ok;
         for (uint32_t k = 0; k < VKSIFT_DL_CHUNKS; k++)
           inst->dl_ev[k] = vksift_hip_event_create();
-        inst->ev_vtab = vksift_hip_event_create(), inst->ev_v[0] = vksift_hip_event_create(), inst->ev_v[1] = vksift_hip_event_create();
+        inst->ev_vtab = vksift_hip_event_create(), inst->timer[T_VERIFY].ev[0] = vksift_hip_event_create(), inst->timer[T_VERIFY].ev[1] = vksift_hip_event_create();
         printf("lazy ok=%d\n", ok);
       }
       else

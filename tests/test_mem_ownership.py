@@ -256,7 +256,7 @@ def test_ensure_allocates_once_and_a_half_failed_group_only_what_is_missing(harn
     lines = harness(*new(SMALL), "ensure", "d_corr", 4096, "ensure", "d_corr", 4096, "ensure", "filt_ids", 64, "ensure", "filt_ids", 64, "destroy", "ledger")
     assert [x for x in calls(lines) if x[0] == "D"] == [("D", 4096)]
     assert_clean(lines)
-    group = ("ensure", "d_corr", 1000, "ensure", "d_vmask", 2000, "ensure", "h_vres", 3000)
+    group = ("ensure", "d_corr", 1000, "ensure", "res[PR_VERIFY_H].d_payload", 2000, "ensure", "res[PR_VERIFY_H].h_words", 3000)
     lines = harness(*new(SMALL), "fail", 2, *group, *group, "destroy", "ledger")
     oks = [fields(l)["ok"] for l in lines if l.startswith("ensure ")]
     assert oks == [1, 0, 1, 1, 1, 1]

@@ -540,6 +540,22 @@ class Instance:
             _check_pending()
         return out
 
+    def _pair_record(self, fn, dtype, pair):
+        """one of the get* accessors of a pair's result record, as a structured scalar"""
+        out = np.zeros(1, dtype)
+        fn(self._h, pair, out.ctypes.data)
+        _check_pending()
+        return out[0]
+
+    def _pair_mask(self, fn, pair):
+        """one of the download*InlierMask accessors: a bool per filtered match of the pair"""
+        n = lib().vksift_ext_getFilteredMatchesNumber(self._h, pair)
+        _check_pending()
+        out = np.zeros(n, np.uint8)
+        fn(self._h, pair, out.ctypes.data)
+        _check_pending()
+        return out.astype(bool)
+
     def verifyHomography(self, nb_hypotheses=1024, threshold_px=2.5, seed=0):
         """RANSAC homography of every pair of the last matchFeaturesFiltered call, on the GPU (vksift_ext_verifyHomography)."""
         lib().vksift_ext_verifyHomography(self._h, nb_hypotheses, threshold_px, seed)
@@ -547,18 +563,10 @@ class Instance:
 
     def getHomography(self, pair=0):
         """structured scalar (HOMOGRAPHY_DTYPE): H 3x3 float32 (pixels of A -> B, H[2, 2] == 1), nb_matches, nb_inliers, best_hypothesis, valid"""
-        out = np.zeros(1, HOMOGRAPHY_DTYPE)
-        lib().vksift_ext_getHomography(self._h, pair, out.ctypes.data)
-        _check_pending()
-        return out[0]
+        return self._pair_record(lib().vksift_ext_getHomography, HOMOGRAPHY_DTYPE, pair)
 
     def downloadInlierMask(self, pair=0):
-        n = lib().vksift_ext_getFilteredMatchesNumber(self._h, pair)
-        _check_pending()
-        out = np.zeros(n, np.uint8)
-        lib().vksift_ext_downloadInlierMask(self._h, pair, out.ctypes.data)
-        _check_pending()
-        return out.astype(bool)
+        return self._pair_mask(lib().vksift_ext_downloadInlierMask, pair)
 
     def verifyFundamental(self, nb_hypotheses=1024, threshold_px=2.5, seed=0):
         """RANSAC fundamental matrix of every pair of the last matchFeaturesFiltered call, on the GPU (vksift_ext_verifyFundamental); its results
@@ -569,18 +577,10 @@ class Instance:
     def getFundamental(self, pair=0):
         """structured scalar (FUNDAMENTAL_DTYPE): F 3x3 float32 (pixels, (xb, yb, 1) F (xa, ya, 1)^T = 0, largest |entry| in [1, 2)), nb_matches,
         nb_inliers, best_hypothesis, best_root, valid"""
-        out = np.zeros(1, FUNDAMENTAL_DTYPE)
-        lib().vksift_ext_getFundamental(self._h, pair, out.ctypes.data)
-        _check_pending()
-        return out[0]
+        return self._pair_record(lib().vksift_ext_getFundamental, FUNDAMENTAL_DTYPE, pair)
 
     def downloadFundamentalInlierMask(self, pair=0):
-        n = lib().vksift_ext_getFilteredMatchesNumber(self._h, pair)
-        _check_pending()
-        out = np.zeros(n, np.uint8)
-        lib().vksift_ext_downloadFundamentalInlierMask(self._h, pair, out.ctypes.data)
-        _check_pending()
-        return out.astype(bool)
+        return self._pair_mask(lib().vksift_ext_downloadFundamentalInlierMask, pair)
 
     def getVerifyTime(self):
         return lib().vksift_ext_getVerifyTime(self._h)
@@ -593,18 +593,10 @@ class Instance:
 
     def getRefinedHomography(self, pair=0):
         """structured scalar (REFINED_HOMOGRAPHY_DTYPE): H 3x3 float32 (pixels of A -> B, H[2, 2] == 1), nb_matches, nb_inliers, rounds, valid"""
-        out = np.zeros(1, REFINED_HOMOGRAPHY_DTYPE)
-        lib().vksift_ext_getRefinedHomography(self._h, pair, out.ctypes.data)
-        _check_pending()
-        return out[0]
+        return self._pair_record(lib().vksift_ext_getRefinedHomography, REFINED_HOMOGRAPHY_DTYPE, pair)
 
     def downloadRefinedInlierMask(self, pair=0):
-        n = lib().vksift_ext_getFilteredMatchesNumber(self._h, pair)
-        _check_pending()
-        out = np.zeros(n, np.uint8)
-        lib().vksift_ext_downloadRefinedInlierMask(self._h, pair, out.ctypes.data)
-        _check_pending()
-        return out.astype(bool)
+        return self._pair_mask(lib().vksift_ext_downloadRefinedInlierMask, pair)
 
     def getRefineTime(self):
         return lib().vksift_ext_getRefineTime(self._h)
@@ -617,18 +609,10 @@ class Instance:
 
     def getRefinedFundamental(self, pair=0):
         """structured scalar (REFINED_FUNDAMENTAL_DTYPE): F 3x3 float32 (pixels, largest |entry| in [1, 2)), nb_matches, nb_inliers, rounds, valid"""
-        out = np.zeros(1, REFINED_FUNDAMENTAL_DTYPE)
-        lib().vksift_ext_getRefinedFundamental(self._h, pair, out.ctypes.data)
-        _check_pending()
-        return out[0]
+        return self._pair_record(lib().vksift_ext_getRefinedFundamental, REFINED_FUNDAMENTAL_DTYPE, pair)
 
     def downloadRefinedFundamentalInlierMask(self, pair=0):
-        n = lib().vksift_ext_getFilteredMatchesNumber(self._h, pair)
-        _check_pending()
-        out = np.zeros(n, np.uint8)
-        lib().vksift_ext_downloadRefinedFundamentalInlierMask(self._h, pair, out.ctypes.data)
-        _check_pending()
-        return out.astype(bool)
+        return self._pair_mask(lib().vksift_ext_downloadRefinedFundamentalInlierMask, pair)
 
     def getRefineFundamentalTime(self):
         return lib().vksift_ext_getRefineFundamentalTime(self._h)

@@ -13,9 +13,7 @@ void vksift_ext_setProfiling(vksift_Instance instance, bool enabled)
   instance->profiling = enabled;
   instance->prof[0].valid = instance->prof[1].valid = false;
   instance->prof[0].accounted = instance->prof[1].accounted = false;
-  instance->match_timing_valid = false;
-  instance->verify_timing_valid = false;
-  instance->guided_timing_valid = false;
+  timers_reset(instance);
   memset(instance->acc_ms, 0, sizeof(instance->acc_ms));
   instance->acc_calls = 0;
   instance->acc_blur_launches = 0;
@@ -151,15 +149,7 @@ void vksift_ext_getDetectTimings(vksift_Instance instance, vksift_ext_DetectTimi
   vksift_ext_getDetectTimingsSized(instance, out, VKSIFT_EXT_DETECT_TIMINGS_V1_BYTES);
 }
 
-float vksift_ext_getMatchTime(vksift_Instance instance)
-{
-  defer_sync(instance);
-  if (!instance->profiling || !instance->match_timing_valid)
-    return -1.f;
-  vksift_hip_set_device(instance->device);
-  wait_all(instance);
-  return vksift_hip_event_elapsed_ms(instance->ev_m[0], instance->ev_m[1]);
-}
+float vksift_ext_getMatchTime(vksift_Instance instance) { return timer_read(instance, T_MATCH); }
 
 uint32_t vksift_ext_exportDescriptorsDevice(vksift_Instance instance, uint32_t gpu_buffer_id, uint8_t *d_descriptors)
 {

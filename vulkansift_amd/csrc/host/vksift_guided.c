@@ -13,34 +13,32 @@ static bool ensure_guided_scratch(vksift_Instance inst)
 {
   const uint32_t bc = inst->batch_cap, nb = inst->cfg.max_nb_sift_per_buffer;
   inst->gxy_side_stride = nb;
-  inst->guided_slot_stride = (((uint64_t)nb * 16u) + 255u) & ~(uint64_t)255u;
   inst->gkeys_u32 = vksift_hip_guided_scratch_u32(bc, nb);
   const bool ok = mem_ensure(&inst->d_gxy, sizeof(float) * 2u * 2u * inst->gxy_side_stride * bc + 8u, MEM_DEVICE) &&
-                  mem_ensure(&inst->d_gkeys, sizeof(uint32_t) * inst->gkeys_u32 + 8u, MEM_DEVICE) && mem_ensure(&inst->d_guided, inst->guided_slot_stride * bc, MEM_DEVICE) &&
-                  mem_ensure(&inst->d_guided_n, sizeof(uint32_t) * bc, MEM_DEVICE) && mem_ensure(&inst->h_guided_n, sizeof(uint32_t) * bc, MEM_PINNED) &&
+                  mem_ensure(&inst->d_gkeys, sizeof(uint32_t) * inst->gkeys_u32 + 8u, MEM_DEVICE) &&
+                  pair_results_ensure(inst, PR_GUIDED, 1, (((uint64_t)nb * 16u) + 255u) & ~(uint64_t)255u, sizeof(vksift_ext_FilteredMatch), PR_GUIDED) &&
                   mem_ensure(&inst->h_gtab, sizeof(uint32_t) * (pair_table_words(inst) + (size_t)10u * bc), MEM_PINNED);
   if (!inst->ev_gtab)
     inst->ev_gtab = vksift_hip_event_create();
-  for (int i = 0; i < 2; i++)
-    if (!inst->ev_g[i])
-      inst->ev_g[i] = vksift_hip_event_create();
-  return ok && inst->ev_gtab && inst->ev_g[0] && inst->ev_g[1];
+  return ok && inst->ev_gtab;
 }
 
 void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, const float *models, float threshold_px, float ratio, float max_distance,
                                     bool cross_check)
 {
   vksift_Instance inst = instance;
-  bool range_open = false;
+  StageFrame frame = {0};
   vksift_hip_set_device(inst->device);
   defer_sync(inst);
-  const uint32_t count = inst->filtered_slots_used;
+  const PairResults *ver = &inst->res[model == VKSIFT_EXT_GUIDE_HOMOGRAPHY ? PR_VERIFY_H : PR_VERIFY_F]; /* (read once `model` has been checked) */
+  PairResults *own = &inst->res[PR_GUIDED];
+  const uint32_t count = inst->res[PR_FILTERED].slots_used;
   /* the squared threshold in pixels, formed like the verification's (threshold_px 2^-13)^2 and brought back by the exact factor 2^26 */
   const float ts = threshold_px * (1.0f / 8192.0f), t2 = (ts * ts) * 67108864.0f;
   bool valid = count > 0 && model <= VKSIFT_EXT_GUIDE_FUNDAMENTAL && threshold_px > 0.f && isfinite(threshold_px) && t2 > 0.f && isfinite(t2) && ratio > 0.f &&
                max_distance > 0.f;
   if (valid && models == NULL)
-    valid = (model == VKSIFT_EXT_GUIDE_HOMOGRAPHY ? inst->verify_slots_used : inst->verify_f_slots_used) == count;
+    valid = ver->slots_used == count;
   for (size_t i = 0; valid && models != NULL && i < (size_t)9u * count; i++)
     valid = isfinite(models[i]);
   if (!valid)
@@ -73,14 +71,9 @@ void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, co
       h_ones[i] = 1u;
     d_models = (const float *)h_models, model_stride = 9u, d_valid = h_ones, valid_stride = 1u;
   }
-  else if (model == VKSIFT_EXT_GUIDE_HOMOGRAPHY)
-    d_models = (const float *)inst->d_vres, model_stride = 13u, d_valid = inst->d_vres + 12u, valid_stride = 13u;
-  else
-    d_models = (const float *)inst->d_fres, model_stride = 14u, d_valid = inst->d_fres + 13u, valid_stride = 14u;
-  if (inst->profiling)
-    vksift_hip_event_record(inst->ev_g[0], inst->stream);
-  vksift_hip_range_push("Guided matching");
-  range_open = true;
+  else /* the verified records: the model's nine floats first, the word `valid` last */
+    d_models = (const float *)ver->d_words, model_stride = ver->words, d_valid = ver->d_words + ver->words - 1u, valid_stride = ver->words;
+  HIP_CHECK(stage_begin(inst, &frame, T_GUIDED, "Guided matching"), "timer start");
   /* the dense rows and norms: the matcher's cache, refreshed the way the matcher does it (a no-op while the buffers are unchanged) */
   HIP_CHECK(refresh_match_cache(inst, inst->filt_ids, count), "descriptor gather");
   HIP_CHECK(refresh_match_cache(inst, inst->filt_ids + inst->batch_cap, count), "descriptor gather");
@@ -96,71 +89,31 @@ void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, co
     HIP_CHECK(vksift_hip_match_guided(inst->d_cache_desc, inst->desc_slot_stride, inst->d_cache_norm, inst->cache_norm_stride, inst->h_gtab + (size_t)PAIR_SLOT_WORDS * r, PAIR_SLOT_WORDS,
                                       inst->d_gxy + (size_t)4u * inst->gxy_side_stride * r, inst->gxy_side_stride, inst->d_match_n + (size_t)4u * r, 4u, max_rows,
                                       d_models + (size_t)model_stride * r, model_stride, d_valid + (size_t)valid_stride * r, valid_stride, model, t2, ratio, max_distance,
-                                      cross_check ? 1u : 0u, n, inst->d_guided + inst->guided_slot_stride * r, inst->guided_slot_stride, inst->d_guided_n + r,
+                                      cross_check ? 1u : 0u, n, own->d_payload + own->stride * r, own->stride, own->d_words + r,
                                       inst->d_gkeys, inst->gkeys_u32, inst->stream),
               "guided matching");
   }
   HIP_CHECK(vksift_hip_event_record(inst->ev_gtab, inst->stream), "event record");
   inst->gtab_pending = true;
-  HIP_CHECK(vksift_hip_post_words(inst->h_guided_n, inst->d_guided_n, count, inst->stream), "guided count read-back");
-  vksift_hip_range_pop();
-  range_open = false;
-  if (inst->profiling)
-  {
-    vksift_hip_event_record(inst->ev_g[1], inst->stream);
-    inst->guided_timing_valid = true;
-  }
-  HIP_CHECK(match_follow(inst, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
-  inst->guided_slots_used = count;
+  HIP_CHECK(vksift_hip_post_words(own->h_words, own->d_words, count, inst->stream), "guided count read-back");
+  HIP_CHECK(stage_end(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
+  own->slots_used = count;
   return;
 gpu_error:
-  if (range_open)
-    vksift_hip_range_pop();
+  (void)stage_abort(&frame);
   logError(LOG_TAG, GUIDED_FN " error: Failed to start the guided-matching pipeline.");
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }
 
 uint32_t vksift_ext_getGuidedMatchesNumber(vksift_Instance instance, uint32_t pair)
 {
-  wait_match(instance);
-  if (pair >= instance->guided_slots_used)
-  {
-    logError(LOG_TAG, "vksift_ext_getGuidedMatchesNumber() error: invalid input.");
-    instance->error_cb(VKSIFT_INVALID_INPUT_ERROR);
-    return 0;
-  }
-  return instance->h_guided_n[pair];
+  const uint32_t *w = pair_words(instance, PR_GUIDED, pair, true, "vksift_ext_getGuidedMatchesNumber");
+  return w ? w[0] : 0;
 }
 
 void vksift_ext_downloadGuidedMatches(vksift_Instance instance, uint32_t pair, vksift_ext_FilteredMatch *matches)
 {
-  vksift_Instance inst = instance;
-  wait_match(inst);
-  if (pair >= inst->guided_slots_used)
-  {
-    logError(LOG_TAG, "vksift_ext_downloadGuidedMatches() error: invalid input.");
-    inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
-    return;
-  }
-  const uint32_t n = inst->h_guided_n[pair];
-  if (n > 0)
-  {
-    HIP_CHECK(vksift_hip_memcpy_d2h(matches, inst->d_guided + (uint64_t)pair * inst->guided_slot_stride, (size_t)n * sizeof(vksift_ext_FilteredMatch), inst->dl_stream),
-              "guided match read-back");
-    HIP_CHECK(vksift_hip_stream_sync(inst->dl_stream), "guided match read-back");
-  }
-  return;
-gpu_error:
-  logError(LOG_TAG, "vksift_ext_downloadGuidedMatches() error when downloading the guided matches from GPU memory.");
-  inst->error_cb(VKSIFT_VULKAN_ERROR);
+  pair_download(instance, PR_GUIDED, pair, matches, "vksift_ext_downloadGuidedMatches", "guided match read-back", "the guided matches");
 }
 
-float vksift_ext_getGuidedMatchTime(vksift_Instance instance)
-{
-  defer_sync(instance);
-  if (!instance->profiling || !instance->guided_timing_valid)
-    return -1.f;
-  vksift_hip_set_device(instance->device);
-  wait_all(instance);
-  return vksift_hip_event_elapsed_ms(instance->ev_g[0], instance->ev_g[1]);
-}
+float vksift_ext_getGuidedMatchTime(vksift_Instance instance) { return timer_read(instance, T_GUIDED); }

@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -86,6 +86,28 @@ typedef struct
   uint8_t *matches;
   uint32_t *redo, *match_n;
 } MatchScratch;
+
+/* the interval of a stage's last run under vksift_ext_setProfiling (vksift_pairs.c). One per getter: both verification models share T_VERIFY */
+enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_COUNT };
+typedef struct
+{
+  vksift_hip_event ev[2];
+  bool valid;
+} StageTimer;
+
+/* What a stage keeps for each pair of the last filtered matching (vksift_pairs.c): `words` posted words per pair (on the device, and in pinned memory
+ * once the launches have passed), and a payload of `stride` bytes per pair that holds `elem` bytes for each of the n elements counted by word 0 of set
+ * `counted_by`'s record (the filtered matches' own count for them and for the masks, the guided matches' for those). slots_used: the pairs that have
+ * results; zero again after a new matching, and for a refit after a new verification of its model. */
+enum { PR_FILTERED, PR_VERIFY_H, PR_VERIFY_F, PR_REFINE_H, PR_REFINE_F, PR_GUIDED, PR_COUNT };
+typedef struct
+{
+  uint32_t *d_words, *h_words;
+  uint8_t *d_payload;
+  uint64_t stride;
+  uint32_t words, elem, counted_by;
+  uint32_t slots_used;
+} PairResults;
 
 typedef struct
 {
@@ -190,7 +212,7 @@ struct vksift_Instance_T
   uint32_t *d_match_n, *h_match_n; /* per match slot: {N_A, N_B, spare, spare} of the last matching pipeline */
   uint64_t desc_slot_stride, match_slot_stride; /* bytes */
   uint64_t redo_slot_stride;                    /* u32 elements */
-  uint32_t match_slots_used;
+  uint32_t match_slots_used; /* (the plain matching's records keep a download path of their own, md_*: not a PairResults) */
   /* per SIFT buffer: the matcher's view of it (dense descriptor rows in download order, shifted norms, row count), filled by a
    * device-side gather when the buffer is first matched after a detection / upload; desc, norm and the partial lists: first matching */
   uint8_t *d_cache_desc;
@@ -208,52 +230,25 @@ struct vksift_Instance_T
   bool md_asked, md_direct;  /* (asked once per matching) the caller's destination of this matching's records is page-locked: per-pair DMA, no packed copy */
   uint32_t md_hits;
 
-  /* ---- filtered matching (vksift_ext_matchFeaturesFiltered): scratch of the reverse (B->A) matching and the survivors; allocated on first use */
-  MatchScratch rev;
-  uint8_t *d_filtered;
-  uint32_t *d_filtered_n, *h_filtered_n;
-  uint64_t filtered_slot_stride;
-  uint32_t filtered_slots_used;
-  /* geometric verification (vksift_ext_verifyHomography / vksift_ext_verifyFundamental, vksift_verify.c): the pairs of the last filtered matching, and scratch allocated on first use */
+  /* ---- the stages behind a filtered matching (vksift_pairs.c): what each keeps per pair, and its scratch; everything allocated on first use */
+  PairResults res[PR_COUNT];
+  MatchScratch rev;         /* vksift_ext_matchFeaturesFiltered: scratch of the reverse (B->A) matching */
+  /* geometric verification (vksift_ext_verifyHomography / vksift_ext_verifyFundamental, vksift_verify.c). Each model keeps records and masks of its
+   * own, so that both can be read after one matching; the refits (vksift_refine.c) read d_corr and their model's verified records and masks */
   uint32_t *filt_ids;       /* 2 * batch_cap: buffers A then buffers B of the last vksift_ext_matchFeaturesFiltered */
-  float *d_corr;            /* per slot: filtered_slot_stride bytes of {xa, ya, xb, yb} */
-  uint8_t *d_vmask;         /* per slot: vmask_slot_stride bytes */
-  uint64_t vmask_slot_stride;
-  uint32_t *d_vres, *h_vres; /* 13 words (vksift_ext_Homography) per slot; the host copy is posted like h_filtered_n */
+  float *d_corr;            /* per slot: res[PR_FILTERED].stride bytes of {xa, ya, xb, yb} */
   uint32_t *d_vscratch;
   size_t vscratch_u32;
   uint32_t *h_vtab;         /* mapped pinned memory read by the gather launch: a pair table (pair_tables) */
   bool vtab_pending;
-  uint32_t verify_slots_used;
-  /* the second model (vksift_ext_verifyFundamental) keeps results and masks of its own, so that both can be read after one matching */
-  uint8_t *d_fmask;            /* per slot: vmask_slot_stride bytes */
-  uint32_t *d_fres, *h_fres;   /* 14 words (vksift_ext_Fundamental) per slot */
-  uint32_t verify_f_slots_used;
-  bool verify_timing_valid;
-  /* refit of the verified homographies on their inliers (vksift_ext_refineHomography, vksift_refine.c): results of its own, read from d_corr, d_vres and
-   * d_vmask; allocated on first use */
-  uint8_t *d_rmask;            /* per slot: vmask_slot_stride bytes */
-  uint32_t *d_rres, *h_rres;   /* 13 words (vksift_ext_RefinedHomography) per slot; the host copy is posted like h_vres */
-  uint32_t refine_slots_used;  /* pairs with refined results: zero again after a new matching or a new vksift_ext_verifyHomography */
-  bool refine_timing_valid;
-  /* the same for the verified fundamental matrices (vksift_ext_refineFundamental): read from d_corr, d_fres and d_fmask */
-  uint8_t *d_rfmask;             /* per slot: vmask_slot_stride bytes */
-  uint32_t *d_rfres, *h_rfres;   /* 13 words (vksift_ext_RefinedFundamental) per slot */
-  uint32_t refine_f_slots_used;  /* zero again after a new matching or a new vksift_ext_verifyFundamental */
-  bool refine_f_timing_valid;
-  /* guided matching (vksift_ext_matchFeaturesGuided, vksift_guided.c): results of its own beside the filtered matches and the models; allocated on first use */
+  /* guided matching (vksift_ext_matchFeaturesGuided, vksift_guided.c) */
   float *d_gxy;             /* per slot: 2 * gxy_side_stride float2, the coordinates of A's rows, then of B's */
   uint64_t gxy_side_stride; /* float2 elements */
   uint32_t *d_gkeys;        /* the sweeps' top-2 keys (vksift_hip_guided_scratch_u32) */
   size_t gkeys_u32;
-  uint8_t *d_guided;        /* per slot: guided_slot_stride bytes of vksift_ext_FilteredMatch */
-  uint64_t guided_slot_stride;
-  uint32_t *d_guided_n, *h_guided_n;
   uint32_t *h_gtab;         /* mapped pinned memory read by the launches: a pair table (pair_tables), then 9 floats per slot of supplied models and
                              * a word 1 per slot */
   bool gtab_pending;
-  uint32_t guided_slots_used;
-  bool guided_timing_valid;
 
   /* ---- download staging. Batched download: the first vksift_downloadFeatures() after a detection of VKSIFT_DL_BATCH_MIN images and more
    * packs the features of ALL its buffers on the device and fetches them with one copy into pinned memory; the downloads of the
@@ -298,15 +293,10 @@ struct vksift_Instance_T
   vksift_hip_event ev_staging;      /* host image staging buffer consumed by the H2D copy */
   vksift_hip_event ev_up[VKSIFT_UP_GROUPS]; /* group g of a batch has arrived in d_input */
   vksift_hip_event ev_match;
-  vksift_hip_event ev_m[2];         /* profiling: the matching interval */
+  StageTimer timer[T_COUNT];        /* profiling: the stages' intervals. The matching's events are created with the instance, the others by their first timed run */
   vksift_hip_event dl_ev[VKSIFT_DL_CHUNKS]; /* the packed copy arrives in pieces (created by the first one) */
-  vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab (created, like ev_v, by the first verification) */
-  vksift_hip_event ev_v[2];
-  vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created, like ev_g, by the first guided matching) */
-  vksift_hip_event ev_g[2];
-  vksift_hip_event ev_r[2]; /* profiling: the refinement interval (created by the first refinement) */
-  vksift_hip_event ev_rf[2]; /* the same for the fundamental matrices' refinement */
-  vksift_hip_event ev_ks[2]; /* profiling: the feature selection's interval (vksift_strongest.c; created by the first one that is timed) */
+  vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab (created by the first verification) */
+  vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created by the first guided matching) */
   bool desc_start_valid, input_free_valid, staging_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];
   uint64_t det_seq, det_done; /* last detection issued / highest one known to have completed */
@@ -315,8 +305,6 @@ struct vksift_Instance_T
   bool profiling;
   ProfSet prof[2]; /* two event sets: the host may enqueue one detection ahead of the one being timed */
   int prof_cur;
-  bool match_timing_valid;
-  bool ks_timing_valid;
   double acc_ms[8]; /* upload, pyramid (octave 0), extrema stage, orientation, descriptor, total, extrema scan kernel alone, pyramid (all octaves) */
   uint32_t acc_calls;
   uint64_t acc_blur_launches, acc_blur_launches_all, acc_alg_bytes, acc_scan_bytes;
@@ -421,5 +409,31 @@ VKSIFT_INTERNAL int match_follow(vksift_Instance inst, const uint32_t *ids_a, co
 static inline uint32_t *pair_layouts(const struct vksift_Instance_T *inst, uint32_t *tab) { return tab + (size_t)PAIR_SLOT_WORDS * inst->batch_cap; }
 static inline size_t pair_table_words(const struct vksift_Instance_T *inst) { return ((size_t)PAIR_SLOT_WORDS + (size_t)VKSIFT_LAYOUT_WORDS * 2u) * inst->batch_cap; }
 VKSIFT_INTERNAL void pair_tables(vksift_Instance inst, uint32_t *tab, uint32_t count, uint32_t *max_rows);
+
+
+/* vksift_pairs.c */
+/* a stage's time getter: the interval of its last run in ms, -1 unless profiling is on and the stage has run since it was switched on */
+VKSIFT_INTERNAL float timer_read(vksift_Instance inst, uint32_t timer);
+VKSIFT_INTERNAL void timers_reset(vksift_Instance inst);
+/* The frame around the launches of a stage. stage_begin starts the timer (when profiling; its events are created by the first timed run) and opens
+ * the profiler range; stage_end closes the range, stops the timer and, given the pairs, ends the sequence the way every one queued on the matching's
+ * contract does (match_follow, whose error code it returns). stage_abort, for the error exit, closes the range if it is open and says whether it was. */
+typedef struct
+{
+  StageTimer *timer;
+  bool open;
+} StageFrame;
+VKSIFT_INTERNAL int stage_begin(vksift_Instance inst, StageFrame *f, uint32_t timer, const char *range);
+VKSIFT_INTERNAL int stage_end(vksift_Instance inst, StageFrame *f, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count);
+VKSIFT_INTERNAL bool stage_abort(StageFrame *f);
+/* storage of batch_cap pairs for set `which` (PR_*) with this shape; false: out of memory (retried by the next call, nothing leaked) */
+VKSIFT_INTERNAL bool pair_results_ensure(vksift_Instance inst, uint32_t which, uint32_t words, uint64_t stride, uint32_t elem, uint32_t counted_by);
+/* a new matching: no set has results any more */
+VKSIFT_INTERNAL void pair_results_invalidate(vksift_Instance inst);
+/* The accessors. Both wait for the pipeline in flight (wait_match), then refuse a pair the set has no results for (and !out_ok: the caller's output
+ * pointer is NULL) with a log line under the public entry's name `fn` and VKSIFT_INVALID_INPUT_ERROR. pair_words: the pair's posted words, NULL when
+ * refused. pair_download: the pair's payload to dst through dl_stream (nothing when it is empty); `what` and `noun` word the failure's log lines. */
+VKSIFT_INTERNAL const uint32_t *pair_words(vksift_Instance inst, uint32_t which, uint32_t pair, bool out_ok, const char *fn);
+VKSIFT_INTERNAL void pair_download(vksift_Instance inst, uint32_t which, uint32_t pair, void *dst, const char *fn, const char *what, const char *noun);
 
 #endif

@@ -181,17 +181,16 @@ static int match_slots(vksift_Instance inst, const MatchScratch *ms, const uint3
 static bool ensure_filter_scratch(vksift_Instance inst)
 {
   const uint32_t bc = inst->batch_cap;
-  inst->filtered_slot_stride = (((uint64_t)inst->cfg.max_nb_sift_per_buffer * 16u) + 255u) & ~(uint64_t)255u;
+  const uint64_t stride = (((uint64_t)inst->cfg.max_nb_sift_per_buffer * 16u) + 255u) & ~(uint64_t)255u;
   return mem_ensure(&inst->rev.matches, inst->match_slot_stride * bc, MEM_DEVICE) && mem_ensure(&inst->rev.redo, sizeof(uint32_t) * inst->redo_slot_stride * bc, MEM_DEVICE) &&
-         mem_ensure(&inst->rev.match_n, sizeof(uint32_t) * 4 * bc, MEM_DEVICE) && mem_ensure(&inst->d_filtered_n, sizeof(uint32_t) * bc, MEM_DEVICE) &&
-         mem_ensure(&inst->d_filtered, inst->filtered_slot_stride * bc, MEM_DEVICE) && mem_ensure(&inst->h_filtered_n, sizeof(uint32_t) * bc, MEM_PINNED) &&
+         mem_ensure(&inst->rev.match_n, sizeof(uint32_t) * 4 * bc, MEM_DEVICE) && pair_results_ensure(inst, PR_FILTERED, 1, stride, sizeof(vksift_ext_FilteredMatch), PR_FILTERED) &&
          mem_ensure(&inst->filt_ids, sizeof(uint32_t) * 2u * bc, MEM_HEAP);
 }
 
 static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count, const char *fn, bool filter, float ratio,
                        bool cross_check)
 {
-  bool range_open = false;
+  StageFrame frame = {0};
   vksift_hip_set_device(inst->device);
   defer_sync(inst);
   bool valid = count >= 1 && count <= inst->batch_cap;
@@ -204,10 +203,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
     return;
   }
   vksift_hip_set_device(inst->device);
-  if (inst->profiling)
-    vksift_hip_event_record(inst->ev_m[0], inst->stream);
-  vksift_hip_range_push("Matching");
-  range_open = true;
+  HIP_CHECK(stage_begin(inst, &frame, T_MATCH, "Matching"), "timer start");
   const MatchScratch fwd = fwd_scratch(inst);
   /* the matcher's view of every buffer of the call first, in one gather launch per 512 buffers (each run below would gather its own) */
   HIP_CHECK(refresh_match_cache(inst, ids_a, count), "descriptor gather");
@@ -218,12 +214,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
   HIP_CHECK(vksift_hip_post_words(inst->h_match_n, inst->d_match_n, (size_t)4 * count, inst->stream), "match count read-back");
   if (inst->desc_start_valid && vksift_hip_tune_get(VKSIFT_TUNE_PYR_GATE) == 1)
     vksift_hip_event_record(inst->ev_desc_start, inst->stream); /* experiment: the next scale-space behind this matching, not beside it */
-  inst->filtered_slots_used = 0;
-  inst->verify_slots_used = 0;
-  inst->verify_f_slots_used = 0;
-  inst->guided_slots_used = 0;
-  inst->refine_slots_used = 0;
-  inst->refine_f_slots_used = 0;
+  pair_results_invalidate(inst);
   inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
   if (filter)
   {
@@ -233,6 +224,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
       logError(LOG_TAG, "%s error: out of device memory for the filtered-matching scratch.", fn);
       goto gpu_error;
     }
+    PairResults *filt = &inst->res[PR_FILTERED];
     for (uint32_t r = 0; r < count; r += VKSIFT_HIP_MATCH_SLOTS)
     {
       const uint32_t n = count - r < VKSIFT_HIP_MATCH_SLOTS ? count - r : VKSIFT_HIP_MATCH_SLOTS;
@@ -240,29 +232,21 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
         HIP_CHECK(match_slots(inst, &inst->rev, ids_b + r, ids_a + r, n, r), "reverse 2-NN matching");
       HIP_CHECK(vksift_hip_filter_matches(inst->d_matches + (uint64_t)r * inst->match_slot_stride, inst->match_slot_stride,
                                           cross_check ? inst->rev.matches + (uint64_t)r * inst->match_slot_stride : NULL, inst->match_slot_stride,
-                                          inst->d_match_n + (size_t)r * 4, 4, ratio, n, inst->d_filtered + (uint64_t)r * inst->filtered_slot_stride,
-                                          inst->filtered_slot_stride, inst->d_filtered_n + r, inst->stream),
+                                          inst->d_match_n + (size_t)r * 4, 4, ratio, n, filt->d_payload + (uint64_t)r * filt->stride, filt->stride,
+                                          filt->d_words + r, inst->stream),
                 "match filtering");
     }
-    HIP_CHECK(vksift_hip_post_words(inst->h_filtered_n, inst->d_filtered_n, count, inst->stream), "filtered count read-back");
-    inst->filtered_slots_used = count;
+    HIP_CHECK(vksift_hip_post_words(filt->h_words, filt->d_words, count, inst->stream), "filtered count read-back");
+    filt->slots_used = count;
     /* the pairs, for vksift_ext_verifyHomography */
     memcpy(inst->filt_ids, ids_a, sizeof(uint32_t) * count);
     memcpy(inst->filt_ids + inst->batch_cap, ids_b, sizeof(uint32_t) * count);
   }
-  vksift_hip_range_pop();
-  range_open = false;
-  if (inst->profiling)
-  {
-    vksift_hip_event_record(inst->ev_m[1], inst->stream);
-    inst->match_timing_valid = true;
-  }
-  HIP_CHECK(match_follow(inst, ids_a, ids_b, count), "event record");
+  HIP_CHECK(stage_end(inst, &frame, ids_a, ids_b, count), "event record");
   inst->match_slots_used = count;
   return;
 gpu_error:
-  if (range_open)
-    vksift_hip_range_pop();
+  (void)stage_abort(&frame);
   logError(LOG_TAG, "%s error: Failed to start the matching pipeline.", fn);
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }
@@ -394,38 +378,13 @@ void vksift_downloadMatches(vksift_Instance instance, vksift_Match_2NN *matches)
 
 uint32_t vksift_ext_getFilteredMatchesNumber(vksift_Instance instance, uint32_t pair)
 {
-  wait_match(instance);
-  if (pair >= instance->filtered_slots_used)
-  {
-    logError(LOG_TAG, "vksift_ext_getFilteredMatchesNumber() error: invalid input.");
-    instance->error_cb(VKSIFT_INVALID_INPUT_ERROR);
-    return 0;
-  }
-  return instance->h_filtered_n[pair];
+  const uint32_t *w = pair_words(instance, PR_FILTERED, pair, true, "vksift_ext_getFilteredMatchesNumber");
+  return w ? w[0] : 0;
 }
 
 void vksift_ext_downloadFilteredMatches(vksift_Instance instance, uint32_t pair, vksift_ext_FilteredMatch *matches)
 {
-  vksift_Instance inst = instance;
-  wait_match(inst);
-  if (pair >= inst->filtered_slots_used)
-  {
-    logError(LOG_TAG, "vksift_ext_downloadFilteredMatches() error: invalid input.");
-    inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
-    return;
-  }
-  const uint32_t n = inst->h_filtered_n[pair];
-  if (n > 0)
-  {
-    HIP_CHECK(vksift_hip_memcpy_d2h(matches, inst->d_filtered + (uint64_t)pair * inst->filtered_slot_stride, (size_t)n * sizeof(vksift_ext_FilteredMatch),
-                                    inst->dl_stream),
-              "filtered match read-back");
-    HIP_CHECK(vksift_hip_stream_sync(inst->dl_stream), "filtered match read-back");
-  }
-  return;
-gpu_error:
-  logError(LOG_TAG, "vksift_ext_downloadFilteredMatches() error when downloading the filtered matches from GPU memory.");
-  inst->error_cb(VKSIFT_VULKAN_ERROR);
+  pair_download(instance, PR_FILTERED, pair, matches, "vksift_ext_downloadFilteredMatches", "filtered match read-back", "the filtered matches");
 }
 
 void vksift_ext_downloadMatchesBatch(vksift_Instance instance, uint32_t pair, vksift_Match_2NN *matches)

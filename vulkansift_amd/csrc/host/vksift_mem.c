@@ -75,6 +75,8 @@ typedef struct
 } Block;
 #define FIELD(f) offsetof(struct vksift_Instance_T, f)
 #define LAZY(f, kind) {FIELD(f), kind, ELSEWHERE, N_ONE, 0}
+/* the three blocks of what a stage keeps per pair (PairResults, vksift_pairs.c: pair_results_ensure) */
+#define PAIR_RESULTS(which) LAZY(res[which].d_payload, MEM_DEVICE), LAZY(res[which].d_words, MEM_DEVICE), LAZY(res[which].h_words, MEM_PINNED)
 /* In the order create_instance() allocates (the scale-space buffers come after them, behind the stream: mem_create); a growth allocates
  * the scale-space, the PER_STRIDE blocks, then the PER_CAPACITY ones, each class in this order. A new scratch block is one line here. */
 static const Block blocks[] = {
@@ -106,12 +108,8 @@ static const Block blocks[] = {
     LAZY(d_pyr_buf[0], MEM_DEVICE), LAZY(d_pyr_buf[1], MEM_DEVICE),
     LAZY(d_cache_desc, MEM_DEVICE), LAZY(d_cache_norm, MEM_DEVICE), LAZY(d_match_partial, MEM_DEVICE), LAZY(h_matches, MEM_PINNED),
     LAZY(rev.matches, MEM_DEVICE), LAZY(rev.redo, MEM_DEVICE), LAZY(rev.match_n, MEM_DEVICE),
-    LAZY(d_filtered, MEM_DEVICE), LAZY(d_filtered_n, MEM_DEVICE), LAZY(h_filtered_n, MEM_PINNED), LAZY(filt_ids, MEM_HEAP),
-    LAZY(d_corr, MEM_DEVICE), LAZY(d_vmask, MEM_DEVICE), LAZY(d_vres, MEM_DEVICE), LAZY(d_vscratch, MEM_DEVICE), LAZY(h_vres, MEM_PINNED), LAZY(h_vtab, MEM_PINNED),
-    LAZY(d_fmask, MEM_DEVICE), LAZY(d_fres, MEM_DEVICE), LAZY(h_fres, MEM_PINNED),
-    LAZY(d_rmask, MEM_DEVICE), LAZY(d_rres, MEM_DEVICE), LAZY(h_rres, MEM_PINNED),
-    LAZY(d_rfmask, MEM_DEVICE), LAZY(d_rfres, MEM_DEVICE), LAZY(h_rfres, MEM_PINNED),
-    LAZY(d_gxy, MEM_DEVICE), LAZY(d_gkeys, MEM_DEVICE), LAZY(d_guided, MEM_DEVICE), LAZY(d_guided_n, MEM_DEVICE), LAZY(h_guided_n, MEM_PINNED), LAZY(h_gtab, MEM_PINNED),
+    LAZY(filt_ids, MEM_HEAP), LAZY(d_corr, MEM_DEVICE), LAZY(d_vscratch, MEM_DEVICE), LAZY(h_vtab, MEM_PINNED), LAZY(d_gxy, MEM_DEVICE), LAZY(d_gkeys, MEM_DEVICE), LAZY(h_gtab, MEM_PINNED),
+    PAIR_RESULTS(PR_FILTERED), PAIR_RESULTS(PR_VERIFY_H), PAIR_RESULTS(PR_VERIFY_F), PAIR_RESULTS(PR_REFINE_H), PAIR_RESULTS(PR_REFINE_F), PAIR_RESULTS(PR_GUIDED),
     LAZY(d_dl, MEM_DEVICE), LAZY(h_dl, MEM_PINNED), LAZY(dl_row, MEM_HEAP), LAZY(h_post[0], MEM_PINNED), LAZY(h_post[1], MEM_PINNED),
 };
 #define N_BLOCKS (sizeof(blocks) / sizeof(blocks[0]))
@@ -195,10 +193,11 @@ typedef struct
 {
   size_t field;
   uint16_t count, step;
-  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_refine.c, vksift_strongest.c), destroyed here */
+  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_pairs.c), destroyed here */
 } Handle;
 #define EVENTS(f, n, step, lazy) {FIELD(f), n, step, false, lazy}
 #define STREAM(f) {FIELD(f), 1, 0, true, false}
+#define TIMER(which, lazy) EVENTS(timer[which].ev, 2, sizeof(vksift_hip_event), lazy) /* a StageTimer's pair (vksift_pairs.c) */
 static const Handle handles[] = {
     STREAM(stream), STREAM(pyr_stream), STREAM(dl_stream), STREAM(up_stream),
     EVENTS(ev_pyr_done, 1, 0, false), EVENTS(ev_desc_start, 1, 0, false), EVENTS(ev_input_free, 1, 0, false),
@@ -208,10 +207,9 @@ static const Handle handles[] = {
     EVENTS(ev_up, VKSIFT_UP_GROUPS, sizeof(vksift_hip_event), false),
     EVENTS(prof[0].ev_t, 8, sizeof(vksift_hip_event), false), EVENTS(prof[1].ev_t, 8, sizeof(vksift_hip_event), false),
     EVENTS(prof[0].ev_pt, 3, sizeof(vksift_hip_event), false), EVENTS(prof[1].ev_pt, 3, sizeof(vksift_hip_event), false),
-    EVENTS(prof[0].ev_scan, 2, sizeof(ProfSet), false), EVENTS(ev_m, 2, sizeof(vksift_hip_event), false),
-    EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_v, 2, sizeof(vksift_hip_event), true),
-    EVENTS(ev_gtab, 1, 0, true), EVENTS(ev_g, 2, sizeof(vksift_hip_event), true), EVENTS(ev_r, 2, sizeof(vksift_hip_event), true),
-    EVENTS(ev_rf, 2, sizeof(vksift_hip_event), true), EVENTS(ev_ks, 2, sizeof(vksift_hip_event), true),
+    EVENTS(prof[0].ev_scan, 2, sizeof(ProfSet), false), TIMER(T_MATCH, false),
+    EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_gtab, 1, 0, true),
+    TIMER(T_VERIFY, true), TIMER(T_REFINE_H, true), TIMER(T_REFINE_F, true), TIMER(T_GUIDED, true), TIMER(T_BUDGET, true),
 };
 #define N_HANDLES (sizeof(handles) / sizeof(handles[0]))
 

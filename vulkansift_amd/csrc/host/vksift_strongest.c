@@ -27,7 +27,7 @@ static void take_sequence(vksift_Instance inst, uint32_t first, uint32_t count)
 void vksift_ext_keepStrongestFeatures(vksift_Instance instance, uint32_t first_gpu_buffer_id, uint32_t count, uint32_t max_features)
 {
   vksift_Instance inst = instance;
-  bool range_open = false;
+  StageFrame frame = {0};
   vksift_hip_set_device(inst->device);
   defer_sync(inst); /* staged plain detections are launched first */
   const uint32_t nbuf = inst->cfg.sift_buffer_count;
@@ -37,9 +37,6 @@ void vksift_ext_keepStrongestFeatures(vksift_Instance instance, uint32_t first_g
     inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
     return;
   }
-  for (int i = 0; i < 2 && inst->profiling; i++)
-    if (!inst->ev_ks[i] && !(inst->ev_ks[i] = vksift_hip_event_create()))
-      goto gpu_error;
   /* pack launches of a packed download that went straight to the caller's memory may still read the records on the download stream */
   if (inst->dl_valid && inst->dl_direct)
     HIP_CHECK(vksift_hip_stream_sync(inst->dl_stream), "download stream synchronisation");
@@ -52,11 +49,8 @@ void vksift_ext_keepStrongestFeatures(vksift_Instance instance, uint32_t first_g
     const BufferInfo *b = &inst->bufs[ids[i]];
     known_changed[i] = (b->nb_sections == 0 || counts_valid(inst, ids[i])) && rows_bound(inst, ids[i]) > max_features;
   }
+  HIP_CHECK(stage_begin(inst, &frame, T_BUDGET, "KeepStrongest"), "timer start"); /* (nothing can fail between here and the sequence number) */
   take_sequence(inst, first_gpu_buffer_id, count);
-  if (inst->profiling)
-    vksift_hip_event_record(inst->ev_ks[0], inst->stream);
-  vksift_hip_range_push("KeepStrongest");
-  range_open = true;
   /* with the matcher's cache in place the launch leaves the selected buffer's entry as the gather pass would */
   const bool cache = inst->d_cache_desc && inst->d_cache_norm;
   uint8_t *const c_desc = cache ? inst->d_cache_desc : NULL;
@@ -91,32 +85,14 @@ void vksift_ext_keepStrongestFeatures(vksift_Instance instance, uint32_t first_g
       else if (!cache)
         inst->cache_valid[ids[k]] = false;
   }
-  vksift_hip_range_pop();
-  range_open = false;
-  if (inst->profiling)
-  {
-    vksift_hip_event_record(inst->ev_ks[1], inst->stream);
-    inst->ks_timing_valid = true;
-  }
+  (void)stage_end(inst, &frame, NULL, NULL, 0); /* no pairs: the call ends on its detection-ring event instead */
   HIP_CHECK(vksift_hip_event_record(inst->det_ring[inst->det_seq % VKSIFT_DETECT_RING].ev, inst->stream), "event record");
   return;
 gpu_error:
-  if (range_open)
-  {
-    vksift_hip_range_pop();
-    /* the buffers carry the new sequence number: its event stands behind whatever part of the call was queued */
+  if (stage_abort(&frame)) /* the buffers carry the new sequence number: its event stands behind whatever part of the call was queued */
     (void)vksift_hip_event_record(inst->det_ring[inst->det_seq % VKSIFT_DETECT_RING].ev, inst->stream);
-  }
   logError(LOG_TAG, "vksift_ext_keepStrongestFeatures() error: Failed to start the feature selection.");
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }
 
-float vksift_ext_getKeepStrongestTime(vksift_Instance instance)
-{
-  defer_sync(instance);
-  if (!instance->profiling || !instance->ks_timing_valid)
-    return -1.f;
-  vksift_hip_set_device(instance->device);
-  wait_all(instance);
-  return vksift_hip_event_elapsed_ms(instance->ev_ks[0], instance->ev_ks[1]);
-}
+float vksift_ext_getKeepStrongestTime(vksift_Instance instance) { return timer_read(instance, T_BUDGET); }
