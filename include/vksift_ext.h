@@ -211,6 +211,41 @@ extern "C"
   /* Time (ms) of the last vksift_ext_keepStrongestFeatures (its launches), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getKeepStrongestTime(vksift_Instance instance);
 
+  /* ---- Describe caller-supplied keypoints ---------------------------------------------------------------------------------
+   * OpenCV's detectAndCompute(useProvidedKeypoints = true), SiftGPU's SetKeypointList, VLFeat's vl_sift with frames: the scale-space of the image is
+   * built as for a detection, and the caller's keypoints take the place of the extraction stage. Keypoint (x, y, sigma) in image pixels goes to the octave and
+   * scale a detection would have found it at — the inverse of sigma = seed_scale_sigma 2^(s / S) 2^octave, s rounded to the nearest scale, a comparison
+   * against S + 1 thresholds (float)(seed_scale_sigma 2^((j + 0.5) / S)); beyond either end of the scale-space it takes the first or the last octave — at
+   * scale_x = x 2^-octave, exactly. A keypoint is described iff x, y and sigma are finite, sigma 2^-octave lies in [0.02, 29], 0 <= scale_x < octave width and
+   * 0 <= scale_y < octave height and, in GIVEN mode, 0 <= orientation <= 2 pi; the others are skipped without a word (tests/np_describe.py restates the rule
+   * bit for bit).
+   * mode VKSIFT_EXT_DESCRIBE_ORIENT: orientations from the image, as in a detection (a keypoint with several histogram peaks yields several features, the
+   * supplied orientation is ignored). VKSIFT_EXT_DESCRIBE_GIVEN: the supplied orientation, exactly one feature per stored keypoint.
+   * The buffer afterwards is an ordinary detected buffer, laid out in octave sections: downloads, matching, vksift_ext_keepStrongestFeatures (whose key is
+   * `response`) and vksift_ext_exportDescriptorsDevice work on it unchanged. Download order: by octave, in each octave the keypoints in input order, then the
+   * orientation copies. A feature carries x, y, sigma and response (its intensity field) of its keypoint bit for bit: that is how the caller joins the
+   * features to its list. An octave's section holds its share of max_nb_sift_per_buffer as after a detection; keypoints beyond it are dropped in input order.
+   * vksift_ext_getPlacedKeypointsNumber: the keypoints of the buffer's last describe call that were stored, before orientation copies (0 when something
+   * else has filled or cut the buffer since); waits like vksift_getFeaturesNumber.
+   * Contract of vksift_detectFeatures / vksift_ext_detectFeaturesBatch: asynchronous, the buffers busy until it has run, the accessors wait; images and
+   * keypoints are copied before the call returns; the scale-space accessors show the described image afterwards (image 0 of a batch). Never deferred, never
+   * replayed from a graph; the detect timings (vksift_ext_getDetectTimings) keep reporting the last detection.
+   * Batch: image i takes the next nb_kps[i] keypoints of kps and SIFT buffer first_gpu_buffer_id + i.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, nothing changed): whatever the detection entry points refuse, kps == NULL with a non-zero count, nb_kps == NULL
+   * (batch), a count above max_nb_sift_per_buffer, an unknown mode. */
+  typedef struct
+  {
+    float x, y, sigma, orientation, response;
+  } vksift_ext_Keypoint;
+#define VKSIFT_EXT_DESCRIBE_ORIENT 0u
+#define VKSIFT_EXT_DESCRIBE_GIVEN 1u
+  VKSIFT_EXPORT void vksift_ext_describeKeypoints(vksift_Instance instance, const uint8_t *image_data, uint32_t image_width, uint32_t image_height,
+                                                  const vksift_ext_Keypoint *kps, uint32_t nb_kps, uint32_t gpu_buffer_id, uint32_t mode);
+  VKSIFT_EXPORT void vksift_ext_describeKeypointsBatch(vksift_Instance instance, const uint8_t *const *images, uint32_t count, uint32_t image_width,
+                                                       uint32_t image_height, const vksift_ext_Keypoint *kps, const uint32_t *nb_kps,
+                                                       uint32_t first_gpu_buffer_id, uint32_t mode);
+  VKSIFT_EXPORT uint32_t vksift_ext_getPlacedKeypointsNumber(vksift_Instance instance, uint32_t gpu_buffer_id);
+
   /* Deferred submission of vksift_detectFeatures (no counterpart in the reference, no change of its contract): consecutive plain
    * detect calls into consecutive SIFT buffers, with nothing asked in between, are staged and launched as ONE batched detection by
    * the first call that needs a result — any other entry point — or when 128 images (VKSIFT_DEFER_MAX) are staged, or 16 (VKSIFT_DEFER_CHUNK)

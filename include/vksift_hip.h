@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 8u      /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version) */
+#define VKSIFT_HIP_ABI_VERSION 9u      /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version) */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -334,6 +334,43 @@ extern "C"
    * queue it behind vksift_hip_orientations_multi of every octave of the detection. */
   int vksift_hip_descriptors_multi_dense(const vksift_hip_OctaveJob *jobs, uint32_t n_jobs, uint32_t batch, const vksift_hip_DenseRows *dense,
                                          vksift_hip_stream s);
+
+  /* ------------------------------------------------------------------ caller-supplied keypoints (place.hip; no counterpart in the reference) */
+  typedef struct
+  {
+    float x, y, sigma, orientation, response; /* image pixels; 20 bytes */
+  } vksift_hip_Keypoint;
+  /* One octave of the placement: its extent, its index (vksift_hip_OctaveJob::octave_idx) and its section of the SIFT buffer of image 0; image b
+   * uses feats + b * feat_img_stride bytes and found[b * found_img_stride] */
+  typedef struct
+  {
+    uint32_t w, h;
+    int32_t octave_idx;
+    uint8_t *feats;
+    uint64_t feat_img_stride; /* bytes */
+    uint32_t cap;             /* section capacity */
+    uint32_t *found;
+    uint32_t found_img_stride;
+  } vksift_hip_PlaceOctave;
+  /* The inverse of the last lines of the keypoint refinement: caller-supplied keypoints (x, y, sigma in image pixels) become records that
+   * vksift_hip_orientations* and vksift_hip_descriptors* accept, placed in the octave sections of their image's SIFT buffer. One launch, one
+   * workgroup of VKSIFT_HIP_PLACE_WG threads per image, no atomics: the order is the input order. Keypoints kp_first[b] .. kp_first[b + 1] - 1 of
+   * kps belong to image b (kps, kp_first, placed: device memory; oct and sigma_steps: host tables, copied by the call).
+   * All arithmetic fp32, every operation rounded once (tests/np_describe.py restates it bit for bit). Octave: the first o of 0 .. n_oct - 1 with
+   * rel = sigma * 2^-octave_idx[o] < sigma_steps[S], the last octave if there is none; scale_idx = the number of j in 0 .. S with rel >=
+   * sigma_steps[j] (0 .. S, up to S + 1 in the last octave); comparisons only. With sigma_steps[j] = (float)(seed_sigma * 2^((j + 0.5) / S)) this
+   * inverts sigma = seed_sigma * 2^(ss / S) * 2^octave_idx, scale_idx = round(ss). scale_x = x * 2^-octave_idx, scale_y likewise: the exact inverse
+   * of x = scale_x * 2^octave_idx. Admissible: x, y, sigma finite; 0.02 <= rel <= 29; 0 <= scale_x < w[o] and 0 <= scale_y < h[o]; with
+   * keep_orientation, 0 <= orientation <= 2 pi. An inadmissible keypoint produces nothing.
+   * WRITTEN, per image: words 0..8 {x, y (the supplied bits), scale_x, scale_y, scale_idx, octave_idx, sigma (the supplied bits), orientation (the
+   * supplied bits with keep_orientation, else 0), intensity = response (the supplied bits)} of records 0, 1, .. of the keypoint's section in input
+   * order, those at and beyond cap dropped; found[o] = the un-clamped number of admissible keypoints of octave o, for every octave, zeros
+   * included; placed[b] = the records stored. Nothing else: not bytes 36..163 of any record, not a record at or beyond cap.
+   * hipErrorInvalidValue, nothing launched: n_oct 0 or above 16, S 0 or above 13, oct, sigma_steps, kp_first or placed NULL, a section or a counter pointer
+   * that is NULL, a section or feat_img_stride that is not a multiple of 4, an octave_idx outside -31 .. 31. batch 0 returns 0 and launches nothing. */
+#define VKSIFT_HIP_PLACE_WG 256u
+  int vksift_hip_place_keypoints(const vksift_hip_Keypoint *kps, const uint32_t *kp_first, const vksift_hip_PlaceOctave *oct, uint32_t n_oct,
+                                 const float *sigma_steps, uint32_t S, uint32_t keep_orientation, uint32_t batch, uint32_t *placed, vksift_hip_stream s);
 
   /* ------------------------------------------------------------------ matcher */
   /* vksift_Feature records (stride 164 B) -> dense 128-byte descriptor rows. Replaces the section packing of sift_memory.c:957-1047 as the

@@ -76,6 +76,10 @@ HOMOGRAPHY_DTYPE = np.dtype([("H", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_i
 FUNDAMENTAL_DTYPE = np.dtype([("F", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("best_hypothesis", "<u4"), ("best_root", "<u4"), ("valid", "<u4")])
 REFINED_HOMOGRAPHY_DTYPE = np.dtype([("H", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("rounds", "<u4"), ("valid", "<u4")])
 REFINED_FUNDAMENTAL_DTYPE = np.dtype([("F", "<f4", (3, 3)), ("nb_matches", "<u4"), ("nb_inliers", "<u4"), ("rounds", "<u4"), ("valid", "<u4")])
+# a caller-supplied keypoint (vksift_ext_Keypoint): image pixels; `response` travels into the feature's intensity field
+KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("sigma", "<f4"), ("orientation", "<f4"), ("response", "<f4")])
+DESCRIBE_ORIENT, DESCRIBE_GIVEN = 0, 1
+assert KEYPOINT_DTYPE.itemsize == 20
 assert FUNDAMENTAL_DTYPE.itemsize == 56 and REFINED_HOMOGRAPHY_DTYPE.itemsize == 52 and REFINED_FUNDAMENTAL_DTYPE.itemsize == 52
 assert FEATURE_DTYPE.itemsize == 164 and MATCH_DTYPE.itemsize == 20 and FILTERED_MATCH_DTYPE.itemsize == 16 and HOMOGRAPHY_DTYPE.itemsize == 52
 
@@ -171,6 +175,12 @@ def lib():
     L.vksift_ext_keepStrongestFeatures.restype = None
     L.vksift_ext_getKeepStrongestTime.argtypes = [inst]
     L.vksift_ext_getKeepStrongestTime.restype = C.c_float
+    L.vksift_ext_describeKeypoints.argtypes = [inst, C.c_void_p, u32, u32, C.c_void_p, u32, u32, u32]
+    L.vksift_ext_describeKeypoints.restype = None
+    L.vksift_ext_describeKeypointsBatch.argtypes = [inst, C.POINTER(C.c_void_p), u32, u32, u32, C.c_void_p, C.POINTER(u32), u32, u32]
+    L.vksift_ext_describeKeypointsBatch.restype = None
+    L.vksift_ext_getPlacedKeypointsNumber.argtypes = [inst, u32]
+    L.vksift_ext_getPlacedKeypointsNumber.restype = u32
     L.vksift_ext_setProfiling.argtypes = [inst, C.c_bool]
     L.vksift_ext_getDetectTimings.argtypes = [inst, C.POINTER(vksift_ext_DetectTimings)]
     L.vksift_ext_getAccumulatedDetectTimings.argtypes = [inst, C.POINTER(vksift_ext_DetectTimings), C.POINTER(u32), C.c_bool]
@@ -647,6 +657,38 @@ class Instance:
 
     def getKeepStrongestTime(self):
         return lib().vksift_ext_getKeepStrongestTime(self._h)
+
+    def describeKeypoints(self, image, keypoints, gpu_buffer_id, mode=DESCRIBE_ORIENT):
+        """describe the caller's keypoints (KEYPOINT_DTYPE, image pixels) on `image` into a SIFT buffer (vksift_ext_describeKeypoints): orientations
+        from the image (DESCRIBE_ORIENT) or the supplied ones (DESCRIBE_GIVEN); asynchronous like detectFeatures. keypoints None: a NULL list"""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        assert image.ndim == 2
+        kps = None if keypoints is None else np.ascontiguousarray(keypoints, dtype=KEYPOINT_DTYPE)
+        n = 0 if kps is None else len(kps)
+        lib().vksift_ext_describeKeypoints(self._h, image.ctypes.data, image.shape[1], image.shape[0], None if kps is None else kps.ctypes.data, n, gpu_buffer_id, mode)
+        _check_pending()
+
+    def describeKeypointsRaw(self, image_ptr, width, height, kps_ptr, nb_kps, gpu_buffer_id, mode):
+        lib().vksift_ext_describeKeypoints(self._h, image_ptr, width, height, kps_ptr, nb_kps, gpu_buffer_id, mode)
+        _check_pending()
+
+    def describeKeypointsBatch(self, images, keypoint_lists, first_gpu_buffer_id, mode=DESCRIBE_ORIENT):
+        """image i with keypoint_lists[i] into SIFT buffer first_gpu_buffer_id + i, one launch sequence (vksift_ext_describeKeypointsBatch)"""
+        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        h, w = imgs[0].shape
+        assert all(im.shape == (h, w) for im in imgs) and len(keypoint_lists) == len(imgs)
+        lists = [np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in keypoint_lists]
+        kps = np.concatenate(lists) if lists else np.zeros(0, KEYPOINT_DTYPE)
+        ptrs = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        counts = (C.c_uint32 * len(imgs))(*[len(k) for k in lists])
+        lib().vksift_ext_describeKeypointsBatch(self._h, ptrs, len(imgs), w, h, kps.ctypes.data if len(kps) else None, counts, first_gpu_buffer_id, mode)
+        _check_pending()
+
+    def getPlacedKeypointsNumber(self, gpu_buffer_id):
+        """keypoints the buffer's last describe call stored, before orientation copies (vksift_ext_getPlacedKeypointsNumber)"""
+        n = lib().vksift_ext_getPlacedKeypointsNumber(self._h, gpu_buffer_id)
+        _check_pending()
+        return n
 
     def getMatchesNumberBatch(self, pair):
         n = lib().vksift_ext_getMatchesNumberBatch(self._h, pair)

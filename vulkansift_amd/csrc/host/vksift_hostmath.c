@@ -118,7 +118,11 @@ uint32_t vksift_hm_desc_fp_table(const vksift_Config *cfg, float *tab, uint32_t 
   /* Largest descriptor window: sub-pixel scale <= S+1 (ExtractKeypoints.comp:198) so
    * sigma_oct <= seed * 2^((S+1)/S); radius = sqrt(2)*3*sigma_oct*2.5 (ComputeDescriptors.comp:107-109). */
   const uint32_t S = cfg->nb_scales_per_octave;
-  float sigma_max = cfg->seed_scale_sigma * powf(2.f, (float)(S + 1) / (float)S) * 1.01f;
+  return vksift_hm_desc_fp_table_for(cfg->seed_scale_sigma * powf(2.f, (float)(S + 1) / (float)S) * 1.01f, tab, cap);
+}
+
+uint32_t vksift_hm_desc_fp_table_for(float sigma_max, float *tab, uint32_t cap)
+{
   uint32_t n_max = (uint32_t)(floorf(sqrtf(2.f) * 3.f * sigma_max * 2.5f + 0.5f)) / 2 + 2;
   if (n_max > cap)
     n_max = cap;

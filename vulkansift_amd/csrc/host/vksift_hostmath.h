@@ -26,5 +26,7 @@ void vksift_hm_blur_taps(const vksift_Config *cfg, float *taps, uint32_t *ntaps)
 /* ComputeDescriptors.comp:116-124: fixed-point multiplier as a function of n = int_radius/2.
  * Returns the number of entries written (<= cap). */
 uint32_t vksift_hm_desc_fp_table(const vksift_Config *cfg, float *tab, uint32_t cap);
+/* the same table for descriptor windows of relative sigma (sigma / 2^octave_idx) up to sigma_max: a longer table starts with the shorter one */
+uint32_t vksift_hm_desc_fp_table_for(float sigma_max, float *tab, uint32_t cap);
 
 #endif

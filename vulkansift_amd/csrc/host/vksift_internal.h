@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_pairs.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -250,6 +250,12 @@ struct vksift_Instance_T
                              * a word 1 per slot */
   bool gtab_pending;
 
+  /* ---- caller-supplied keypoints (vksift_describe.c); everything allocated by the first describe call */
+  uint8_t *d_kps, *h_kps;        /* one call's keypoint offsets (count + 1 words, padded to 256 bytes) and, behind them, its keypoints: pinned staging and the device copy */
+  size_t kps_cap;                /* bytes of each (grows with the largest call) */
+  uint32_t *d_placed, *h_placed; /* per SIFT buffer: the records its last placement stored, before orientation copies */
+  uint64_t *placed_seq;          /* per SIFT buffer: the describe call whose count h_placed holds (0: none) */
+
   /* ---- download staging. Batched download: the first vksift_downloadFeatures() after a detection of VKSIFT_DL_BATCH_MIN images and more
    * packs the features of ALL its buffers on the device and fetches them with one copy into pinned memory; the downloads of the
    * other buffers are host copies out of it (one copy per section and buffer costs 80 us per buffer otherwise) */
@@ -297,7 +303,8 @@ struct vksift_Instance_T
   vksift_hip_event dl_ev[VKSIFT_DL_CHUNKS]; /* the packed copy arrives in pieces (created by the first one) */
   vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab (created by the first verification) */
   vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created by the first guided matching) */
-  bool desc_start_valid, input_free_valid, staging_pending;
+  vksift_hip_event ev_kps;  /* the last describe call's copy has read h_kps (created by the first describe call) */
+  bool desc_start_valid, input_free_valid, staging_pending, kps_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];
   uint64_t det_seq, det_done; /* last detection issued / highest one known to have completed */
 

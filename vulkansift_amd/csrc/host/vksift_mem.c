@@ -111,6 +111,7 @@ static const Block blocks[] = {
     LAZY(filt_ids, MEM_HEAP), LAZY(d_corr, MEM_DEVICE), LAZY(d_vscratch, MEM_DEVICE), LAZY(h_vtab, MEM_PINNED), LAZY(d_gxy, MEM_DEVICE), LAZY(d_gkeys, MEM_DEVICE), LAZY(h_gtab, MEM_PINNED),
     PAIR_RESULTS(PR_FILTERED), PAIR_RESULTS(PR_VERIFY_H), PAIR_RESULTS(PR_VERIFY_F), PAIR_RESULTS(PR_REFINE_H), PAIR_RESULTS(PR_REFINE_F), PAIR_RESULTS(PR_GUIDED),
     LAZY(d_dl, MEM_DEVICE), LAZY(h_dl, MEM_PINNED), LAZY(dl_row, MEM_HEAP), LAZY(h_post[0], MEM_PINNED), LAZY(h_post[1], MEM_PINNED),
+    LAZY(d_kps, MEM_DEVICE), LAZY(h_kps, MEM_PINNED), LAZY(d_placed, MEM_DEVICE), LAZY(h_placed, MEM_PINNED), LAZY(placed_seq, MEM_HEAP),
 };
 #define N_BLOCKS (sizeof(blocks) / sizeof(blocks[0]))
 
@@ -193,7 +194,7 @@ typedef struct
 {
   size_t field;
   uint16_t count, step;
-  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_pairs.c), destroyed here */
+  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_pairs.c, vksift_describe.c), destroyed here */
 } Handle;
 #define EVENTS(f, n, step, lazy) {FIELD(f), n, step, false, lazy}
 #define STREAM(f) {FIELD(f), 1, 0, true, false}
@@ -208,7 +209,7 @@ static const Handle handles[] = {
     EVENTS(prof[0].ev_t, 8, sizeof(vksift_hip_event), false), EVENTS(prof[1].ev_t, 8, sizeof(vksift_hip_event), false),
     EVENTS(prof[0].ev_pt, 3, sizeof(vksift_hip_event), false), EVENTS(prof[1].ev_pt, 3, sizeof(vksift_hip_event), false),
     EVENTS(prof[0].ev_scan, 2, sizeof(ProfSet), false), TIMER(T_MATCH, false),
-    EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_gtab, 1, 0, true),
+    EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_gtab, 1, 0, true), EVENTS(ev_kps, 1, 0, true),
     TIMER(T_VERIFY, true), TIMER(T_REFINE_H, true), TIMER(T_REFINE_F, true), TIMER(T_GUIDED, true), TIMER(T_BUDGET, true),
 };
 #define N_HANDLES (sizeof(handles) / sizeof(handles[0]))
