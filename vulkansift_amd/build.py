@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(OUT_DIR, "libvulkansift.so")
 
 HOST_SRCS = ["host/vksift_api.c", "host/vksift_instance.c", "host/vksift_mem.c", "host/vksift_detect.c", "host/vksift_stage.c", "host/vksift_defer.c", "host/vksift_buffers.c", "host/vksift_match.c", "host/vksift_verify.c", "host/vksift_refine.c", "host/vksift_guided.c", "host/vksift_strongest.c", "host/vksift_describe.c", "host/vksift_pairs.c",
              "host/vksift_ext.c", "host/vksift_sharded.c", "host/vksift_hostmath.c", "host/vksift_log.c", "host/vksift_synth.c"]
-HIP_SRCS = ["hip/runtime.hip", "hip/pyramid.hip", "hip/extrema.hip", "hip/extract_tail.hip", "hip/features.hip", "hip/match.hip", "hip/records.hip", "hip/strongest.hip", "hip/place.hip", "hip/verify.hip", "hip/refine.hip", "hip/refine_f.hip", "hip/guided.hip"]
+HIP_SRCS = ["hip/runtime.hip", "hip/pyramid.hip", "hip/extrema.hip", "hip/extract_tail.hip", "hip/features.hip", "hip/features_selftest.hip", "hip/match.hip", "hip/records.hip", "hip/strongest.hip", "hip/place.hip", "hip/verify.hip", "hip/refine.hip", "hip/refine_f.hip", "hip/guided.hip"]
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
@@ -118,6 +118,8 @@ HIP_EXTRA = {
     # chains — each packed op issues like two scalar ones AND waits for its predecessor (s_nop after every one), where the two
     # scalar chains interleave without wait states. Same operations, same results; descriptor kernel -5.6 % (1.98 -> 1.87 ms)
     "hip/features.hip": ["-fno-slp-vectorize"],
+    # (the self-test of the short forms is compiled like the kernels that use them)
+    "hip/features_selftest.hip": ["-fno-slp-vectorize"],
     # the same for the blur kernels, whose unrolled filters are written with explicit two-row interleaving already: 128 x 640x480
     # detect + match +1.8 % (the whole detection 5.33 -> 5.01 ms per call, most of it in the coarse octaves' launches)
     "hip/pyramid.hip": ["-fno-slp-vectorize"],

@@ -21,6 +21,7 @@
 #include "multi.h"
 #include "records.h"
 #include "vksift_hip.h"
+#include "wave.h"
 
 namespace
 {
@@ -64,7 +65,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6, 8)
     if (lane == 0)
       s_cnt[rpar][wave] = (uint32_t)__popcll(bal);
     __syncthreads();
-    uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), total = 0;
+    uint32_t rank = ballot_rank(bal, (int)lane), total = 0;
     for (uint32_t wv = 0; wv < nw; wv++)
     {
       const uint32_t n = s_cnt[rpar][wv];
@@ -95,14 +96,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6, 8)
 #pragma unroll
     for (uint32_t k = 0; k < TAIL_SPT; k++)
       tsum += (uint32_t)__popcll(cur[k]);
-    uint32_t incl = tsum;
-#pragma unroll
-    for (int dlt = 1; dlt < 64; dlt <<= 1)
-    {
-      const uint32_t t = __shfl_up(incl, dlt, 64);
-      if ((int)lane >= dlt)
-        incl += t;
-    }
+    const uint32_t incl = wave_scan_incl_u32(tsum, (int)lane);
     if (lane == 63u)
       s_wtot[tpar][wave] = incl;
     __syncthreads();

@@ -30,6 +30,7 @@
 #include "multi.h"
 #include "records.h"
 #include "vksift_hip.h"
+#include "wave.h"
 
 namespace
 {
@@ -333,14 +334,7 @@ __global__ void __launch_bounds__(1024) k_segment_scan(Multi<ExtremaArgs> m)
   for (int k = 0; k < 4; k++)
     p[k] = i0 + k < n ? (uint32_t)__popcll(mask[i0 + k]) : 0u;
   const uint32_t tsum = p[0] + p[1] + p[2] + p[3];
-  uint32_t incl = tsum;
-#pragma unroll
-  for (int dlt = 1; dlt < 64; dlt <<= 1)
-  {
-    uint32_t t = __shfl_up(incl, dlt, 64);
-    if (lane >= dlt)
-      incl += t;
-  }
+  const uint32_t incl = wave_scan_incl_u32(tsum, lane);
   if (lane == 63)
     wave_tot[wave] = incl;
   __syncthreads();
@@ -471,7 +465,7 @@ __global__ void __launch_bounds__(256) k_cand_emit(Multi<ExtremaArgs> m)
       s_cnt[wave] = (uint32_t)__popcll(bal), s_red[wave] = part;
     __syncthreads();
     const uint32_t cbase = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    uint32_t rank = ballot_rank(bal, lane);
     for (int wv = 0; wv < wave; wv++)
       rank += s_cnt[wv];
     const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];

@@ -252,15 +252,6 @@ __device__ __forceinline__ void store_record(uint32_t *rec, const KpRecord &kp)
   rec[8] = __float_as_uint(kp.intensity);
 }
 
-// sum over the lanes of a wave, in every lane (xor butterfly)
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1)
-    v += __shfl_xor(v, dlt, 64);
-  return v;
-}
-
 // What both refinement kernels derive from their octave and image: the candidate list and its (clamped) length, the image's octave as
 // a view and as one buffer resource (BUF: the launcher has checked that it stays below 2 GiB), the accept flags and per-chunk accept counts
 // (in the segment-offset array, free again after k_cand_list).

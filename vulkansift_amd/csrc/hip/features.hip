@@ -12,43 +12,23 @@
 //
 // All per-pixel arithmetic mirrors oracle/sift_oracle.c (orc_orientations / orc_descriptor) in its
 // "det" math mode operation for operation; exp/atan2/sin/cos come from detmath.h.
+//
+// Shared steps are stated once: image_view() and keypoint_head() below, the short arithmetic forms in features_math.h, the wave primitives in
+// wave.h. k_descriptor is a sequence of named steps (desc_*) with explicit inputs and outputs, all inlined.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "../detmath.h"
+#include "features_math.h"
 #include "multi.h"
 #include "records.h"
 #include "vksift_hip.h"
+#include "wave.h"
 
 namespace
 {
-
-#define PI_F 3.14159265358979323846f
-
-struct GaussView
-{
-  const float *base; // Gaussian layer 0 of this image/octave
-  int w, h, pitch;
-  size_t plane;
-};
-
-// One texel of the keypoint's Gaussian layer through its buffer resource. voff / soff are the byte offsets of the fp32 layout;
-// a binary16 pyramid (VKSIFT_PYRAMID_PRECISION_FLOAT16) halves them and widens the texel exactly.
-// (F16 is a template parameter of the kernels: as a run-time flag it cost the VALU-bound descriptor kernel 60 %)
-template <bool F16>
-__device__ __forceinline__ float tap_ld(const __amdgpu_buffer_rsrc_t rs, unsigned voff, int soff)
-{
-  if (F16)
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs, voff >> 1, soff >> 1, 0));
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
-}
-// layer `layer` of image `img` (strides in texels)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t layer_rsrc(const float *gauss, size_t texel_off, int pitch, int h, bool f16)
-{
-  const void *p = f16 ? (const void *)((const _Float16 *)gauss + texel_off) : (const void *)(gauss + texel_off);
-  return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, pitch * h * (f16 ? 2 : 4), 0x00020000);
-}
 
 struct FeatArgs
 {
@@ -71,81 +51,47 @@ struct FeatArgs
   uint32_t sec; // section of the SIFT buffer this octave fills (k_descriptor's dense rows)
 };
 
-// ComputeDescriptors.comp:160-171 / ComputeOrientation.comp:100-104 wrap an angle with "if (t < 0) t += 2 pi; else if
-// (t > 2 pi) t -= 2 pi". Both places only ever see t <= 2 pi — atan2 returns (-pi, pi], and the relative orientation is the
-// difference of two angles of [0, 2 pi] (the keypoint orientations are (k/2 + 0.5) * 2 pi / 36 with k/2 <= 35.5) — so the
-// second branch is dead and the wrap is one add, one compare, one select.
-__device__ __forceinline__ float wrap_2pi(float t)
+// What all three kernels derive from their octave and image b (w, h, pitch, plane: copies the window loops read from registers — read
+// through FeatArgs they are loaded again behind every atomic, +28 instructions in k_orientation's border loop)
+struct ImageView
 {
-  const float up = t + 2.f * PI_F;
-  return t < 0 ? up : t;
+  uint32_t found, n; // the section's device-side feature count; min(found, cap): the records that exist
+  uint8_t *feats;    // the image's section records
+  int w, h, pitch;
+  size_t plane;
+};
+__device__ __forceinline__ ImageView image_view(const FeatArgs &a, int b)
+{
+  ImageView v;
+  v.found = a.found[(size_t)b * a.found_img_stride];
+  v.n = v.found < a.cap ? v.found : a.cap;
+  v.feats = a.feats + (size_t)b * a.feat_img_stride;
+  v.w = a.w, v.h = a.h, v.pitch = a.pitch;
+  v.plane = (size_t)a.plane_stride;
+  return v;
 }
 
-// sqrtf(x) and a / b as hipcc expands them, minus the parts that only matter outside the range the caller has checked:
-// * sqrt_inrange: v_sqrt_f32 (<= 1 ulp), then one step down / up by the signs of two exact residuals — the compiler's own correctly rounded
-//   expansion without the 2^32 input scaling for x < 2^-96 and without the class test for 0 / inf behind it (x = 0: both residual tests fail
-//   on NaN / zero, the result is the 0 v_sqrt_f32 returned);
-// * div_inrange: v_rcp_f32, one Newton step, quotient, two remainder corrections — the compiler's expansion without v_div_scale (operands
-//   with exponents far apart or near the ends of the range), v_div_fmas' rescaling and v_div_fixup (zeros, infinities, NaN). With
-//   2^-64 <= a <= b <= 2^2 (or a = 0) no intermediate leaves the normal range, so every step computes what the scaled sequence computes.
-// Both return the bits of the IEEE operation (the descriptor parity tests run both paths against the oracle's sqrtf and '/').
-// 14 instead of 26 and 8 instead of 11 instructions; k_descriptor is bound by VALU issue (profiles/r05_descriptor_floor.md).
-__device__ __forceinline__ float sqrt_inrange(float x)
+// The head of keypoint k's record and the buffer resource of its Gaussian layer (both per-keypoint kernels open a keypoint with it)
+struct KeyHead
 {
-  const float s = __builtin_amdgcn_sqrtf(x);
-  const float sd = __uint_as_float(__float_as_uint(s) - 1u), su = __uint_as_float(__float_as_uint(s) + 1u);
-  const float rd = fmaf(-sd, s, x), ru = fmaf(-su, s, x);
-  float r = rd <= 0.f ? sd : s;
-  r = ru > 0.f ? su : r;
-  return r;
-}
-__device__ __forceinline__ float div_inrange(float a, float b)
+  const float *rec;
+  float scale_x, scale_y, sigma, theta;
+  int octave_idx;
+  __amdgpu_buffer_rsrc_t rs;
+};
+template <bool F16>
+__device__ __forceinline__ KeyHead keypoint_head(const FeatArgs &a, const ImageView &v, int b, uint32_t k)
 {
-  float r = __builtin_amdgcn_rcpf(b);
-  const float e = fmaf(-b, r, 1.f);
-  r = fmaf(e, r, r);
-  float q = a * r;
-  float m = fmaf(-b, q, a);
-  q = fmaf(m, r, q);
-  m = fmaf(-b, q, a);
-  return fmaf(m, r, q);
-}
-// v is 0 or at least 2^(E - 127) (v >= 0): one subtract, one unsigned compare
-template <uint32_t E>
-__device__ __forceinline__ bool below_range(float v) { return __float_as_uint(v) - 1u < (E << 23) - 1u; }
-
-// x / (2*pi): the 3-operation form of dm_div_2pi (detmath.h) without its tests. The caller checks the range (non-zero magnitudes below 2^-96
-// take the general form); a zero comes out as +0 whatever its sign, and floor and remainder of a zero bin coordinate are the same for both.
-__device__ __forceinline__ float div_2pi_inrange(float x)
-{
-  const float c2 = 2.f * PI_F, rc = 0x1.45f306p-3f;
-  const float q = x * rc;
-  return fmaf(fmaf(-q, c2, x), rc, q);
-}
-
-// Angle and length of a gradient for both per-keypoint kernels (ComputeOrientation.comp:102-106, ComputeDescriptors.comp:146-162): atan2 and
-// sqrt. INRANGE: the short forms; *odd is set where their range conditions do not hold (the caller then repeats the step with the general
-// forms: a wave-uniform branch that real images take in regions darker than ~2^-30, if at all; black synthetic backgrounds do, in the
-// tails of the blurs: tests/test_gpu_descriptor_ranges.py)
-template <bool INRANGE>
-__device__ __forceinline__ void grad_polar(float gradX, float gradY, float *ori, float *len, bool *odd)
-{
-  const float g2 = (gradX * gradX) + (gradY * gradY);
-  if (INRANGE)
-  {
-    const float ax = fabsf(gradX), ay = fabsf(gradY);
-    const float mx = ax > ay ? ax : ay, mn = ax > ay ? ay : ax;
-    *ori = dm_atan2f_ratio(div_inrange(mn, mx == 0.f ? 1.f : mx), ax, ay, gradX, gradY);
-    *len = sqrt_inrange(g2);
-    // mx >= 2^-48 (then g2 >= 2^-96 and no square underflowed) or 0; mn >= 2^-64 or 0. (Tested on mx, not on g2: a denormal mx beside
-    // mn = 0 squares to an exact 0, which a test of g2 lets through to rcp(denormal) = inf.)
-    *odd = below_range<127 - 48>(mx) || below_range<127 - 64>(mn);
-  }
-  else
-  {
-    *ori = dm_atan2f(gradY, gradX);
-    *len = sqrtf(g2);
-  }
+  KeyHead kh;
+  kh.rec = (const float *)(v.feats + (size_t)k * VKSIFT_RECORD_BYTES);
+  // wave-uniform (every wave of a keypoint reads the same record): keeps the resource in SGPRs
+  const uint32_t scale_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)((const uint32_t *)kh.rec)[4]);
+  kh.octave_idx = ((const int *)kh.rec)[5];
+  kh.sigma = kh.rec[6];
+  kh.scale_x = kh.rec[2], kh.scale_y = kh.rec[3], kh.theta = kh.rec[7];
+  // planes stay below 2 GiB (vksift_hip_extract_keypoints refuses sides of 16384 and more): 32-bit byte offsets
+  kh.rs = layer_rsrc(a.gauss, (size_t)b * a.img_stride + (size_t)scale_idx * v.plane, v.pitch, v.h, F16);
+  return kh;
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -162,30 +108,20 @@ __global__ void __launch_bounds__(256) k_orientation(Multi<FeatArgs> m)
   __shared__ uint32_t s_hist[4][36];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = (int)(IMG_FAST ? vb.x : vb.y);
-  const uint32_t found = a.found[(size_t)b * a.found_img_stride];
-  const uint32_t n0 = found < a.cap ? found : a.cap;
-  GaussView g{a.gauss + (size_t)b * a.img_stride, a.w, a.h, a.pitch, (size_t)a.plane_stride};
-  uint8_t *feats = a.feats + (size_t)b * a.feat_img_stride;
+  const ImageView g = image_view(a, b);
   uint32_t *hist = s_hist[wave];
 
   const uint32_t bk = IMG_FAST ? vb.y : vb.x, nbk = IMG_FAST ? vb.gy : vb.gx;
-  for (uint32_t k = bk * 4 + wave; k < n0; k += nbk * 4)
+  for (uint32_t k = bk * 4 + wave; k < g.n; k += nbk * 4)
   {
     if (lane < 36)
       hist[lane] = 0;
     __builtin_amdgcn_wave_barrier();
     float fp = 0.f;
     {
-      const float *rec = (const float *)(feats + (size_t)k * VKSIFT_RECORD_BYTES);
-      const float scale_x = rec[2], scale_y = rec[3];
-      const uint32_t scale_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)((const uint32_t *)rec)[4]); // one keypoint per wave
-      const int octave_idx = ((const int *)rec)[5];
-      const float sigma = rec[6];
-      // planes stay below 2 GiB (vksift_hip_extract_keypoints refuses sides of 16384 and more)
-      const __amdgpu_buffer_rsrc_t rs = layer_rsrc(a.gauss, (size_t)b * a.img_stride + (size_t)scale_idx * g.plane, g.pitch, g.h, F16);
-
+      const KeyHead kh = keypoint_head<F16>(a, g, b, k);
       // sigma / 2^octave_idx as a product with 2^-octave_idx: the same real number, rounded once either way
-      float lambda = 1.5f * (sigma * dm_pow2i(-octave_idx));
+      float lambda = 1.5f * (kh.sigma * dm_pow2i(-kh.octave_idx));
       int r = (int)floorf(3 * lambda);
       float es = -1.f / (2.f * lambda * lambda);
       // the window's largest squared distance is 2 (r + 1)^2 (offsets of at most r + 0.5 + 0.5 per axis): can es * d2 pass the clamp of dm_expf?
@@ -208,7 +144,7 @@ __global__ void __launch_bounds__(256) k_orientation(Multi<FeatArgs> m)
       float M = (gsum * gsum) * sqrtf(2.f);
       fp = (float)(1u << (uint32_t)(30 - dm_ceil_log2f(M)));
 
-      float rsx = roundf(scale_x), rsy = roundf(scale_y);
+      float rsx = roundf(kh.scale_x), rsy = roundf(kh.scale_y);
       int box = 2 * r + 1;
       int npix = box * box;
       // lane l visits window pixels l, l + 64, ...: (row, column) advance by (64 / box, 64 % box) with at most one carry
@@ -228,17 +164,16 @@ __global__ void __launch_bounds__(256) k_orientation(Multi<FeatArgs> m)
         float e = dm_expf_core_nonpos(fmaxf(xe, -87.3f));
         if (may_clamp)
           e = xe < -87.3f ? 0.f : e;
-        float ori, len, fbin;
+        float ori, len;
         bool odd;
         grad_polar<true>(gradX, gradY, &ori, &len, &odd);
         float x36 = wrap_2pi(ori) * 36.f;
-        fbin = div_2pi_inrange(x36); // == ori * 36 / (2 pi)
-        odd |= below_range<127 - 96>(fabsf(x36));
+        float fbin = angle_bin<true>(x36); // == ori * 36 / (2 pi)
+        odd |= angle_bin_odd(x36);
         if (__builtin_expect(__ballot(odd) != 0ull, 0))
         {
           grad_polar<false>(gradX, gradY, &ori, &len, nullptr);
-          x36 = wrap_2pi(ori) * 36.f;
-          fbin = dm_div_2pi(x36);
+          fbin = angle_bin<false>(wrap_2pi(ori) * 36.f);
         }
         const float mag = e * len;
         // ComputeOrientation.comp:107-112 wraps bin < 0 and bin >= 36; the angle is in [0, 2 pi] here (wrap_2pi), its quotient by 2 pi is
@@ -249,48 +184,48 @@ __global__ void __launch_bounds__(256) k_orientation(Multi<FeatArgs> m)
       };
       const int cxi = (int)rsx, cyi = (int)rsy;
       const int pitch4 = g.pitch * 4;
+      // The window loop: the lane walk and the window offsets once, the tap addressing in two forms.
+      auto window = [&](auto INTERIOR) {
+        for (int pix = lane; pix < npix; pix += 64)
+        {
+          const int dy = py - r, dx = px - r;
+          px += step_r, py += step_q;
+          if (px >= box)
+            px -= box, py++;
+          const float sdx = (rsx + (float)dx) - kh.scale_x;
+          const float sdy = (rsy + (float)dy) - kh.scale_y;
+          const float d2 = (sdx * sdx) + (sdy * sdy);
+          if constexpr (decltype(INTERIOR)::value)
+          {
+            // byte offset of texel (x - 1, y - 1): the four taps are immediate / scalar offsets from it (scalar offsets are unsigned)
+            const unsigned v0 = (__umul24((unsigned)(cyi + dy - 1), (unsigned)g.pitch) + (unsigned)(cxi + dx - 1)) * 4u;
+            accumulate(d2, tap_ld<F16>(kh.rs, v0 + 8u, pitch4), tap_ld<F16>(kh.rs, v0, pitch4), tap_ld<F16>(kh.rs, v0 + 4u, 2 * pitch4), tap_ld<F16>(kh.rs, v0 + 4u, 0));
+          }
+          else
+          {
+            const int gx = cxi + dx, gy = cyi + dy;
+            if ((gx < 1 || gx >= (g.w - 1) || gy < 1 || gy >= (g.h - 1)) && (d2 > (float)(r * r)))
+              continue; // quirk Q2 ('&&')
+            // imageLoad semantics (0 outside the image, quirk Q2 relies on it) through the layer's buffer resource: a tap
+            // outside the image gets an out-of-range offset, which the hardware answers with 0 — no branches, 32-bit offsets
+            const bool xin = (unsigned)gx < (unsigned)g.w, yin = (unsigned)gy < (unsigned)g.h;
+            // (each row offset from its own, in-range, row index: the 24-bit multiply must not see a negative row)
+            const unsigned o0 = (__umul24((unsigned)gy, (unsigned)g.pitch) + (unsigned)gx) * 4u;
+            const unsigned o_r = (yin && (unsigned)(gx + 1) < (unsigned)g.w) ? o0 + 4u : 0x80000000u;
+            const unsigned o_l = (yin && (unsigned)(gx - 1) < (unsigned)g.w) ? o0 - 4u : 0x80000000u;
+            const unsigned o_d = (xin && (unsigned)(gy + 1) < (unsigned)g.h) ? (__umul24((unsigned)(gy + 1), (unsigned)g.pitch) + (unsigned)gx) * 4u : 0x80000000u;
+            const unsigned o_u = (xin && (unsigned)(gy - 1) < (unsigned)g.h) ? (__umul24((unsigned)(gy - 1), (unsigned)g.pitch) + (unsigned)gx) * 4u : 0x80000000u;
+            accumulate(d2, tap_ld<F16>(kh.rs, o_r, 0), tap_ld<F16>(kh.rs, o_l, 0), tap_ld<F16>(kh.rs, o_d, 0), tap_ld<F16>(kh.rs, o_u, 0));
+          }
+        }
+      };
       // (wave-uniform: one keypoint per wave) the whole window and its taps inside the image interior — all but the keypoints
       // within r + 1 texels of a border: no texel is skipped (quirk Q2's test needs a texel outside the interior) and no tap needs
       // the out-of-image handling, which is a third of the general loop's instructions
       if (cxi - r >= 1 && cxi + r <= g.w - 2 && cyi - r >= 1 && cyi + r <= g.h - 2)
-      {
-        for (int pix = lane; pix < npix; pix += 64)
-        {
-          const int dy = py - r, dx = px - r;
-          px += step_r, py += step_q;
-          if (px >= box)
-            px -= box, py++;
-          const float sdx = (rsx + (float)dx) - scale_x;
-          const float sdy = (rsy + (float)dy) - scale_y;
-          // byte offset of texel (x - 1, y - 1): the four taps are immediate / scalar offsets from it (scalar offsets are unsigned)
-          const unsigned v0 = (__umul24((unsigned)(cyi + dy - 1), (unsigned)g.pitch) + (unsigned)(cxi + dx - 1)) * 4u;
-          accumulate((sdx * sdx) + (sdy * sdy), tap_ld<F16>(rs, v0 + 8u, pitch4), tap_ld<F16>(rs, v0, pitch4), tap_ld<F16>(rs, v0 + 4u, 2 * pitch4), tap_ld<F16>(rs, v0 + 4u, 0));
-        }
-      }
+        window(std::true_type{});
       else
-        for (int pix = lane; pix < npix; pix += 64)
-        {
-          const int dy = py - r, dx = px - r;
-          px += step_r, py += step_q;
-          if (px >= box)
-            px -= box, py++;
-          int gx = cxi + dx, gy = cyi + dy;
-          float sdx = (rsx + (float)dx) - scale_x;
-          float sdy = (rsy + (float)dy) - scale_y;
-          float d2 = (sdx * sdx) + (sdy * sdy);
-          if ((gx < 1 || gx >= (g.w - 1) || gy < 1 || gy >= (g.h - 1)) && (d2 > (float)(r * r)))
-            continue; // quirk Q2 ('&&')
-          // imageLoad semantics (0 outside the image, quirk Q2 relies on it) through the layer's buffer resource: a tap
-          // outside the image gets an out-of-range offset, which the hardware answers with 0 — no branches, 32-bit offsets
-          const bool xin = (unsigned)gx < (unsigned)g.w, yin = (unsigned)gy < (unsigned)g.h;
-          // (each row offset from its own, in-range, row index: the 24-bit multiply must not see a negative row)
-          const unsigned o0 = (__umul24((unsigned)gy, (unsigned)g.pitch) + (unsigned)gx) * 4u;
-          const unsigned o_r = (yin && (unsigned)(gx + 1) < (unsigned)g.w) ? o0 + 4u : 0x80000000u;
-          const unsigned o_l = (yin && (unsigned)(gx - 1) < (unsigned)g.w) ? o0 - 4u : 0x80000000u;
-          const unsigned o_d = (xin && (unsigned)(gy + 1) < (unsigned)g.h) ? (__umul24((unsigned)(gy + 1), (unsigned)g.pitch) + (unsigned)gx) * 4u : 0x80000000u;
-          const unsigned o_u = (xin && (unsigned)(gy - 1) < (unsigned)g.h) ? (__umul24((unsigned)(gy - 1), (unsigned)g.pitch) + (unsigned)gx) * 4u : 0x80000000u;
-          accumulate(d2, tap_ld<F16>(rs, o_r, 0), tap_ld<F16>(rs, o_l, 0), tap_ld<F16>(rs, o_d, 0), tap_ld<F16>(rs, o_u, 0));
-        }
+        window(std::false_type{});
     }
     __builtin_amdgcn_wave_barrier();
     {
@@ -305,19 +240,13 @@ __global__ void __launch_bounds__(256) k_orientation(Multi<FeatArgs> m)
         hv = (uint32_t)dm_div_3((float)(hm + hv + hp)); // == / 3.f for every integer-valued float up to 2^32 (detmath.h)
       }
       uint32_t hm = __shfl(hv, lm, 64), hp = __shfl(hv, lp, 64);
-      uint32_t mx = lane < 36 ? hv : 0u;
-#pragma unroll
-      for (int dlt = 32; dlt >= 1; dlt >>= 1)
-      {
-        uint32_t t = __shfl_xor(mx, dlt, 64);
-        mx = t > mx ? t : mx;
-      }
+      const uint32_t mx = wave_max_u32(lane < 36 ? hv : 0u);
       bool peak = lane < 36 && ((float)hv >= (0.8f * (float)mx)) && (hv > hm) && (hv > hp);
       unsigned long long pm = __ballot(peak);
       uint32_t npk = (uint32_t)__popcll(pm);
       if (peak)
       {
-        uint32_t rank = (uint32_t)__popcll(pm & ((1ull << lane) - 1ull));
+        uint32_t rank = ballot_rank(pm, lane);
         if (rank < a.max_keep)
         {
           uint32_t num = hm - hp;                 // quirk Q3: uint32 wrap-around
@@ -346,27 +275,18 @@ __global__ void __launch_bounds__(1024) k_orientation_finalize(Multi<FeatArgs> m
   const FeatArgs &a = m.oct[vb.o];
   const int b = (int)vb.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t found = a.found[(size_t)b * a.found_img_stride];
-  const uint32_t n0 = found < a.cap ? found : a.cap;
-  uint8_t *feats = a.feats + (size_t)b * a.feat_img_stride;
+  const ImageView g = image_view(a, b);
   const uint32_t *cnt = a.ori_cnt + (size_t)b * a.ori_img_stride;
   const float *ang = a.ori_ang + (size_t)b * a.ori_img_stride * VKSIFT_HIP_MAX_ORI;
   if (threadIdx.x == 0)
     carry_s = 0;
   __syncthreads();
-  for (uint32_t base = 0; base < n0; base += 1024)
+  for (uint32_t base = 0; base < g.n; base += 1024)
   {
     uint32_t k = base + threadIdx.x;
-    uint32_t c = k < n0 ? cnt[k] : 0u;
+    uint32_t c = k < g.n ? cnt[k] : 0u;
     uint32_t v = c > 1 ? c - 1 : 0u;
-    uint32_t incl = v;
-#pragma unroll
-    for (int dlt = 1; dlt < 64; dlt <<= 1)
-    {
-      uint32_t t = __shfl_up(incl, dlt, 64);
-      if (lane >= dlt)
-        incl += t;
-    }
+    const uint32_t incl = wave_scan_incl_u32(v, lane);
     if (lane == 63)
       wave_tot[wave] = incl;
     __syncthreads();
@@ -375,16 +295,16 @@ __global__ void __launch_bounds__(1024) k_orientation_finalize(Multi<FeatArgs> m
       wave_base += wave_tot[wv];
     uint32_t carry = carry_s;
     uint32_t excl = carry + wave_base + incl - v;
-    if (k < n0 && c >= 1)
+    if (k < g.n && c >= 1)
     {
-      uint32_t *rec = (uint32_t *)(feats + (size_t)k * VKSIFT_RECORD_BYTES);
+      uint32_t *rec = (uint32_t *)(g.feats + (size_t)k * VKSIFT_RECORD_BYTES);
       rec[7] = __float_as_uint(ang[(size_t)k * VKSIFT_HIP_MAX_ORI]);
       for (uint32_t j = 1; j < c; j++)
       {
-        uint32_t idx = found + excl + (j - 1);
+        uint32_t idx = g.found + excl + (j - 1);
         if (idx < a.cap)
         {
-          uint32_t *dst = (uint32_t *)(feats + (size_t)idx * VKSIFT_RECORD_BYTES);
+          uint32_t *dst = (uint32_t *)(g.feats + (size_t)idx * VKSIFT_RECORD_BYTES);
 #pragma unroll
           for (int q = 0; q < (int)VKSIFT_RECORD_HEAD_WORDS; q++)
             dst[q] = rec[q];
@@ -398,14 +318,13 @@ __global__ void __launch_bounds__(1024) k_orientation_finalize(Multi<FeatArgs> m
     __syncthreads();
   }
   if (threadIdx.x == 0)
-    a.found[(size_t)b * a.found_img_stride] = found + carry_s;
+    a.found[(size_t)b * a.found_img_stride] = g.found + carry_s;
 }
 
 // -------------------------------------------------------------------------------------------------
-// Descriptor (ComputeDescriptors.comp:84-274). grid = (blocks, batch); 4 keypoints per block.
+// Descriptor (ComputeDescriptors.comp:84-274). grid = (blocks, batch); one keypoint per block.
 // -------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int smod8(int v) { return v & 7; } // floored modulo for a power of two (quirk Q5, OpSMod)
-
 
 // Per-pixel descriptor contribution (ComputeDescriptors.comp:139-197) for window offset (cdx, cdy).
 struct DescCtx
@@ -413,6 +332,10 @@ struct DescCtx
   __amdgpu_buffer_rsrc_t rs; // the keypoint's Gaussian layer
   int pitch, pitch4;
   float scale_x, scale_y, rsx, rsy, kcos, ksin, kori, fp, bin_scale;
+  // for the row spans: the window [-R, R]^2 clipped to the image interior, relative to the rounded position (rsx, rsy) (ComputeDescriptors.comp:151
+  // skips the border texels); rounded minus exact position; 1 / kcos and 1 / -ksin
+  int dx0, dx1, dy0, dy1;
+  float offx, offy, ia0, ia1;
 };
 
 // The contribution of one window pixel in two straight-line halves (no branch in either, so that the scheduler can
@@ -465,7 +388,7 @@ __device__ __forceinline__ void desc_taps_pair(const DescCtx &c, unsigned v0, De
   a.dn = __uint_as_float(dn.x), b.dn = __uint_as_float(dn.y);
 }
 
-// INRANGE: see grad_polar
+// INRANGE: see grad_polar (features_math.h)
 template <bool INRANGE>
 __device__ __forceinline__ DescSample desc_sample(const DescCtx &c, int cdx, int cdy, const DescTaps &t, bool *odd)
 {
@@ -546,12 +469,333 @@ __device__ __forceinline__ void desc_scatter(const DescCtx &c, const DescSample 
     }
 }
 
-// One 256-thread workgroup per keypoint (the window of a coarse-scale keypoint has up to ~7.5k pixels; a single wave
-// would make it the critical path of the whole launch). About half of the window falls outside the rotated 4x4 grid:
-// the reference evaluates atan/exp for those pixels and then drops the contribution (ComputeDescriptors.comp:189);
-// here they are never visited (analytic row spans, see below), which changes no bit. The expensive part (gradient,
-// atan2, exp, 8 fixed-point atomics) runs on full 64-lane batches.
+// One 64 * NWV-thread workgroup per keypoint (the window of a coarse-scale keypoint has up to ~7.5k pixels; a single wave would make it the
+// critical path of the whole launch). About half of the window falls outside the rotated 4x4 grid: the reference evaluates atan/exp for those
+// pixels and then drops the contribution (ComputeDescriptors.comp:189); here they are never visited (analytic row spans, desc_row_spans), which
+// changes no bit. The expensive part (gradient, atan2, exp, 8 fixed-point atomics) runs on full 64-lane batches.
 constexpr int DESC_MAX_ROWS = 256; // window rows handled per pass (R <= 127: every stock configuration); taller windows take several passes
+
+// ---- step: dense rows for the matcher and posting (vksift_hip_DenseRows), once per workgroup. This section's features follow the stored features
+// of the sections in front of it: *s_row0 = their number (it waits in LDS for the epilogue: nothing of this stays in registers across the sample
+// loop). All counters are final here (the orientation launches of every octave precede this one); uniform scalar loads. The first workgroup of
+// section 0's share of an image (first_block) also writes the buffer's row count, the zero rows of quirk Q6 and the posted counters.
+template <bool CAN_POST>
+__device__ __forceinline__ void desc_dense_prologue(const FeatArgs &a, const vksift_hip_DenseRows &dr, int b, bool first_block, int tid, uint32_t *s_row0)
+{
+  if (!(dr.desc || (CAN_POST && dr.post)))
+    return;
+  const uint32_t *fsec = a.found + (size_t)b * a.found_img_stride - a.sec; // counter of section 0 of this image's buffer
+  uint32_t row0 = 0, total = 0;
+  // (constant indices into the by-value argument: a run-time index would send the struct through scratch memory — 8 bytes of scratch
+  // cost this kernel 4 %, tests/test_kernel_resources.py)
+#pragma unroll
+  for (uint32_t j = 0; j < 16u; j++)
+    if (j < dr.nsec)
+    {
+      const uint32_t f = fsec[j], n = f < dr.sec_cap[j] ? f : dr.sec_cap[j];
+      row0 += j < a.sec ? n : 0u;
+      total += n;
+    }
+  if (tid == 0)
+    *s_row0 = row0; // read behind the barriers of the keypoint loop
+  if (a.sec == 0 && first_block)
+  {
+    if (CAN_POST && dr.post && (uint32_t)tid < dr.found_post_n)
+      dr.found_post[(size_t)b * dr.found_post_n + tid] = fsec[tid]; // the counters travel with the posted records
+    if (dr.desc && tid == 0)
+      dr.n[(size_t)b * dr.n_img_stride] = total;
+    if (dr.desc && total < 2u && tid < 64)
+    {
+      uint32_t *z = (uint32_t *)(dr.desc + (size_t)b * dr.desc_img_stride);
+      if (tid >= (int)total * 32)
+        z[tid] = 0u;
+      if (tid < 2 && tid >= (int)total)
+        dr.norm[(size_t)b * dr.norm_img_stride + tid] = 128u * 128u * 128u;
+    }
+  }
+}
+
+// ---- step: per-keypoint set-up
+__device__ __forceinline__ DescCtx desc_setup(const FeatArgs &a, const ImageView &g, const KeyHead &kh)
+{
+  DescCtx c;
+  c.scale_x = kh.scale_x, c.scale_y = kh.scale_y, c.kori = kh.theta;
+  c.rs = kh.rs;
+  c.pitch = g.pitch, c.pitch4 = g.pitch * 4;
+  c.bin_scale = a.use_vlfeat ? 8.f : -8.f;
+  float scale_factor = dm_pow2i(kh.octave_idx);
+  float lambda = 3.0f * (kh.sigma / scale_factor);
+  float radius = sqrtf(2.f) * lambda * 5.f * 0.5f;
+  int R = (int)floorf(radius + 0.5f);
+  float sn, cs;
+  dm_sincosf(c.kori, &sn, &cs);
+  c.kcos = cs / lambda, c.ksin = sn / lambda;
+  uint32_t ti = (uint32_t)(R / 2);
+  c.fp = a.desc_fp_tab[ti < a.desc_fp_tab_len ? ti : a.desc_fp_tab_len - 1];
+  c.rsx = roundf(c.scale_x), c.rsy = roundf(c.scale_y);
+
+  const int cxi = (int)c.rsx, cyi = (int)c.rsy;
+  c.dx0 = max(-R, 1 - cxi), c.dx1 = min(R, g.w - 2 - cxi);
+  c.dy0 = max(-R, 1 - cyi), c.dy1 = min(R, g.h - 2 - cyi);
+  c.offx = c.rsx - c.scale_x, c.offy = c.rsy - c.scale_y;
+  // (reciprocals by v_rcp_f32, 1 ulp: the spans are conservative by 0.01 in T and 0.01 px at both ends, six orders of magnitude more than
+  // that error on coordinates below 2^14 — the four IEEE divisions per row cost every wave 44 instructions per keypoint, round 6)
+  c.ia0 = __builtin_amdgcn_rcpf(c.kcos), c.ia1 = __builtin_amdgcn_rcpf(-c.ksin);
+  return c;
+}
+
+// The rows of one pass (at most DESC_MAX_ROWS window rows from window row y0) in LDS
+struct DescRows
+{
+  int *lo;             // first dx of a row's span
+  uint32_t *cnt;       // its length
+  const uint32_t *pre; // this wave's exclusive prefix of the lengths, pre[nrows] = N
+  int y0, nrows;
+};
+
+// ---- step: the row spans of one pass. Only pixels whose rotated position (ox, oy) lies within the 5x5-cell footprint |ox|, |oy| < 2.5 of the 4x4
+// grid can touch a bin (about half of the window). Instead of testing every pixel, each window row gets its span of such pixels analytically: ox and
+// oy are linear in dx, so {dx : |kcos*fx + ksin*fy| < T and |kcos*fy - ksin*fx| < T} is an interval. The spans are approximate (fused arithmetic) and
+// conservative (margin): desc_scatter re-derives the cells exactly and drops the out-of-grid ones, so a false positive costs a sample slot, never a bit.
+template <int NT>
+__device__ __forceinline__ void desc_row_spans(const DescCtx &c, const DescRows &rows, int tid)
+{
+  const float T = 2.5f + 0.01f;
+  for (int row = tid; row < rows.nrows; row += NT)
+  {
+    const float fy = (float)(rows.y0 + row) + c.offy;
+    float lo = (float)c.dx0 - 0.5f, hi = (float)c.dx1 + 0.5f; // in dx
+    // |a * fx + bb| < T for (a, bb) = (kcos, ksin*fy) and (-ksin, kcos*fy); fx = dx + offx
+#pragma unroll
+    for (int e = 0; e < 2; e++)
+    {
+      const float aa = e == 0 ? c.kcos : -c.ksin, ia = e == 0 ? c.ia0 : c.ia1;
+      const float bb = e == 0 ? c.ksin * fy : c.kcos * fy;
+      if (fabsf(aa) > 1e-12f)
+      {
+        const float ctr = -bb * ia - c.offx, half = T * fabsf(ia);
+        lo = fmaxf(lo, ctr - half);
+        hi = fminf(hi, ctr + half);
+      }
+      else if (!(fabsf(bb) < T))
+        hi = lo - 2.f; // empty
+    }
+    const int ilo = (int)ceilf(lo - 0.01f), ihi = (int)floorf(hi + 0.01f);
+    const int xl = max(ilo, c.dx0), xh = min(ihi, c.dx1);
+    rows.lo[row] = xl;
+    rows.cnt[row] = xh >= xl ? (uint32_t)(xh - xl + 1) : 0u;
+  }
+}
+
+// ---- step: exclusive scan of the row counts (nrows <= DESC_MAX_ROWS), total in pre[nrows]. Every wave computes it for itself from the counts
+// (read-only here) into its own copy of the prefix array: no workgroup barrier afterwards.
+__device__ __forceinline__ void desc_row_prefix(const DescRows &rows, uint32_t *pre, int lane)
+{
+  uint32_t carry = 0;
+  for (int base = 0; base < rows.nrows; base += 64)
+  {
+    const int i = base + lane;
+    const uint32_t v = i < rows.nrows ? rows.cnt[i] : 0u;
+    const uint32_t incl = wave_scan_incl_u32(v, lane);
+    if (i < rows.nrows)
+      pre[i] = carry + incl - v;
+    carry += __shfl(incl, 63, 64);
+  }
+  if (lane == 0)
+    pre[rows.nrows] = carry;
+}
+
+// ---- step: the run of a wave and of a lane. The concatenated spans form the index space [0, N); the N samples need T = ceil(N / 64) wave-steps,
+// dealt out to the waves in whole steps (the first T % NWV waves take one more), so only the last step of the last wave has idle lanes. Splitting
+// N into NWV equal parts first and rounding each up to whole steps cost up to NWV - 1 extra steps (11 % of a typical 25-step keypoint). Inside its
+// wave's share lane l walks its own contiguous run — at any step the 64 lanes sit a run length apart and spread over all 16 spatial cells, so the
+// 8 fixed-point LDS atomics of a step hit mostly distinct addresses (row-adjacent samples pile onto 1-2 cells and serialise: measured 8 % slower).
+// Integer adds commute: the result does not depend on the order.
+struct DescRun
+{
+  uint32_t steps;      // samples per lane = steps of this wave
+  uint32_t sidx, send; // the lane's samples [sidx, send) of [0, N)
+  int row, cdx;        // row and dx of sample sidx
+  uint32_t row_end;    // pre[row + 1]
+};
+template <int NWV>
+__device__ __forceinline__ DescRun desc_run(const DescRows &rows, int wave, int lane)
+{
+  const uint32_t *s_pre = rows.pre;
+  const uint32_t N = s_pre[rows.nrows];
+  const uint32_t T = (N + 63u) / 64u, tq = T / NWV, tr = T % NWV;
+  DescRun r;
+  r.steps = tq + ((uint32_t)wave < tr ? 1u : 0u);
+  const uint32_t step0 = (uint32_t)wave * tq + min((uint32_t)wave, tr);
+  r.sidx = min(N, step0 * 64u + (uint32_t)lane * r.steps);
+  r.send = min(N, r.sidx + r.steps);
+  // locate the row of the first sample of this lane's run: largest row with pre[row] <= sidx
+  int row = 0;
+  if (r.sidx < r.send)
+  {
+    int lo_r = 0, hi_r = rows.nrows - 1;
+    while (lo_r < hi_r)
+    {
+      const int mid = (lo_r + hi_r + 1) >> 1;
+      if (s_pre[mid] <= r.sidx)
+        lo_r = mid;
+      else
+        hi_r = mid - 1;
+    }
+    row = lo_r;
+    while (s_pre[row + 1] <= r.sidx) // skip empty rows that share the same prefix value
+      row++;
+  }
+  r.row = row;
+  r.cdx = rows.lo[row] + (int)(r.sidx - s_pre[row]);
+  r.row_end = s_pre[row + 1];
+  return r;
+}
+
+// the lane's next sample: its window offset (sx, sy); false for a lane whose run has ended (it gets a dead one)
+__device__ __forceinline__ bool desc_next_sample(const DescRows &rows, DescRun &r, int &sx, int &sy)
+{
+  const bool live = r.sidx < r.send;
+  if (live && r.sidx >= r.row_end)
+  {
+    do
+      r.row++;
+    while (rows.pre[r.row + 1] <= r.sidx);
+    r.row_end = rows.pre[r.row + 1];
+    r.cdx = rows.lo[r.row];
+  }
+  sx = r.cdx, sy = rows.y0 + r.row;
+  r.cdx++, r.sidx++;
+  return live;
+}
+
+// ---- step: two samples per lane. Their (straight-line) contribution code is independent, so the scheduler interleaves the two dependency chains
+// instead of padding every compare -> select and transcendental with wait states. A lane whose run has ended carries a dead sample: the taps go
+// through the buffer resource (any offset is safe) and no contribution is executed.
+template <bool F16>
+__device__ __forceinline__ void desc_step_pair(const DescCtx &c, const DescRows &rows, DescRun &run, uint32_t *s_work)
+{
+  int sx[2], sy[2];
+  const bool live[2] = {desc_next_sample(rows, run, sx[0], sy[0]), desc_next_sample(rows, run, sx[1], sy[1])};
+  DescTaps t0, t1;
+  const unsigned v0 = desc_tap_base(c, sx[0], sy[0]);
+  if (F16)
+  {
+    t0 = desc_taps<F16>(c, v0);
+    t1 = desc_taps<F16>(c, desc_tap_base(c, sx[1], sy[1]));
+  }
+  else
+  {
+    // (a dead second sample takes whatever the pair load returns: it contributes nothing; the loads go through the buffer resource, so the texels
+    // past a row end are harmless too)
+    desc_taps_pair(c, v0, t0, t1);
+    if (live[1] && !(sy[1] == sy[0] && sx[1] == sx[0] + 1))
+      t1 = desc_taps<F16>(c, desc_tap_base(c, sx[1], sy[1])); // the run crossed into the next row span
+  }
+  bool o0, o1;
+  DescSample s0 = desc_sample<true>(c, sx[0], sy[0], t0, &o0), s1 = desc_sample<true>(c, sx[1], sy[1], t1, &o1);
+  float f0 = angle_bin<true>(s0.xb), f1 = angle_bin<true>(s1.xb);
+  o0 |= angle_bin_odd(s0.xb), o1 |= angle_bin_odd(s1.xb);
+  if (__builtin_expect(__ballot(o0 || o1) != 0ull, 0))
+  {
+    // some lane holds a value outside the ranges of the short forms (see desc_sample): the general forms for this step
+    s0 = desc_sample<false>(c, sx[0], sy[0], t0, nullptr), s1 = desc_sample<false>(c, sx[1], sy[1], t1, nullptr);
+    f0 = angle_bin<false>(s0.xb), f1 = angle_bin<false>(s1.xb);
+  }
+  desc_scatter(c, s0, f0, live[0], s_work);
+  desc_scatter(c, s1, f1, live[1], s_work);
+}
+
+// ---- step: the last step of a wave with an odd number of them, one sample per lane (general forms)
+template <bool F16>
+__device__ __forceinline__ void desc_step_odd(const DescCtx &c, const DescRows &rows, DescRun &run, uint32_t *s_work)
+{
+  int sx, sy;
+  const bool live = desc_next_sample(rows, run, sx, sy);
+  const DescSample s0 = desc_sample<false>(c, sx, sy, desc_taps<F16>(c, desc_tap_base(c, sx, sy)), nullptr);
+  desc_scatter(c, s0, angle_bin<false>(s0.xb), live, s_work);
+}
+
+// ---- step: the epilogue (wave 0), in three parts.
+// (1) normalise -> clamp at 0.2*norm -> renormalise -> x512 -> u8 (:200-265): lane l gets the bytes of elements l and l + 64
+__device__ __forceinline__ uint32_t desc_byte(float v) { return (v != v) ? 0u : (v < 0.f ? 0u : (v > 255.f ? 255u : (uint32_t)v)); }
+__device__ __forceinline__ void desc_bytes(const uint32_t *s_work, int ln, uint32_t &b0, uint32_t &b1)
+{
+  uint32_t w0 = desc_hist_read(s_work, ln), w1 = desc_hist_read(s_work, ln + 64);
+  float norm = sqrtf((float)wave_sum_u32(w0 * w0 + w1 * w1));
+  uint32_t lim = (uint32_t)(norm * 0.2f);
+  w0 = w0 < lim ? w0 : lim;
+  w1 = w1 < lim ? w1 : lim;
+  norm = sqrtf((float)wave_sum_u32(w0 * w0 + w1 * w1));
+  float scale = 512.f / norm;
+  b0 = desc_byte((float)w0 * scale), b1 = desc_byte((float)w1 * scale);
+}
+// (2) pack 4 consecutive bytes per dword: lanes 4q..4q+3 all get dword q (of their half of the descriptor)
+__device__ __forceinline__ uint32_t desc_pack4(uint32_t byte, int ln)
+{
+  uint32_t p = byte << ((uint32_t)(ln & 3) * 8u);
+  p |= __shfl_xor(p, 1, 64);
+  p |= __shfl_xor(p, 2, 64);
+  return p;
+}
+// (3) the sinks. The descriptor's 32 dwords at dst: the first lane of every group of four stores the group's two
+__device__ __forceinline__ void desc_store_dwords(uint32_t *dst, int ln, uint32_t p0, uint32_t p1)
+{
+  if ((ln & 3) == 0)
+  {
+    dst[ln >> 2] = p0;
+    dst[16 + (ln >> 2)] = p1;
+  }
+}
+// the posted record: its header words from the section record (written by the extraction and orientation launches), the descriptor's 32 words from
+// the registers of the lanes that hold them
+__device__ __forceinline__ void desc_post_record(const vksift_hip_DenseRows &dr, int b, uint32_t row, const float *rec, int ln, uint32_t p0, uint32_t p1)
+{
+  const uint32_t j = (uint32_t)ln & 15u;
+  const uint32_t d0 = __shfl(p0, (int)(4u * j), 64), d1 = __shfl(p1, (int)(4u * j), 64);
+  uint32_t *out = (uint32_t *)(dr.post + (size_t)b * dr.post_img_stride) + (size_t)row * VKSIFT_RECORD_WORDS;
+  if (ln < 32)
+    out[(int)VKSIFT_RECORD_HEAD_WORDS + ln] = ln < 16 ? d0 : d1;
+  else if (ln < (int)VKSIFT_RECORD_WORDS)
+    out[ln - 32] = ((const uint32_t *)rec)[ln - 32];
+}
+// the same 128 bytes as a dense row + |d - 128|^2 = sum d^2 - 256 sum d + 128 * 128^2 (k_shifted_norms): every lane of a group of four holds the
+// group's two dwords, the sums run over the 16 groups
+__device__ __forceinline__ void desc_dense_row(const vksift_hip_DenseRows &dr, int b, uint32_t row0, uint32_t k, int ln, uint32_t p0, uint32_t p1)
+{
+  uint32_t *dense = (uint32_t *)(dr.desc + (size_t)b * dr.desc_img_stride) + (size_t)row0 * 32;
+  uint32_t *dense_norm = dr.norm + (size_t)b * dr.norm_img_stride + row0;
+  uint32_t s2 = __builtin_amdgcn_udot4(p0, p0, 0u, false), s1 = __builtin_amdgcn_udot4(p0, 0x01010101u, 0u, false);
+  s2 = __builtin_amdgcn_udot4(p1, p1, s2, false), s1 = __builtin_amdgcn_udot4(p1, 0x01010101u, s1, false);
+#pragma unroll
+  for (int dlt = 32; dlt >= 4; dlt >>= 1)
+  {
+    s2 += __shfl_xor(s2, dlt, 64);
+    s1 += __shfl_xor(s1, dlt, 64);
+  }
+  desc_store_dwords(dense + (size_t)k * 32, ln, p0, p1);
+  if (ln == 0)
+    dense_norm[k] = s2 - 256u * s1 + 128u * 128u * 128u;
+}
+
+template <bool CAN_POST>
+__device__ __forceinline__ void desc_epilogue(const vksift_hip_DenseRows &dr, const ImageView &g, int b, uint32_t k, const float *rec, const uint32_t *s_work,
+                                              const uint32_t *s_row0, int lane)
+{
+  // (an opaque copy of the lane index for the whole epilogue: addresses and masks derived from it are recomputed per keypoint instead of being
+  // hoisted out of the keypoint loop into registers the sample loop cannot spare — hoisted, one of them was spilled, and any scratch costs this
+  // kernel per wave launched: tests/test_kernel_resources.py)
+  int ln = lane;
+  asm volatile("" : "+v"(ln));
+  uint32_t b0, b1;
+  desc_bytes(s_work, ln, b0, b1);
+  const uint32_t p0 = desc_pack4(b0, ln), p1 = desc_pack4(b1, ln);
+  desc_store_dwords((uint32_t *)(g.feats + (size_t)k * VKSIFT_RECORD_BYTES + VKSIFT_RECORD_DESC_AT), ln, p0, p1); // the section record
+  if (CAN_POST && dr.post)
+    desc_post_record(dr, b, *s_row0 + k, rec, ln, p0, p1);
+  if (dr.desc)
+    desc_dense_row(dr, b, *s_row0, k, ln, p0, p1);
+}
 
 template <int NWV, bool IMG_FAST, bool F16>
 __global__ void __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu((NWV == 2 && !F16) ? 8 : 6, 8)))
@@ -564,320 +808,43 @@ k_descriptor(Multi<FeatArgs> m, vksift_hip_DenseRows dr)
   __shared__ int s_row_lo[DESC_MAX_ROWS];
   __shared__ uint32_t s_row_cnt[DESC_MAX_ROWS];
   __shared__ uint32_t s_row_pre[NWV][DESC_MAX_ROWS + 1];
+  __shared__ uint32_t s_row0;
   const int tid = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = (int)(IMG_FAST ? vb.x : vb.y);
-  const uint32_t found = a.found[(size_t)b * a.found_img_stride];
-  const uint32_t n1 = found < a.cap ? found : a.cap;
-  GaussView g{a.gauss + (size_t)b * a.img_stride, a.w, a.h, a.pitch, (size_t)a.plane_stride};
-  uint8_t *feats = a.feats + (size_t)b * a.feat_img_stride;
-  // Dense rows for the matcher (vksift_hip_DenseRows): this section's features follow the stored features of the sections in front of
-  // it. All counters are final here (the orientation launches of every octave precede this one); uniform scalar loads.
-  // (the row offset waits in LDS for the epilogue: nothing of this stays in registers across the sample loop)
-  __shared__ uint32_t s_row0;
+  const ImageView g = image_view(a, b);
+  const uint32_t bk = IMG_FAST ? vb.y : vb.x, nbk = IMG_FAST ? vb.gy : vb.gx;
   // (posting belongs to single-image detections, which take the four-wave form: the two-wave instantiation of batches — the kernel that
   // sits on its instruction floor with 64 VGPRs — does not carry that code)
   constexpr bool CAN_POST = NWV == 4;
-  if (dr.desc || (CAN_POST && dr.post))
-  {
-    const uint32_t *fsec = a.found + (size_t)b * a.found_img_stride - a.sec; // counter of section 0 of this image's buffer
-    uint32_t row0 = 0, total = 0;
-    // (constant indices into the by-value argument: a run-time index would send the struct through scratch memory — 8 bytes of scratch
-    // cost this kernel 4 %, tests/test_kernel_resources.py)
-#pragma unroll
-    for (uint32_t j = 0; j < 16u; j++)
-      if (j < dr.nsec)
-      {
-        const uint32_t f = fsec[j], n = f < dr.sec_cap[j] ? f : dr.sec_cap[j];
-        row0 += j < a.sec ? n : 0u;
-        total += n;
-      }
-    if (tid == 0)
-      s_row0 = row0; // read behind the barriers of the keypoint loop
-    // the buffer's row count and the zero rows of quirk Q6: first workgroup of section 0's share of this image
-    if (a.sec == 0 && (IMG_FAST ? vb.y : vb.x) == 0)
-    {
-      if (CAN_POST && dr.post && (uint32_t)tid < dr.found_post_n)
-        dr.found_post[(size_t)b * dr.found_post_n + tid] = fsec[tid]; // the counters travel with the posted records
-      if (dr.desc && tid == 0)
-        dr.n[(size_t)b * dr.n_img_stride] = total;
-      if (dr.desc && total < 2u && tid < 64)
-      {
-        uint32_t *z = (uint32_t *)(dr.desc + (size_t)b * dr.desc_img_stride);
-        if (tid >= (int)total * 32)
-          z[tid] = 0u;
-        if (tid < 2 && tid >= (int)total)
-          dr.norm[(size_t)b * dr.norm_img_stride + tid] = 128u * 128u * 128u;
-      }
-    }
-  }
+  desc_dense_prologue<CAN_POST>(a, dr, b, bk == 0, tid, &s_row0);
 
-  for (uint32_t k = IMG_FAST ? vb.y : vb.x; k < n1; k += IMG_FAST ? vb.gy : vb.gx)
+  for (uint32_t k = bk; k < g.n; k += nbk)
   {
     __syncthreads(); // the previous keypoint's epilogue has read the histogram
     for (int i = tid; i < 256; i += NT_)
       s_work[desc_cell_word(i >> 4) + (i & 15)] = 0; // the 16 grid cells; made visible by the barrier behind the row-span pass below
 
-    const float *rec = (const float *)(feats + (size_t)k * VKSIFT_RECORD_BYTES);
-    const uint32_t scale_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)((const uint32_t *)rec)[4]); // uniform: keeps the resource in SGPRs
-    const int octave_idx = ((const int *)rec)[5];
-    const float sigma = rec[6];
-    DescCtx c;
-    c.scale_x = rec[2], c.scale_y = rec[3], c.kori = rec[7];
-    // planes stay below 2 GiB (vksift_hip_extract_keypoints refuses sides of 16384 and more): 32-bit byte offsets
-    c.rs = layer_rsrc(a.gauss, (size_t)b * a.img_stride + (size_t)scale_idx * g.plane, g.pitch, g.h, F16);
-    c.pitch = g.pitch, c.pitch4 = g.pitch * 4;
-    c.bin_scale = a.use_vlfeat ? 8.f : -8.f;
-    float scale_factor = dm_pow2i(octave_idx);
-    float lambda = 3.0f * (sigma / scale_factor);
-    float radius = sqrtf(2.f) * lambda * 5.f * 0.5f;
-    int R = (int)floorf(radius + 0.5f);
-    float sn, cs;
-    dm_sincosf(c.kori, &sn, &cs);
-    c.kcos = cs / lambda, c.ksin = sn / lambda;
-    uint32_t ti = (uint32_t)(R / 2);
-    c.fp = a.desc_fp_tab[ti < a.desc_fp_tab_len ? ti : a.desc_fp_tab_len - 1];
-    c.rsx = roundf(c.scale_x), c.rsy = roundf(c.scale_y);
-
-    // The window [-R, R]^2 is clipped to the image interior up front (ComputeDescriptors.comp:151 skips the border texels).
-    const int cxi = (int)c.rsx, cyi = (int)c.rsy;
-    const int dx0 = max(-R, 1 - cxi), dx1 = min(R, g.w - 2 - cxi);
-    const int dy0 = max(-R, 1 - cyi), dy1 = min(R, g.h - 2 - cyi);
-    const int bh = dy1 - dy0 + 1;
-    // Only pixels whose rotated position (ox, oy) lies within the 5x5-cell footprint |ox|, |oy| < 2.5 of the 4x4 grid can
-    // touch a bin (about half of the window). Instead of testing every pixel, each window row gets its span of such
-    // pixels analytically: ox and oy are linear in dx, so {dx : |kcos*fx + ksin*fy| < T and |kcos*fy - ksin*fx| < T} is an
-    // interval. The spans are approximate (fused arithmetic) and conservative (margin): desc_accumulate re-derives the
-    // cells exactly and drops the out-of-grid ones, so a false positive costs a sample slot, never a bit.
-    // Sample enumeration: the concatenated spans form the index space [0, N); wave v owns [v, v+1) * N / NWV and inside it
-    // lane l walks its own contiguous run — at any step the 64 lanes sit a run length apart and spread over all 16 spatial
-    // cells, so the 8 fixed-point LDS atomics of a step hit mostly distinct addresses (row-adjacent samples pile onto
-    // 1-2 cells and serialise: measured 8 % slower). Integer adds commute: the result does not depend on the order.
-    const float offx = c.rsx - c.scale_x, offy = c.rsy - c.scale_y;
-    const float T = 2.5f + 0.01f;
-    // (reciprocals by v_rcp_f32, 1 ulp: the spans are conservative by 0.01 in T and 0.01 px at both ends, six orders of magnitude more than
-    // that error on coordinates below 2^14 — the four IEEE divisions per row cost every wave 44 instructions per keypoint, round 6)
-    const float ia0 = __builtin_amdgcn_rcpf(c.kcos), ia1 = __builtin_amdgcn_rcpf(-c.ksin);
+    const KeyHead kh = keypoint_head<F16>(a, g, b, k);
+    const DescCtx c = desc_setup(a, g, kh);
+    const int bh = c.dy1 - c.dy0 + 1;
     for (int rb = 0; rb < bh; rb += DESC_MAX_ROWS)
     {
-      const int nrows = min(DESC_MAX_ROWS, bh - rb);
+      const DescRows rows{s_row_lo, s_row_cnt, s_row_pre[wave], c.dy0 + rb, min(DESC_MAX_ROWS, bh - rb)};
       __syncthreads();
-      for (int row = tid; row < nrows; row += NT_)
-      {
-        const float fy = (float)(dy0 + rb + row) + offy;
-        float lo = (float)dx0 - 0.5f, hi = (float)dx1 + 0.5f; // in dx
-        // |a * fx + bb| < T for (a, bb) = (kcos, ksin*fy) and (-ksin, kcos*fy); fx = dx + offx
-#pragma unroll
-        for (int e = 0; e < 2; e++)
-        {
-          const float aa = e == 0 ? c.kcos : -c.ksin, ia = e == 0 ? ia0 : ia1;
-          const float bb = e == 0 ? c.ksin * fy : c.kcos * fy;
-          if (fabsf(aa) > 1e-12f)
-          {
-            const float ctr = -bb * ia - offx, half = T * fabsf(ia);
-            lo = fmaxf(lo, ctr - half);
-            hi = fminf(hi, ctr + half);
-          }
-          else if (!(fabsf(bb) < T))
-            hi = lo - 2.f; // empty
-        }
-        const int ilo = (int)ceilf(lo - 0.01f), ihi = (int)floorf(hi + 0.01f);
-        const int xl = max(ilo, dx0), xh = min(ihi, dx1);
-        s_row_lo[row] = xl;
-        s_row_cnt[row] = xh >= xl ? (uint32_t)(xh - xl + 1) : 0u;
-      }
+      desc_row_spans<NT_>(c, rows, tid);
       __syncthreads();
-      {
-        // exclusive scan of the row counts (nrows <= DESC_MAX_ROWS), total in s_row_pre[nrows]. Every wave computes it for
-        // itself from the counts (s_row_cnt is read-only here) into its own copy of the prefix array: no barrier afterwards.
-        uint32_t *pre = s_row_pre[wave];
-        uint32_t carry = 0;
-        for (int base = 0; base < nrows; base += 64)
-        {
-          const int i = base + lane;
-          const uint32_t v = i < nrows ? s_row_cnt[i] : 0u;
-          uint32_t incl = v;
-#pragma unroll
-          for (int dlt = 1; dlt < 64; dlt <<= 1)
-          {
-            const uint32_t t = __shfl_up(incl, dlt, 64);
-            if (lane >= dlt)
-              incl += t;
-          }
-          if (i < nrows)
-            pre[i] = carry + incl - v;
-          carry += __shfl(incl, 63, 64);
-        }
-        if (lane == 0)
-          pre[nrows] = carry;
-      }
+      desc_row_prefix(rows, s_row_pre[wave], lane);
       __builtin_amdgcn_wave_barrier();
-      const uint32_t *s_pre = s_row_pre[wave];
-      const uint32_t N = s_pre[nrows];
-      // The N samples need T = ceil(N / 64) wave-steps; they are dealt out to the waves in whole steps (the first T % NWV
-      // waves take one more), so only the last step of the last wave has idle lanes. Splitting N into NWV equal parts
-      // first and rounding each up to whole steps cost up to NWV - 1 extra steps (11 % of a typical 25-step keypoint).
-      const uint32_t T = (N + 63u) / 64u, tq = T / NWV, tr = T % NWV;
-      uint32_t run = tq + ((uint32_t)wave < tr ? 1u : 0u); // samples per lane = steps of this wave
-      const uint32_t step0 = (uint32_t)wave * tq + min((uint32_t)wave, tr);
-      uint32_t sidx = min(N, step0 * 64u + (uint32_t)lane * run);
-      uint32_t send = min(N, sidx + run);
-      // locate the row of the first sample of this lane's run: largest row with pre[row] <= sidx
-      int row = 0;
-      if (sidx < send)
-      {
-        int lo_r = 0, hi_r = nrows - 1;
-        while (lo_r < hi_r)
-        {
-          const int mid = (lo_r + hi_r + 1) >> 1;
-          if (s_pre[mid] <= sidx)
-            lo_r = mid;
-          else
-            hi_r = mid - 1;
-        }
-        row = lo_r;
-        while (s_pre[row + 1] <= sidx) // skip empty rows that share the same prefix value
-          row++;
-      }
-      int cdx = s_row_lo[row] + (int)(sidx - s_pre[row]);
-      uint32_t row_end = s_pre[row + 1];
-      // Two samples per iteration: their (straight-line) contribution code is independent, so the scheduler interleaves
-      // the two dependency chains instead of padding every compare -> select and transcendental with wait states. A lane
-      // whose run has ended carries a dead sample: the taps go through the buffer resource (any offset is safe) and
-      // no contribution is executed.
-      auto next_sample = [&](int &sx, int &sy, bool &live) {
-        live = sidx < send;
-        if (live && sidx >= row_end)
-        {
-          do
-            row++;
-          while (s_pre[row + 1] <= sidx);
-          row_end = s_pre[row + 1];
-          cdx = s_row_lo[row];
-        }
-        sx = cdx, sy = dy0 + rb + row;
-        cdx++, sidx++;
-      };
+      DescRun run = desc_run<NWV>(rows, wave, lane);
       uint32_t it = 0;
-      for (; it + 1 < run; it += 2)
-      {
-        int sx[2], sy[2];
-        bool live[2];
-        next_sample(sx[0], sy[0], live[0]);
-        next_sample(sx[1], sy[1], live[1]);
-        DescTaps t0, t1;
-        const unsigned v0 = desc_tap_base(c, sx[0], sy[0]);
-        if (F16)
-        {
-          t0 = desc_taps<F16>(c, v0);
-          t1 = desc_taps<F16>(c, desc_tap_base(c, sx[1], sy[1]));
-        }
-        else
-        {
-          // (a dead second sample takes whatever the pair load returns: it contributes nothing; the loads go
-          // through the buffer resource, so the texels past a row end are harmless too)
-          desc_taps_pair(c, v0, t0, t1);
-          if (live[1] && !(sy[1] == sy[0] && sx[1] == sx[0] + 1))
-            t1 = desc_taps<F16>(c, desc_tap_base(c, sx[1], sy[1])); // the run crossed into the next row span
-        }
-        bool o0, o1;
-        DescSample s0 = desc_sample<true>(c, sx[0], sy[0], t0, &o0), s1 = desc_sample<true>(c, sx[1], sy[1], t1, &o1);
-        float f0 = div_2pi_inrange(s0.xb), f1 = div_2pi_inrange(s1.xb);
-        o0 |= below_range<127 - 96>(fabsf(s0.xb)), o1 |= below_range<127 - 96>(fabsf(s1.xb));
-        if (__builtin_expect(__ballot(o0 || o1) != 0ull, 0))
-        {
-          // some lane holds a value outside the ranges of the short forms (see desc_sample): the general forms for this step
-          s0 = desc_sample<false>(c, sx[0], sy[0], t0, nullptr), s1 = desc_sample<false>(c, sx[1], sy[1], t1, nullptr);
-          f0 = dm_div_2pi(s0.xb), f1 = dm_div_2pi(s1.xb);
-        }
-        desc_scatter(c, s0, f0, live[0], s_work);
-        desc_scatter(c, s1, f1, live[1], s_work);
-      }
-      if (it < run) // odd number of steps
-      {
-        int sx, sy;
-        bool live;
-        next_sample(sx, sy, live);
-        const DescSample s0 = desc_sample<false>(c, sx, sy, desc_taps<F16>(c, desc_tap_base(c, sx, sy)), nullptr);
-        desc_scatter(c, s0, dm_div_2pi(s0.xb), live, s_work);
-      }
+      for (; it + 1 < run.steps; it += 2)
+        desc_step_pair<F16>(c, rows, run, s_work);
+      if (it < run.steps) // odd number of steps
+        desc_step_odd<F16>(c, rows, run, s_work);
     }
     __syncthreads();
     if (wave == 0)
-    {
-      // (an opaque copy of the lane index for the whole epilogue: addresses and masks derived from it are recomputed per keypoint instead
-      // of being hoisted out of the keypoint loop into registers the sample loop cannot spare — hoisted, one of them was spilled, and any
-      // scratch costs this kernel per wave launched: tests/test_kernel_resources.py)
-      int ln = lane;
-      asm volatile("" : "+v"(ln));
-      // normalise -> clamp at 0.2*norm -> renormalise -> x512 -> u8 (:200-265)
-      uint32_t w0 = desc_hist_read(s_work, ln), w1 = desc_hist_read(s_work, ln + 64);
-      uint32_t acc = w0 * w0 + w1 * w1;
-#pragma unroll
-      for (int dlt = 32; dlt >= 1; dlt >>= 1)
-        acc += __shfl_xor(acc, dlt, 64);
-      float norm = sqrtf((float)acc);
-      uint32_t lim = (uint32_t)(norm * 0.2f);
-      w0 = w0 < lim ? w0 : lim;
-      w1 = w1 < lim ? w1 : lim;
-      acc = w0 * w0 + w1 * w1;
-#pragma unroll
-      for (int dlt = 32; dlt >= 1; dlt >>= 1)
-        acc += __shfl_xor(acc, dlt, 64);
-      norm = sqrtf((float)acc);
-      float scale = 512.f / norm;
-      float v0 = (float)w0 * scale, v1 = (float)w1 * scale;
-      uint32_t b0 = (v0 != v0) ? 0u : (v0 < 0.f ? 0u : (v0 > 255.f ? 255u : (uint32_t)v0));
-      uint32_t b1 = (v1 != v1) ? 0u : (v1 < 0.f ? 0u : (v1 > 255.f ? 255u : (uint32_t)v1));
-      // pack 4 consecutive bytes per dword: lanes 4q..4q+3 hold bytes of dword q (first half) / q+16 (second half)
-      uint32_t sh = (uint32_t)(ln & 3) * 8u;
-      uint32_t p0 = b0 << sh, p1 = b1 << sh;
-      p0 |= __shfl_xor(p0, 1, 64);
-      p0 |= __shfl_xor(p0, 2, 64);
-      p1 |= __shfl_xor(p1, 1, 64);
-      p1 |= __shfl_xor(p1, 2, 64);
-      if ((ln & 3) == 0)
-      {
-        uint32_t *desc = (uint32_t *)(feats + (size_t)k * VKSIFT_RECORD_BYTES + VKSIFT_RECORD_DESC_AT);
-        desc[ln >> 2] = p0;
-        desc[16 + (ln >> 2)] = p1;
-      }
-      if (CAN_POST && dr.post)
-      {
-        // the posted record: its header words from the section record (written by the extraction and orientation launches), the
-        // descriptor's 32 words from the registers of the lanes that hold them
-        const uint32_t j = (uint32_t)ln & 15u;
-        const uint32_t d0 = __shfl(p0, (int)(4u * j), 64), d1 = __shfl(p1, (int)(4u * j), 64);
-        uint32_t *out = (uint32_t *)(dr.post + (size_t)b * dr.post_img_stride) + (size_t)(s_row0 + k) * VKSIFT_RECORD_WORDS;
-        if (ln < 32)
-          out[(int)VKSIFT_RECORD_HEAD_WORDS + ln] = ln < 16 ? d0 : d1;
-        else if (ln < (int)VKSIFT_RECORD_WORDS)
-          out[ln - 32] = ((const uint32_t *)rec)[ln - 32];
-      }
-      if (dr.desc)
-      {
-        const uint32_t row0 = s_row0;
-        uint32_t *dense = (uint32_t *)(dr.desc + (size_t)b * dr.desc_img_stride) + (size_t)row0 * 32;
-        uint32_t *dense_norm = dr.norm + (size_t)b * dr.norm_img_stride + row0;
-        // the same 128 bytes as a dense row + |d - 128|^2 = sum d^2 - 256 sum d + 128 * 128^2 (k_shifted_norms): every lane of a
-        // group of four holds the group's two dwords, the sums run over the 16 groups
-        uint32_t s2 = __builtin_amdgcn_udot4(p0, p0, 0u, false), s1 = __builtin_amdgcn_udot4(p0, 0x01010101u, 0u, false);
-        s2 = __builtin_amdgcn_udot4(p1, p1, s2, false), s1 = __builtin_amdgcn_udot4(p1, 0x01010101u, s1, false);
-#pragma unroll
-        for (int dlt = 32; dlt >= 4; dlt >>= 1)
-        {
-          s2 += __shfl_xor(s2, dlt, 64);
-          s1 += __shfl_xor(s1, dlt, 64);
-        }
-        if ((ln & 3) == 0)
-        {
-          uint32_t *row = dense + (size_t)k * 32;
-          row[ln >> 2] = p0;
-          row[16 + (ln >> 2)] = p1;
-        }
-        if (ln == 0)
-          dense_norm[k] = s2 - 256u * s1 + 128u * 128u * 128u;
-      }
-    }
+      desc_epilogue<CAN_POST>(dr, g, b, k, kh.rec, s_work, &s_row0, lane);
   }
 }
 
@@ -912,6 +879,12 @@ bool img_fast(uint32_t batch, bool descriptor)
   return batch > 1 && !descriptor;
 }
 
+// an octave's share of a per-keypoint kernel's grid, in either order of the virtual grid
+bool add_octave(Multi<FeatArgs> &m, const FeatArgs &a, bool img_fast, uint32_t batch, uint32_t blocks)
+{
+  return multi_add(m, a, img_fast ? batch : blocks, img_fast ? blocks : batch, 1u);
+}
+
 // grid sizing only (the kernels stride over the real, device-side count): a generous estimate of the keypoints of an octave
 uint32_t expected_keypoints(const vksift_hip_OctaveJob *job, uint32_t batch)
 {
@@ -922,6 +895,19 @@ uint32_t expected_keypoints(const vksift_hip_OctaveJob *job, uint32_t batch)
   return n < 32u ? 32u : (n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n);
 }
 
+/* Workgroups per image of an octave's share, kp_per_block keypoints each, at most cap_blocks. The keypoint count is only known on the
+ * device; the share is sized for a dense octave (one keypoint per 512 pixels, twice the usual yield) and strides over whatever is there.
+ * Sizing it by the section capacity alone gave the coarse octaves 131 k workgroups per stage for a few hundred keypoints: 40-70 us of
+ * pure dispatch each. */
+uint32_t octave_blocks(const vksift_hip_OctaveJob *job, uint32_t batch, uint32_t kp_per_block, uint32_t cap_blocks)
+{
+  const uint32_t dense = expected_keypoints(job, batch);
+  uint32_t blocks = ((job->cap < dense ? job->cap : dense) + (kp_per_block - 1)) / kp_per_block;
+  if (blocks > cap_blocks)
+    blocks = cap_blocks;
+  return blocks == 0 ? 1 : blocks;
+}
+
 } // namespace
 
 // the launches of one run of at most MULTI_MAX octaves
@@ -930,23 +916,14 @@ static int orientation_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_
   Multi<FeatArgs> mo, mf;
   mo.n = mf.n = 0;
   const bool f = img_fast(batch, false);
+  /* capped so that an octave's share is ~16 k workgroups whatever the batch: the workgroups stride over the keypoints,
+   * and beyond that more (mostly idle) workgroups only cost dispatch — 512 frames: 1024 per image 1.97 ms, 128: 1.84, 32: 1.71 */
+  uint32_t cap_blocks = 16384u / batch;
+  cap_blocks = cap_blocks < 32u ? 32u : (cap_blocks > 1024u ? 1024u : cap_blocks);
   for (uint32_t i = 0; i < n; i++)
   {
     const FeatArgs a = make_args(&jobs[i]);
-    /* The keypoint count is only known on the device; an octave's share of the grid is sized for a dense octave (one keypoint per
-     * 512 pixels, twice the usual yield) and strides over whatever is there. Sizing it by the section capacity alone gave the
-     * coarse octaves 131 k workgroups per stage for a few hundred keypoints: 40-70 us of pure dispatch each. */
-    const uint32_t dense = expected_keypoints(&jobs[i], batch);
-    uint32_t blocks = ((jobs[i].cap < dense ? jobs[i].cap : dense) + 3) / 4;
-    /* ... and capped so that an octave's share is ~16 k workgroups whatever the batch: the workgroups stride over the keypoints,
-     * and beyond that more (mostly idle) workgroups only cost dispatch — 512 frames: 1024 per image 1.97 ms, 128: 1.84, 32: 1.71 */
-    uint32_t cap_blocks = 16384u / batch;
-    cap_blocks = cap_blocks < 32u ? 32u : (cap_blocks > 1024u ? 1024u : cap_blocks);
-    if (blocks > cap_blocks)
-      blocks = cap_blocks;
-    if (blocks == 0)
-      blocks = 1;
-    if (!multi_add(mo, a, f ? batch : blocks, f ? blocks : batch, 1u) || !multi_add(mf, a, batch, 1u, 1u))
+    if (!add_octave(mo, a, f, batch, octave_blocks(&jobs[i], batch, 4, cap_blocks)) || !multi_add(mf, a, batch, 1u, 1u))
       return (int)hipErrorInvalidValue;
   }
   const bool f16 = mo.oct[0].fp16 != 0;
@@ -964,17 +941,8 @@ static int descriptor_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t
   md.n = 0;
   const bool f = img_fast(batch, true);
   for (uint32_t i = 0; i < n; i++)
-  {
-    const FeatArgs a = make_args(&jobs[i]);
-    const uint32_t dense = expected_keypoints(&jobs[i], batch);
-    uint32_t blocks = jobs[i].cap < dense ? jobs[i].cap : dense;
-    if (blocks > 2048)
-      blocks = 2048;
-    if (blocks == 0)
-      blocks = 1;
-    if (!multi_add(md, a, f ? batch : blocks, f ? blocks : batch, 1u))
+    if (!add_octave(md, make_args(&jobs[i]), f, batch, octave_blocks(&jobs[i], batch, 1, 2048)))
       return (int)hipErrorInvalidValue;
-  }
   /* waves per keypoint: 4 keep the critical path of a single image short (1 wave: 55 % slower, 8: no faster than 4); a batch has keypoints
    * to spare and runs 3-4 % faster with 2 (less redundant per-keypoint work, measured under the overlapped batch schedule) */
   const bool two_waves = batch >= 8u;
@@ -1009,78 +977,8 @@ static int for_runs(const vksift_hip_OctaveJob *jobs, uint32_t n_jobs, F run)
   return 0;
 }
 
-namespace
-{
-// test only (vksift_hip_selftest_inrange): the short forms against the compiler's general ones on pseudo-random operands inside their ranges
-__device__ __forceinline__ uint32_t st_hash(uint32_t x)
-{
-  x ^= x >> 16, x *= 0x7feb352du, x ^= x >> 15, x *= 0x846ca68bu, x ^= x >> 16;
-  return x;
-}
-// 2^e * (1 + m / 2^23) with e uniform in [elo, ehi]
-__device__ __forceinline__ float st_float(uint32_t h, int elo, int ehi)
-{
-  const int e = elo + (int)((h >> 23) % (uint32_t)(ehi - elo + 1));
-  return __uint_as_float(((uint32_t)(e + 127) << 23) | (h & 0x7FFFFFu));
-}
-__global__ void __launch_bounds__(256) k_inrange_selftest(uint32_t n, uint32_t seed, uint32_t *bad)
-{
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n)
-    return;
-  const uint32_t h0 = st_hash(i * 3u + seed), h1 = st_hash(i * 3u + 1u + seed), h2 = st_hash(i * 3u + 2u + seed);
-  uint32_t miss = 0;
-  // sqrt: 0 and [2^-96, 2^8), the ends of the range in the first lanes
-  float x = i == 0 ? 0.f : (i == 1 ? 0x1p-96f : (i == 2 ? __uint_as_float(0x0F800001u) : st_float(h0, -96, 7)));
-  asm volatile("" : "+v"(x));
-  miss += __float_as_uint(sqrt_inrange(x)) != __float_as_uint(sqrtf(x));
-  // a / b: b in [2^-49, 4), a = 0 or in [2^-64, b]
-  float b = st_float(h1, -49, 1), a = st_float(h2, -64, 1);
-  a = (i & 15u) == 3u ? 0.f : (a > b ? b * __uint_as_float(0x3F000000u | (h2 & 0x7FFFFFu)) : a); // b * [0.5, 1) where the draw exceeds b
-  a = a < 0x1p-64f && a != 0.f ? 0x1p-64f : a;
-  asm volatile("" : "+v"(a), "+v"(b));
-  miss += __float_as_uint(div_inrange(a, b)) != __float_as_uint(a / b);
-  // x / 2 pi: +-[2^-96, 2^8)
-  float y = st_float(h0 ^ h1, -96, 7);
-  y = (h2 & 1u) ? -y : y;
-  asm volatile("" : "+v"(y));
-  miss += __float_as_uint(div_2pi_inrange(y)) != __float_as_uint(y / (2.f * PI_F));
-  // grad_polar's own guard: wherever it does not ask for the general forms, the short forms must give their bits — components from
-  // denormals to 4 and exact zeros, incl. (0, denormal), whose squares underflow to 0
-  {
-    auto comp = [](uint32_t h, uint32_t i) {
-      const uint32_t kind = (h >> 27) & 7u;
-      float v = kind == 0u ? 0.f : (kind == 1u ? __uint_as_float(h & 0x7FFFFFu) /* denormal */ : __uint_as_float((((h >> 23) & 0xFFu) % 129u) << 23 | (h & 0x7FFFFFu)));
-      if (i == 4u)
-        v = __uint_as_float(1u);
-      return (h & 0x80000000u) ? -v : v;
-    };
-    float gx = comp(st_hash(h0 ^ 0x9E3779B9u), 0u), gy = comp(st_hash(h1 ^ 0x85EBCA6Bu), i);
-    if (i == 4u || i == 5u)
-      gx = 0.f;
-    asm volatile("" : "+v"(gx), "+v"(gy));
-    float o1, l1, o2, l2;
-    bool odd;
-    grad_polar<true>(gx, gy, &o1, &l1, &odd);
-    grad_polar<false>(gx, gy, &o2, &l2, nullptr);
-    miss += !odd && (__float_as_uint(o1) != __float_as_uint(o2) || __float_as_uint(l1) != __float_as_uint(l2));
-  }
-  if (miss)
-    atomicAdd(bad, miss);
-}
-} // namespace
-
 extern "C"
 {
-  int vksift_hip_selftest_inrange(uint32_t n, uint32_t seed, uint32_t *d_mismatches, vksift_hip_stream s)
-  {
-    hipError_t e = hipMemsetAsync(d_mismatches, 0, sizeof(uint32_t), (hipStream_t)s);
-    if (e != hipSuccess)
-      return (int)e;
-    hipLaunchKernelGGL(k_inrange_selftest, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)s, n, seed, d_mismatches);
-    return (int)hipGetLastError();
-  }
-
   int vksift_hip_orientations_multi(const vksift_hip_OctaveJob *jobs, uint32_t n_jobs, uint32_t batch, vksift_hip_stream s)
   {
     if (batch == 0)

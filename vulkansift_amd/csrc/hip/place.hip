@@ -14,6 +14,7 @@
 #include "../detmath.h"
 #include "records.h"
 #include "vksift_hip.h"
+#include "wave.h"
 
 #define PLACE_WAVES (VKSIFT_HIP_PLACE_WG / 64u)
 #define PLACE_MAX_STEPS 14u /* S + 1 thresholds, S <= 13 */
@@ -78,7 +79,7 @@ __global__ void __launch_bounds__(VKSIFT_HIP_PLACE_WG) k_place_keypoints(const u
     {
       const unsigned long long bal = __ballot(adm && oct == o);
       if (oct == o)
-        rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        rank = ballot_rank(bal, (int)lane);
       if (lane == 0u)
         wave_tot[wave][o] = (uint32_t)__popcll(bal);
     }

@@ -67,6 +67,7 @@ template <class Cnt, class Off> static inline VKSIFT_HD uint32_t section_row(con
 #if defined(__HIPCC__)
 
 #include "vksift_hip.h" /* VKSIFT_HIP_GATHER_SLOTS */
+#include "wave.h"
 
 /* ---- launch arguments -----------------------------------------------------------------------------------------------------------------
  * What the launches over sectioned buffers take by value (vksift_hip_gather_sections, vksift_hip_pack_features, vksift_hip_keep_strongest): the
@@ -162,7 +163,7 @@ __device__ __forceinline__ uint32_t ordered_keep(bool keep, uint32_t (&wave_tot)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned long long bal = __ballot(keep);
-  const uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+  const uint32_t rank = ballot_rank(bal, lane);
   if (lane == 0)
     wave_tot[wave] = (uint32_t)__popcll(bal);
   __syncthreads();

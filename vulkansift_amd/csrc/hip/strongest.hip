@@ -22,6 +22,7 @@
 
 #include "vksift_hip.h"
 #include "hip/records.h"
+#include "hip/wave.h"
 
 #define STRONGEST_LDS_KEYS 8192u
 #define STRONGEST_KEY_WORD 8u /* intensity: word 8 of the record's head */
@@ -95,13 +96,7 @@ __global__ void __launch_bounds__(1024) k_keep_strongest(uint8_t *__restrict__ f
       uint32_t h[4], sum = 0;
       for (uint32_t i = 0; i < 4u; i++)
         h[i] = hist[255u - 4u * tid - i], sum += h[i];
-      uint32_t incl = sum;
-      for (uint32_t d = 1; d < 64u; d <<= 1)
-      {
-        const uint32_t below = __shfl_up(incl, d, 64);
-        if (lane >= d)
-          incl += below;
-      }
+      const uint32_t incl = wave_scan_incl_u32(sum, (int)lane);
       uint32_t above = incl - sum;
       if (above < want && want <= incl) // one lane: the keys that start with `prefix` are at least `want`
       {
