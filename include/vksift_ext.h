@@ -211,6 +211,32 @@ extern "C"
   /* Time (ms) of the last vksift_ext_keepStrongestFeatures (its launches), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getKeepStrongestTime(vksift_Instance instance);
 
+  /* ---- RootSIFT descriptors ------------------------------------------------------------------------------------------------
+   * The descriptors of every feature of the SIFT buffers [first_gpu_buffer_id, first_gpu_buffer_id + count) are converted to RootSIFT (Arandjelovic &
+   * Zisserman 2012: COLMAP's default L1_ROOT normalisation, PopSift's --root-sift, the two lines most OpenCV callers write after detectAndCompute) in
+   * place on the device: no download, conversion on the host and upload into another buffer. A descriptor d[0..127] with s = the sum of its bytes becomes
+   * out[i] = min(255, round-half-up(512 sqrt(d[i] / s))), taken exactly — r is the integer with (2r - 1)^2 s <= 2^20 d[i] < (2r + 1)^2 s; integer
+   * arithmetic decides, not a float rounding —, and an all-zero descriptor stays all zero. A bin is zero afterwards iff it was zero. The Euclidean
+   * distance of two converted descriptors is the Hellinger distance of the originals; their norm is that of SIFT descriptors (about 512), so the
+   * matcher, the ratio test, the verification, the refits and the guided matching take them as they are. Of a feature only the 128 descriptor bytes
+   * change: x, y, the scales, sigma, orientation and intensity keep every bit, vksift_getFeaturesNumber its value, a detected buffer its octave
+   * sections, an uploaded one its dense run, vksift_ext_getPlacedKeypointsNumber its count. The feature budget's key is untouched: budget, then
+   * convert, and convert, then budget, give the same bytes.
+   * The call converts whatever the buffers hold. It is NOT idempotent: two calls convert twice. The instance does not track which form a buffer is
+   * in — that is the caller's to know; a detection, a describe call or an upload into the buffer makes it what they store. Matching a converted
+   * buffer against an unconverted one is defined (exact distances between the rows as they are) and meaningless.
+   * Contract of vksift_detectFeatures, as for vksift_ext_keepStrongestFeatures: asynchronous, queued on the instance stream behind every detection,
+   * selection and matching already queued (staged plain detections are launched first); the buffers are busy (vksift_isBufferAvailable false) until
+   * it has run, and every accessor of them waits for it: vksift_downloadFeatures and vksift_ext_exportDescriptorsDevice return converted descriptors,
+   * a matching queued afterwards sees them.
+   * Earlier results: matches, filtered matches, verified or refined models and guided matches of an earlier matching stay valid as indices — the
+   * rows have not moved — but their distances are those of the old descriptors. Match again.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, nothing changed): count 0 or above 512, a range outside sift_buffer_count. A launch failure is
+   * VKSIFT_VULKAN_ERROR. */
+  VKSIFT_EXPORT void vksift_ext_convertToRootSift(vksift_Instance instance, uint32_t first_gpu_buffer_id, uint32_t count);
+  /* Time (ms) of the last vksift_ext_convertToRootSift (its launches), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getRootSiftTime(vksift_Instance instance);
+
   /* ---- Describe caller-supplied keypoints ---------------------------------------------------------------------------------
    * OpenCV's detectAndCompute(useProvidedKeypoints = true), SiftGPU's SetKeypointList, VLFeat's vl_sift with frames: the scale-space of the image is
    * built as for a detection, and the caller's keypoints take the place of the extraction stage. Keypoint (x, y, sigma) in image pixels goes to the octave and

@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 9u      /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version) */
+#define VKSIFT_HIP_ABI_VERSION 10u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 10: vksift_hip_root_descriptors */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -504,6 +504,29 @@ extern "C"
                                 const uint32_t *sec_cap, const uint32_t *fixed_counts, uint32_t *found_base, uint32_t found_buf_stride, uint32_t *found_post,
                                 uint32_t max_features, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms, uint64_t norm_stride,
                                 uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s);
+  /* RootSIFT descriptors (rootsift.hip): the 128 descriptor bytes of every stored record of the SIFT buffers buf_ids[0..nslots), nslots <=
+   * VKSIFT_HIP_GATHER_SLOTS, are converted in place; one launch, all buffers of the call share the section table (named as for
+   * vksift_hip_gather_sections: the counters are found_base + id*found_buf_stride, or fixed_counts for uploaded buffers — exactly one of the two).
+   * A row d[0..127] with s = the sum of its bytes: s == 0 leaves it all zero; otherwise out[i] = min(255, r), r the integer with
+   * (2r - 1)^2 s <= 2^20 d[i] < (2r + 1)^2 s — 512 sqrt(d[i] / s) rounded half up, taken exactly (integer arithmetic decides, not a float
+   * rounding); out[i] == 0 iff d[i] == 0. tests/np_rootsift.py restates it. The launch converts whatever the rows hold: a second launch
+   * converts a second time. max_rows sizes the grid and nothing else (0 and values far above the total give the same bytes).
+   * READ, per named buffer id: its nsec counters (or fixed_counts[o], o < nsec), as vksift_hip_gather_sections reads them, and bytes 36..163 of
+   * its stored records. WRITTEN, per named buffer: bytes 36..163 of its stored records; with desc != NULL the buffer's matcher-cache entry
+   * exactly as vksift_hip_gather_sections would write it for the converted buffer (max(total, pad_rows_to) rows of 128 bytes at desc +
+   * id*desc_stride, rows total .. pad_rows_to - 1 all zero; as many norms at norms + id*norm_stride words, 128^3 for a zero row;
+   * n_out_dev[id*n_stride] = total), addressed by the BUFFER's id. Nothing else: not a record at or beyond a section's stored count, not one of
+   * the nine head words of a record (the feature budget's key included), not a counter, not the gap between two buffers, not the entry of a
+   * buffer that is not named, not a cache row at or beyond that count, not the padding of a stride; without desc, pad_rows_to, norms and
+   * n_out_dev are not looked at. A buffer must not be named twice (it would be converted twice, by workgroups that do not wait for each
+   * other). nsec == 0: every buffer is empty. Alignment: feats_base and buf_stride multiples of 4 (descriptors are loaded and stored as dwords),
+   * desc and desc_stride multiples of 16 (rows are stored 16 bytes at a time). hipErrorInvalidValue, nothing launched: nslots 0 or above
+   * VKSIFT_HIP_GATHER_SLOTS, nsec above 16, a misaligned feats_base, buf_stride, desc or desc_stride, desc without norms or n_out_dev,
+   * fixed_counts and found_base both given or both NULL. */
+  int vksift_hip_root_descriptors(uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, uint32_t nslots, uint32_t nsec, const uint32_t *sec_off,
+                                  const uint32_t *sec_cap, const uint32_t *fixed_counts, const uint32_t *found_base, uint32_t found_buf_stride,
+                                  uint32_t max_rows, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms, uint64_t norm_stride,
+                                  uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s);
   int vksift_hip_match_2nn_async(const uint8_t *cache_desc, const uint32_t *cache_norm, const uint32_t *cache_n, const uint32_t *ids_a, const uint32_t *ids_b,
                                  uint32_t max_na, uint32_t max_nb, uint32_t nb_exact, uint32_t *redo, uint32_t *n_dev, uint8_t *matches, uint32_t nslots, uint64_t cache_desc_stride,
                                  uint64_t cache_norm_stride, uint64_t redo_slot_stride, uint64_t match_slot_stride, uint32_t n_slot_stride,

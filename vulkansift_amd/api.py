@@ -175,6 +175,10 @@ def lib():
     L.vksift_ext_keepStrongestFeatures.restype = None
     L.vksift_ext_getKeepStrongestTime.argtypes = [inst]
     L.vksift_ext_getKeepStrongestTime.restype = C.c_float
+    L.vksift_ext_convertToRootSift.argtypes = [inst, u32, u32]
+    L.vksift_ext_convertToRootSift.restype = None
+    L.vksift_ext_getRootSiftTime.argtypes = [inst]
+    L.vksift_ext_getRootSiftTime.restype = C.c_float
     L.vksift_ext_describeKeypoints.argtypes = [inst, C.c_void_p, u32, u32, C.c_void_p, u32, u32, u32]
     L.vksift_ext_describeKeypoints.restype = None
     L.vksift_ext_describeKeypointsBatch.argtypes = [inst, C.POINTER(C.c_void_p), u32, u32, u32, C.c_void_p, C.POINTER(u32), u32, u32]
@@ -657,6 +661,16 @@ class Instance:
 
     def getKeepStrongestTime(self):
         return lib().vksift_ext_getKeepStrongestTime(self._h)
+
+    def convertToRootSift(self, first_buffer, count):
+        """the descriptors of every SIFT buffer of [first_buffer, first_buffer + count) become RootSIFT descriptors (L1-normalised, square-rooted,
+        512 sqrt(d / sum) rounded half up exactly, saturated to 255), in place on the GPU (vksift_ext_convertToRootSift); asynchronous like
+        detectFeatures. Not idempotent: a second call converts a second time"""
+        lib().vksift_ext_convertToRootSift(self._h, first_buffer, count)
+        _check_pending()
+
+    def getRootSiftTime(self):
+        return lib().vksift_ext_getRootSiftTime(self._h)
 
     def describeKeypoints(self, image, keypoints, gpu_buffer_id, mode=DESCRIBE_ORIENT):
         """describe the caller's keypoints (KEYPOINT_DTYPE, image pixels) on `image` into a SIFT buffer (vksift_ext_describeKeypoints): orientations

@@ -70,7 +70,8 @@ template <class Cnt, class Off> static inline VKSIFT_HD uint32_t section_row(con
 #include "wave.h"
 
 /* ---- launch arguments -----------------------------------------------------------------------------------------------------------------
- * What the launches over sectioned buffers take by value (vksift_hip_gather_sections, vksift_hip_pack_features, vksift_hip_keep_strongest): the
+ * What the launches over sectioned buffers take by value (vksift_hip_gather_sections, vksift_hip_pack_features, vksift_hip_keep_strongest,
+ * vksift_hip_root_descriptors): the
  * section table every buffer of the launch shares, and the buffer each slot serves. */
 struct SectionTable
 {
@@ -108,6 +109,15 @@ static inline GatherMap gather_map(const uint32_t *buf_ids, uint32_t nslots)
     m.buf[i] = i < nslots ? buf_ids[i] : 0u;
   return m;
 }
+
+/* The matcher's cache block as the launches that rewrite records in place take it (vksift_hip_keep_strongest, vksift_hip_root_descriptors): they
+ * leave the entry of a buffer as vksift_hip_gather_sections would write it for the buffer afterwards. rows == nullptr: none. */
+struct CacheEntry
+{
+  uint32_t *rows, *norms, *n;
+  uint64_t row_stride, norm_stride; // dwords per buffer
+  uint32_t n_stride, pad_rows_to;
+};
 
 /* ---- layout decode --------------------------------------------------------------------------------------------------------------------
  * One side of a pair-table slot, resolved into LDS: what section_row needs, the total and the buffer. */

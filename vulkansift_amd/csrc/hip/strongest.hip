@@ -30,13 +30,6 @@
 namespace
 {
 
-struct CacheEntry // the matcher's cache block (vksift_hip_gather_sections); rows == nullptr: none
-{
-  uint32_t *rows, *norms, *n;
-  uint64_t row_stride, norm_stride; // dwords per buffer
-  uint32_t n_stride, pad_rows_to;
-};
-
 __global__ void __launch_bounds__(1024) k_keep_strongest(uint8_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
                                                          uint32_t *__restrict__ found_base, uint32_t found_buf_stride, uint32_t *__restrict__ found_post,
                                                          uint32_t max_features, CacheEntry cache)

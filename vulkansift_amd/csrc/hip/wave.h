@@ -6,14 +6,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// sum over the lanes of a wave, in every lane (xor butterfly)
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
+// sum over every aligned group of LANES lanes (a power of two, at most 64), in every lane of the group (xor butterfly)
+template <int LANES> __device__ __forceinline__ uint32_t lanes_sum_u32(uint32_t v)
 {
 #pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1)
+  for (int dlt = LANES / 2; dlt >= 1; dlt >>= 1)
     v += __shfl_xor(v, dlt, 64);
   return v;
 }
+
+// sum over the lanes of a wave, in every lane
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return lanes_sum_u32<64>(v); }
 
 // maximum over the lanes of a wave, in every lane
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)

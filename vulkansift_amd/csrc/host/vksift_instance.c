@@ -243,6 +243,26 @@ int wait_detect_seq(vksift_Instance inst, uint64_t seq)
   return e;
 }
 
+/* A call that rewrites the records of a range of buffers in place (the feature budget, the RootSIFT conversion) is a "detection" of the buffers it
+ * names as far as the waits are concerned: it takes the next sequence number and a ring slot,
+ * so that counts_valid(), wait_for_buffer(), vksift_isBufferAvailable() and rows_bound() (capacity bound until the new counters have arrived)
+ * hold for it without a code path of their own, and a posted or packed copy of the records as they were (post_seq, dl_seq) is no longer
+ * served. The packed download of the range (download_from_batch) assumes one section table for all of it: a range that mixes tables or holds
+ * uploaded buffers gets a slot that names no buffer, and its downloads take the per-buffer paths. */
+void take_sequence(vksift_Instance inst, uint32_t first, uint32_t count)
+{
+  const uint64_t seq = inst->det_seq + 1u;
+  bool uniform = inst->bufs[first].nb_sections != 0;
+  for (uint32_t i = 0; i < count; i++)
+  {
+    uniform = uniform && same_layout(&inst->bufs[first], &inst->bufs[first + i]);
+    inst->bufs[first + i].seq = seq;
+  }
+  DetectSlot *d = &inst->det_ring[seq % VKSIFT_DETECT_RING];
+  d->seq = seq, d->first = first, d->count = uniform ? count : 0u;
+  inst->det_seq = seq;
+}
+
 bool match_running(vksift_Instance inst)
 {
   if (!inst->match_pending)

@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_rootsift.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -88,7 +88,7 @@ typedef struct
 } MatchScratch;
 
 /* the interval of a stage's last run under vksift_ext_setProfiling (vksift_pairs.c). One per getter: both verification models share T_VERIFY */
-enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_COUNT };
+enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_ROOTSIFT, T_COUNT };
 typedef struct
 {
   vksift_hip_event ev[2];
@@ -364,6 +364,9 @@ VKSIFT_INTERNAL void set_buffer_sections(vksift_Instance inst, uint32_t buf, uin
 VKSIFT_INTERNAL void mark_detect_done(vksift_Instance inst);
 VKSIFT_INTERNAL bool detect_running(vksift_Instance inst);
 VKSIFT_INTERNAL int wait_detect_seq(vksift_Instance inst, uint64_t seq);
+/* buffers [first, first + count) are rewritten in place by what the caller queues next (vksift_strongest.c, vksift_rootsift.c): they take the next
+ * sequence number and a ring slot; the caller records the slot's event behind its launches */
+VKSIFT_INTERNAL void take_sequence(vksift_Instance inst, uint32_t first, uint32_t count);
 VKSIFT_INTERNAL bool match_running(vksift_Instance inst);
 VKSIFT_INTERNAL int wait_all(vksift_Instance inst);
 VKSIFT_INTERNAL int grow_image_scratch(vksift_Instance inst, const PyrLayout *L);
