@@ -19,6 +19,7 @@ import hip_planes as HP
 import np_records as NR
 import record_cases as RC
 from hip_features import GUARD, POISON_BYTE, POISON_WORD, Block
+from test_section_walk import TABLES, _table, stored_rows
 
 HIP_ERROR_INVALID_VALUE = 1
 REC = NR.REC
@@ -162,9 +163,10 @@ class Norms(Launch):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- sectioned buffers
-def feature_block(launch, nbuf, extent, seed, gap_words=3):
-    """nbuf SIFT buffers of `extent` records, buf_stride = extent * 164 + 4 * gap_words bytes, the gaps poisoned -> (block, bytes, buf_stride)"""
-    bufs = RC.buffer_bytes(nbuf, extent, seed)
+def feature_block(launch, bufs, gap_words=3):
+    """bufs: (nbuf, extent, 164) record bytes. The SIFT buffers buf_stride = extent * 164 + 4 * gap_words bytes apart, the gaps poisoned
+    -> (block, bufs, buf_stride)"""
+    nbuf, extent = bufs.shape[:2]
     stride = extent * REC + 4 * gap_words
     flat = np.full(nbuf * stride, POISON_BYTE, np.uint8)
     for b in range(nbuf):
@@ -180,41 +182,95 @@ def counter_block(launch, counts, fbs):
     return launch.block("section counters", words, slot_bytes=4 * fbs, row_bytes=4)
 
 
-class Sections(Launch):
+GATHER_SLOTS = 512
+
+
+def sectioned_case(name, table, *, nbuf=1, buf_ids=None, counts=None, fixed=False, cache=False, pad=2, fbs=16, seed=1, desc_extra=0, norm_extra=0, n_stride=1,
+                   **own):
+    """The fields the cases of hip_strongest and hip_rootsift share. table: a name of test_section_walk.TABLES or (nsec, off, cap, found). counts:
+    raw counters per buffer (default: the table's own for every buffer). own: the fields of one entry's cases."""
+    table = TABLES[table] if isinstance(table, str) else table
+    nsec, off, cap, found = table
+    counts = [list(c) for c in counts] if counts is not None else [list(found[:nsec])] * nbuf
+    assert len(counts) == nbuf and (fbs >= nsec or fixed)
+    buf_ids = list(buf_ids if buf_ids is not None else range(nbuf))
+    assert len(set(buf_ids)) == len(buf_ids)
+    totals = [len(stored_rows(nsec, off, cap, c)) for c in counts]
+    return dict(name=name, table=table, nbuf=nbuf, buf_ids=buf_ids, counts=counts, totals=totals, fixed=fixed, cache=cache, pad=pad, fbs=fbs, seed=seed,
+                desc_extra=desc_extra, norm_extra=norm_extra, n_stride=n_stride, **own)
+
+
+def one(total, cap=None):
+    return _table(1, [cap if cap is not None else total + 3], [total])
+
+
+def case_named(cases, name):
+    (c,) = [c for c in cases if c["name"] == name]
+    return c
+
+
+class Sectioned(Launch):
+    """What the launches over sectioned buffers share (gather_sections, keep_strongest, root_descriptors): the SIFT buffers and their counters,
+    the matcher-cache blocks where the case has them, and the argument names. A subclass declares its blocks in arena order — sift_blocks(), any
+    of its own, cache_blocks() — and ends with finish(its own arguments), which builds the arena."""
+
+    def sift_blocks(self, bufs):
+        c = self.case
+        self.nsec, self.off, self.cap, _ = c["table"]
+        self.totals = c["totals"] if "totals" in c else RC.sec_totals(c)
+        self.named = [self.totals[b] for b in c["buf_ids"]]
+        self.feats, self.bufs, self.buf_stride = feature_block(self, bufs)
+        self.found = None if c["fixed"] else counter_block(self, c["counts"], c["fbs"])
+
+    def cache_blocks(self, rows, present=True):
+        """entries of `rows` rows and two more, plus the slack the case asks for"""
+        c = self.case
+        self.rows_cap = rows + 2
+        self.desc_stride = self.rows_cap * 128 + 16 * c["desc_extra"]
+        self.norm_stride = self.rows_cap + c["norm_extra"]
+        self.desc = self.norms = self.n = None
+        if present:
+            self.desc = self.poison("cache rows", c["nbuf"] * self.desc_stride, slot_bytes=self.desc_stride, row_bytes=128)
+            self.norms = self.poison("cache norms", c["nbuf"] * self.norm_stride * 4, slot_bytes=self.norm_stride * 4, row_bytes=4)
+            self.n = self.poison("cache n", c["nbuf"] * c["n_stride"] * 4, slot_bytes=c["n_stride"] * 4)
+
+    def max_rows(self):
+        return max(self.named) if self.case["max_rows"] == "exact" else self.case["max_rows"]
+
+    def finish(self, **own):
+        """own: the entry's arguments between found_buf_stride and pad_rows_to (a block stands for its address, None for NULL)"""
+        c = self.case
+        self.build()
+        ptr = lambda blk: blk.ptr if isinstance(blk, Block) else blk
+        self.args = dict(feats_base=self.feats.ptr, buf_stride=self.buf_stride, buf_ids=host_words(c["buf_ids"], GATHER_SLOTS + 8), nslots=len(c["buf_ids"]),
+                         nsec=self.nsec, sec_off=host_words(self.off, 20), sec_cap=host_words(self.cap, 20),
+                         fixed_counts=host_words(c["table"][3], 20) if c["fixed"] else None, found_base=ptr(self.found),
+                         found_buf_stride=0 if c["fixed"] else c["fbs"], **{k: ptr(v) for k, v in own.items()}, pad_rows_to=c["pad"], desc=ptr(self.desc),
+                         desc_stride=self.desc_stride, norms=ptr(self.norms), norm_stride=self.norm_stride, n_out=ptr(self.n), n_stride=c["n_stride"])
+
+    def expect_entry(self, exp, b, records, counts):
+        """the cache entry of buffer b in `exp` as the gather pass writes it for `records` with raw counters `counts`; returns its row count"""
+        rows, norms, total = NR.gather_sections(records, self.nsec, self.off, self.cap, counts, self.case["pad"])
+        self.view(exp, self.desc)[b * self.desc_stride:][:rows.size] = rows.reshape(-1)
+        self.view(exp, self.norms, u32)[b * self.norm_stride:][:len(norms)] = norms
+        self.view(exp, self.n, u32)[b * self.case["n_stride"]] = total
+        return total
+
+
+class Sections(Sectioned):
     entry = "gather_sections"
 
     def __init__(self, case, device="cuda"):
         super().__init__(case, device)
-        c = case
-        self.nsec, self.off, self.cap, _ = c["table"]
-        self.totals = RC.sec_totals(c)
-        named = [self.totals[b] for b in c["buf_ids"]]
-        self.rows_cap = max(max(named), c["pad"]) + 2
-        self.feats, self.bufs, self.buf_stride = feature_block(self, c["nbuf"], RC.extent_of(self.off, self.cap, self.nsec), c["seed"])
-        self.found = None if c["fixed"] else counter_block(self, c["counts"], c["fbs"])
-        self.desc_stride = self.rows_cap * 128 + 16 * c["desc_extra"]
-        self.norm_stride = self.rows_cap + c["norm_extra"]
-        self.desc = self.poison("cache rows", c["nbuf"] * self.desc_stride, slot_bytes=self.desc_stride, row_bytes=128)
-        self.norms = self.poison("cache norms", c["nbuf"] * self.norm_stride * 4, slot_bytes=self.norm_stride * 4, row_bytes=4)
-        self.n = self.poison("cache n", c["nbuf"] * c["n_stride"] * 4, slot_bytes=c["n_stride"] * 4)
-        self.build()
-        max_rows = max(named) if c["max_rows"] == "exact" else c["max_rows"]
-        nslots = len(c["buf_ids"])
-        self.args = dict(feats_base=self.feats.ptr, buf_stride=self.buf_stride, buf_ids=host_words(c["buf_ids"], 520), nslots=nslots, nsec=self.nsec,
-                         sec_off=host_words(self.off, 20), sec_cap=host_words(self.cap, 20),
-                         fixed_counts=host_words(c["table"][3], 20) if c["fixed"] else None,
-                         found_base=None if c["fixed"] else self.found.ptr, found_buf_stride=0 if c["fixed"] else c["fbs"], max_rows=max_rows,
-                         pad_rows_to=c["pad"], desc=self.desc.ptr, desc_stride=self.desc_stride, norms=self.norms.ptr, norm_stride=self.norm_stride,
-                         n_out=self.n.ptr, n_stride=c["n_stride"])
+        nsec, off, cap, _ = case["table"]
+        self.sift_blocks(RC.buffer_bytes(case["nbuf"], RC.extent_of(off, cap, nsec), case["seed"]))
+        self.cache_blocks(max(max(self.named), case["pad"]))
+        self.finish(max_rows=self.max_rows())
 
     def expected(self):
-        c = self.case
         exp = self.host.copy()
-        for b in set(c["buf_ids"]):   # the entry of BUFFER b, whichever slot names it
-            rows, norms, total = NR.gather_sections(self.bufs[b], self.nsec, self.off, self.cap, c["counts"][b], c["pad"])
-            self.view(exp, self.desc)[b * self.desc_stride:][:rows.size] = rows.reshape(-1)
-            self.view(exp, self.norms, u32)[b * self.norm_stride:][:len(norms)] = norms
-            self.view(exp, self.n, u32)[b * c["n_stride"]] = total
+        for b in set(self.case["buf_ids"]):   # the entry of BUFFER b, whichever slot names it
+            self.expect_entry(exp, b, self.bufs[b], self.case["counts"][b])
         return exp
 
 
@@ -226,7 +282,7 @@ class Pack(Launch):
         c = case
         self.nsec, self.off, self.cap, _ = c["table"]
         self.totals = RC.sec_totals(c)
-        self.feats, self.bufs, self.buf_stride = feature_block(self, c["nbuf"], RC.extent_of(self.off, self.cap, self.nsec), c["seed"])
+        self.feats, self.bufs, self.buf_stride = feature_block(self, RC.buffer_bytes(c["nbuf"], RC.extent_of(self.off, self.cap, self.nsec), c["seed"]))
         self.found = counter_block(self, c["counts"], c["fbs"])
         self.out = self.poison("packed records", c["out_records"] * REC, row_bytes=REC)
         self.post = self.poison("found_post", c["nbuf"] * c["fbs"] * 4, slot_bytes=4 * c["fbs"], row_bytes=4) if c["post"] else None
@@ -302,7 +358,7 @@ class PairTable(Launch):
 
     def world_blocks(self):
         w = self.case["world"]
-        self.feats, self.bufs, self.buf_stride = feature_block(self, w["nbuf"], w["extent"], w["seed"])
+        self.feats, self.bufs, self.buf_stride = feature_block(self, RC.buffer_bytes(w["nbuf"], w["extent"], w["seed"]))
         self.found = self.block("section counters", RC.world_found_words(w), slot_bytes=4 * w["fbs"], row_bytes=4)
         self.layouts = self.block("layouts", RC.world_layout_words(w), slot_bytes=4 * NR.LAYOUT_WORDS, row_bytes=4)
         tab = np.array([list(s["buf"]) + list(s["word"]) for s in self.case["slots"]], u32)

@@ -11,17 +11,15 @@ import functools
 import numpy as np
 
 import hip_records as HR
-import np_records as NR
 import np_rootsift as RS
 import record_cases as RC
-from hip_features import POISON_BYTE
-from test_section_walk import TABLES, _table, stored_rows
+from test_section_walk import _table, stored_rows
 
 REC = RS.REC
 u32 = np.uint32
 ROWS_PER_WAVE, ROWS_PER_BLOCK = 8, 32     # rootsift.hip: eight lanes per row, 256 threads
 MAX_BLOCKS, MIN_BLOCKS = 256, 8           # ... and the grid of one buffer alone; 8 per buffer with 512 slots
-GATHER_SLOTS = 512
+GATHER_SLOTS = HR.GATHER_SLOTS
 REST_MAX = 127 * 255                      # what the other 127 bins of a row can add to one bin
 
 
@@ -100,23 +98,12 @@ def make_rows(kind, n, rng):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- cases
-def case(name, table, *, rows="random", nbuf=1, buf_ids=None, counts=None, fixed=False, cache=False, pad=2, max_rows="exact", fbs=16, seed=1,
-         desc_extra=0, norm_extra=0, n_stride=1):
-    """table: a name of test_section_walk.TABLES or (nsec, off, cap, found). counts: raw counters per buffer (default: the table's own for every
-    buffer). max_rows: "exact" = the largest total of the named buffers."""
-    table = TABLES[table] if isinstance(table, str) else table
-    nsec, off, cap, found = table
-    counts = [list(c) for c in counts] if counts is not None else [list(found[:nsec])] * nbuf
-    assert len(counts) == nbuf and (fbs >= nsec or fixed)
-    buf_ids = list(buf_ids if buf_ids is not None else range(nbuf))
-    assert len(set(buf_ids)) == len(buf_ids)
-    totals = [len(stored_rows(nsec, off, cap, c)) for c in counts]
-    return dict(name=name, table=table, nbuf=nbuf, buf_ids=buf_ids, counts=counts, totals=totals, rows=rows, fixed=fixed, cache=cache, pad=pad,
-                max_rows=max_rows, fbs=fbs, seed=seed, desc_extra=desc_extra, norm_extra=norm_extra, n_stride=n_stride)
+def case(name, table, *, rows="random", max_rows="exact", **shared):
+    """max_rows: "exact" = the largest total of the named buffers; shared: hip_records.sectioned_case"""
+    return HR.sectioned_case(name, table, rows=rows, max_rows=max_rows, **shared)
 
 
-def one(total, cap=None):
-    return _table(1, [cap if cap is not None else total + 3], [total])
+one = HR.one
 
 
 _EIGHT = [[4, 3, 2], [50, 20, 8], [31, 20, 3], [0, 20, 9], [7, 7, 7], [50, 0, 8], [1, 1, 1], [31, 77, 3]]
@@ -180,9 +167,7 @@ def all_pairs_case():
 assert len({c["name"] for c in CASES}) == len(CASES)
 
 
-def case_named(name):
-    (c,) = [c for c in CASES if c["name"] == name]
-    return c
+case_named = functools.partial(HR.case_named, CASES)
 
 
 def case_buffers(c):
@@ -197,37 +182,14 @@ def case_buffers(c):
     return bufs
 
 
-class Root(HR.Launch):
+class Root(HR.Sectioned):
     entry = "root_descriptors"
 
     def __init__(self, c, device="cuda"):
         super().__init__(c, device)
-        self.nsec, self.off, self.cap, _ = c["table"]
-        self.bufs = case_buffers(c)
-        extent = self.bufs.shape[1]
-        self.buf_stride = extent * REC + 12
-        flat = np.full(c["nbuf"] * self.buf_stride, POISON_BYTE, np.uint8)
-        for b in range(c["nbuf"]):
-            flat[b * self.buf_stride:b * self.buf_stride + extent * REC] = self.bufs[b].reshape(-1)
-        self.feats = self.block("SIFT buffers", flat, slot_bytes=self.buf_stride, row_bytes=REC)
-        self.found = None if c["fixed"] else HR.counter_block(self, c["counts"], c["fbs"])
-        named = [c["totals"][b] for b in c["buf_ids"]]
-        self.rows_cap = max(max(named), c["pad"]) + 2
-        self.desc_stride = self.rows_cap * 128 + 16 * c["desc_extra"]
-        self.norm_stride = self.rows_cap + c["norm_extra"]
-        self.desc = self.norms = self.n = None
-        if c["cache"]:
-            self.desc = self.poison("cache rows", c["nbuf"] * self.desc_stride, slot_bytes=self.desc_stride, row_bytes=128)
-            self.norms = self.poison("cache norms", c["nbuf"] * self.norm_stride * 4, slot_bytes=self.norm_stride * 4, row_bytes=4)
-            self.n = self.poison("cache n", c["nbuf"] * c["n_stride"] * 4, slot_bytes=c["n_stride"] * 4)
-        self.build()
-        ptr = lambda blk: blk.ptr if blk is not None else None
-        self.args = dict(feats_base=self.feats.ptr, buf_stride=self.buf_stride, buf_ids=HR.host_words(c["buf_ids"], GATHER_SLOTS + 8), nslots=len(c["buf_ids"]),
-                         nsec=self.nsec, sec_off=HR.host_words(self.off, 20), sec_cap=HR.host_words(self.cap, 20),
-                         fixed_counts=HR.host_words(c["table"][3], 20) if c["fixed"] else None, found_base=ptr(self.found),
-                         found_buf_stride=0 if c["fixed"] else c["fbs"], max_rows=max(named) if c["max_rows"] == "exact" else c["max_rows"],
-                         pad_rows_to=c["pad"], desc=ptr(self.desc), desc_stride=self.desc_stride, norms=ptr(self.norms), norm_stride=self.norm_stride,
-                         n_out=ptr(self.n), n_stride=c["n_stride"])
+        self.sift_blocks(case_buffers(c))
+        self.cache_blocks(max(max(self.named), c["pad"]), c["cache"])
+        self.finish(max_rows=self.max_rows())
         self._expected = None
 
     def expected(self):
@@ -240,10 +202,7 @@ class Root(HR.Launch):
                 lo = self.feats.off + b * self.buf_stride
                 exp[lo:lo + extent * REC] = out.reshape(-1)
                 if c["cache"]:
-                    rows, norms, total = NR.gather_sections(out, self.nsec, self.off, self.cap, c["counts"][b], c["pad"])
-                    self.view(exp, self.desc)[b * self.desc_stride:][:rows.size] = rows.reshape(-1)
-                    self.view(exp, self.norms, u32)[b * self.norm_stride:][:len(norms)] = norms
-                    self.view(exp, self.n, u32)[b * c["n_stride"]] = total
+                    self.expect_entry(exp, b, out, c["counts"][b])
             self._expected = exp
         return self._expected
 

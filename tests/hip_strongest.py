@@ -9,20 +9,20 @@ section from its new count up to its old stored count (Strongest.masked puts the
 A case is small: the smallest shapes at which the kernel can go wrong — totals around the round size of 1024 rows, one total beyond the
 8192 keys the kernel holds in LDS (it reads the others from the records again), budgets around the total, ties at the threshold across a
 section and a round boundary, keys that differ in one byte only, and the bit patterns a float comparison would get wrong."""
+import functools
+
 import numpy as np
 
 import hip_records as HR
-import np_records as NR
 import np_strongest as NS
 import record_cases as RC
-from hip_features import POISON_BYTE
-from test_section_walk import TABLES, _table, stored_rows
+from test_section_walk import _table, stored_rows
 
 REC = NS.REC
 u32 = np.uint32
 ROUND = 1024          # rows per round of the ordered pass
 LDS_KEYS = 8192       # STRONGEST_LDS_KEYS of strongest.hip
-GATHER_SLOTS = 512
+GATHER_SLOTS = HR.GATHER_SLOTS
 
 
 def _bits(v):
@@ -64,24 +64,14 @@ def _ties_budget(total, upto):
     return int((k > _bits(0.05)).sum() + (k[:upto] == _bits(0.05)).sum())
 
 
-def case(name, table, max_features, *, keys="random", nbuf=1, buf_ids=None, counts=None, fixed=False, cache=False, pad=2, fbs=16, post=True, seed=1,
-         desc_extra=0, norm_extra=0, n_stride=1):
-    """table: a name of test_section_walk.TABLES or (nsec, off, cap, found). counts: raw counters per buffer (default: the table's own for every
-    buffer). max_features: a number, or a function of the totals of the named buffers (a list) that returns one."""
-    table = TABLES[table] if isinstance(table, str) else table
-    nsec, off, cap, found = table
-    counts = [list(c) for c in counts] if counts is not None else [list(found[:nsec])] * nbuf
-    assert len(counts) == nbuf and (fbs >= nsec or fixed)
-    buf_ids = list(buf_ids if buf_ids is not None else range(nbuf))
-    assert len(set(buf_ids)) == len(buf_ids)
-    totals = [len(stored_rows(nsec, off, cap, c)) for c in counts]
-    n = max_features([totals[b] for b in buf_ids]) if callable(max_features) else max_features
-    return dict(name=name, table=table, nbuf=nbuf, buf_ids=buf_ids, counts=counts, totals=totals, N=n, keys=keys, fixed=fixed, cache=cache, pad=pad, fbs=fbs,
-                post=post and not fixed, seed=seed, desc_extra=desc_extra, norm_extra=norm_extra, n_stride=n_stride)
+def case(name, table, max_features, *, keys="random", post=True, fixed=False, **shared):
+    """max_features: a number, or a function of the totals of the named buffers (a list) that returns one; shared: hip_records.sectioned_case"""
+    c = HR.sectioned_case(name, table, fixed=fixed, keys=keys, post=post and not fixed, **shared)
+    c["N"] = max_features([c["totals"][b] for b in c["buf_ids"]]) if callable(max_features) else max_features
+    return c
 
 
-def one(total, cap=None):
-    return _table(1, [cap if cap is not None else total + 3], [total])
+one = HR.one
 
 
 def two(a, b):
@@ -137,9 +127,7 @@ CASES += [
 assert len({c["name"] for c in CASES}) == len(CASES)
 
 
-def case_named(name):
-    (c,) = [c for c in CASES if c["name"] == name]
-    return c
+case_named = functools.partial(HR.case_named, CASES)
 
 
 def case_buffers(c):
@@ -160,37 +148,15 @@ def case_buffers(c):
     return bufs
 
 
-class Strongest(HR.Launch):
+class Strongest(HR.Sectioned):
     entry = "keep_strongest"
 
     def __init__(self, c, device="cuda"):
         super().__init__(c, device)
-        self.nsec, self.off, self.cap, _ = c["table"]
-        self.bufs = case_buffers(c)
-        extent = self.bufs.shape[1]
-        self.buf_stride = extent * REC + 12
-        flat = np.full(c["nbuf"] * self.buf_stride, POISON_BYTE, np.uint8)
-        for b in range(c["nbuf"]):
-            flat[b * self.buf_stride:b * self.buf_stride + extent * REC] = self.bufs[b].reshape(-1)
-        self.feats = self.block("SIFT buffers", flat, slot_bytes=self.buf_stride, row_bytes=REC)
-        self.found = None if c["fixed"] else HR.counter_block(self, c["counts"], c["fbs"])
+        self.sift_blocks(case_buffers(c))
         self.post = self.poison("found_post", c["nbuf"] * c["fbs"] * 4, slot_bytes=4 * c["fbs"], row_bytes=4) if c["post"] else None
-        self.rows_cap = max(min(max(c["totals"]), c["N"]), c["pad"]) + 2
-        self.desc_stride = self.rows_cap * 128 + 16 * c["desc_extra"]
-        self.norm_stride = self.rows_cap + c["norm_extra"]
-        self.desc = self.norms = self.n = None
-        if c["cache"]:
-            self.desc = self.poison("cache rows", c["nbuf"] * self.desc_stride, slot_bytes=self.desc_stride, row_bytes=128)
-            self.norms = self.poison("cache norms", c["nbuf"] * self.norm_stride * 4, slot_bytes=self.norm_stride * 4, row_bytes=4)
-            self.n = self.poison("cache n", c["nbuf"] * c["n_stride"] * 4, slot_bytes=c["n_stride"] * 4)
-        self.build()
-        ptr = lambda blk: blk.ptr if blk is not None else None
-        self.args = dict(feats_base=self.feats.ptr, buf_stride=self.buf_stride, buf_ids=HR.host_words(c["buf_ids"], GATHER_SLOTS + 8), nslots=len(c["buf_ids"]),
-                         nsec=self.nsec, sec_off=HR.host_words(self.off, 20), sec_cap=HR.host_words(self.cap, 20),
-                         fixed_counts=HR.host_words(c["table"][3], 20) if c["fixed"] else None, found_base=ptr(self.found),
-                         found_buf_stride=0 if c["fixed"] else c["fbs"], found_post=ptr(self.post), max_features=c["N"], pad_rows_to=c["pad"],
-                         desc=ptr(self.desc), desc_stride=self.desc_stride, norms=ptr(self.norms), norm_stride=self.norm_stride, n_out=ptr(self.n),
-                         n_stride=c["n_stride"])
+        self.cache_blocks(max(min(max(c["totals"]), c["N"]), c["pad"]), c["cache"])
+        self.finish(found_post=self.post, max_features=c["N"])
         self._expected = None
 
     def _state(self):
@@ -211,11 +177,8 @@ class Strongest(HR.Launch):
                     if c["post"]:
                         self.view(exp, self.post, u32)[b * c["fbs"]:][:self.nsec] = found_out[:self.nsec]
                 if c["cache"]:
-                    rows, norms, total = NR.gather_sections(out, self.nsec, self.off, self.cap, found_out, c["pad"])
+                    total = self.expect_entry(exp, b, out, found_out)
                     assert total == c["N"]
-                    self.view(exp, self.desc)[b * self.desc_stride:][:rows.size] = rows.reshape(-1)
-                    self.view(exp, self.norms, u32)[b * self.norm_stride:][:len(norms)] = norms
-                    self.view(exp, self.n, u32)[b * c["n_stride"]] = total
             self._expected = exp, loose
         return self._expected
 

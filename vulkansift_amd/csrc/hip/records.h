@@ -1,8 +1,10 @@
-/* records.h — the steps every launch that moves or addresses SIFT records shares (hip/records.hip, hip/verify.hip, hip/guided.hip), each
- * defined once: the record and section-table constants, the walk from a download-order row to a stored row, the decode of a pair table's
- * layout word, the by-value launch arguments, and the ordered append of a 1024-thread workgroup. The constants compile as C (host/vksift_internal.h takes them from
- * here), the walk as host C++ too: plain integer arithmetic, checked row by row by tests/test_section_walk.py, which compiles this header
- * with the host compiler. The rest is device code. */
+/* records.h — the steps every launch that moves or addresses SIFT records shares (hip/records.hip, hip/strongest.hip, hip/rootsift.hip,
+ * hip/verify.hip, hip/guided.hip), each defined once: the record and section-table constants, the walk from a download-order row to a stored
+ * row, the decode of a pair table's layout word, the ordered append of a 1024-thread workgroup, and what the launches over sectioned buffers
+ * (vksift_hip_gather_sections, _pack_features, _keep_strongest, _root_descriptors) have in common — the by-value launch arguments, the
+ * prologue check of their entries, the grid of the gather walk, the per-buffer resolve, the stored counts and the cache row step. The
+ * constants compile as C (host/vksift_internal.h takes them from here), the walk as host C++ too: plain integer arithmetic, checked row by
+ * row by tests/test_section_walk.py, which compiles this header with the host compiler. The rest is device code and its launchers' host side. */
 #ifndef VKSIFT_RECORDS_H
 #define VKSIFT_RECORDS_H
 
@@ -110,14 +112,97 @@ static inline GatherMap gather_map(const uint32_t *buf_ids, uint32_t nslots)
   return m;
 }
 
-/* The matcher's cache block as the launches that rewrite records in place take it (vksift_hip_keep_strongest, vksift_hip_root_descriptors): they
- * leave the entry of a buffer as vksift_hip_gather_sections would write it for the buffer afterwards. rows == nullptr: none. */
+/* The matcher's cache block as the launches of the family take it: vksift_hip_gather_sections fills the entry of a buffer, and the launches that
+ * rewrite records in place (vksift_hip_keep_strongest, vksift_hip_root_descriptors) leave it as the gather pass would write it for the buffer
+ * afterwards. rows == nullptr: none. */
 struct CacheEntry
 {
   uint32_t *rows, *norms, *n;
   uint64_t row_stride, norm_stride; // dwords per buffer
   uint32_t n_stride, pad_rows_to;
 };
+
+/* from the entry arguments: the byte stride of the rows in dwords; without desc there is no entry, whatever the other arguments say */
+static inline CacheEntry cache_entry(uint8_t *desc, uint64_t desc_stride, uint32_t *norms, uint64_t norm_stride, uint32_t *n_out, uint32_t n_stride, uint32_t pad_rows_to)
+{
+  return CacheEntry{(uint32_t *)desc, desc ? norms : nullptr, desc ? n_out : nullptr, desc_stride / 4u, norm_stride, n_stride, desc ? pad_rows_to : 0u};
+}
+/* the entry of buffer bufi (strides no longer apply) */
+__device__ __forceinline__ CacheEntry cache_entry_of(CacheEntry c, uint32_t bufi)
+{
+  if (c.rows)
+    c.rows += (size_t)bufi * c.row_stride, c.norms += (size_t)bufi * c.norm_stride, c.n += (size_t)bufi * c.n_stride;
+  return c;
+}
+
+/* ---- the launch prologue ---------------------------------------------------------------------------------------------------------------
+ * What the entries of the family refuse before they launch, once. Always: 1 <= nslots <= max_slots, nsec <= 16, records that move dword by
+ * dword, at most 256 posted counters per buffer (one thread each), cache rows that are stored 16 bytes at a time. An entry without one of the
+ * arguments passes nullptr / 0. The parts an entry asks for: */
+#define ARGS_ONE_COUNTER_SOURCE 1u /* exactly one of fixed_counts / found_base */
+#define ARGS_CACHE_OPTIONAL 2u     /* the cache block is looked at only with desc, and then norms and n_out are there too */
+static inline bool sectioned_args_ok(uint32_t parts, uint32_t nslots, uint32_t max_slots, uint32_t nsec, const uint8_t *feats_base, uint64_t buf_stride,
+                                     const uint32_t *fixed_counts, const uint32_t *found_base, uint32_t found_buf_stride, const uint32_t *found_post,
+                                     const uint8_t *desc, uint64_t desc_stride, const uint32_t *norms, const uint32_t *n_out)
+{
+  const bool one_source = !(parts & ARGS_ONE_COUNTER_SOURCE) || (fixed_counts != nullptr) != (found_base != nullptr);
+  const bool cache = desc || !(parts & ARGS_CACHE_OPTIONAL), complete = !(parts & ARGS_CACHE_OPTIONAL) || !desc || (norms && n_out);
+  return nslots >= 1 && nslots <= max_slots && nsec <= VKSIFT_MAX_SECTIONS && !((uintptr_t)feats_base & 3u) && !(buf_stride & 3u) && one_source &&
+         !(found_post && found_buf_stride > 256u) && !(cache && (((uintptr_t)desc & 15u) || (desc_stride & 15u))) && complete;
+}
+
+/* The grid of the gather walk (vksift_hip_gather_sections, vksift_hip_root_descriptors): a grid-stride walk over the rows that exist (the count
+ * is read on the device), some 4096 workgroups of 32 rows (256 threads, eight lanes per row) per launch whatever the batch — a buffer alone
+ * gets up to 256, 512 buffers 8 each (8 rounds over 1900 rows) */
+#define GATHER_ROWS_PER_BLOCK 32u
+static inline uint32_t gather_walk_blocks(uint32_t max_rows, uint32_t pad_rows_to, uint32_t nslots)
+{
+  max_rows = max_rows < pad_rows_to ? pad_rows_to : max_rows;
+  uint32_t blocks = (max_rows + GATHER_ROWS_PER_BLOCK - 1u) / GATHER_ROWS_PER_BLOCK, cap_blocks = 4096u / nslots;
+  cap_blocks = cap_blocks < 8u ? 8u : (cap_blocks > 256u ? 256u : cap_blocks);
+  return blocks < 1u ? 1u : (blocks > cap_blocks ? cap_blocks : blocks);
+}
+
+/* ---- per buffer ------------------------------------------------------------------------------------------------------------------------
+ * The records and the counters of buffer bufi (buf_stride in dwords; found == nullptr: no counters on the device, the table's fixed counts) */
+template <class Word, class Count> struct BufferRef
+{
+  Word *recs;
+  Count *found;
+};
+template <class Word, class Count> __device__ __forceinline__ BufferRef<Word, Count> buffer_ref(Word *feats_base, uint64_t buf_stride, Count *found_base, uint32_t found_buf_stride, uint32_t bufi)
+{
+  return {feats_base + (size_t)bufi * buf_stride, found_base ? found_base + (size_t)bufi * found_buf_stride : nullptr};
+}
+
+/* raw count of section o, and the stored counts of all sections (section_counts) from it */
+template <class Count> __device__ __forceinline__ uint32_t raw_count(const SectionTable &tab, Count *found, uint32_t o) { return found ? found[o] : tab.fixed[o]; }
+template <class Count> __device__ __forceinline__ uint32_t stored_counts(const SectionTable &tab, Count *found, uint32_t (&cnt)[VKSIFT_MAX_SECTIONS])
+{
+  return section_counts(tab.nsec, [&](uint32_t o) { return raw_count(tab, found, o); }, tab.cap, cnt);
+}
+
+/* ---- the cache row step ----------------------------------------------------------------------------------------------------------------
+ * A cache row is the 128 descriptor bytes and their shifted norm, the sum of (byte - 128)^2 = s2 - 256 s1 + 128 * 128^2. Sixteen bytes contribute
+ * their own s2 - 256 s1 + 16 * 128^2: modulo 2^32 on the way, exact in the end, whatever the grouping. */
+#define VKSIFT_ZERO_ROW_NORM (128u * 128u * 128u) /* of the all-zero rows of quirk Q6 */
+__device__ __forceinline__ uint32_t shifted_norm_part(uint4 v)
+{
+  uint32_t s2 = __builtin_amdgcn_udot4(v.x, v.x, 0u, false), s1 = __builtin_amdgcn_udot4(v.x, 0x01010101u, 0u, false);
+  s2 = __builtin_amdgcn_udot4(v.y, v.y, s2, false), s1 = __builtin_amdgcn_udot4(v.y, 0x01010101u, s1, false);
+  s2 = __builtin_amdgcn_udot4(v.z, v.z, s2, false), s1 = __builtin_amdgcn_udot4(v.z, 0x01010101u, s1, false);
+  s2 = __builtin_amdgcn_udot4(v.w, v.w, s2, false), s1 = __builtin_amdgcn_udot4(v.w, 0x01010101u, s1, false);
+  return s2 - 256u * s1 + VKSIFT_ZERO_ROW_NORM / 8u;
+}
+
+/* eight lanes per row, lane j of them holds bytes 16 j .. 16 j + 15: called by all eight */
+__device__ __forceinline__ void cache_row_store(const CacheEntry &e, uint32_t row, uint32_t j, uint4 v)
+{
+  *(uint4 *)(e.rows + (size_t)row * 32u + 4u * j) = v;
+  const uint32_t norm = lanes_sum_u32<8>(shifted_norm_part(v));
+  if (j == 0u)
+    e.norms[row] = norm;
+}
 
 /* ---- layout decode --------------------------------------------------------------------------------------------------------------------
  * One side of a pair-table slot, resolved into LDS: what section_row needs, the total and the buffer. */

@@ -25,84 +25,65 @@ __global__ void __launch_bounds__(256) k_gather_desc(const uint8_t *__restrict__
 
 // Gather the descriptors of a (sectioned or packed) SIFT buffer into dense rows in download order AND compute
 // their shifted norms, with the per-section feature counts read on the device (no host round trip):
-// row -> section by scanning the <= 16 section counts; eight lanes per row, 16 bytes per lane.
-struct SlotMap
+// row -> section by scanning the <= 16 section counts; eight lanes per row, 16 bytes per lane (the cache row step of records.h).
+__global__ void __launch_bounds__(256) k_gather_sections(const uint32_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
+                                                         const uint32_t *__restrict__ found_base, uint32_t found_buf_stride, CacheEntry cache)
 {
-  uint32_t buf[64]; // SIFT buffer index handled by slot blockIdx.y
-};
-
-__global__ void __launch_bounds__(256) k_gather_sections(const uint8_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
-                                                         const uint32_t *__restrict__ found_base, uint32_t found_buf_stride, uint32_t *__restrict__ desc,
-                                                         uint64_t desc_slot_stride, uint32_t *__restrict__ norms, uint64_t norm_slot_stride,
-                                                         uint32_t *__restrict__ n_out, uint32_t n_slot_stride, uint32_t pad_rows_to)
-{
-  const uint32_t slot = blockIdx.y;
-  const uint32_t bufi = map.buf[slot];
-  const uint8_t *feats = feats_base + (size_t)bufi * buf_stride;
-  const uint32_t *found = found_base ? found_base + (size_t)bufi * found_buf_stride : nullptr;
+  const uint32_t bufi = map.buf[blockIdx.y];
+  const auto buf = buffer_ref(feats_base, buf_stride, found_base, found_buf_stride, bufi);
   // the dense rows, their norms and the row count land in the per-BUFFER cache entry (reused by every later match of the buffer)
-  desc += (size_t)bufi * desc_slot_stride;
-  norms += (size_t)bufi * norm_slot_stride;
-  n_out += (size_t)bufi * n_slot_stride;
+  const CacheEntry entry = cache_entry_of(cache, bufi);
 
   const uint32_t j = threadIdx.x & 7u; // 16 bytes of a row per lane: a wave moves 8 rows at a time, a workgroup 32
   // stored count of every section (uniform), then a grid-stride walk over the rows that exist
   uint32_t cnt[VKSIFT_MAX_SECTIONS];
-  const uint32_t total = section_counts(tab.nsec, [&](uint32_t o) { return found ? found[o] : tab.fixed[o]; }, tab.cap, cnt);
+  const uint32_t total = stored_counts(tab, buf.found, cnt);
   if (blockIdx.x == 0 && threadIdx.x == 0)
-    *n_out = total;
-  const uint32_t nrows = total > pad_rows_to ? total : pad_rows_to;
-  for (uint32_t row = blockIdx.x * 32 + (threadIdx.x >> 3); row < nrows; row += gridDim.x * 32)
+    *entry.n = total;
+  const uint32_t nrows = total > cache.pad_rows_to ? total : cache.pad_rows_to;
+  for (uint32_t row = blockIdx.x * GATHER_ROWS_PER_BLOCK + (threadIdx.x >> 3); row < nrows; row += gridDim.x * GATHER_ROWS_PER_BLOCK)
   {
     uint4 v = uint4{0u, 0u, 0u, 0u}; // rows in [total, pad_rows_to): quirk Q6 padding, all-zero descriptors
     if (row < total)
     {
       // (records are 164 bytes, the descriptor starts at byte 36: dword-aligned 16-byte loads)
-      const uint32_t *p = (const uint32_t *)(feats + (size_t)section_row(cnt, tab.off, row) * VKSIFT_RECORD_BYTES + VKSIFT_RECORD_DESC_AT + 16 * j);
+      const uint32_t *p = buf.recs + (size_t)section_row(cnt, tab.off, row) * VKSIFT_RECORD_WORDS + VKSIFT_RECORD_HEAD_WORDS + 4u * j;
       v = uint4{p[0], p[1], p[2], p[3]};
     }
-    *(uint4 *)(desc + (size_t)row * 32 + 4 * j) = v;
-    uint32_t s2 = __builtin_amdgcn_udot4(v.x, v.x, 0u, false), s1 = __builtin_amdgcn_udot4(v.x, 0x01010101u, 0u, false);
-    s2 = __builtin_amdgcn_udot4(v.y, v.y, s2, false), s1 = __builtin_amdgcn_udot4(v.y, 0x01010101u, s1, false);
-    s2 = __builtin_amdgcn_udot4(v.z, v.z, s2, false), s1 = __builtin_amdgcn_udot4(v.z, 0x01010101u, s1, false);
-    s2 = __builtin_amdgcn_udot4(v.w, v.w, s2, false), s1 = __builtin_amdgcn_udot4(v.w, 0x01010101u, s1, false);
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1)
-    {
-      s2 += __shfl_xor(s2, d, 64);
-      s1 += __shfl_xor(s1, d, 64);
-    }
-    if (j == 0)
-      norms[row] = s2 - 256u * s1 + 128u * 128u * 128u;
+    cache_row_store(entry, row, j, v);
   }
 }
 
 // Download packing (sift_memory.c:957-1047 pack_BufferMemory, here for a whole batch of buffers at once): the stored features of
 // slot blockIdx.y's buffer — its sections in order, min(found, capacity) records each — as dense 164-byte records at
 // out + out_row[slot] * 164. One dword per thread step; the host then fetches all buffers of a detection with ONE copy.
+// (64 slots, not the 512 of GatherMap: two maps of that size would add 3.5 KB to the launch's kernel arguments)
+struct SlotMap
+{
+  uint32_t buf[64]; // SIFT buffer index handled by slot blockIdx.y
+};
 struct PackOffsets
 {
   uint32_t row[64];
 };
-__global__ void __launch_bounds__(256) k_pack_features(const uint8_t *__restrict__ feats_base, uint64_t buf_stride, SlotMap map, SectionTable tab,
+__global__ void __launch_bounds__(256) k_pack_features(const uint32_t *__restrict__ feats_base, uint64_t buf_stride, SlotMap map, SectionTable tab,
                                                        const uint32_t *__restrict__ found_base, uint32_t found_buf_stride, uint32_t *__restrict__ out,
                                                        PackOffsets offs, uint32_t *__restrict__ found_post)
 {
   const uint32_t slot = blockIdx.y;
   const uint32_t bufi = map.buf[slot];
-  const uint32_t *feats = (const uint32_t *)(feats_base + (size_t)bufi * buf_stride);
-  const uint32_t *found = found_base + (size_t)bufi * found_buf_stride;
+  const auto buf = buffer_ref(feats_base, buf_stride, found_base, found_buf_stride, bufi);
   // feature posting: the buffer's counters go to the host mirror with the records (same layout as found_base, mapped pinned memory)
   if (found_post && blockIdx.x == 0 && threadIdx.x < found_buf_stride)
-    found_post[(size_t)bufi * found_buf_stride + threadIdx.x] = found[threadIdx.x];
+    found_post[(size_t)bufi * found_buf_stride + threadIdx.x] = buf.found[threadIdx.x];
   uint32_t cnt[VKSIFT_MAX_SECTIONS];
-  const uint32_t total = section_counts(tab.nsec, [&](uint32_t o) { return found[o]; }, tab.cap, cnt);
+  const uint32_t total = stored_counts(tab, buf.found, cnt);
   uint32_t *dst = out + (size_t)offs.row[slot] * VKSIFT_RECORD_WORDS;
   const uint32_t ndw = total * VKSIFT_RECORD_WORDS;
   for (uint32_t d = blockIdx.x * 256u + threadIdx.x; d < ndw; d += gridDim.x * 256u)
   {
     const uint32_t row = d / VKSIFT_RECORD_WORDS, w = d - row * VKSIFT_RECORD_WORDS;
-    dst[d] = feats[(size_t)section_row(cnt, tab.off, row) * VKSIFT_RECORD_WORDS + w];
+    dst[d] = buf.recs[(size_t)section_row(cnt, tab.off, row) * VKSIFT_RECORD_WORDS + w];
   }
 }
 
@@ -171,25 +152,13 @@ extern "C"
                                  uint32_t found_buf_stride, uint32_t max_rows, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_slot_stride,
                                  uint32_t *norms, uint64_t norm_slot_stride, uint32_t *n_out_dev, uint32_t n_slot_stride, vksift_hip_stream s)
   {
-    if (nsec > 16 || nslots < 1 || nslots > VKSIFT_HIP_GATHER_SLOTS)
+    /* (this entry predates the others: it takes either counter source as it comes, and its cache block is not optional) */
+    if (!sectioned_args_ok(0u, nslots, VKSIFT_HIP_GATHER_SLOTS, nsec, feats_base, buf_stride, fixed_counts, found_base, found_buf_stride, nullptr, desc,
+                           desc_slot_stride, norms, n_out_dev))
       return (int)hipErrorInvalidValue;
-    /* the kernel loads dwords from the records and stores 16-byte row pieces; the byte stride of the rows is handed to it in dwords */
-    if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || ((uintptr_t)desc & 15u) || (desc_slot_stride & 15u))
-      return (int)hipErrorInvalidValue;
-    const SectionTable t = section_table(nsec, sec_off, sec_cap, fixed_counts);
-    const GatherMap m = gather_map(buf_ids, nslots);
-    if (max_rows < pad_rows_to)
-      max_rows = pad_rows_to;
-    /* grid-stride over the rows that actually exist (count read on the device): ~4096 workgroups per launch whatever the batch — a
-     * buffer alone gets up to 256 blocks of 32 rows, 512 buffers 8 each (8 rounds over 1900 rows) */
-    uint32_t blocks = (max_rows + 31u) / 32u, cap_blocks = 4096u / nslots;
-    cap_blocks = cap_blocks < 8u ? 8u : (cap_blocks > 256u ? 256u : cap_blocks);
-    if (blocks > cap_blocks)
-      blocks = cap_blocks;
-    if (blocks == 0)
-      blocks = 1;
-    hipLaunchKernelGGL(k_gather_sections, dim3(blocks, nslots), dim3(256), 0, (hipStream_t)s, feats_base, buf_stride, m, t, found_base, found_buf_stride,
-                       (uint32_t *)desc, desc_slot_stride / 4, norms, norm_slot_stride, n_out_dev, n_slot_stride, pad_rows_to);
+    hipLaunchKernelGGL(k_gather_sections, dim3(gather_walk_blocks(max_rows, pad_rows_to, nslots), nslots), dim3(256), 0, (hipStream_t)s, (const uint32_t *)feats_base,
+                       buf_stride / 4u, gather_map(buf_ids, nslots), section_table(nsec, sec_off, sec_cap, fixed_counts), found_base, found_buf_stride,
+                       cache_entry(desc, desc_slot_stride, norms, norm_slot_stride, n_out_dev, n_slot_stride, pad_rows_to));
     return (int)hipGetLastError();
   }
 
@@ -197,9 +166,8 @@ extern "C"
                                const uint32_t *sec_off, const uint32_t *sec_cap, const uint32_t *found_base, uint32_t found_buf_stride, uint8_t *out,
                                uint32_t max_rows, uint32_t *found_post, vksift_hip_stream s)
   {
-    if (nslots < 1 || nslots > 64 || nsec > 16 || (found_post && found_buf_stride > 256u))
-      return (int)hipErrorInvalidValue;
-    if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || ((uintptr_t)out & 3u)) /* records are copied dword by dword */
+    if (!sectioned_args_ok(0u, nslots, 64u, nsec, feats_base, buf_stride, nullptr, found_base, found_buf_stride, found_post, nullptr, 0, nullptr, nullptr) ||
+        ((uintptr_t)out & 3u)) /* records are copied dword by dword */
       return (int)hipErrorInvalidValue;
     const SectionTable t = section_table(nsec, sec_off, sec_cap, nullptr);
     SlotMap m;
@@ -208,8 +176,8 @@ extern "C"
       m.buf[i] = i < nslots ? buf_ids[i] : 0u, po.row[i] = i < nslots ? out_rows[i] : 0u;
     uint32_t blocks = (uint32_t)(((uint64_t)max_rows * VKSIFT_RECORD_WORDS + 1023u) / 1024u); /* four dwords per thread */
     blocks = blocks < 1u ? 1u : (blocks > 128u ? 128u : blocks);
-    hipLaunchKernelGGL(k_pack_features, dim3(blocks, nslots), dim3(256), 0, (hipStream_t)s, feats_base, buf_stride, m, t, found_base, found_buf_stride,
-                       (uint32_t *)out, po, found_post);
+    hipLaunchKernelGGL(k_pack_features, dim3(blocks, nslots), dim3(256), 0, (hipStream_t)s, (const uint32_t *)feats_base, buf_stride / 4u, m, t, found_base,
+                       found_buf_stride, (uint32_t *)out, po, found_post);
     return (int)hipGetLastError();
   }
 

@@ -1,7 +1,7 @@
 // rootsift.hip — RootSIFT descriptors (vksift_ext_convertToRootSift; Arandjelovic & Zisserman 2012: COLMAP's L1_ROOT, PopSift's --root-sift, the
 // two lines after OpenCV's detectAndCompute; no counterpart in the reference): every stored record of every named SIFT buffer gets its 128 descriptor
-// bytes converted in place, and with cache pointers the same launch leaves the matcher's view of the converted buffer. The section walk and the
-// launch arguments are those of records.h, the reductions those of wave.h.
+// bytes converted in place, and with cache pointers the same launch leaves the matcher's view of the converted buffer. The section walk, the
+// launch arguments, the per-buffer resolve and the cache row step are those of records.h, the reductions those of wave.h.
 //
 //   s        the sum of the row's 128 bytes (0 .. 32640); s == 0: the row stays all zero
 //   out[i]   min(255, r), r the integer with (2r - 1)^2 s <= 2^20 d[i] < (2r + 1)^2 s: 512 sqrt(d[i] / s) rounded half up, exactly; 0 for d[i] == 0
@@ -22,8 +22,6 @@
 #include "vksift_hip.h"
 #include "hip/records.h"
 #include "hip/wave.h"
-
-#define ROOT_ROWS_PER_BLOCK 32u /* 256 threads: four waves of eight rows */
 
 namespace
 {
@@ -61,41 +59,30 @@ __device__ __forceinline__ uint32_t bytes_sum(uint4 v)
   return __builtin_amdgcn_udot4(v.w, 0x01010101u, s, false);
 }
 
-__device__ __forceinline__ uint32_t squares_sum(uint4 v)
-{
-  uint32_t s = __builtin_amdgcn_udot4(v.x, v.x, 0u, false);
-  s = __builtin_amdgcn_udot4(v.y, v.y, s, false);
-  s = __builtin_amdgcn_udot4(v.z, v.z, s, false);
-  return __builtin_amdgcn_udot4(v.w, v.w, s, false);
-}
-
-__global__ void __launch_bounds__(256) k_root_descriptors(uint8_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
+__global__ void __launch_bounds__(256) k_root_descriptors(uint32_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
                                                           const uint32_t *__restrict__ found_base, uint32_t found_buf_stride, CacheEntry cache)
 {
   const uint32_t bufi = map.buf[blockIdx.y];
-  uint32_t *feats = (uint32_t *)(feats_base + (size_t)bufi * buf_stride);
-  const uint32_t *found = found_base ? found_base + (size_t)bufi * found_buf_stride : nullptr;
+  const auto buf = buffer_ref(feats_base, buf_stride, found_base, found_buf_stride, bufi);
+  const CacheEntry entry = cache_entry_of(cache, bufi);
   const uint32_t j = threadIdx.x & 7u; // 16 bytes of a row per lane: a wave converts 8 rows at a time, a workgroup 32
 
   uint32_t cnt[VKSIFT_MAX_SECTIONS];
-  const uint32_t total = section_counts(tab.nsec, [&](uint32_t o) { return found ? found[o] : tab.fixed[o]; }, tab.cap, cnt);
-  uint32_t *c_rows = nullptr, *c_norms = nullptr;
+  const uint32_t total = stored_counts(tab, buf.found, cnt);
   uint32_t nrows = total;
-  if (cache.rows)
+  if (entry.rows)
   {
-    c_rows = cache.rows + (size_t)bufi * cache.row_stride;
-    c_norms = cache.norms + (size_t)bufi * cache.norm_stride;
     if (blockIdx.x == 0 && threadIdx.x == 0)
-      cache.n[(size_t)bufi * cache.n_stride] = total;
+      *entry.n = total;
     nrows = total > cache.pad_rows_to ? total : cache.pad_rows_to;
   }
-  for (uint32_t row = blockIdx.x * ROOT_ROWS_PER_BLOCK + (threadIdx.x >> 3); row < nrows; row += gridDim.x * ROOT_ROWS_PER_BLOCK)
+  for (uint32_t row = blockIdx.x * GATHER_ROWS_PER_BLOCK + (threadIdx.x >> 3); row < nrows; row += gridDim.x * GATHER_ROWS_PER_BLOCK)
   {
     uint32_t *p = nullptr;
     uint4 v = uint4{0u, 0u, 0u, 0u}; // rows in [total, pad_rows_to): the zero rows of the cache entry only
     if (row < total)
     {
-      p = feats + (size_t)section_row(cnt, tab.off, row) * VKSIFT_RECORD_WORDS + VKSIFT_RECORD_HEAD_WORDS + 4u * j;
+      p = buf.recs + (size_t)section_row(cnt, tab.off, row) * VKSIFT_RECORD_WORDS + VKSIFT_RECORD_HEAD_WORDS + 4u * j;
       v = uint4{p[0], p[1], p[2], p[3]};
     }
     uint32_t s = lanes_sum_u32<8>(bytes_sum(v));
@@ -104,15 +91,8 @@ __global__ void __launch_bounds__(256) k_root_descriptors(uint8_t *__restrict__ 
     const uint4 out = uint4{root_dword(v.x, s, inv_s), root_dword(v.y, s, inv_s), root_dword(v.z, s, inv_s), root_dword(v.w, s, inv_s)};
     if (p)
       p[0] = out.x, p[1] = out.y, p[2] = out.z, p[3] = out.w;
-    if (c_rows)
-    {
-      // the bytes k_gather_sections writes for the converted buffer: the row, and its shifted norm — the sum of (byte - 128)^2, a lane's sixteen
-      // bytes first (modulo 2^32 on the way, exact in the end)
-      *(uint4 *)(c_rows + (size_t)row * 32u + 4u * j) = out;
-      const uint32_t norm = lanes_sum_u32<8>(squares_sum(out) - 256u * bytes_sum(out) + 16u * 128u * 128u);
-      if (j == 0u)
-        c_norms[row] = norm;
-    }
+    if (entry.rows)
+      cache_row_store(entry, row, j, out); // the bytes k_gather_sections writes for the converted buffer
   }
 }
 
@@ -123,20 +103,11 @@ extern "C" int vksift_hip_root_descriptors(uint8_t *feats_base, uint64_t buf_str
                                            uint32_t max_rows, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms, uint64_t norm_stride,
                                            uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s)
 {
-  if (nslots < 1 || nslots > VKSIFT_HIP_GATHER_SLOTS || nsec > VKSIFT_MAX_SECTIONS || (fixed_counts != nullptr) == (found_base != nullptr))
+  if (!sectioned_args_ok(ARGS_ONE_COUNTER_SOURCE | ARGS_CACHE_OPTIONAL, nslots, VKSIFT_HIP_GATHER_SLOTS, nsec, feats_base, buf_stride, fixed_counts, found_base,
+                         found_buf_stride, nullptr, desc, desc_stride, norms, n_out_dev))
     return (int)hipErrorInvalidValue;
-  /* records are loaded and stored dword by dword; cache rows are stored 16 bytes at a time, the byte stride of the rows is handed to the kernel in dwords */
-  if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || (desc && (((uintptr_t)desc & 15u) || (desc_stride & 15u) || !norms || !n_out_dev)))
-    return (int)hipErrorInvalidValue;
-  const CacheEntry cache = {(uint32_t *)desc, desc ? norms : nullptr, desc ? n_out_dev : nullptr, desc_stride / 4u, norm_stride, n_stride, desc ? pad_rows_to : 0u};
-  if (max_rows < cache.pad_rows_to)
-    max_rows = cache.pad_rows_to;
-  /* the grid of the gather pass: a grid-stride walk over the rows that exist (the count is read on the device), some 4096 workgroups of 32 rows
-   * per launch whatever the batch — a buffer alone gets up to 256, 512 buffers 8 each (8 rounds over 1900 rows) */
-  uint32_t blocks = (max_rows + ROOT_ROWS_PER_BLOCK - 1u) / ROOT_ROWS_PER_BLOCK, cap_blocks = 4096u / nslots;
-  cap_blocks = cap_blocks < 8u ? 8u : (cap_blocks > 256u ? 256u : cap_blocks);
-  blocks = blocks < 1u ? 1u : (blocks > cap_blocks ? cap_blocks : blocks);
-  hipLaunchKernelGGL(k_root_descriptors, dim3(blocks, nslots), dim3(256), 0, (hipStream_t)s, feats_base, buf_stride, gather_map(buf_ids, nslots),
-                     section_table(nsec, sec_off, sec_cap, fixed_counts), found_base, found_buf_stride, cache);
+  const CacheEntry cache = cache_entry(desc, desc_stride, norms, norm_stride, n_out_dev, n_stride, pad_rows_to);
+  hipLaunchKernelGGL(k_root_descriptors, dim3(gather_walk_blocks(max_rows, cache.pad_rows_to, nslots), nslots), dim3(256), 0, (hipStream_t)s, (uint32_t *)feats_base,
+                     buf_stride / 4u, gather_map(buf_ids, nslots), section_table(nsec, sec_off, sec_cap, fixed_counts), found_base, found_buf_stride, cache);
   return (int)hipGetLastError();
 }

@@ -1,8 +1,8 @@
 // strongest.hip — the feature budget (vksift_ext_keepStrongestFeatures; OpenCV's nfeatures, SiftGPU's -tc, PopSift's --filter-max-extrema; no
 // counterpart in the reference, whose only limit is the capacity of a section): every named SIFT buffer keeps its max_features strongest
 // records, in place and in download order, and with cache pointers the same launch leaves the matcher's view of the selected buffer.
-// One 1024-thread workgroup per buffer: the compaction is ordered, so it takes no atomics on global memory, and the section walk and the
-// ordered append are those of records.h.
+// One 1024-thread workgroup per buffer: the compaction is ordered, so it takes no atomics on global memory, and the section walk, the
+// ordered append, the per-buffer resolve and the cache row's norm are those of records.h.
 //
 //   key(row)   the record's intensity word (|DoG response|) with the sign bit cleared, compared as an unsigned integer: a total order on
 //              every bit pattern (-0 == +0 < denormals < normals < inf < NaN patterns); no float comparison takes place
@@ -30,7 +30,7 @@
 namespace
 {
 
-__global__ void __launch_bounds__(1024) k_keep_strongest(uint8_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
+__global__ void __launch_bounds__(1024) k_keep_strongest(uint32_t *__restrict__ feats_base, uint64_t buf_stride, GatherMap map, SectionTable tab,
                                                          uint32_t *__restrict__ found_base, uint32_t found_buf_stride, uint32_t *__restrict__ found_post,
                                                          uint32_t max_features, CacheEntry cache)
 {
@@ -39,13 +39,13 @@ __global__ void __launch_bounds__(1024) k_keep_strongest(uint8_t *__restrict__ f
   __shared__ uint32_t wave_tot[16], tie_carry, keep_carry, sel_s[2];
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t bufi = map.buf[blockIdx.x];
-  uint32_t *feats = (uint32_t *)(feats_base + (size_t)bufi * buf_stride);
-  uint32_t *found = found_base ? found_base + (size_t)bufi * found_buf_stride : nullptr;
+  const auto buf = buffer_ref(feats_base, buf_stride, found_base, found_buf_stride, bufi);
+  uint32_t *const feats = buf.recs, *const found = buf.found;
 
   // ---- 1
   if (tid < VKSIFT_MAX_SECTIONS)
   {
-    const uint32_t raw = tid < tab.nsec ? (found ? found[tid] : tab.fixed[tid]) : 0u;
+    const uint32_t raw = tid < tab.nsec ? raw_count(tab, found, tid) : 0u;
     off_s[tid] = tab.off[tid];
     cnt_s[tid] = section_stored(raw, tab.cap[tid]); // (cap is zero from nsec on)
     kept_s[tid] = 0;
@@ -106,12 +106,7 @@ __global__ void __launch_bounds__(1024) k_keep_strongest(uint8_t *__restrict__ f
   const uint32_t threshold = prefix, quota = want; // `quota` of the rows at the threshold are kept, max_features - quota rows lie above it
 
   // ---- 4
-  uint32_t *c_rows = nullptr, *c_norms = nullptr;
-  if (cache.rows)
-  {
-    c_rows = cache.rows + (size_t)bufi * cache.row_stride;
-    c_norms = cache.norms + (size_t)bufi * cache.norm_stride;
-  }
+  const CacheEntry entry = cache_entry_of(cache, bufi);
   for (uint32_t base = 0; base < total; base += 1024u)
   {
     const uint32_t row = base + tid;
@@ -167,20 +162,19 @@ __global__ void __launch_bounds__(1024) k_keep_strongest(uint8_t *__restrict__ f
         for (uint32_t w = 0; w < VKSIFT_RECORD_WORDS; w++)
           dst[w] = rec[w];
       }
-      if (c_rows && out_row < max_features) // (always: max_features rows are kept; the entry holds no more)
+      if (entry.rows && out_row < max_features) // (always: max_features rows are kept; the entry holds no more)
       {
-        // the bytes k_gather_sections writes for the selected buffer: the 128 descriptor bytes and their shifted norm
-        uint32_t s2 = 0, s1 = 0;
+        // the bytes k_gather_sections writes for the selected buffer: one thread stores the eight pieces of the row and sums their norm parts
+        uint32_t norm = 0;
         VKSIFT_UNROLL
         for (uint32_t q = 0; q < 8u; q++)
         {
           const uint32_t *d = rec + VKSIFT_RECORD_HEAD_WORDS + 4u * q;
-          *(uint4 *)(c_rows + (size_t)out_row * 32u + 4u * q) = uint4{d[0], d[1], d[2], d[3]};
-          VKSIFT_UNROLL
-          for (uint32_t k = 0; k < 4u; k++)
-            s2 = __builtin_amdgcn_udot4(d[k], d[k], s2, false), s1 = __builtin_amdgcn_udot4(d[k], 0x01010101u, s1, false);
+          const uint4 v = uint4{d[0], d[1], d[2], d[3]};
+          *(uint4 *)(entry.rows + (size_t)out_row * 32u + 4u * q) = v;
+          norm += shifted_norm_part(v);
         }
-        c_norms[out_row] = s2 - 256u * s1 + 128u * 128u * 128u;
+        entry.norms[out_row] = norm;
       }
     }
   }
@@ -192,16 +186,16 @@ __global__ void __launch_bounds__(1024) k_keep_strongest(uint8_t *__restrict__ f
     if (found_post)
       found_post[(size_t)bufi * found_buf_stride + tid] = kept_s[tid];
   }
-  if (c_rows)
+  if (entry.rows)
   {
     if (tid == 0)
-      cache.n[(size_t)bufi * cache.n_stride] = max_features;
+      *entry.n = max_features;
     // quirk Q6: all-zero rows from the row count up to pad_rows_to
     for (uint32_t i = max_features * 32u + tid; i < cache.pad_rows_to * 32u && max_features < cache.pad_rows_to; i += 1024u)
     {
-      c_rows[i] = 0u;
+      entry.rows[i] = 0u;
       if ((i & 31u) == 0u)
-        c_norms[i >> 5] = 128u * 128u * 128u;
+        entry.norms[i >> 5] = VKSIFT_ZERO_ROW_NORM;
     }
   }
 }
@@ -213,17 +207,12 @@ extern "C" int vksift_hip_keep_strongest(uint8_t *feats_base, uint64_t buf_strid
                                          uint32_t *found_post, uint32_t max_features, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms,
                                          uint64_t norm_stride, uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s)
 {
-  if (nslots < 1 || nslots > VKSIFT_HIP_GATHER_SLOTS || nsec > VKSIFT_MAX_SECTIONS || max_features < 1 || (found_post && found_buf_stride > 256u) ||
-      (fixed_counts != nullptr) == (found_base != nullptr))
+  if (!sectioned_args_ok(ARGS_ONE_COUNTER_SOURCE | ARGS_CACHE_OPTIONAL, nslots, VKSIFT_HIP_GATHER_SLOTS, nsec, feats_base, buf_stride, fixed_counts, found_base,
+                         found_buf_stride, found_post, desc, desc_stride, norms, n_out_dev) ||
+      max_features < 1 || (found_post && !found_base)) /* (the mirror without device counters has nothing to mirror) */
     return (int)hipErrorInvalidValue;
-  /* records move dword by dword; cache rows are stored 16 bytes at a time, the byte stride of the rows is handed to the kernel in dwords */
-  if (((uintptr_t)feats_base & 3u) || (buf_stride & 3u) || (desc && (((uintptr_t)desc & 15u) || (desc_stride & 15u) || !norms || !n_out_dev)))
-    return (int)hipErrorInvalidValue;
-  /* (the mirror without device counters has nothing to mirror) */
-  if (found_post && !found_base)
-    return (int)hipErrorInvalidValue;
-  const CacheEntry cache = {(uint32_t *)desc, desc ? norms : nullptr, desc ? n_out_dev : nullptr, desc_stride / 4u, norm_stride, n_stride, pad_rows_to};
-  hipLaunchKernelGGL(k_keep_strongest, dim3(nslots), dim3(1024), 0, (hipStream_t)s, feats_base, buf_stride, gather_map(buf_ids, nslots),
-                     section_table(nsec, sec_off, sec_cap, fixed_counts), found_base, found_buf_stride, found_post, max_features, cache);
+  hipLaunchKernelGGL(k_keep_strongest, dim3(nslots), dim3(1024), 0, (hipStream_t)s, (uint32_t *)feats_base, buf_stride / 4u, gather_map(buf_ids, nslots),
+                     section_table(nsec, sec_off, sec_cap, fixed_counts), found_base, found_buf_stride, found_post, max_features,
+                     cache_entry(desc, desc_stride, norms, norm_stride, n_out_dev, n_stride, pad_rows_to));
   return (int)hipGetLastError();
 }

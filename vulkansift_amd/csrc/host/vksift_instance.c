@@ -263,6 +263,32 @@ void take_sequence(vksift_Instance inst, uint32_t first, uint32_t count)
   inst->det_seq = seq;
 }
 
+int inplace_begin(vksift_Instance inst, uint32_t first, uint32_t count, uint32_t *ids)
+{
+  /* pack launches of a packed download that went straight to the caller's memory may still read the records on the download stream */
+  const int e = inst->dl_valid && inst->dl_direct ? vksift_hip_stream_sync(inst->dl_stream) : 0;
+  if (e)
+    return e;
+  (void)detect_running(inst);
+  for (uint32_t i = 0; i < count; i++)
+    ids[i] = first + i;
+  return 0;
+}
+
+int inplace_end(vksift_Instance inst, StageFrame *f)
+{
+  (void)stage_end(inst, f, NULL, NULL, 0);
+  return vksift_hip_event_record(inst->det_ring[inst->det_seq % VKSIFT_DETECT_RING].ev, inst->stream);
+}
+
+void inplace_fail(vksift_Instance inst, StageFrame *f, const char *msg)
+{
+  if (stage_abort(f)) /* the buffers carry the new sequence number: its event stands behind whatever part of the call was queued */
+    (void)vksift_hip_event_record(inst->det_ring[inst->det_seq % VKSIFT_DETECT_RING].ev, inst->stream);
+  logError(LOG_TAG, "%s", msg);
+  inst->error_cb(VKSIFT_VULKAN_ERROR);
+}
+
 bool match_running(vksift_Instance inst)
 {
   if (!inst->match_pending)

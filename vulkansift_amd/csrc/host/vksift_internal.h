@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_rootsift.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -11,6 +11,7 @@
 #include "hip/records.h" /* the record and section-table constants */
 #include "vksift_hostmath.h"
 #include "vksift_log.h"
+#include "vksift_runs.h" /* BufferInfo, the layout runs, VKSIFT_INTERNAL */
 #include "vulkansift/vulkansift.h"
 
 #include <assert.h>
@@ -18,8 +19,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-
-#define VKSIFT_INTERNAL __attribute__((visibility("hidden")))
 
 #define LOG_TAG "VulkanSift"
 
@@ -31,18 +30,6 @@
 #define MATCH_BYTES 20u
 #define PITCH_ALIGN 64u
 #define DESC_FP_TAB_MAX 1024u
-
-typedef struct
-{
-  bool is_packed;       /* true: one section [0, nb_stored) (after upload / after matching) */
-  uint32_t nb_stored;   /* valid when is_packed */
-  uint32_t nb_sections; /* octaves of the detection that last filled the buffer */
-  uint32_t sec_off[VKSIFT_MAX_OCTAVES]; /* in features */
-  uint32_t sec_cap[VKSIFT_MAX_OCTAVES];
-  uint32_t in_w, in_h;  /* resolution of that detection */
-  uint64_t seq;         /* sequence number of the detection that last filled the buffer (0: filled from the host / never). The host
-                         * mirror of its per-octave counters is valid once that detection has completed (seq <= det_done) */
-} BufferInfo;
 
 /* One slot per detection in flight. A caller that pipelines (detection N+1 queued while it downloads the results of detection N,
  * the way vksift_isBufferAvailable is meant to be used) waits for the detection that filled the buffer it reads, not for the
@@ -401,8 +388,17 @@ VKSIFT_INTERNAL void wait_for_buffer(vksift_Instance inst, uint32_t buf);
 VKSIFT_INTERNAL uint32_t buffer_counts(vksift_Instance inst, uint32_t buf, uint32_t *cnt, bool log_lost);
 
 /* vksift_match.c */
-/* the same section layout (so one kernel launch can serve both buffers)? */
-VKSIFT_INTERNAL bool same_layout(const BufferInfo *x, const BufferInfo *y);
+/* the matcher's cache blocks as the launches over sectioned buffers take them; all NULL until the first matching has made them */
+typedef struct
+{
+  uint8_t *desc;
+  uint32_t *norm, *n;
+} CacheBlocks;
+static inline CacheBlocks cache_blocks(const struct vksift_Instance_T *inst)
+{
+  const bool made = inst->d_cache_desc && inst->d_cache_norm;
+  return (CacheBlocks){made ? inst->d_cache_desc : NULL, made ? inst->d_cache_norm : NULL, made ? inst->d_cache_n : NULL};
+}
 VKSIFT_INTERNAL MatchScratch fwd_scratch(vksift_Instance inst);
 VKSIFT_INTERNAL int refresh_match_cache(vksift_Instance inst, const uint32_t *ids, uint32_t count);
 VKSIFT_INTERNAL uint32_t rows_bound(vksift_Instance inst, uint32_t id);
@@ -436,6 +432,20 @@ typedef struct
 VKSIFT_INTERNAL int stage_begin(vksift_Instance inst, StageFrame *f, uint32_t timer, const char *range);
 VKSIFT_INTERNAL int stage_end(vksift_Instance inst, StageFrame *f, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count);
 VKSIFT_INTERNAL bool stage_abort(StageFrame *f);
+
+/* vksift_instance.c, behind take_sequence: what the calls that rewrite a range of SIFT buffers in place share (vksift_strongest.c, vksift_rootsift.c). They are queued like a
+ * detection: between the two halves the caller opens its stage, takes the sequence number (take_sequence) and makes one launch per layout run. */
+static inline bool inplace_range_valid(const struct vksift_Instance_T *inst, uint32_t first, uint32_t count)
+{
+  return count != 0 && count <= VKSIFT_HIP_GATHER_SLOTS && first < inst->cfg.sift_buffer_count && count <= inst->cfg.sift_buffer_count - first;
+}
+/* waits for a direct packed download that may still read the records, polls the detections in flight (counts_valid() and rows_bound() are up to
+ * date) and fills ids[0 .. count) with first + i. Returns the wait's error code, ids filled or not. */
+VKSIFT_INTERNAL int inplace_begin(vksift_Instance inst, uint32_t first, uint32_t count, uint32_t *ids);
+/* closes the stage; the call ends on the event of its detection-ring slot, not on pairs. Returns the event record's error code. */
+VKSIFT_INTERNAL int inplace_end(vksift_Instance inst, StageFrame *f);
+/* the error exit: the slot's event behind whatever part of the call was queued, `msg` logged, VKSIFT_VULKAN_ERROR reported */
+VKSIFT_INTERNAL void inplace_fail(vksift_Instance inst, StageFrame *f, const char *msg);
 /* storage of batch_cap pairs for set `which` (PR_*) with this shape; false: out of memory (retried by the next call, nothing leaked) */
 VKSIFT_INTERNAL bool pair_results_ensure(vksift_Instance inst, uint32_t which, uint32_t words, uint64_t stride, uint32_t elem, uint32_t counted_by);
 /* a new matching: no set has results any more */

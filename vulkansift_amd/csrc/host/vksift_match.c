@@ -6,18 +6,6 @@
 /* ------------------------------------------------------------------------------------------------ */
 /* matching (vulkansift.c:417-462, sift_memory.c:957-1058, sift_matcher.c:408-486)                  */
 /* ------------------------------------------------------------------------------------------------ */
-bool same_layout(const BufferInfo *x, const BufferInfo *y)
-{
-  if (x->nb_sections != y->nb_sections)
-    return false;
-  if (x->nb_sections == 0)
-    return x->nb_stored == y->nb_stored;
-  for (uint32_t o = 0; o < x->nb_sections; o++)
-    if (x->sec_off[o] != y->sec_off[o] || x->sec_cap[o] != y->sec_cap[o])
-      return false;
-  return true;
-}
-
 /* Launch bound on the number of stored rows of a buffer: the real total if its counters have reached the host, else the
  * sum of its section capacities. */
 uint32_t rows_bound(vksift_Instance inst, uint32_t id)
@@ -98,7 +86,7 @@ int refresh_match_cache(vksift_Instance inst, const uint32_t *ids, uint32_t coun
    * name that many distinct buffers per side, and every one of them must be gathered before the matching kernels read its cache entry. */
   for (;;)
   {
-    uint32_t todo[VKSIFT_HIP_GATHER_SLOTS];
+    uint32_t todo[VKSIFT_HIP_GATHER_SLOTS], bound[VKSIFT_HIP_GATHER_SLOTS];
     uint32_t n = 0;
     bool more = false;
     for (uint32_t i = 0; i < count; i++)
@@ -114,35 +102,17 @@ int refresh_match_cache(vksift_Instance inst, const uint32_t *ids, uint32_t coun
       todo[n++] = ids[i];
     }
     for (uint32_t k = 0; k < n; k++)
-      inst->cache_queued[todo[k]] = false;
-    uint32_t i0 = 0;
-    while (i0 < n)
+      inst->cache_queued[todo[k]] = false, bound[k] = rows_bound(inst, todo[k]);
+    LayoutRun run;
+    for (uint32_t pos = 0; next_layout_run(inst->bufs, todo, n, bound, &pos, &run);)
     {
-      /* one launch per run of buffers that share a section layout (always all of them after a batched detection) */
-      const BufferInfo *b = &inst->bufs[todo[i0]];
-      uint32_t i1 = i0 + 1, max_rows = rows_bound(inst, todo[i0]);
-      while (i1 < n && same_layout(b, &inst->bufs[todo[i1]]))
-      {
-        const uint32_t r = rows_bound(inst, todo[i1]);
-        max_rows = r > max_rows ? r : max_rows;
-        i1++;
-      }
-      int e;
-      if (b->nb_sections == 0)
-      {
-        uint32_t zero_off = 0, cap1 = b->nb_stored, fixed1 = b->nb_stored;
-        e = vksift_hip_gather_sections(inst->d_feats, inst->buf_stride, todo + i0, i1 - i0, 1, &zero_off, &cap1, &fixed1, NULL, 0, max_rows, 2u,
-                                       inst->d_cache_desc, inst->desc_slot_stride, inst->d_cache_norm, inst->cache_norm_stride, inst->d_cache_n, 1, inst->stream);
-      }
-      else
-        e = vksift_hip_gather_sections(inst->d_feats, inst->buf_stride, todo + i0, i1 - i0, b->nb_sections, b->sec_off, b->sec_cap, NULL, inst->d_found,
-                                       VKSIFT_MAX_OCTAVES, max_rows, 2u, inst->d_cache_desc, inst->desc_slot_stride, inst->d_cache_norm, inst->cache_norm_stride,
-                                       inst->d_cache_n, 1, inst->stream);
+      const int e = vksift_hip_gather_sections(inst->d_feats, inst->buf_stride, run.ids, run.n, run.nsec, run.off, run.cap, run.fixed, run.fixed ? NULL : inst->d_found,
+                                               run.found_stride, run.max_rows, 2u, inst->d_cache_desc, inst->desc_slot_stride, inst->d_cache_norm,
+                                               inst->cache_norm_stride, inst->d_cache_n, 1, inst->stream);
       if (e)
         return e;
-      for (uint32_t k = i0; k < i1; k++)
-        inst->cache_valid[todo[k]] = true;
-      i0 = i1;
+      for (uint32_t k = 0; k < run.n; k++)
+        inst->cache_valid[run.ids[k]] = true;
     }
     if (!more)
       return 0;
