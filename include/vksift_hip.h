@@ -556,13 +556,17 @@ extern "C"
    * the mask are zero. No refinement on the inliers here: H is the four-point model of the winning sample. vksift_hip_refit_homography (below) refits it
    * on its inliers, bit for bit reproducible because every sum has a fixed order; the mask is also what a caller's own refit needs.
    * tests/np_verify.py restates every output bit for bit. scratch: scratch_u32 >= vksift_hip_ransac_scratch_u32(nslots, nb_hypotheses) words, need not be
-   * initialised. hipErrorInvalidValue, nothing launched: nb_hypotheses 0 or above 65536, threshold_px not positive and finite, too little scratch, strides below
-   * max_n records. */
+   * initialised, contents unspecified afterwards. WRITTEN: the nslots records, bytes 0 .. n-1 of every slot's mask, the scratch, nothing else (not the
+   * mask bytes from n to mask_slot_stride, not a record beyond nslots; corr and n_dev are only read, n_dev only at the strided words).
+   * hipErrorInvalidValue, nothing launched: nslots 0, nb_hypotheses 0 or above 65536, threshold_px not positive and finite, too little scratch, corr not
+   * 16-byte aligned or corr_slot_stride not a multiple of 16, results not 4-byte aligned, strides below max_n records (corr_slot_stride < 16 max_n,
+   * mask_slot_stride < max_n; only with nslots > 1: a single slot's strides address nothing and may be anything, 0 included, corr_slot_stride still a multiple of 16),
+   * nslots * ceil(nb_hypotheses / 256) above 2^31 - 1. */
   size_t vksift_hip_ransac_scratch_u32(uint32_t nslots, uint32_t nb_hypotheses);
   int vksift_hip_ransac_homography(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
                                    uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride,
                                    uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
-  /* The same for a fundamental matrix (same arguments, scratch and refusals; seven-point samples). Each hypothesis gives up to three models (the real roots of
+  /* The same for a fundamental matrix (same arguments, scratch, WRITTEN set and refusals; seven-point samples). Each hypothesis gives up to three models (the real roots of
    * the seven-point cubic, numbered in increasing order), model id = 4*j + root; a correspondence is an inlier when its Sampson distance is below threshold_px;
    * the best is the largest count, ties to the lowest model id. results + 56*i: float F[9] (row-major, pixel coordinates, (xb, yb, 1) F (xa, ya, 1)^T = 0, largest
    * |entry| in [1, 2)), uint32 nb_matches (= n), nb_inliers, best_hypothesis, best_root, valid; masks as above. n < 7, a best count below 8 (the seven sample
@@ -635,7 +639,10 @@ extern "C"
    * out + i*out_slot_stride (bytes): 16-byte records {idx_a, idx_b, dist1, dist2} in increasing idx_a, out_n[i] their number. tests/np_guided.py restates every
    * record bit for bit. scratch: scratch_u32 >= vksift_hip_guided_scratch_u32(nslots, max_n) words, 8-byte aligned, need not be initialised.
    * hipErrorInvalidValue, nothing launched: unknown model_kind, t2 not positive and finite, ratio or max_distance not greater than 0 (+inf is a max_distance),
-   * too little scratch, a stride below max_n rows (records, norms, coordinates, output), max_n above 2^24, nslots 0 or above 65535. */
+   * too little scratch, a stride below max_n rows (records, norms, coordinates, output), slot_tab_stride or n_stride below 2, model_stride below 9,
+   * valid_stride 0, max_n above 2^24, nslots 0 or above 65535, cache_desc not 16-byte aligned or cache_desc_stride not a multiple of 16, xy or scratch not
+   * 8-byte aligned, out not 4-byte aligned or out_slot_stride not a multiple of 4. WRITTEN: records 0 .. out_n[i]-1 of every slot of out, the nslots words
+   * of out_n, the scratch (not the part of a slot whose valid word is 0: nslots * max_n * 8 words, slot i's at scratch + i * max_n * 8), nothing else. */
   size_t vksift_hip_guided_scratch_u32(uint32_t nslots, uint32_t max_n);
   int vksift_hip_match_guided(const uint8_t *cache_desc, uint64_t cache_desc_stride, const uint32_t *cache_norm, uint64_t cache_norm_stride, const uint32_t *slot_tab,
                               uint32_t slot_tab_stride, const float *xy, uint64_t xy_side_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n,
