@@ -211,6 +211,30 @@ extern "C"
   /* Time (ms) of the last vksift_ext_keepStrongestFeatures (its launches), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getKeepStrongestTime(vksift_Instance instance);
 
+  /* ---- GPU-side feature budget, spread over the image --------------------------------------------------------------------
+   * vksift_ext_keepStrongestFeatures ranks the whole image, which on real frames leaves the kept features on the most textured region. This call pairs the
+   * count limit with a spatial rule (PopSift's --filter-grid, AliceVision's gridFiltering, OpenCV's GridAdaptedFeatureDetector, ORB-SLAM's bucketing): the
+   * frame of image_width x image_height pixels is cut into grid_cols x grid_rows cells and every cell keeps its own strongest features first.
+   * The cell of a feature: column bound j (1 <= j < grid_cols) is (float)((double)j * image_width / grid_cols), row bound j likewise from image_height and
+   * grid_rows; the feature's column is the number of column bounds its x is at or above, its row likewise from y. Only comparisons take place: a NaN or a
+   * negative coordinate falls into column / row 0, anything at or beyond the last bound into the last one, -0.0 is 0.0. An uploaded buffer carries no image
+   * size, so the caller names it; it need not be the size of the detected image.
+   * The rule, with key(row) and the row numbers of vksift_ext_keepStrongestFeatures, C = grid_cols * grid_rows and q = max_features / C (integer division):
+   * a buffer of at most max_features features is not touched at all. Otherwise every cell keeps the first min(n_cell, q) of its rows by (key descending, row
+   * ascending); then, among the rows not kept so far, the first max_features - (rows kept so far) by (key descending, row ascending) are kept as well. Exactly
+   * max_features features remain: max_features is the TOTAL per buffer, not a number per cell; cells with fewer than q features pass their share on to the
+   * strongest features elsewhere, and every cell that held at least q features keeps at least q. A 1 x 1 grid is vksift_ext_keepStrongestFeatures byte for
+   * byte, and so is any grid with max_features < C (q = 0). Selecting again with the same arguments changes nothing. tests/np_spread.py restates the rule.
+   * In every other respect — the kept features stay in download order and in their octave sections, asynchronous queueing behind staged detections, busy
+   * buffers, accessors that wait, the precondition on earlier matching results — the contract is that of vksift_ext_keepStrongestFeatures.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, nothing changed): whatever vksift_ext_keepStrongestFeatures refuses, image_width or image_height 0, grid_cols
+   * or grid_rows 0 or above 16. A launch failure is VKSIFT_VULKAN_ERROR. */
+  VKSIFT_EXPORT void vksift_ext_keepStrongestFeaturesGrid(vksift_Instance instance, uint32_t first_gpu_buffer_id, uint32_t count, uint32_t max_features,
+                                                          uint32_t image_width, uint32_t image_height, uint32_t grid_cols, uint32_t grid_rows);
+  /* Time (ms) of the last vksift_ext_keepStrongestFeaturesGrid (its launches), HIP events; needs profiling on. -1 when there is none. A timer of its own:
+   * vksift_ext_getKeepStrongestTime reports the plain budget only. */
+  VKSIFT_EXPORT float vksift_ext_getKeepStrongestGridTime(vksift_Instance instance);
+
   /* ---- RootSIFT descriptors ------------------------------------------------------------------------------------------------
    * The descriptors of every feature of the SIFT buffers [first_gpu_buffer_id, first_gpu_buffer_id + count) are converted to RootSIFT (Arandjelovic &
    * Zisserman 2012: COLMAP's default L1_ROOT normalisation, PopSift's --root-sift, the two lines most OpenCV callers write after detectAndCompute) in

@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 10u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 10: vksift_hip_root_descriptors */
+#define VKSIFT_HIP_ABI_VERSION 11u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 11: vksift_hip_keep_grid */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -504,6 +504,26 @@ extern "C"
                                 const uint32_t *sec_cap, const uint32_t *fixed_counts, uint32_t *found_base, uint32_t found_buf_stride, uint32_t *found_post,
                                 uint32_t max_features, uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms, uint64_t norm_stride,
                                 uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s);
+  /* The spatially distributed feature budget (spread.hip): vksift_hip_keep_strongest with a grid rule — every argument it shares means what it
+   * means there, and the launch reads, writes and leaves alone exactly what that one does (a buffer whose total is at most max_features is not
+   * written at all; kept rows stay in their section, keep their order and move to its front; counters, posted mirror and cache entry likewise).
+   * Which rows are kept differs. key(row) is that launch's key. x is word 0 and y word 1 of the record, as fp32; cx(row) = the number of j <
+   * grid_cols - 1 with x >= col_bounds[j], cy(row) likewise from y and row_bounds, cell = cy * grid_cols + cx. Only these comparisons take place:
+   * a NaN or a negative coordinate satisfies none of the usual bounds and falls into column / row 0, -0.0 compares as 0.0, no bit pattern is
+   * refused, and the bounds need not be monotone — the cell is the count of satisfied comparisons whatever they are. With C = grid_cols *
+   * grid_rows and q = max_features / C: in every cell the first min(n_cell, q) rows of the cell by (key descending, row ascending) are kept; among
+   * the rows these leave, the first max_features - (rows kept so far) by (key descending, row ascending) are kept too. Exactly max_features rows:
+   * it is a total, not a number per cell. A 1 x 1 grid, and any grid with max_features < C, is vksift_hip_keep_strongest byte for byte; a second
+   * launch with the same arguments changes nothing. tests/np_spread.py restates the rule.
+   * col_bounds / row_bounds: HOST pointers to grid_cols - 1 / grid_rows - 1 floats, copied into the kernel's arguments by this call; NULL is
+   * accepted where the count is 1. One 1024-thread workgroup per buffer, no atomics on global memory.
+   * hipErrorInvalidValue, nothing launched: whatever vksift_hip_keep_strongest refuses, grid_cols or grid_rows 0 or above 16, a NULL bounds pointer
+   * with a count above 1. */
+  int vksift_hip_keep_grid(uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, uint32_t nslots, uint32_t nsec, const uint32_t *sec_off,
+                           const uint32_t *sec_cap, const uint32_t *fixed_counts, uint32_t *found_base, uint32_t found_buf_stride, uint32_t *found_post,
+                           uint32_t max_features, uint32_t grid_cols, uint32_t grid_rows, const float *col_bounds, const float *row_bounds,
+                           uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms, uint64_t norm_stride, uint32_t *n_out_dev,
+                           uint32_t n_stride, vksift_hip_stream s);
   /* RootSIFT descriptors (rootsift.hip): the 128 descriptor bytes of every stored record of the SIFT buffers buf_ids[0..nslots), nslots <=
    * VKSIFT_HIP_GATHER_SLOTS, are converted in place; one launch, all buffers of the call share the section table (named as for
    * vksift_hip_gather_sections: the counters are found_base + id*found_buf_stride, or fixed_counts for uploaded buffers — exactly one of the two).

@@ -175,6 +175,10 @@ def lib():
     L.vksift_ext_keepStrongestFeatures.restype = None
     L.vksift_ext_getKeepStrongestTime.argtypes = [inst]
     L.vksift_ext_getKeepStrongestTime.restype = C.c_float
+    L.vksift_ext_keepStrongestFeaturesGrid.argtypes = [inst, u32, u32, u32, u32, u32, u32, u32]
+    L.vksift_ext_keepStrongestFeaturesGrid.restype = None
+    L.vksift_ext_getKeepStrongestGridTime.argtypes = [inst]
+    L.vksift_ext_getKeepStrongestGridTime.restype = C.c_float
     L.vksift_ext_convertToRootSift.argtypes = [inst, u32, u32]
     L.vksift_ext_convertToRootSift.restype = None
     L.vksift_ext_getRootSiftTime.argtypes = [inst]
@@ -661,6 +665,16 @@ class Instance:
 
     def getKeepStrongestTime(self):
         return lib().vksift_ext_getKeepStrongestTime(self._h)
+
+    def keepStrongestFeaturesGrid(self, first_buffer, count, max_features, image_width, image_height, grid_cols, grid_rows):
+        """keepStrongestFeatures spread over the image (vksift_ext_keepStrongestFeaturesGrid): every cell of a grid_cols x grid_rows grid over an
+        image_width x image_height frame keeps its max_features // cells strongest features first, the strongest of the rest fill the budget up.
+        max_features is the total per buffer, not a number per cell; asynchronous like detectFeatures"""
+        lib().vksift_ext_keepStrongestFeaturesGrid(self._h, first_buffer, count, max_features, image_width, image_height, grid_cols, grid_rows)
+        _check_pending()
+
+    def getKeepStrongestGridTime(self):
+        return lib().vksift_ext_getKeepStrongestGridTime(self._h)
 
     def convertToRootSift(self, first_buffer, count):
         """the descriptors of every SIFT buffer of [first_buffer, first_buffer + count) become RootSIFT descriptors (L1-normalised, square-rooted,

@@ -1,8 +1,9 @@
-/* records.h — the steps every launch that moves or addresses SIFT records shares (hip/records.hip, hip/strongest.hip, hip/rootsift.hip,
- * hip/verify.hip, hip/guided.hip), each defined once: the record and section-table constants, the walk from a download-order row to a stored
- * row, the decode of a pair table's layout word, the ordered append of a 1024-thread workgroup, and what the launches over sectioned buffers
- * (vksift_hip_gather_sections, _pack_features, _keep_strongest, _root_descriptors) have in common — the by-value launch arguments, the
- * prologue check of their entries, the grid of the gather walk, the per-buffer resolve, the stored counts and the cache row step. The
+/* records.h — the steps every launch that moves or addresses SIFT records shares (hip/records.hip, hip/strongest.hip, hip/spread.hip,
+ * hip/rootsift.hip, hip/verify.hip, hip/guided.hip), each defined once: the record and section-table constants, the walk from a download-order
+ * row to a stored row, the decode of a pair table's layout word, the ordered append of a 1024-thread workgroup, what the launches over
+ * sectioned buffers (vksift_hip_gather_sections, _pack_features, _keep_strongest, _keep_grid, _root_descriptors) have in common — the by-value
+ * launch arguments, the prologue check of their entries, the grid of the gather walk, the per-buffer resolve, the stored counts and the cache
+ * row step — and the in-place ordered compaction of the two budgets (vksift_hip_keep_strongest, _keep_grid) with what follows it. The
  * constants compile as C (host/vksift_internal.h takes them from here), the walk as host C++ too: plain integer arithmetic, checked row by
  * row by tests/test_section_walk.py, which compiles this header with the host compiler. The rest is device code and its launchers' host side. */
 #ifndef VKSIFT_RECORDS_H
@@ -275,6 +276,134 @@ __device__ __forceinline__ uint32_t ordered_keep(bool keep, uint32_t (&wave_tot)
     carry_s = carry + total;
   __syncthreads();
   return carry + wave_base + rank;
+}
+
+/* ---- select and compact in place ---------------------------------------------------------------------------------------------------------
+ * What the launches that keep some rows of a buffer where they are share (strongest.hip, spread.hip; one 1024-thread workgroup per buffer): the
+ * bin of a 256-bin radix pass, and the ordered compaction with everything that follows it. */
+
+/* Called by the 64 lanes of the first wave after a 256-bin histogram pass: sel_s = {the bin that holds the want-th largest key, how many keys of
+ * that bin are still wanted}. Lane l owns bins 255 - 4l .. 252 - 4l: an inclusive scan over the lanes counts the keys from the top bin down. The
+ * histogram holds at least `want` keys, want >= 1. */
+__device__ __forceinline__ void radix_pick_256(const uint32_t (&hist)[256], uint32_t want, uint32_t (&sel_s)[2])
+{
+  const uint32_t tid = threadIdx.x;
+  uint32_t h[4], sum = 0;
+  for (uint32_t i = 0; i < 4u; i++)
+    h[i] = hist[255u - 4u * tid - i], sum += h[i];
+  const uint32_t incl = wave_scan_incl_u32(sum, (int)tid);
+  uint32_t above = incl - sum;
+  if (above < want && want <= incl) // one lane
+  {
+    uint32_t bin = 255u - 4u * tid;
+    for (uint32_t i = 0; i < 3u && want > above + h[i]; i++)
+      above += h[i], bin--;
+    sel_s[0] = bin, sel_s[1] = want - above;
+  }
+}
+
+/* the section of download-order row `row` < total (section_row's walk) */
+template <class Cnt> __device__ __forceinline__ uint32_t section_of(const Cnt &cnt, uint32_t row)
+{
+  uint32_t first = 0, sec = 0;
+  VKSIFT_UNROLL
+  for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
+  {
+    if (row >= first && row < first + cnt[o])
+      sec = o;
+    first += cnt[o];
+  }
+  return sec;
+}
+
+/* One round of 1024 download-order rows of the ordered compaction, rounds in order; called by every thread. keep: the thread's row — stored row
+ * src_row, of section sec — is kept. A kept row's place is its section's start plus the kept rows of that section in front of it. Every kept
+ * record of the round is loaded into registers, a barrier is passed, then it is stored: a destination never lies beyond its source (the kept rows
+ * in front of a row are at most the rows in front of it) and never beyond the round (it is the old place of a row at or in front of the source),
+ * so a store can only land on a record of an earlier round, already consumed, or of this round, already in registers. With an entry the kept
+ * row is written to the matcher's cache from the same registers. kept_s (the kept rows per section) and keep_carry are zero, and a barrier
+ * passed, before the first round; max_rows: the entry's rows (the launch keeps no more). */
+__device__ __forceinline__ void compact_round(uint32_t *feats, bool keep, uint32_t sec, uint32_t src_row, const uint32_t (&off_s)[VKSIFT_MAX_SECTIONS],
+                                              uint32_t (&kept_s)[VKSIFT_MAX_SECTIONS], uint32_t (&wave_tot)[16], uint32_t &keep_carry, const CacheEntry &entry,
+                                              uint32_t max_rows)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t out_row = ordered_keep(keep, wave_tot, keep_carry); // its download-order row afterwards
+  // kept rows of every section, this round's included: those of the sections in front of a row's own are complete when it is placed
+  VKSIFT_UNROLL
+  for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
+  {
+    const unsigned long long bal = __ballot(keep && sec == o);
+    if (lane == 0u && bal)
+      atomicAdd(&kept_s[o], (uint32_t)__popcll(bal)); // LDS
+  }
+  __syncthreads();
+  uint32_t rec[VKSIFT_RECORD_WORDS], dst_row = 0;
+  if (keep)
+  {
+    uint32_t in_front = 0;
+    VKSIFT_UNROLL
+    for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
+      in_front += o < sec ? kept_s[o] : 0u;
+    dst_row = off_s[sec] + (out_row - in_front);
+    const uint32_t *src = feats + (size_t)src_row * VKSIFT_RECORD_WORDS;
+    VKSIFT_UNROLL
+    for (uint32_t w = 0; w < VKSIFT_RECORD_WORDS; w++)
+      rec[w] = src[w];
+  }
+  __builtin_amdgcn_s_waitcnt(0); // every record of the round is in registers ...
+  __syncthreads();               // ... in every wave, before any is overwritten
+  if (keep)
+  {
+    if (dst_row != src_row)
+    {
+      uint32_t *dst = feats + (size_t)dst_row * VKSIFT_RECORD_WORDS;
+      VKSIFT_UNROLL
+      for (uint32_t w = 0; w < VKSIFT_RECORD_WORDS; w++)
+        dst[w] = rec[w];
+    }
+    if (entry.rows && out_row < max_rows) // (always: max_rows rows are kept; the entry holds no more)
+    {
+      // the bytes k_gather_sections writes for the selected buffer: one thread stores the eight pieces of the row and sums their norm parts
+      uint32_t norm = 0;
+      VKSIFT_UNROLL
+      for (uint32_t q = 0; q < 8u; q++)
+      {
+        const uint32_t *d = rec + VKSIFT_RECORD_HEAD_WORDS + 4u * q;
+        const uint4 v = uint4{d[0], d[1], d[2], d[3]};
+        *(uint4 *)(entry.rows + (size_t)out_row * 32u + 4u * q) = v;
+        norm += shifted_norm_part(v);
+      }
+      entry.norms[out_row] = norm;
+    }
+  }
+}
+
+/* After the last round, called by every thread: the counters become the kept counts, on the device and posted to the host mirror by this launch
+ * (mapped pinned memory; no dependent copy), and the cache entry gets its row count (rows_kept) and the all-zero rows of quirk Q6 from there up
+ * to pad_rows_to. */
+__device__ __forceinline__ void compact_finish(uint32_t nsec, uint32_t *found, uint32_t *found_post, uint32_t bufi, uint32_t found_buf_stride,
+                                               const uint32_t (&kept_s)[VKSIFT_MAX_SECTIONS], const CacheEntry &entry, uint32_t pad_rows_to, uint32_t rows_kept)
+{
+  const uint32_t tid = threadIdx.x;
+  if (tid < nsec)
+  {
+    if (found)
+      found[tid] = kept_s[tid];
+    if (found_post)
+      found_post[(size_t)bufi * found_buf_stride + tid] = kept_s[tid];
+  }
+  if (entry.rows)
+  {
+    if (tid == 0)
+      *entry.n = rows_kept;
+    for (uint32_t i = rows_kept * 32u + tid; i < pad_rows_to * 32u && rows_kept < pad_rows_to; i += 1024u)
+    {
+      entry.rows[i] = 0u;
+      if ((i & 31u) == 0u)
+        entry.norms[i >> 5] = VKSIFT_ZERO_ROW_NORM;
+    }
+  }
 }
 
 #endif /* __HIPCC__ */

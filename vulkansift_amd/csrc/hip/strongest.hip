@@ -2,7 +2,8 @@
 // counterpart in the reference, whose only limit is the capacity of a section): every named SIFT buffer keeps its max_features strongest
 // records, in place and in download order, and with cache pointers the same launch leaves the matcher's view of the selected buffer.
 // One 1024-thread workgroup per buffer: the compaction is ordered, so it takes no atomics on global memory, and the section walk, the
-// ordered append, the per-buffer resolve and the cache row's norm are those of records.h.
+// ordered append, the per-buffer resolve, the cache row's norm, the pick of a radix pass's bin and the compaction round with what follows it
+// (shared with the grid rule of spread.hip) are those of records.h.
 //
 //   key(row)   the record's intensity word (|DoG response|) with the sign bit cleared, compared as an unsigned integer: a total order on
 //              every bit pattern (-0 == +0 < denormals < normals < inf < NaN patterns); no float comparison takes place
@@ -37,7 +38,7 @@ __global__ void __launch_bounds__(1024) k_keep_strongest(uint32_t *__restrict__ 
   __shared__ uint32_t off_s[VKSIFT_MAX_SECTIONS], cnt_s[VKSIFT_MAX_SECTIONS], kept_s[VKSIFT_MAX_SECTIONS];
   __shared__ uint32_t hist[256], keys_s[STRONGEST_LDS_KEYS];
   __shared__ uint32_t wave_tot[16], tie_carry, keep_carry, sel_s[2];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t tid = threadIdx.x;
   const uint32_t bufi = map.buf[blockIdx.x];
   const auto buf = buffer_ref(feats_base, buf_stride, found_base, found_buf_stride, bufi);
   uint32_t *const feats = buf.recs, *const found = buf.found;
@@ -84,21 +85,7 @@ __global__ void __launch_bounds__(1024) k_keep_strongest(uint32_t *__restrict__ 
     }
     __syncthreads();
     if (tid < 64u)
-    {
-      // lane l owns bins 255 - 4l .. 252 - 4l: an inclusive scan over the lanes counts the keys from the top bin down
-      uint32_t h[4], sum = 0;
-      for (uint32_t i = 0; i < 4u; i++)
-        h[i] = hist[255u - 4u * tid - i], sum += h[i];
-      const uint32_t incl = wave_scan_incl_u32(sum, (int)lane);
-      uint32_t above = incl - sum;
-      if (above < want && want <= incl) // one lane: the keys that start with `prefix` are at least `want`
-      {
-        uint32_t bin = 255u - 4u * tid;
-        for (uint32_t i = 0; i < 3u && want > above + h[i]; i++)
-          above += h[i], bin--;
-        sel_s[0] = bin, sel_s[1] = want - above;
-      }
-    }
+      radix_pick_256(hist, want, sel_s);
     __syncthreads();
     prefix |= sel_s[0] << shift;
     want = sel_s[1];
@@ -116,88 +103,14 @@ __global__ void __launch_bounds__(1024) k_keep_strongest(uint32_t *__restrict__ 
     {
       key = row < STRONGEST_LDS_KEYS ? keys_s[row] : key_at(row);
       src_row = section_row(cnt, off_s, row);
-      uint32_t first = 0;
-      VKSIFT_UNROLL
-      for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
-      {
-        if (row >= first && row < first + cnt[o])
-          sec = o;
-        first += cnt[o];
-      }
+      sec = section_of(cnt, row);
     }
     const bool tie = valid && key == threshold;
     const uint32_t tie_rank = ordered_keep(tie, wave_tot, tie_carry);
     const bool keep = valid && (key > threshold || (tie && tie_rank < quota));
-    const uint32_t out_row = ordered_keep(keep, wave_tot, keep_carry); // its download-order row afterwards
-    // kept rows of every section, this round's included: those of the sections in front of a row's own are complete when it is placed
-    VKSIFT_UNROLL
-    for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
-    {
-      const unsigned long long bal = __ballot(keep && sec == o);
-      if (lane == 0u && bal)
-        atomicAdd(&kept_s[o], (uint32_t)__popcll(bal)); // LDS
-    }
-    __syncthreads();
-    uint32_t rec[VKSIFT_RECORD_WORDS], dst_row = 0;
-    if (keep)
-    {
-      uint32_t in_front = 0;
-      VKSIFT_UNROLL
-      for (uint32_t o = 0; o < VKSIFT_MAX_SECTIONS; o++)
-        in_front += o < sec ? kept_s[o] : 0u;
-      dst_row = off_s[sec] + (out_row - in_front);
-      const uint32_t *src = feats + (size_t)src_row * VKSIFT_RECORD_WORDS;
-      VKSIFT_UNROLL
-      for (uint32_t w = 0; w < VKSIFT_RECORD_WORDS; w++)
-        rec[w] = src[w];
-    }
-    __builtin_amdgcn_s_waitcnt(0); // every record of the round is in registers ...
-    __syncthreads();               // ... in every wave, before any is overwritten
-    if (keep)
-    {
-      if (dst_row != src_row)
-      {
-        uint32_t *dst = feats + (size_t)dst_row * VKSIFT_RECORD_WORDS;
-        VKSIFT_UNROLL
-        for (uint32_t w = 0; w < VKSIFT_RECORD_WORDS; w++)
-          dst[w] = rec[w];
-      }
-      if (entry.rows && out_row < max_features) // (always: max_features rows are kept; the entry holds no more)
-      {
-        // the bytes k_gather_sections writes for the selected buffer: one thread stores the eight pieces of the row and sums their norm parts
-        uint32_t norm = 0;
-        VKSIFT_UNROLL
-        for (uint32_t q = 0; q < 8u; q++)
-        {
-          const uint32_t *d = rec + VKSIFT_RECORD_HEAD_WORDS + 4u * q;
-          const uint4 v = uint4{d[0], d[1], d[2], d[3]};
-          *(uint4 *)(entry.rows + (size_t)out_row * 32u + 4u * q) = v;
-          norm += shifted_norm_part(v);
-        }
-        entry.norms[out_row] = norm;
-      }
-    }
+    compact_round(feats, keep, sec, src_row, off_s, kept_s, wave_tot, keep_carry, entry, max_features);
   }
-  // the counters: on the device, and posted to the host mirror by this launch (mapped pinned memory; no dependent copy)
-  if (tid < tab.nsec)
-  {
-    if (found)
-      found[tid] = kept_s[tid];
-    if (found_post)
-      found_post[(size_t)bufi * found_buf_stride + tid] = kept_s[tid];
-  }
-  if (entry.rows)
-  {
-    if (tid == 0)
-      *entry.n = max_features;
-    // quirk Q6: all-zero rows from the row count up to pad_rows_to
-    for (uint32_t i = max_features * 32u + tid; i < cache.pad_rows_to * 32u && max_features < cache.pad_rows_to; i += 1024u)
-    {
-      entry.rows[i] = 0u;
-      if ((i & 31u) == 0u)
-        entry.norms[i >> 5] = VKSIFT_ZERO_ROW_NORM;
-    }
-  }
+  compact_finish(tab.nsec, found, found_post, bufi, found_buf_stride, kept_s, entry, cache.pad_rows_to, max_features);
 }
 
 } // namespace

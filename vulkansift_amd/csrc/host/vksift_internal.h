@@ -75,7 +75,7 @@ typedef struct
 } MatchScratch;
 
 /* the interval of a stage's last run under vksift_ext_setProfiling (vksift_pairs.c). One per getter: both verification models share T_VERIFY */
-enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_ROOTSIFT, T_COUNT };
+enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_COUNT };
 typedef struct
 {
   vksift_hip_event ev[2];

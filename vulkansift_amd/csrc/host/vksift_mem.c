@@ -210,7 +210,7 @@ static const Handle handles[] = {
     EVENTS(prof[0].ev_pt, 3, sizeof(vksift_hip_event), false), EVENTS(prof[1].ev_pt, 3, sizeof(vksift_hip_event), false),
     EVENTS(prof[0].ev_scan, 2, sizeof(ProfSet), false), TIMER(T_MATCH, false),
     EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_gtab, 1, 0, true), EVENTS(ev_kps, 1, 0, true),
-    TIMER(T_VERIFY, true), TIMER(T_REFINE_H, true), TIMER(T_REFINE_F, true), TIMER(T_GUIDED, true), TIMER(T_BUDGET, true), TIMER(T_ROOTSIFT, true),
+    TIMER(T_VERIFY, true), TIMER(T_REFINE_H, true), TIMER(T_REFINE_F, true), TIMER(T_GUIDED, true), TIMER(T_BUDGET, true), TIMER(T_BUDGET_GRID, true), TIMER(T_ROOTSIFT, true),
 };
 #define N_HANDLES (sizeof(handles) / sizeof(handles[0]))
 
