@@ -198,7 +198,8 @@ extern "C"
    * those). The first min(n, max_features) rows by (key descending, row ascending) are kept, in download order: vksift_getFeaturesNumber becomes min(n,
    * max_features), vksift_downloadFeatures returns the kept records as they were, and a matching sees those rows. Deterministic. The orientations of one
    * keypoint are separate features with equal keys: a tie at the threshold is broken by row, so the budget may keep some of them and not the others.
-   * A buffer that holds at most max_features features is not touched at all; selecting again with the same budget changes nothing. A detected buffer stays
+   * A buffer that holds at most max_features features is not touched at all (its records, their order and its count; of what the instance keeps about it
+   * only vksift_ext_getPlacedKeypointsNumber changes, which reads 0 after every budget call); selecting again with the same budget changes nothing. A detected buffer stays
    * laid out in its octave sections (the kept features of an octave stay in it), an uploaded one stays one dense run.
    * Contract of vksift_detectFeatures: asynchronous, queued on the instance stream behind every detection and matching already queued (staged plain
    * detections are launched first); the buffers are busy (vksift_isBufferAvailable false) until it has run, and every accessor of them waits for it.
@@ -275,8 +276,10 @@ extern "C"
    * `response`) and vksift_ext_exportDescriptorsDevice work on it unchanged. Download order: by octave, in each octave the keypoints in input order, then the
    * orientation copies. A feature carries x, y, sigma and response (its intensity field) of its keypoint bit for bit: that is how the caller joins the
    * features to its list. An octave's section holds its share of max_nb_sift_per_buffer as after a detection; keypoints beyond it are dropped in input order.
-   * vksift_ext_getPlacedKeypointsNumber: the keypoints of the buffer's last describe call that were stored, before orientation copies (0 when something
-   * else has filled or cut the buffer since); waits like vksift_getFeaturesNumber.
+   * vksift_ext_getPlacedKeypointsNumber: the keypoints of the buffer's last describe call that were stored, before orientation copies; waits like
+   * vksift_getFeaturesNumber. 0 once something else has filled the buffer, and once vksift_ext_keepStrongestFeatures or ...Grid has named it, whether or
+   * not that call cut anything (when it is queued the host need not know yet how many features the buffer holds, so the count ends with the call, not
+   * with its outcome); vksift_ext_convertToRootSift keeps it.
    * Contract of vksift_detectFeatures / vksift_ext_detectFeaturesBatch: asynchronous, the buffers busy until it has run, the accessors wait; images and
    * keypoints are copied before the call returns; the scale-space accessors show the described image afterwards (image 0 of a batch). Never deferred, never
    * replayed from a graph; the detect timings (vksift_ext_getDetectTimings) keep reporting the last detection.

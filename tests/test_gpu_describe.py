@@ -14,6 +14,7 @@ import pytest
 
 import np_describe as ND
 import np_features as NF
+import np_rootsift as NR
 import np_strongest as NS
 from test_np_describe import ROUND_TRIP_MIN, SEED_SIGMA, as_keypoints, reproducible
 
@@ -208,6 +209,32 @@ def test_described_buffer_matches_and_is_budgeted_like_a_detected_one(vk, images
         want = np.sort(np.abs(kps["response"][order]))[::-1][:budget]
         assert np.array_equal(np.sort(np.abs(kept["intensity"]))[::-1], want)
         assert inst.getPlacedKeypointsNumber(1) == 0       # the buffer is no longer what the placement left
+
+
+def test_placed_count_ends_with_any_budget_call_and_follows_a_conversion(vk, images):
+    """the rule of vksift_ext_getPlacedKeypointsNumber as include/vksift_ext.h states it (the walks of tests/test_gpu_api_model.py met the case the
+    header used to describe differently): a budget call that names the buffer ends the count whether or not it cuts — the host does not know, when
+    the call is queued, how many features a buffer holds whose counters have not arrived —, and leaves the records of a buffer it does not cut
+    alone; a conversion keeps the count"""
+    img = images["192x144"]
+    with vk.Instance(config(vk, img)) as inst:
+        inst.detectFeatures(img, 0)
+        kps = as_keypoints(inst.downloadFeatures(0))
+        for queued_blind in (True, False):                # the budget behind a describe call nobody has waited for, and behind one whose counts are known
+            inst.describeKeypoints(img, kps, 1, vk.DESCRIBE_GIVEN)
+            inst.describeKeypoints(img, kps, 2, vk.DESCRIBE_GIVEN)
+            if not queued_blind:
+                assert inst.getPlacedKeypointsNumber(1) == inst.getPlacedKeypointsNumber(2) > 20
+            inst.convertToRootSift(2, 1)
+            inst.keepStrongestFeatures(1, 1, len(kps) + 1)                               # does not bind
+            assert inst.getPlacedKeypointsNumber(1) == 0, queued_blind
+            assert inst.getPlacedKeypointsNumber(2) > 20, queued_blind
+            out = inst.downloadFeatures(1)
+            inst.keepStrongestFeaturesGrid(2, 1, len(kps) + 1, img.shape[1], img.shape[0], 4, 3)     # nor does this one
+            assert inst.getPlacedKeypointsNumber(2) == 0, queued_blind
+            assert raw(inst.downloadFeatures(2)).tobytes() == NR.convert_records(raw(out)).tobytes(), queued_blind   # untouched but for the conversion
+            inst.describeKeypoints(img, kps, 1, vk.DESCRIBE_GIVEN)
+            assert inst.getPlacedKeypointsNumber(1) == len(out) and inst.downloadFeatures(1).tobytes() == out.tobytes(), queued_blind
 
 
 # ---------------------------------------------------------------------------------------------------------------------- no side effects

@@ -8,6 +8,7 @@ import np_guided as G
 import np_refine as R
 import np_verify as V
 import quality as Q
+from pair_checks import corr as _corr, same_refined_homography as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -20,12 +21,6 @@ def _record_words(rec):
     w[:9] = np.asarray(rec["H"], np.float32).reshape(9).view(np.uint32)
     w[9], w[10], w[11], w[12] = rec["nb_matches"], rec["nb_inliers"], rec["best_hypothesis"], rec["valid"]
     return w
-
-
-def _same(got, want, ctx):
-    assert (int(got["valid"]), int(got["nb_matches"]), int(got["nb_inliers"]), int(got["rounds"])) == (want["valid"], want["nb_matches"], want["nb_inliers"], want["rounds"]), \
-        (ctx, got, {k: v for k, v in want.items() if k != "mask"})
-    assert np.asarray(got["H"], np.float32).tobytes() == np.asarray(want["H"], np.float32).tobytes(), (ctx, got["H"], want["H"])
 
 
 def test_kernel_level_every_size_round_count_and_threshold_is_bit_equal(vk):
@@ -112,10 +107,6 @@ def _pairs(vk, seed=33):
     base = vk.gen_synthetic_image(seed, W, H)
     Hs = [Q.homography(W, H, **kw) for kw in Q.WARPS]
     return [base] + [Q.warp(base, Ht) for Ht in Hs], Hs
-
-
-def _corr(fa, fb, fm):
-    return np.stack([fa["x"][fm["idx_a"]], fa["y"][fm["idx_a"]], fb["x"][fm["idx_b"]], fb["y"][fm["idx_b"]]], axis=1).astype(np.float32).reshape(-1, 4)
 
 
 def _existing_bytes(inst, n):

@@ -8,6 +8,7 @@ import np_guided as G
 import np_refine_f as RF
 import np_verify_f as VF
 import quality as Q
+from pair_checks import corr as _corr, same_refined_fundamental as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -20,12 +21,6 @@ def _record_words(rec):
     w[:9] = np.asarray(rec["F"], np.float32).reshape(9).view(np.uint32)
     w[9], w[10], w[11], w[12], w[13] = rec["nb_matches"], rec["nb_inliers"], rec["best_hypothesis"], rec["best_root"], rec["valid"]
     return w
-
-
-def _same(got, want, ctx):
-    assert (int(got["valid"]), int(got["nb_matches"]), int(got["nb_inliers"]), int(got["rounds"])) == (want["valid"], want["nb_matches"], want["nb_inliers"], want["rounds"]), \
-        (ctx, got, {k: v for k, v in want.items() if k != "mask"})
-    assert np.asarray(got["F"], np.float32).tobytes() == np.asarray(want["F"], np.float32).tobytes(), (ctx, got["F"], want["F"])
 
 
 def test_kernel_level_every_size_round_count_and_threshold_is_bit_equal(vk):
@@ -125,10 +120,6 @@ def _two_view_features(vk, seed=77):
     fa["x"], fa["y"], fa["descriptor"] = s["xa"], s["ya"], s["desc_a"]
     fb["x"], fb["y"], fb["descriptor"] = s["xb"], s["yb"], s["desc_b"]
     return fa, fb, s["F"]
-
-
-def _corr(fa, fb, fm):
-    return np.stack([fa["x"][fm["idx_a"]], fa["y"][fm["idx_a"]], fb["x"][fm["idx_b"]], fb["y"][fm["idx_b"]]], axis=1).astype(np.float32).reshape(-1, 4)
 
 
 def _existing_bytes(inst, n):

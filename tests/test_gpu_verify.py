@@ -6,6 +6,7 @@ import pytest
 
 import np_verify as V
 import quality as Q
+from pair_checks import corr as _corr, same_homography as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -13,13 +14,6 @@ SLOT_N = [0, 1, 3, 4, 5, 63, 64, 65, 257, 1000, 4097, 100000]   # the last: vksi
 NB_HYP = [1, 64, 100, 256, 1024, 4096]
 SEEDS = [0, 0x5EED0000C0FFEE]
 THRESHOLDS = [0.5, 2.5, 10.0]
-
-
-def _same(got, want, ctx):
-    assert int(got["valid"]) == want["valid"], ctx
-    assert int(got["nb_matches"]) == want["nb_matches"], ctx
-    assert (int(got["best_hypothesis"]), int(got["nb_inliers"])) == (want["best_hypothesis"], want["nb_inliers"]), ctx
-    assert np.asarray(got["H"], np.float32).tobytes() == want["H"].tobytes(), (ctx, got["H"], want["H"])
 
 
 def _slots():
@@ -98,10 +92,6 @@ def _pairs(vk, seed=33):
     base = vk.gen_synthetic_image(seed, W, H)
     Hs = [Q.homography(W, H, **kw) for kw in Q.WARPS]
     return [base] + [Q.warp(base, Ht) for Ht in Hs], Hs
-
-
-def _corr(fa, fb, fm):
-    return np.stack([fa["x"][fm["idx_a"]], fa["y"][fm["idx_a"]], fb["x"][fm["idx_b"]], fb["y"][fm["idx_b"]]], axis=1).astype(np.float32).reshape(-1, 4)
 
 
 def _verify_all(inst, ids_a, ids_b, nh, thr, seed):

@@ -8,6 +8,7 @@ import pytest
 import np_verify as V
 import np_verify_f as VF
 import quality as Q
+from pair_checks import corr as _corr, same_fundamental as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -16,13 +17,6 @@ assert SLOT_N == [0, 6, 7, 8, 63, 64, 65, 255, 256, 257, 1000]
 NB_HYP = [1, 100, 256, 257, 1024]
 SEEDS = [0, 0x5EED0000C0FFEE]
 THRESHOLDS = [0.5, 2.5]
-
-
-def _same(got, want, ctx):
-    assert int(got["valid"]) == want["valid"], ctx
-    assert int(got["nb_matches"]) == want["nb_matches"], ctx
-    assert (int(got["best_hypothesis"]), int(got["best_root"]), int(got["nb_inliers"])) == (want["best_hypothesis"], want["best_root"], want["nb_inliers"]), ctx
-    assert np.asarray(got["F"], np.float32).tobytes() == want["F"].tobytes(), (ctx, got["F"], want["F"])
 
 
 def test_kernel_level_every_size_hypothesis_count_seed_and_threshold_is_bit_equal(vk):
@@ -101,10 +95,6 @@ def _pairs(vk, seed=33):
     base = vk.gen_synthetic_image(seed, W, H)
     Hs = [Q.homography(W, H, **kw) for kw in Q.WARPS]
     return [base] + [Q.warp(base, Ht) for Ht in Hs], Hs
-
-
-def _corr(fa, fb, fm):
-    return np.stack([fa["x"][fm["idx_a"]], fa["y"][fm["idx_a"]], fb["x"][fm["idx_b"]], fb["y"][fm["idx_b"]]], axis=1).astype(np.float32).reshape(-1, 4)
 
 
 def _same_h(got, want, ctx):

@@ -212,7 +212,8 @@ uint32_t vksift_ext_getPlacedKeypointsNumber(vksift_Instance instance, uint32_t 
     return 0;
   }
   wait_for_buffer(inst, gpu_buffer_id);
-  /* the count of the describe call that filled the buffer, unless something else has filled or cut it since */
+  /* the count of the describe call that filled the buffer, unless something else has filled it or a budget call has named it since (a conversion
+   * takes the count along: vksift_rootsift.c) */
   const uint64_t seq = inst->bufs[gpu_buffer_id].seq;
   return inst->placed_seq && seq != 0 && inst->placed_seq[gpu_buffer_id] == seq ? inst->h_placed[gpu_buffer_id] : 0u;
 }
