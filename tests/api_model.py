@@ -49,7 +49,9 @@ SETS = ("filtered", "H", "F", "refined H", "refined F", "guided")
 PROFILES = {
     # batch_capacity 1: plain detections only, staged and launched as batches (VKSIFT_DEFER), default posting
     "plain": dict(nbuf=6, bc=1, cap=None, env={"VKSIFT_DEFER": "1", "VKSIFT_DEFER_MAX": "3"}),
-    # two pyramid buffers, batched detections of 8 (the packed download), graph replay
+    # batch capacity 8: every detection with an octave overlaps (a scale-space stream of its own), batched detections of 8 (the packed download).
+    # An overlapped detection is never captured: VKSIFT_GRAPH=1 lifts the size limit of the replay, but this profile never captures or replays
+    # a graph (tests/test_detect_plan.py: batch_profile holds that on the simulated device; tests/test_gpu_graph_cache.py covers the replay)
     "batch": dict(nbuf=12, bc=8, cap=None, env={"VKSIFT_GRAPH": "1"}),
     # every section of every image clamps; the records are fetched, not posted
     "clamped": dict(nbuf=8, bc=4, cap=120, env={"VKSIFT_POST_FEATURES": "0"}),

@@ -1,5 +1,6 @@
 """Random walks over every stateful entry of the API on real instances, checked against the model of tests/api_model.py: three profiles (plain
-detections staged and launched as batches; batches of 8 with graph replay and the packed download; clamped sections without record posting), two
+detections staged and launched as batches; overlapped batches of 8 with the packed download — no graph replay: overlapped detections are never
+captured, tests/test_gpu_graph_cache.py covers the replay —; clamped sections without record posting), two
 seeds each. This test checks STATE — which launch reads which rows, and when —, not kernels: the expected records come from the oracle and the
 numpy restatements, those of the describe calls from describe calls on a fresh quiet instance made before the walk (tests/test_gpu_describe.py holds
 the describe kernels to their restatement). tests/test_api_model.py pins on the CPU which edges these walks reach and that the executor notices

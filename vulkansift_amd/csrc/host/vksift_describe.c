@@ -62,7 +62,8 @@ static int fit_keypoint_blocks(vksift_Instance inst, size_t bytes)
 
 /* A detection's keypoints have a relative sigma of at most seed_scale_sigma 2^((S + 1) / S), and the table of the descriptor's fixed-point scales
  * (vksift_hm_desc_fp_table) ends there; the launch clamps its index. Supplied keypoints reach the whole window range, so the first describe call
- * extends the table to it. The entries a detection reads stay what they were. */
+ * extends the table to it. The entries a detection reads stay what they were; the table's length is an argument of every descriptor launch, so
+ * the detection graphs captured with the old one are dropped (the stream has been drained: none of them is in flight). */
 #define DESCRIBE_MAX_REL 29.f
 static int fit_desc_fp_table(vksift_Instance inst)
 {
@@ -73,6 +74,7 @@ static int fit_desc_fp_table(vksift_Instance inst)
   TRY(vksift_hip_memcpy_h2d(inst->d_desc_fp, tab, sizeof(float) * n, inst->stream), "descriptor scale table");
   TRY(vksift_hip_stream_sync(inst->stream), "descriptor scale table");
   inst->desc_fp_len = n;
+  drop_detect_graphs(inst);
   return 0;
 }
 

@@ -444,9 +444,11 @@ static int enqueue_clears(DetectCtx *c, vksift_hip_stream sp)
   TRY(vksift_hip_event_record(inst->ev_join[1], sp), "event record");
   TRY(vksift_hip_stream_wait_event(inst->pyr_stream, inst->ev_join[1]), "scale fork");
   TRY(vksift_hip_memset(found_dev(inst, c->first_buf), 0, bytes, inst->pyr_stream), "counter reset");
-  if (c->L->n_oct > 0 && vksift_hip_clear_segment_masks(c->jobs, c->L->n_oct, c->count, inst->pyr_stream) == 0)
-    for (uint32_t o = 0; o < c->L->n_oct; o++)
-      c->jobs[o].masks_cleared = 1u;
+  bool cleared = false;
+  if (c->L->n_oct > 0)
+    TRY(optional(vksift_hip_clear_segment_masks(c->jobs, c->L->n_oct, c->count, inst->pyr_stream), &cleared), "mask reset");
+  for (uint32_t o = 0; cleared && o < c->L->n_oct; o++)
+    c->jobs[o].masks_cleared = 1u;
   return 0;
 }
 
@@ -638,8 +640,11 @@ static int enqueue_detection(DetectCtx *c)
 /* ------------------------------------------------------------------------------------------------ */
 /* hipGraph replay (VKSIFT_GRAPH=1): the launch sequence depends only on (resolution, batch, first buffer, input pointer) —
  * counts and candidate lists live on the device — so it is captured once per such key and replayed with a single launch.
- * Returns the cache entry for the key (hit: ->exec != NULL) or the least recently used entry, emptied (miss). */
-static DetectGraph *graph_lookup(vksift_Instance inst, const DetectCtx *c)
+ * *out: the cache entry for the key (hit: ->exec != NULL) or the least recently used entry, emptied (miss). The evicted exec is
+ * destroyed only once the stream has passed its last launch: a caller that cycles through more keys than the cache holds and never
+ * waits (device input: no staging buffer to recycle) would otherwise destroy an exec that is still executing. A wait that fails is
+ * the detection's failure: the exec stays, and detect_failed() drops the cache behind drained streams. */
+static int graph_lookup(vksift_Instance inst, const DetectCtx *c, DetectGraph **out)
 {
   DetectGraph *victim = &inst->graphs[0];
   for (int i = 0; i < VKSIFT_GRAPH_CACHE; i++)
@@ -647,13 +652,19 @@ static DetectGraph *graph_lookup(vksift_Instance inst, const DetectCtx *c)
     DetectGraph *g = &inst->graphs[i];
     if (g->exec && g->w == c->w && g->h == c->h && g->count == c->count && g->first_buf == c->first_buf && g->d_src == c->d_src && g->post == c->post &&
         g->dense == c->dense)
-      return g;
+    {
+      *out = g;
+      return 0;
+    }
     if (g->stamp < victim->stamp)
       victim = g;
   }
+  if (victim->exec)
+    TRY(wait_detect_passed(inst, victim->last_seq), "detection graph retirement");
   vksift_hip_graph_destroy(victim->exec);
   memset(victim, 0, sizeof(*victim));
-  return victim;
+  *out = victim;
+  return 0;
 }
 
 /* The sequence reaches the GPU: queued directly, captured and launched, or replayed from the graph cache (after prepare_detection: c->post is
@@ -662,7 +673,9 @@ static int launch_detection(DetectCtx *c)
 {
   vksift_Instance inst = c->inst;
   vksift_hip_stream st = inst->stream;
-  DetectGraph *dg = c->replay_ok ? graph_lookup(inst, c) : NULL;
+  DetectGraph *dg = NULL;
+  if (c->replay_ok)
+    TRY(graph_lookup(inst, c, &dg), "detection graph lookup");
   if (dg && dg->exec)
   {
     if (c->images) /* the upload is a node of the graph: the staging buffer has to be filled before the replay */
@@ -695,7 +708,7 @@ static int launch_detection(DetectCtx *c)
     }
   }
   if (dg)
-    dg->stamp = ++inst->graph_stamp;
+    dg->stamp = ++inst->graph_stamp, dg->last_seq = inst->det_seq + 1u; /* (the number finish_detection gives this detection) */
   /* (recorded by enqueue_detection for every sequence that is not captured) a later overlapped detection recycles the buffer
    * behind this one's readers */
   if (dg && inst->pyr_pingpong)
@@ -817,6 +830,8 @@ void detect_failed(vksift_Instance inst, const DetectCtx *c, const char *fn)
       (void)vksift_hip_stream_sync(inst->pyr_stream);
     if (inst->side_stream)
       (void)vksift_hip_stream_sync(inst->side_stream);
+    /* whatever failed, no captured sequence is trusted after it: the next detection of every key captures afresh (nothing is in flight) */
+    drop_detect_graphs(inst);
     for (uint32_t i = 0; i < c->count; i++)
     {
       inst->bufs[c->first_buf + i].seq = 0;

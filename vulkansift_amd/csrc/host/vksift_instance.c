@@ -243,6 +243,28 @@ int wait_detect_seq(vksift_Instance inst, uint64_t seq)
   return e;
 }
 
+/* blocks until the instance stream has passed detection `seq`, waiting for as little as the ring allows: the OLDEST detection at or behind it
+ * that still has a slot (the stream is in-order). A number no slot reaches — a detection that failed before it was queued — waits for nothing.
+ * Returns the wait's error code: after a failed wait nothing is known about `seq`, and det_done stays what it was. */
+int wait_detect_passed(vksift_Instance inst, uint64_t seq)
+{
+  const DetectSlot *best = NULL;
+  if (seq <= inst->det_done)
+    return 0;
+  for (int i = 0; i < VKSIFT_DETECT_RING; i++)
+  {
+    const DetectSlot *d = &inst->det_ring[i];
+    if (d->ev && d->seq >= seq && (!best || d->seq < best->seq))
+      best = d;
+  }
+  if (!best)
+    return 0;
+  const int e = vksift_hip_event_sync(best->ev);
+  if (e == 0 && best->seq > inst->det_done)
+    inst->det_done = best->seq;
+  return e;
+}
+
 /* A call that rewrites the records of a range of buffers in place (the feature budget, the RootSIFT conversion) is a "detection" of the buffers it
  * names as far as the waits are concerned: it takes the next sequence number and a ring slot,
  * so that counts_valid(), wait_for_buffer(), vksift_isBufferAvailable() and rows_bound() (capacity bound until the new counters have arrived)
@@ -300,6 +322,17 @@ bool match_running(vksift_Instance inst)
   return false;
 }
 
+/* Captured launch graphs hold the addresses and the launch arguments of the instance as it was when they were captured: whoever changes
+ * one of them (the detection scratch, the descriptor scale table) drops them all. The caller has drained the instance's streams. */
+void drop_detect_graphs(vksift_Instance inst)
+{
+  for (int i = 0; i < VKSIFT_GRAPH_CACHE; i++)
+  {
+    vksift_hip_graph_destroy(inst->graphs[i].exec);
+    memset(&inst->graphs[i], 0, sizeof(inst->graphs[i]));
+  }
+}
+
 /* The reservation made at creation covers `det_cap` square images of input_image_max_size pixels plus 25 %. Two things outgrow it:
  * a narrow image of the same area (every row is padded to 64 floats on every octave: 139x356 needs 1.5x; the reference re-creates its
  * images for every new input resolution, sift_memory.c:362-452) — L != NULL, the per-image strides grow to what the layout needs —
@@ -318,11 +351,7 @@ int resize_detect_scratch(vksift_Instance inst, const PyrLayout *L, uint32_t new
       vksift_hip_stream_sync(drain[i]);
   inst->staging_pending = false;
   inst->input_free_valid = false;
-  for (int i = 0; i < VKSIFT_GRAPH_CACHE; i++)
-  {
-    vksift_hip_graph_destroy(inst->graphs[i].exec);
-    memset(&inst->graphs[i], 0, sizeof(inst->graphs[i]));
-  }
+  drop_detect_graphs(inst);
   inst->pyr_free_valid[0] = inst->pyr_free_valid[1] = false;
   const int rc = mem_resize_scratch(inst, L, new_cap);
   inst->cur_w = inst->cur_h = 0; /* no scale-space to download until the next detection */

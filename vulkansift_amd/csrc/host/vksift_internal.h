@@ -65,6 +65,7 @@ typedef struct
   bool post;  /* the sequence ends with the feature posting (see h_post) */
   bool dense; /* its descriptor launch writes the buffer's matcher cache entry (captured before the first matching: it does not) */
   uint64_t stamp;
+  uint64_t last_seq; /* the detection that launched it last: it may be executing until that one has completed */
 } DetectGraph;
 
 /* device scratch of one set of matching slots (slot i serves pair i of a batched call) */
@@ -351,6 +352,7 @@ VKSIFT_INTERNAL void set_buffer_sections(vksift_Instance inst, uint32_t buf, uin
 VKSIFT_INTERNAL void mark_detect_done(vksift_Instance inst);
 VKSIFT_INTERNAL bool detect_running(vksift_Instance inst);
 VKSIFT_INTERNAL int wait_detect_seq(vksift_Instance inst, uint64_t seq);
+VKSIFT_INTERNAL int wait_detect_passed(vksift_Instance inst, uint64_t seq);
 /* buffers [first, first + count) are rewritten in place by what the caller queues next (vksift_strongest.c, vksift_rootsift.c): they take the next
  * sequence number and a ring slot; the caller records the slot's event behind its launches */
 VKSIFT_INTERNAL void take_sequence(vksift_Instance inst, uint32_t first, uint32_t count);
@@ -358,6 +360,7 @@ VKSIFT_INTERNAL bool match_running(vksift_Instance inst);
 VKSIFT_INTERNAL int wait_all(vksift_Instance inst);
 VKSIFT_INTERNAL int grow_image_scratch(vksift_Instance inst, const PyrLayout *L);
 VKSIFT_INTERNAL int resize_detect_scratch(vksift_Instance inst, const PyrLayout *L, uint32_t new_cap);
+VKSIFT_INTERNAL void drop_detect_graphs(vksift_Instance inst);
 
 /* vksift_stage.c: images [i0, i1) -> dst (the pinned staging buffer), by a small pool of copy threads */
 VKSIFT_INTERNAL void stage_images(uint8_t *dst, const uint8_t *const *images, uint32_t i0, uint32_t i1, size_t img_bytes);
