@@ -188,6 +188,53 @@ extern "C"
   /* Time (ms) of the last guided matching (gather + sweeps + decision + the count posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getGuidedMatchTime(vksift_Instance instance);
 
+  /* ---- Multi-view feature tracks ------------------------------------------------------------------------------------------
+   * The step every structure-from-motion or SLAM caller takes after the pair stages (COLMAP's correspondence graph, OpenMVG's TracksBuilder, OpenSfM's
+   * create_tracks): the matches of ALL pairs of the last vksift_ext_matchFeaturesFiltered call are merged, and every connected set of features is one scene
+   * point, a track — on the device, by a lock-free union-find over the results the pair stages left there, without one download of matches and masks per pair.
+   * A node is (gpu_buffer_id, row), row in download order. The edges come from `source`: FILTERED and GUIDED take every record (idx_a, idx_b) of every pair p,
+   * which joins (A[p], idx_a) and (B[p], idx_b); the four mask sources take the filtered records whose byte in that stage's mask is 1, of the pairs whose
+   * record of that stage has valid != 0 (a pair whose model is not valid contributes no edge). A pair with A == B contributes edges like any other; an edge
+   * with both ends on one node joins nothing. A track is a connected component of at least two nodes. Tracks are numbered from 0 in the order of their smallest
+   * member, members compared by (gpu_buffer_id, row). vksift_ext_Track: gpu_buffer_id and row of the smallest member, length = the number of members,
+   * nb_buffers = the number of distinct buffers among them. A track is CONFLICTING iff length > nb_buffers: two features of one image have been merged; callers
+   * drop or split such tracks, the library only reports them. vksift_ext_TrackStats: nb_tracks; nb_conflicting; nb_features = the sum of the lengths; nb_edges =
+   * the edges taken from the source, edges inside one buffer, on one node and duplicates included.
+   * vksift_ext_downloadTracks writes nb_tracks records. vksift_ext_downloadFeatureTracks(b, out) writes vksift_getFeaturesNumber(b) words, the track number of
+   * every row of b or VKSIFT_EXT_NO_TRACK; b must be a buffer of the pair list.
+   * Deterministic: the same inputs give the same bytes on every run, whatever the scheduling; the numbering depends on nothing but the graph
+   * (tests/np_tracks.py restates it).
+   * Not attempted: no member list per track (the caller groups the per-feature words in one pass); no splitting of conflicting tracks; no tracks across two
+   * matching calls.
+   * Contract of guided matching: asynchronous, queued on the instance stream behind the matching and whatever produced the source, the pairs' buffers stay
+   * busy, the accessors wait; results of its own (every pair result stays readable and unchanged), replaced by the next vksift_ext_buildTracks, invalidated by
+   * a new matching, plain or filtered. A verification or refit queued after a build does not touch the tracks already built. Precondition, as for guided
+   * matching: the buffers of the pairs still hold the features that were matched (the row counts are the matching's).
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, earlier tracks untouched): no filtered matching, an unknown source, a source whose stage has not been run for
+   * the present matching, out == NULL, a buffer outside the pair list, an accessor called before any build. A launch or allocation failure is
+   * VKSIFT_VULKAN_ERROR. */
+#define VKSIFT_EXT_TRACKS_FILTERED 0u   /* every filtered match of every pair */
+#define VKSIFT_EXT_TRACKS_VERIFIED_H 1u /* matches whose byte in the verified homography's mask is 1 */
+#define VKSIFT_EXT_TRACKS_VERIFIED_F 2u
+#define VKSIFT_EXT_TRACKS_REFINED_H 3u
+#define VKSIFT_EXT_TRACKS_REFINED_F 4u
+#define VKSIFT_EXT_TRACKS_GUIDED 5u     /* the guided matches of every pair */
+#define VKSIFT_EXT_NO_TRACK 0xFFFFFFFFu
+  typedef struct
+  {
+    uint32_t gpu_buffer_id, row, length, nb_buffers;
+  } vksift_ext_Track; /* 16 bytes */
+  typedef struct
+  {
+    uint32_t nb_tracks, nb_conflicting, nb_features, nb_edges;
+  } vksift_ext_TrackStats; /* 16 bytes */
+  VKSIFT_EXPORT void vksift_ext_buildTracks(vksift_Instance instance, uint32_t source);
+  VKSIFT_EXPORT void vksift_ext_getTrackStats(vksift_Instance instance, vksift_ext_TrackStats *out);
+  VKSIFT_EXPORT void vksift_ext_downloadTracks(vksift_Instance instance, vksift_ext_Track *tracks);
+  VKSIFT_EXPORT void vksift_ext_downloadFeatureTracks(vksift_Instance instance, uint32_t gpu_buffer_id, uint32_t *track_ids);
+  /* Time (ms) of the last vksift_ext_buildTracks (its launches + the statistics' posting), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getTracksTime(vksift_Instance instance);
+
   /* ---- GPU-side feature budget ------------------------------------------------------------------------------------------
    * Every SIFT buffer of [first_gpu_buffer_id, first_gpu_buffer_id + count) keeps its max_features strongest features (OpenCV's nfeatures, SiftGPU's -tc,
    * PopSift's --filter-max-extrema), selected and compacted on the device: no download, host sort and upload. The capacity max_nb_sift_per_buffer drops the

@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 11u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 11: vksift_hip_keep_grid */
+#define VKSIFT_HIP_ABI_VERSION 12u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -669,6 +669,31 @@ extern "C"
                               const float *models, uint32_t model_stride, const uint32_t *valid, uint32_t valid_stride, uint32_t model_kind, float t2, float ratio,
                               float max_distance, uint32_t cross_check, uint32_t nslots, uint8_t *out, uint64_t out_slot_stride, uint32_t *out_n, uint32_t *scratch,
                               size_t scratch_u32, vksift_hip_stream s);
+
+  /* ------------------------------------------------------------------ feature tracks (tracks.hip; no counterpart in the reference) */
+  /* The connected components of the graph over the stored rows of nbufs SIFT buffers whose edges are the records of nslots pairs. buf_tab: two words per
+   * participating buffer, in increasing gpu_buffer_id — {gpu_buffer_id, index into rows_dev of the word that holds its row count}; the buffer at position r
+   * has rank r and min(rows_dev[that word], max_rows) stored rows; node (rank, row) has the index rank * node_stride + row, so index order is the order
+   * (gpu_buffer_id, row). slot_tab + i*slot_tab_stride: {rank of A, rank of B} of slot i. Slot i holds n = min(n_dev[i*n_stride], max_n) 16-byte records
+   * {idx_a, idx_b, ...} at records + i*rec_slot_stride; record e is an edge between (rank A, idx_a) and (rank B, idx_b) iff valid == NULL or
+   * valid[i*valid_stride] != 0, and masks == NULL or the byte masks[i*mask_slot_stride + e] is 1, and both ranks are below nbufs and both rows stored (the
+   * library's own producers never leave a record that names a row that is not). A track is a component of at least two nodes; tracks are numbered from 0 in the
+   * order of their smallest node. tracks + 16*t: {gpu_buffer_id, row} of the smallest node, length (nodes), nb_buffers (distinct buffers among them);
+   * node_words[index]: the track number of every stored row, 0xFFFFFFFF without one; stats: {tracks, tracks with length > nb_buffers, sum of the lengths,
+   * edges taken (edges inside one buffer, on one node and duplicates included)}. Deterministic: every output depends on the graph alone.
+   * tests/np_tracks.py restates it. slot_tab, buf_tab and rows_dev are read by the launches (device-accessible memory). scratch: scratch_u32 >=
+   * vksift_hip_tracks_scratch_u32(nbufs, node_stride) words, 8-byte aligned, need not be initialised, contents unspecified afterwards (only the words of
+   * stored rows and of the launch's blocks are touched). WRITTEN: the four words of stats, records 0 .. stats[0]-1 of tracks, node_words of the stored rows, the
+   * scratch, nothing else. hipErrorInvalidValue, nothing launched: nslots, nbufs, max_n or max_rows 0, max_rows above node_stride, nbufs * node_stride above
+   * 2^32 - 2, n_stride 0, slot_tab_stride below 2, valid given with valid_stride 0, records or tracks not 4-byte aligned, rec_slot_stride not a multiple of 4,
+   * scratch not 8-byte aligned, with nslots > 1 a stride below max_n records (rec_slot_stride < 16 max_n, mask_slot_stride < max_n), tracks_cap (records)
+   * below nbufs * max_rows / 2, too little scratch. */
+  size_t vksift_hip_tracks_scratch_u32(uint32_t nbufs, uint32_t node_stride);
+  int vksift_hip_build_tracks(const uint8_t *records, uint64_t rec_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, const uint8_t *masks,
+                              uint64_t mask_slot_stride, const uint32_t *valid, uint32_t valid_stride, const uint32_t *slot_tab, uint32_t slot_tab_stride,
+                              uint32_t nslots, const uint32_t *buf_tab, uint32_t nbufs, const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows,
+                              uint32_t *node_words, uint8_t *tracks, uint64_t tracks_cap, uint32_t *stats, uint32_t *scratch, size_t scratch_u32,
+                              vksift_hip_stream s);
 
 #ifdef __cplusplus
 }

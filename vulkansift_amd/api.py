@@ -171,6 +171,16 @@ def lib():
     L.vksift_ext_downloadGuidedMatches.restype = None
     L.vksift_ext_getGuidedMatchTime.argtypes = [inst]
     L.vksift_ext_getGuidedMatchTime.restype = C.c_float
+    L.vksift_ext_buildTracks.argtypes = [inst, u32]
+    L.vksift_ext_buildTracks.restype = None
+    L.vksift_ext_getTrackStats.argtypes = [inst, C.c_void_p]
+    L.vksift_ext_getTrackStats.restype = None
+    L.vksift_ext_downloadTracks.argtypes = [inst, C.c_void_p]
+    L.vksift_ext_downloadTracks.restype = None
+    L.vksift_ext_downloadFeatureTracks.argtypes = [inst, u32, C.c_void_p]
+    L.vksift_ext_downloadFeatureTracks.restype = None
+    L.vksift_ext_getTracksTime.argtypes = [inst]
+    L.vksift_ext_getTracksTime.restype = C.c_float
     L.vksift_ext_keepStrongestFeatures.argtypes = [inst, u32, u32, u32]
     L.vksift_ext_keepStrongestFeatures.restype = None
     L.vksift_ext_getKeepStrongestTime.argtypes = [inst]
@@ -259,6 +269,11 @@ def lib():
                                           C.c_void_p, u32, C.c_void_p, u32, u32, C.c_float, C.c_float, C.c_float, u32, u32, C.c_void_p, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p]
     L.vksift_hip_match_guided.restype = C.c_int
+    L.vksift_hip_tracks_scratch_u32.argtypes = [u32, u32]
+    L.vksift_hip_tracks_scratch_u32.restype = C.c_size_t
+    L.vksift_hip_build_tracks.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, u32, u32, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p, u32,
+                                          C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.vksift_hip_build_tracks.restype = C.c_int
     _lib = L
     return L
 
@@ -415,6 +430,10 @@ def refit_fundamental(d_corr, d_n, start_results, start_masks, nb_rounds, thresh
 
 
 GUIDE_HOMOGRAPHY, GUIDE_FUNDAMENTAL = 0, 1
+TRACKS_FILTERED, TRACKS_VERIFIED_H, TRACKS_VERIFIED_F, TRACKS_REFINED_H, TRACKS_REFINED_F, TRACKS_GUIDED = range(6)
+NO_TRACK = 0xFFFFFFFF
+TRACK_DTYPE = np.dtype([("gpu_buffer_id", "<u4"), ("row", "<u4"), ("length", "<u4"), ("nb_buffers", "<u4")])
+TRACK_STATS_DTYPE = np.dtype([("nb_tracks", "<u4"), ("nb_conflicting", "<u4"), ("nb_features", "<u4"), ("nb_edges", "<u4")])
 
 
 def guided_match(desc_a, xy_a, desc_b, xy_b, n, models, valid, model_kind, t2, ratio, max_distance, cross_check, scratch_u32=None, strides=None, buffers=None):
@@ -656,6 +675,39 @@ class Instance:
 
     def getGuidedMatchTime(self):
         return lib().vksift_ext_getGuidedMatchTime(self._h)
+
+    def buildTracks(self, source=TRACKS_FILTERED):
+        """merges the matches of every pair of the last matchFeaturesFiltered call into feature tracks on the GPU (vksift_ext_buildTracks); `source` is one
+        of TRACKS_FILTERED, TRACKS_VERIFIED_H / _F, TRACKS_REFINED_H / _F, TRACKS_GUIDED; asynchronous like the pair stages"""
+        lib().vksift_ext_buildTracks(self._h, source)
+        _check_pending()
+
+    def getTrackStats(self):
+        """{nb_tracks, nb_conflicting, nb_features, nb_edges} of the last buildTracks"""
+        out = np.zeros(1, TRACK_STATS_DTYPE)
+        lib().vksift_ext_getTrackStats(self._h, out.ctypes.data)
+        _check_pending()
+        return {k: int(out[0][k]) for k in TRACK_STATS_DTYPE.names}
+
+    def downloadTracks(self):
+        """the track records (TRACK_DTYPE), in track order"""
+        n = self.getTrackStats()["nb_tracks"]
+        out = np.zeros(n, TRACK_DTYPE)
+        if n:
+            lib().vksift_ext_downloadTracks(self._h, out.ctypes.data)
+            _check_pending()
+        return out
+
+    def downloadFeatureTracks(self, buffer_id, nb_features=None):
+        """uint32 per feature of the buffer, in download order: its track number or NO_TRACK"""
+        n = self.getFeaturesNumber(buffer_id) if nb_features is None else nb_features
+        out = np.full(n, NO_TRACK, np.uint32)
+        lib().vksift_ext_downloadFeatureTracks(self._h, buffer_id, out.ctypes.data)
+        _check_pending()
+        return out
+
+    def getTracksTime(self):
+        return lib().vksift_ext_getTracksTime(self._h)
 
     def keepStrongestFeatures(self, first_buffer, count, max_features):
         """every SIFT buffer of [first_buffer, first_buffer + count) keeps its max_features strongest features (|DoG response|, ties by download

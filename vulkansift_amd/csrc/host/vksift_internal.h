@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -76,7 +76,7 @@ typedef struct
 } MatchScratch;
 
 /* the interval of a stage's last run under vksift_ext_setProfiling (vksift_pairs.c). One per getter: both verification models share T_VERIFY */
-enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_COUNT };
+enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_COUNT };
 typedef struct
 {
   vksift_hip_event ev[2];
@@ -96,6 +96,24 @@ typedef struct
   uint32_t words, elem, counted_by;
   uint32_t slots_used;
 } PairResults;
+
+/* What vksift_ext_buildTracks keeps (vksift_tracks.c): not per pair, so not a PairResults. Sized by the configuration when the first build allocates it:
+ * cap_bufs = min(2 batch_cap, sift_buffer_count) participating buffers of max_nb_sift_per_buffer nodes each. `valid`: the accessors have something to
+ * read; cleared by a new matching (beside pair_results_invalidate). */
+typedef struct
+{
+  uint32_t *d_node_words; /* per node (rank * max_nb_sift_per_buffer + row): its track number */
+  uint8_t *d_records;     /* the vksift_ext_Track records */
+  uint32_t *d_stats, *h_stats; /* the four words of vksift_ext_TrackStats, posted */
+  uint32_t *d_scratch;    /* parent, length, buffer count and presence words (vksift_hip_tracks_scratch_u32) */
+  size_t scratch_u32;
+  uint32_t *h_tab, *d_tab; /* {rank A, rank B} per slot of batch_cap, then {gpu_buffer_id, word of d_match_n} per rank: filled in pinned memory, copied to the
+                            * device in front of the launches (every edge reads its pair's and its buffers' entries) */
+  uint32_t *rank_of;      /* per SIFT buffer: its rank in the last build, VKSIFT_EXT_NO_TRACK outside the pair list */
+  uint32_t *count_word;   /* per rank: the word of h_match_n / d_match_n that holds the buffer's row count */
+  uint32_t cap_bufs, nbufs, max_rows;
+  bool valid, tab_pending;
+} TrackResults;
 
 typedef struct
 {
@@ -237,6 +255,8 @@ struct vksift_Instance_T
   uint32_t *h_gtab;         /* mapped pinned memory read by the launches: a pair table (pair_tables), then 9 floats per slot of supplied models and
                              * a word 1 per slot */
   bool gtab_pending;
+  /* feature tracks over the pair list (vksift_ext_buildTracks, vksift_tracks.c) */
+  TrackResults tracks;
 
   /* ---- caller-supplied keypoints (vksift_describe.c); everything allocated by the first describe call */
   uint8_t *d_kps, *h_kps;        /* one call's keypoint offsets (count + 1 words, padded to 256 bytes) and, behind them, its keypoints: pinned staging and the device copy */
@@ -291,6 +311,7 @@ struct vksift_Instance_T
   vksift_hip_event dl_ev[VKSIFT_DL_CHUNKS]; /* the packed copy arrives in pieces (created by the first one) */
   vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab (created by the first verification) */
   vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created by the first guided matching) */
+  vksift_hip_event ev_ttab; /* the last track build has copied tracks.h_tab (created by the first build) */
   vksift_hip_event ev_kps;  /* the last describe call's copy has read h_kps (created by the first describe call) */
   bool desc_start_valid, input_free_valid, staging_pending, kps_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];

@@ -185,6 +185,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
   if (inst->desc_start_valid && vksift_hip_tune_get(VKSIFT_TUNE_PYR_GATE) == 1)
     vksift_hip_event_record(inst->ev_desc_start, inst->stream); /* experiment: the next scale-space behind this matching, not beside it */
   pair_results_invalidate(inst);
+  inst->tracks.valid = false; /* tracks are built from the pairs of a matching (vksift_tracks.c) */
   inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
   if (filter)
   {
