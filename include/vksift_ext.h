@@ -32,7 +32,14 @@ extern "C"
 
   /* 2-NN matching of `count` buffer pairs (A[i], B[i]) in one launch sequence; count <= batch capacity.
    * Same asynchronous contract and error behaviour as vksift_matchFeatures; pair 0 is also what
-   * vksift_getMatchesNumber / vksift_downloadMatches return. */
+   * vksift_getMatchesNumber / vksift_downloadMatches return.
+   * A call that fails with VKSIFT_VULKAN_ERROR (here, and in every stage queued behind a matching: filtered matching, verification, refit,
+   * guided matching, tracks): a result whose device storage a launch of the failed call had begun to overwrite is refused by all its
+   * accessors (VKSIFT_INVALID_INPUT_ERROR), together with what was computed from it — after a failed matching every per-pair result and the
+   * tracks, after a failed verification its model's records, masks and refit —, until a later call has succeeded; every other result stays
+   * served and unchanged; the buffers of the pairs stay busy (vksift_isBufferAvailable) until what was queued has run.
+   * vksift_downloadMatches and vksift_ext_downloadMatchesBatch(0) keep the reference's contract, which knows no refusal: after a failed
+   * matching they return as many records as vksift_getMatchesNumber counts, of unspecified content. */
   VKSIFT_EXPORT void vksift_ext_matchFeaturesBatch(vksift_Instance instance, uint32_t count, const uint32_t *gpu_buffer_ids_A,
                                                    const uint32_t *gpu_buffer_ids_B);
   VKSIFT_EXPORT uint32_t vksift_ext_getMatchesNumberBatch(vksift_Instance instance, uint32_t pair);
@@ -412,7 +419,10 @@ extern "C"
   VKSIFT_EXPORT vksift_Result vksift_ext_pinHostMemory(void *ptr, size_t bytes);
   VKSIFT_EXPORT vksift_Result vksift_ext_unpinHostMemory(void *ptr);
 
-  /* Time (ms) of the last matching pipeline (gather + 2-NN kernel), HIP events; needs profiling on. */
+  /* Time (ms) of the last matching pipeline (gather + 2-NN kernel), HIP events; needs profiling on.
+   * This getter and every other stage getter (vksift_ext_getVerifyTime ... vksift_ext_getTracksTime, vksift_ext_getRootSiftTime) waits for the
+   * instance's streams before it reads its events: if that wait fails the error callback fires with VKSIFT_VULKAN_ERROR and the getter returns -1.
+   * A stage whose interval could not be closed (the end event's record failed: the stage itself reports VKSIFT_VULKAN_ERROR) has no time: -1. */
   VKSIFT_EXPORT float vksift_ext_getMatchTime(vksift_Instance instance);
 
   /* Copy the descriptors of a SIFT buffer, in download order, as dense 128-byte rows into caller

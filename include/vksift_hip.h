@@ -560,6 +560,8 @@ extern "C"
    * {nsec, off[16], cap[16]}, whose stored counts min(found, cap) are read on the device (found_base + buffer*found_buf_stride) like vksift_hip_gather_sections
    * does. slot_tab / layouts are read by the kernel (device or mapped pinned memory). A record naming a row its buffer does not hold gives a NaN
    * correspondence. One launch whatever nslots.
+   * READ of the two tables: slot_tab[0 .. 4 nslots), and of layouts the entries the slots' layout words name — one per distinct section table, so at
+   * most 2 nslots entries of 33 words: a caller that provides 2 nslots * 33 words behind `layouts` covers every list (vksift_hip_gather_xy likewise).
    * Sections of a table at or beyond found_buf_stride count as empty and their counters are not read (a found_buf_stride below nsec cuts the
    * table). A row >= the buffer's total makes THAT side's two floats the quiet NaN 0x7fc00000; the other side is gathered as usual. WRITTEN:
    * records 0 .. min(filtered_n[i], max_n) - 1 of every slot, nothing else. hipErrorInvalidValue, nothing launched: nslots 0,
@@ -681,7 +683,9 @@ extern "C"
    * order of their smallest node. tracks + 16*t: {gpu_buffer_id, row} of the smallest node, length (nodes), nb_buffers (distinct buffers among them);
    * node_words[index]: the track number of every stored row, 0xFFFFFFFF without one; stats: {tracks, tracks with length > nb_buffers, sum of the lengths,
    * edges taken (edges inside one buffer, on one node and duplicates included)}. Deterministic: every output depends on the graph alone.
-   * tests/np_tracks.py restates it. slot_tab, buf_tab and rows_dev are read by the launches (device-accessible memory). scratch: scratch_u32 >=
+   * tests/np_tracks.py restates it. slot_tab, buf_tab and rows_dev are read by the launches (device-accessible memory): slot_tab
+   * at the two words of each of the nslots strides, buf_tab[0 .. 2 nbufs), rows_dev at the nbufs words buf_tab names and nowhere else (its extent is the
+   * caller's: the launch's own scalars do not bound it). scratch: scratch_u32 >=
    * vksift_hip_tracks_scratch_u32(nbufs, node_stride) words, 8-byte aligned, need not be initialised, contents unspecified afterwards (only the words of
    * stored rows and of the launch's blocks are touched). WRITTEN: the four words of stats, records 0 .. stats[0]-1 of tracks, node_words of the stored rows, the
    * scratch, nothing else. hipErrorInvalidValue, nothing launched: nslots, nbufs, max_n or max_rows 0, max_rows above node_stride, nbufs * node_stride above

@@ -6,8 +6,20 @@
  *
  *   create BC MAX_PX MAX_FEATS NBUF UPSAMPLE FP16   vksift_loadVulkan + vksift_createInstance (BC 1) / vksift_ext_createInstanceBatched
  *   detect W H BUF | batch W H FIRST COUNT | batchdev W H FIRST COUNT WHICH (device input block 0 or 1)
- *   num BUF | download BUF | avail BUF | match A B | prof 0|1 | describe W H BUF N | destroy
- *   busy 0|1 | drain | covered 0|1 | counts V | failin K | ledger
+ *   num BUF | download BUF | avail BUF | match A B | prof 0|1 | describe W H BUF N [GIVEN] | destroy
+ *   busy 0|1 | drain | covered 0|1 | counts V | failin K [J] | ledger
+ * and, for the stages behind a matching (tests/test_pair_plan.py):
+ *   bmatch N A0 B0 A1 B1 ... | filtered CROSS N A0 B0 ...   vksift_ext_matchFeaturesBatch / vksift_ext_matchFeaturesFiltered (ratio 0.8)
+ *   pmatch A B                                               vksift_matchFeatures alone (`match` also reads the result)
+ *   mnum PAIR | mdl PAIR | mnum0 | mdl0                      the matching's number and download accessors, batch and plain
+ *   verify M NH SEED | refine M ROUNDS | guided M SUPPLIED CROSS | tracks SOURCE      (M: 0 homography, 1 fundamental matrix; threshold 2.5)
+ *   acc K PAIR                                               accessor K of `accnames` (the order of tests/api_model.py: ACCESSORS)
+ *   tstats | tdl | tfeat BUF                                 the tracks' accessors
+ *   budget FIRST COUNT MAX | grid FIRST COUNT MAX W H COLS ROWS | rootsift FIRST COUNT
+ *   upload BUF N | export BUF | times | accnames
+ *   roles 0|1 | late 0|1 | countallocs 0|1                   the device's switches
+ * An accessor's "<" line carries served (the call reported no error), a hash of everything it returned and poison (1: the device's poison word
+ * is among it: the accessor read before it waited). The error callback's code is logged as "error CODE".
  */
 #include "vksift_ext.h"
 #include "vulkansift/vulkansift.h"
@@ -20,7 +32,9 @@
 /* sim_device.c */
 extern int sim_busy_mode, sim_covered;
 extern uint32_t sim_counts;
-extern uint64_t sim_fail_in, sim_violations;
+extern uint64_t sim_fail_in, sim_fail_then, sim_violations;
+extern int sim_roles, sim_late_posts, sim_count_allocs;
+#define SIM_POISON 0xD0D0D0D0u
 void sim_drain(void);
 void sim_api_return(void);
 void sim_report_ledger(void);
@@ -31,8 +45,26 @@ void vksift_hip_free(void *p);
 
 static vksift_Instance inst;
 static vksift_Config cfg;
-static uint8_t *d_in[2];
+static uint8_t *d_in[2], *d_out;
 static uint32_t errors;
+
+/* what an accessor returned: FNV-1a of the bytes, and whether the device's poison word is among them */
+static void report(const char *cmd, const void *p, size_t bytes, uint32_t n, uint32_t errors_before)
+{
+  uint64_t h = 0xcbf29ce484222325ull;
+  bool poison = n == SIM_POISON;
+  for (size_t i = 0; i < bytes; i++)
+    h = (h ^ ((const uint8_t *)p)[i]) * 0x100000001b3ull;
+  for (size_t i = 0; i + 4 <= bytes && !poison; i += 4)
+  {
+    uint32_t w;
+    memcpy(&w, (const uint8_t *)p + i, 4);
+    poison = w == SIM_POISON;
+  }
+  printf("< %s served=%d n=%u hash=%llu poison=%d errors=%u\n", cmd, errors == errors_before, n, (unsigned long long)(h >> 1), poison, errors - errors_before);
+}
+
+static const char *const acc_names[12] = {"filtered n", "filtered", "H", "H mask", "F", "F mask", "refined H", "refined H mask", "refined F", "refined F mask", "guided n", "guided"};
 
 static void on_error(vksift_Result r)
 {
@@ -48,13 +80,24 @@ static uint8_t *image(uint32_t w, uint32_t h, uint32_t salt)
   return p;
 }
 
+#define MAX_ARGS 1100
 static int run(char *line)
 {
-  unsigned long long a[8] = {0};
+  static unsigned long long a[MAX_ARGS];
   char cmd[32] = "";
-  const int n = sscanf(line, "%31s %llu %llu %llu %llu %llu %llu %llu", cmd, &a[0], &a[1], &a[2], &a[3], &a[4], &a[5], &a[6]);
+  int n = sscanf(line, "%31s", cmd), at = 0;
   if (n < 1)
     return 0;
+  memset(a, 0, sizeof(a));
+  sscanf(line, "%*s%n", &at);
+  for (char *q = line + at, *end; n - 1 < MAX_ARGS; q = end, n++)
+  {
+    a[n - 1] = strtoull(q, &end, 10);
+    if (end == q)
+      break;
+  }
+  const uint32_t nargs = (uint32_t)(n - 1);
+  (void)nargs;
   printf("> %s\n", line);
   const uint32_t errors_before = errors;
   if (!strcmp(cmd, "create"))
@@ -134,7 +177,7 @@ static int run(char *line)
     vksift_ext_Keypoint *kp = (vksift_ext_Keypoint *)calloc(nk ? nk : 1, sizeof(*kp));
     for (uint32_t i = 0; i < nk; i++)
       kp[i].x = (float)((i * 7u) % w), kp[i].y = (float)((i * 5u) % h), kp[i].sigma = 2.0f, kp[i].response = 1.0f;
-    vksift_ext_describeKeypoints(inst, img, w, h, kp, nk, (uint32_t)a[2], VKSIFT_EXT_DESCRIBE_ORIENT);
+    vksift_ext_describeKeypoints(inst, img, w, h, kp, nk, (uint32_t)a[2], a[4] ? VKSIFT_EXT_DESCRIBE_GIVEN : VKSIFT_EXT_DESCRIBE_ORIENT);
     free(kp);
     free(img);
     printf("< describe errors=%u\n", errors - errors_before);
@@ -143,9 +186,173 @@ static int run(char *line)
   {
     for (int i = 0; i < 2; i++)
       vksift_hip_free(d_in[i]), d_in[i] = NULL;
+    vksift_hip_free(d_out), d_out = NULL;
     vksift_destroyInstance(&inst);
     printf("< destroy\n");
   }
+  else if (!strcmp(cmd, "bmatch") || !strcmp(cmd, "filtered"))
+  {
+    const bool filt = cmd[0] == 'f';
+    const uint32_t count = (uint32_t)a[filt ? 1 : 0];
+    uint32_t *ids = (uint32_t *)malloc(sizeof(uint32_t) * 2u * (count ? count : 1));
+    for (uint32_t i = 0; i < count; i++)
+      ids[i] = (uint32_t)a[(filt ? 2 : 1) + 2u * i], ids[count + i] = (uint32_t)a[(filt ? 2 : 1) + 2u * i + 1u];
+    if (filt)
+      vksift_ext_matchFeaturesFiltered(inst, count, ids, ids + count, 0.8f, a[0] != 0);
+    else
+      vksift_ext_matchFeaturesBatch(inst, count, ids, ids + count);
+    free(ids); /* the call has copied them */
+    printf("< %s errors=%u\n", cmd, errors - errors_before);
+  }
+  else if (!strcmp(cmd, "pmatch"))
+  {
+    vksift_matchFeatures(inst, (uint32_t)a[0], (uint32_t)a[1]);
+    printf("< pmatch errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "mnum") || !strcmp(cmd, "mnum0"))
+  {
+    const uint32_t k = cmd[4] ? vksift_getMatchesNumber(inst) : vksift_ext_getMatchesNumberBatch(inst, (uint32_t)a[0]);
+    report(cmd, &k, 4, k, errors_before);
+  }
+  else if (!strcmp(cmd, "mdl") || !strcmp(cmd, "mdl0"))
+  {
+    const size_t bytes = (size_t)cfg.max_nb_sift_per_buffer * sizeof(vksift_Match_2NN);
+    vksift_Match_2NN *m = (vksift_Match_2NN *)calloc(1, bytes);
+    if (cmd[3])
+      vksift_downloadMatches(inst, m);
+    else
+      vksift_ext_downloadMatchesBatch(inst, (uint32_t)a[0], m);
+    report(cmd, m, bytes, 0, errors_before);
+    free(m);
+  }
+  else if (!strcmp(cmd, "verify"))
+  {
+    if (a[0])
+      vksift_ext_verifyFundamental(inst, (uint32_t)a[1], 2.5f, a[2]);
+    else
+      vksift_ext_verifyHomography(inst, (uint32_t)a[1], 2.5f, a[2]);
+    printf("< verify errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "refine"))
+  {
+    if (a[0])
+      vksift_ext_refineFundamental(inst, (uint32_t)a[1], 2.5f);
+    else
+      vksift_ext_refineHomography(inst, (uint32_t)a[1], 2.5f);
+    printf("< refine errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "guided"))
+  {
+    const uint32_t cap = cfg.sift_buffer_count * 64u; /* (more pairs than any instance of the tests holds) */
+    float *models = (float *)calloc((size_t)9u * cap, sizeof(float));
+    for (uint32_t i = 0; i < cap; i++)
+      models[9u * i] = models[9u * i + 4u] = models[9u * i + 8u] = 1.f;
+    vksift_ext_matchFeaturesGuided(inst, a[0] ? VKSIFT_EXT_GUIDE_FUNDAMENTAL : VKSIFT_EXT_GUIDE_HOMOGRAPHY, a[1] ? models : NULL, 2.5f, 0.8f, 300.f, a[2] != 0);
+    free(models); /* the call has copied them */
+    printf("< guided errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "tracks"))
+  {
+    vksift_ext_buildTracks(inst, (uint32_t)a[0]);
+    printf("< tracks errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "acc"))
+  {
+    const size_t bytes = (size_t)cfg.max_nb_sift_per_buffer * 16u + 64u;
+    uint8_t *out = (uint8_t *)calloc(1, bytes);
+    const uint32_t pair = (uint32_t)a[1];
+    uint32_t k = 0;
+    switch (a[0])
+    {
+    case 0: k = vksift_ext_getFilteredMatchesNumber(inst, pair), memcpy(out, &k, 4); break;
+    case 1: vksift_ext_downloadFilteredMatches(inst, pair, (vksift_ext_FilteredMatch *)out); break;
+    case 2: vksift_ext_getHomography(inst, pair, (vksift_ext_Homography *)out); break;
+    case 3: vksift_ext_downloadInlierMask(inst, pair, out); break;
+    case 4: vksift_ext_getFundamental(inst, pair, (vksift_ext_Fundamental *)out); break;
+    case 5: vksift_ext_downloadFundamentalInlierMask(inst, pair, out); break;
+    case 6: vksift_ext_getRefinedHomography(inst, pair, (vksift_ext_RefinedHomography *)out); break;
+    case 7: vksift_ext_downloadRefinedInlierMask(inst, pair, out); break;
+    case 8: vksift_ext_getRefinedFundamental(inst, pair, (vksift_ext_RefinedFundamental *)out); break;
+    case 9: vksift_ext_downloadRefinedFundamentalInlierMask(inst, pair, out); break;
+    case 10: k = vksift_ext_getGuidedMatchesNumber(inst, pair), memcpy(out, &k, 4); break;
+    case 11: vksift_ext_downloadGuidedMatches(inst, pair, (vksift_ext_FilteredMatch *)out); break;
+    default: free(out); return 2;
+    }
+    report("acc", out, bytes, k, errors_before);
+    free(out);
+  }
+  else if (!strcmp(cmd, "accnames"))
+  {
+    for (int i = 0; i < 12; i++)
+      printf("accname %d %s\n", i, acc_names[i]);
+  }
+  else if (!strcmp(cmd, "tstats"))
+  {
+    vksift_ext_TrackStats st = {0};
+    vksift_ext_getTrackStats(inst, &st);
+    report("tstats", &st, sizeof(st), st.nb_tracks, errors_before);
+  }
+  else if (!strcmp(cmd, "tdl") || !strcmp(cmd, "tfeat"))
+  {
+    const size_t bytes = (size_t)cfg.max_nb_sift_per_buffer * 16u + 64u; /* (the device reports `counts` tracks: a handful) */
+    uint8_t *out = (uint8_t *)calloc(1, bytes);
+    if (cmd[1] == 'd')
+      vksift_ext_downloadTracks(inst, (vksift_ext_Track *)out);
+    else
+      vksift_ext_downloadFeatureTracks(inst, (uint32_t)a[0], (uint32_t *)out);
+    report(cmd, out, bytes, 0, errors_before);
+    free(out);
+  }
+  else if (!strcmp(cmd, "budget"))
+  {
+    vksift_ext_keepStrongestFeatures(inst, (uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2]);
+    printf("< budget errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "grid"))
+  {
+    vksift_ext_keepStrongestFeaturesGrid(inst, (uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2], (uint32_t)a[3], (uint32_t)a[4], (uint32_t)a[5], (uint32_t)a[6]);
+    printf("< grid errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "rootsift"))
+  {
+    vksift_ext_convertToRootSift(inst, (uint32_t)a[0], (uint32_t)a[1]);
+    printf("< rootsift errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "upload"))
+  {
+    vksift_Feature *f = (vksift_Feature *)calloc(a[1] ? a[1] : 1, sizeof(vksift_Feature));
+    vksift_uploadFeatures(inst, f, (uint32_t)a[1], (uint32_t)a[0]);
+    free(f); /* the call has copied them */
+    printf("< upload errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "export"))
+  {
+    if (!d_out) /* (by the first export: the ledger of a script without one is what it was) */
+    {
+      const int counted = sim_count_allocs;
+      sim_count_allocs = 0; /* (the harness's own block: not a call of the entry) */
+      d_out = (uint8_t *)vksift_hip_malloc((size_t)cfg.max_nb_sift_per_buffer * 128u);
+      sim_count_allocs = counted;
+    }
+    const uint32_t k = vksift_ext_exportDescriptorsDevice(inst, (uint32_t)a[0], d_out);
+    report("export", &k, 4, k, errors_before);
+  }
+  else if (!strcmp(cmd, "times"))
+  {
+    const float t[9] = {vksift_ext_getMatchTime(inst),           vksift_ext_getVerifyTime(inst),      vksift_ext_getRefineTime(inst),
+                        vksift_ext_getRefineFundamentalTime(inst), vksift_ext_getGuidedMatchTime(inst), vksift_ext_getTracksTime(inst),
+                        vksift_ext_getKeepStrongestTime(inst),   vksift_ext_getKeepStrongestGridTime(inst), vksift_ext_getRootSiftTime(inst)};
+    printf("< times");
+    for (int i = 0; i < 9; i++)
+      printf(" t%d=%d", i, (int)t[i]);
+    printf(" errors=%u\n", errors - errors_before);
+  }
+  else if (!strcmp(cmd, "roles"))
+    sim_roles = (int)a[0];
+  else if (!strcmp(cmd, "late"))
+    sim_late_posts = (int)a[0];
+  else if (!strcmp(cmd, "countallocs"))
+    sim_count_allocs = (int)a[0];
   else if (!strcmp(cmd, "busy"))
     sim_busy_mode = (int)a[0];
   else if (!strcmp(cmd, "drain"))
@@ -154,8 +361,8 @@ static int run(char *line)
     sim_covered = (int)a[0];
   else if (!strcmp(cmd, "counts"))
     sim_counts = (uint32_t)a[0];
-  else if (!strcmp(cmd, "failin"))
-    sim_fail_in = a[0];
+  else if (!strcmp(cmd, "failin")) /* failin K [J]: the K-th counted call fails, and the J-th behind it */
+    sim_fail_in = a[0], sim_fail_then = a[1];
   else if (!strcmp(cmd, "ledger"))
     sim_report_ledger();
   else
@@ -170,7 +377,7 @@ static int run(char *line)
 
 int main(int argc, char **argv)
 {
-  char line[256];
+  static char line[1 << 15];
   int rc = 0;
   setvbuf(stdout, NULL, _IOFBF, 1 << 16);
   if (argc > 1)

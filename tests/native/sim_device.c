@@ -31,7 +31,26 @@
  *      open when an API call returns (sim_api_return);
  *   C3 no exec launched or destroyed after its destruction, none destroyed on a busy GPU before the host has seen its last launch complete
  *      (a wait for a later event or a sync of its stream); a clean ledger after vksift_destroyInstance (sim_report_ledger).
- * Fault injection: sim_fail_in = k makes the k-th counted call from now (every line that starts with "#") return an error.
+ * Fault injection: sim_fail_in = k makes the k-th counted call from now (every line that starts with "#") return an error; sim_fail_then = j, set
+ * with it, makes the j-th counted call behind that failure fail as well (an error exit whose own device call fails).
+ *
+ * The stages behind a matching (tests/test_pair_plan.py). Nothing below changes a log line or a digest unless its switch is set:
+ *   Pointer arguments by role (sim_roles). For the copies and for the launchers of the matcher, the in-place passes and the pair stages, the
+ *      operation's line is followed by "args NAME arg=bN+OFFSET:r|w:EXTENT ...": per pointer argument the ledger block, the offset, the role
+ *      (`w` iff the prototype of include/vksift_hip.h has no `const`) and the bytes it may touch (0: the header states none). "-" : not a
+ *      ledger address (NULL, caller memory).
+ *   C4 extents (sim_roles). The extent is derived from the launch's own scalar arguments as include/vksift_hip.h words it (stride x slots,
+ *      words x slots x 4, max_n x element, scratch_u32 x 4, nbufs x node_stride x 4, tracks_cap x 16 ...); offset + extent beyond the block is
+ *      a VIOLATION, and so is, with more than one slot, a stride below what a slot may hold (max_n x element).
+ *   C5 pinned inputs stay put (sim_roles, busy mode). An operation with a read argument inside a pinned block stores a hash of the bytes it
+ *      will read; the hash is checked when the host first sees the operation complete (a synchronisation of its stream or of a later event
+ *      on it, of a stream that waited for it, or sim_drain). A difference is a VIOLATION: the host rewrote a table in flight.
+ *   Late posts (sim_late_posts, busy mode). vksift_hip_post_words and the device-to-host copies fill their destination with SIM_POISON when
+ *      issued and with the real value only at the synchronisation that covers them: an accessor that returns the poison read before it
+ *      waited. A pitched two-dimensional copy is filled row by row, the gaps between its rows left alone.
+ *   Counted allocations (sim_count_allocs). vksift_hip_malloc, vksift_hip_host_malloc and vksift_hip_event_create are counted calls: fault
+ *      injection can refuse them.
+ *   Balanced ranges. vksift_hip_range_push / _pop are balanced whenever an API call returns (sim_api_return; C2).
  */
 #include "vksift_hip.h"
 
@@ -61,8 +80,15 @@ int sim_busy_mode;           /* 1: events stay busy until synchronised or draine
 int sim_covered = 1;         /* answer of the optional launchers: 1 launched, 0 "not covered" (-1) */
 uint32_t sim_counts;         /* value the counter postings write */
 uint64_t sim_fail_in;        /* 1: the next counted call fails */
+uint64_t sim_fail_then;      /* j: ... and the j-th counted call behind that failure too (0: none) */
 uint64_t sim_violations;
+int sim_roles;               /* 1: "args" lines, C4, and (busy mode) C5 */
+int sim_late_posts;          /* 1 (busy mode): postings and device-to-host copies arrive at the synchronisation that covers them */
+int sim_count_allocs;        /* 1: allocations and event creations are counted calls */
+#define SIM_POISON 0xD0D0D0D0u
 static uint64_t call_no;
+static int range_depth;
+static bool counted(const char *name);
 
 /* ------------------------------------------------------------------------------------------------ ledger */
 typedef struct
@@ -107,6 +133,8 @@ typedef struct
   uint32_t blk[MAX_REC_BLOCKS];
   uint32_t *fill; /* effect when it is issued or replayed: the fill_bytes bytes at fill become sim_counts per word (fill_counts) or 0 */
   size_t fill_bytes;
+  size_t fill_pitch; /* 0: one run of fill_bytes; else fill_rows rows of fill_bytes, fill_pitch apart (a pitched copy: the gaps stay as they are) */
+  size_t fill_rows;
   bool fill_counts;
 } Record;
 typedef struct
@@ -144,6 +172,8 @@ static void *acquire(char kind, size_t bytes)
 {
   if (n_blocks == MAX_BLOCKS)
     return NULL;
+  if (sim_count_allocs && counted("alloc"))
+    return NULL;
   Block *b = &blocks[n_blocks];
   if (kind == 'D')
   {
@@ -159,6 +189,8 @@ static void *acquire(char kind, size_t bytes)
     b->base = (uintptr_t)p;
   }
   b->bytes = bytes, b->kind = kind, b->live = true;
+  if (sim_count_allocs)
+    printf("#%llu ", (unsigned long long)call_no);
   printf("alloc %c b%u %zu\n", kind, n_blocks, bytes);
   n_blocks++;
   return (void *)b->base;
@@ -197,13 +229,24 @@ int vksift_hip_device_count(void) { return 1; }
 int vksift_hip_device_name(int idx, char *out256) { return (void)idx, snprintf(out256, 256, "simulated device"), 0; }
 int vksift_hip_set_device(int idx) { return idx == 0 ? 0 : 1; }
 const char *vksift_hip_error_string(int err) { return err == SIM_ERR ? "injected failure" : "simulated error"; }
-void vksift_hip_range_push(const char *name) { (void)name; }
-void vksift_hip_range_pop(void) {}
+void vksift_hip_range_push(const char *name) { (void)name, range_depth++; }
+void vksift_hip_range_pop(void)
+{
+  if (--range_depth < 0)
+  {
+    sim_violations++, range_depth = 0;
+    printf("VIOLATION C2 a range is popped that was not pushed\n");
+  }
+}
 int vksift_hip_tune_get(int knob) { return (void)knob, 0; }
 int vksift_hip_blur_form(vksift_hip_Plane src, vksift_hip_Plane dst, uint32_t ntaps, uint32_t batch) { return (void)src, (void)dst, (void)ntaps, (void)batch, sim_covered ? 1 : 0; }
 size_t vksift_hip_match_scratch_u32(uint32_t na, uint32_t nb) { return VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb); }
 size_t vksift_hip_ransac_scratch_u32(uint32_t nslots, uint32_t nb_hypotheses) { return 64u + (size_t)nslots * nb_hypotheses; }
 size_t vksift_hip_guided_scratch_u32(uint32_t nslots, uint32_t max_n) { return (size_t)nslots * max_n * 8u; }
+size_t vksift_hip_tracks_scratch_u32(uint32_t nbufs, uint32_t node_stride)
+{
+  return (size_t)(5u * (uint64_t)nbufs * node_stride + 3u * (uint64_t)nbufs * (((uint64_t)node_stride + 255u) / 256u) + 64u + 2u);
+}
 
 /* ------------------------------------------------------------------------------------------------ streams and events */
 static int stream_id(vksift_hip_stream s, const char *who)
@@ -233,6 +276,7 @@ static bool counted(const char *name)
   if (sim_fail_in && --sim_fail_in == 0)
   {
     printf("#%llu FAIL %s\n", (unsigned long long)call_no, name);
+    sim_fail_in = sim_fail_then, sim_fail_then = 0;
     cap_invalid = open_cap != 0;
     return true;
   }
@@ -257,6 +301,12 @@ vksift_hip_event vksift_hip_event_create(void)
 {
   if (n_events == MAX_EVENTS)
     return NULL;
+  if (sim_count_allocs)
+  {
+    if (counted("event_create"))
+      return NULL;
+    printf("#%llu evcreate e%u\n", (unsigned long long)call_no, n_events);
+  }
   memset(&events[n_events], 0, sizeof(Event));
   events[n_events].live = true;
   return &events[n_events++];
@@ -268,8 +318,111 @@ void vksift_hip_event_destroy(vksift_hip_event e)
     events[i].live = false;
 }
 
+/* What waits for the host to SEE an operation complete (sim_roles, sim_late_posts; busy mode): the hash of a pinned input (C5) and the real
+ * value of a late post, per stream position; and the stream waits, through which seeing one stream pass a position shows another's. */
+typedef struct
+{
+  int stream;
+  uint64_t seq;
+  char kind; /* c: check the hash; f: fill; 0: done */
+  void *p;
+  size_t n;
+  uint64_t hash;
+  bool counts;
+  char name[28];
+  size_t pitch, rows; /* a fill of `rows` rows of n bytes (pitch 0: one run) */
+} Pending;
+typedef struct
+{
+  int stream, on;
+  uint64_t at, upto;
+} Dep;
+static Pending *pend;
+static Dep *deps;
+static uint32_t n_pend, room_pend, n_deps, room_deps;
+
+static uint64_t hash_bytes(const void *p, size_t n)
+{
+  uint64_t h = 0xcbf29ce484222325ull;
+  for (size_t i = 0; i < n; i++)
+    h = (h ^ ((const uint8_t *)p)[i]) * 0x100000001b3ull;
+  return h;
+}
+static int block_of(uintptr_t v);
+static void fill_run(uint32_t *dst, size_t bytes, bool counts, uint32_t poison);
+static void fill_words(uint32_t *dst, size_t bytes, size_t pitch, size_t rows, bool counts, uint32_t poison)
+{
+  const int bi = block_of((uintptr_t)dst);
+  if (bi >= 0 && !blocks[bi].live)
+    return; /* (C1 has reported it) */
+  if (!pitch)
+    fill_run(dst, bytes, counts, poison);
+  else
+    for (size_t r = 0; r < rows; r++)
+      fill_run((uint32_t *)((uint8_t *)dst + r * pitch), bytes, counts, poison);
+}
+static void fill_run(uint32_t *dst, size_t bytes, bool counts, uint32_t poison)
+{
+  if (poison || counts)
+  {
+    for (size_t i = 0; i < bytes / 4; i++)
+      dst[i] = poison ? poison : sim_counts;
+    if (poison)
+      memset((uint8_t *)dst + (bytes & ~(size_t)3), 0xD0, bytes & 3);
+  }
+  else
+    memset(dst, 0, bytes);
+}
+static void add_pending(Pending q)
+{
+  if (n_pend == room_pend)
+    room_pend = room_pend ? 2 * room_pend : 256, pend = (Pending *)realloc(pend, room_pend * sizeof(Pending));
+  pend[n_pend++] = q;
+}
+static int seen_depth;
+static void seen(int s, uint64_t upto)
+{
+  seen_depth++;
+  for (uint32_t i = 0; i < n_pend; i++)
+  {
+    Pending *q = &pend[i];
+    if (!q->kind || q->stream != s || q->seq > upto)
+      continue;
+    const int bi = block_of((uintptr_t)q->p);
+    if (q->kind == 'c' && bi >= 0 && blocks[bi].live && hash_bytes(q->p, q->n) != q->hash)
+    {
+      sim_violations++;
+      printf("VIOLATION C5 the pinned input of %s (b%d+%zu, %zu bytes) was rewritten before the host saw it complete\n", q->name, bi,
+             (size_t)((uintptr_t)q->p - blocks[bi].base), q->n);
+    }
+    if (q->kind == 'f')
+      fill_words((uint32_t *)q->p, q->n, q->pitch, q->rows, q->counts, 0);
+    q->kind = 0;
+  }
+  for (uint32_t i = 0; i < n_deps; i++)
+    if (deps[i].stream == s && deps[i].at <= upto && deps[i].on >= 0)
+    {
+      const int on = deps[i].on;
+      deps[i].on = -1;
+      seen(on, deps[i].upto);
+    }
+  if (--seen_depth)
+    return;
+  uint32_t k = 0; /* compact */
+  for (uint32_t i = 0; i < n_pend; i++)
+    if (pend[i].kind)
+      pend[k++] = pend[i];
+  n_pend = k;
+  k = 0;
+  for (uint32_t i = 0; i < n_deps; i++)
+    if (deps[i].on >= 0)
+      deps[k++] = deps[i];
+  n_deps = k;
+}
+
 static void complete_stream(int s, uint64_t upto)
 {
+  seen(s, upto);
   if (upto > streams[s].done_upto)
     streams[s].done_upto = upto;
   for (uint32_t i = 0; i < n_events; i++)
@@ -311,6 +464,12 @@ int vksift_hip_stream_wait_event(vksift_hip_stream s, vksift_hip_event e)
   else if (!ev->cap && streams[si].cap && ev->recorded && ev->busy)
     printf("note s%d (capturing) waits on e%d recorded outside the capture\n", si, ei);
   streams[si].seq++;
+  if ((sim_roles || sim_late_posts) && sim_busy_mode && ev->recorded && ev->cap == 0 && streams[si].cap == 0)
+  {
+    if (n_deps == room_deps)
+      room_deps = room_deps ? 2 * room_deps : 256, deps = (Dep *)realloc(deps, room_deps * sizeof(Dep));
+    deps[n_deps++] = (Dep){si, ev->stream, streams[si].seq, ev->seq};
+  }
   return 0;
 }
 int vksift_hip_stream_sync(vksift_hip_stream s)
@@ -377,7 +536,7 @@ void sim_drain(void)
   for (uint32_t i = 0; i < n_events; i++)
     events[i].busy = false;
   for (uint32_t i = 0; i < n_streams; i++)
-    streams[i].busy = false, streams[i].done_upto = streams[i].seq;
+    seen((int)i, streams[i].seq), streams[i].busy = false, streams[i].done_upto = streams[i].seq;
 }
 
 /* ------------------------------------------------------------------------------------------------ operations */
@@ -453,10 +612,61 @@ static void arg_planes(const vksift_hip_Plane *p, uint32_t n)
     arg_plane(&p[i]);
 }
 
+/* the roles of the operation being recorded (sim_roles): the text of its "args" line, and the pinned inputs to hash (C5) */
+static char roles[2048];
+static size_t roles_n;
+static struct
+{
+  const void *p;
+  size_t n;
+} pinned_in[8];
+static uint32_t n_pinned_in;
+static bool cur_late; /* its effect is a posting or a device-to-host copy (sim_late_posts) */
+
+/* a pointer argument of a role-known operation: digested as P() digests it; role 'r' / 'w', `bytes` it may touch (0: not stated) */
+static void arg_role(const char *arg_name, const void *p, size_t bytes, char role)
+{
+  arg_arr(p, 0);
+  if (!sim_roles)
+    return;
+  const int bi = block_of((uintptr_t)p);
+  if (bi < 0)
+  {
+    roles_n += (size_t)snprintf(roles + roles_n, sizeof(roles) - roles_n, " %s=-:%c:%zu", arg_name, role, bytes);
+    return;
+  }
+  const size_t off = (size_t)((uintptr_t)p - blocks[bi].base);
+  roles_n += (size_t)snprintf(roles + roles_n, sizeof(roles) - roles_n, " %s=b%d+%zu:%c:%zu", arg_name, bi, off, role, bytes);
+  if (roles_n >= sizeof(roles))
+    roles_n = sizeof(roles) - 1;
+  if (off + bytes > blocks[bi].bytes)
+  {
+    sim_violations++;
+    printf("VIOLATION C4 %s %s: %zu bytes from offset %zu of b%d, which holds %zu\n", cur.name, arg_name, bytes, off, bi, blocks[bi].bytes);
+  }
+  else if (role == 'r' && bytes && blocks[bi].kind == 'H' && blocks[bi].live && sim_busy_mode && n_pinned_in < 8)
+    pinned_in[n_pinned_in].p = p, pinned_in[n_pinned_in++].n = bytes;
+}
+/* C4, the other half: with more than one slot, what a slot may hold (max_n x element) fits its stride — what the launchers themselves refuse */
+static void slot_fits(const char *what, uint64_t per_slot, uint64_t stride, uint32_t nslots)
+{
+  if (sim_roles && nslots > 1 && per_slot > stride)
+  {
+    sim_violations++;
+    printf("VIOLATION C4 %s %s: a slot may hold %llu bytes, its stride is %llu\n", cur.name, what, (unsigned long long)per_slot, (unsigned long long)stride);
+  }
+}
+#define FITS(x, per_slot, stride) slot_fits(#x, (uint64_t)(per_slot), (uint64_t)(stride), nslots)
+#define RD(x, bytes) arg_role(#x, x, (size_t)(bytes), 'r')
+#define WR(x, bytes) arg_role(#x, x, (size_t)(bytes), 'w')
+/* words of a strided single-word (or `k`-word) read per slot: the last slot's words end it */
+#define STRIDED(nslots, stride, k) ((nslots) ? (((size_t)(nslots) - 1u) * (size_t)(stride) + (size_t)(k)) * 4u : 0u)
+
 static bool op_begin(const char *name, vksift_hip_stream s)
 {
   const int si = stream_id(s, name);
   memset(&cur, 0, sizeof(cur));
+  roles_n = 0, roles[0] = 0, n_pinned_in = 0, cur_late = false;
   if (counted(name))
     return true;
   snprintf(cur.name, sizeof(cur.name), "%s", name);
@@ -471,7 +681,9 @@ static void run_effect(const Record *r)
   const int bi = block_of((uintptr_t)r->fill);
   if (bi >= 0 && !blocks[bi].live)
     return; /* (C1 has reported it) */
-  if (r->fill_counts)
+  if (r->fill_pitch)
+    fill_words(r->fill, r->fill_bytes, r->fill_pitch, r->fill_rows, r->fill_counts, 0);
+  else if (r->fill_counts)
     for (size_t i = 0; i < r->fill_bytes / 4; i++)
       r->fill[i] = sim_counts;
   else
@@ -507,6 +719,22 @@ static int op_end(void)
   }
   st->busy = sim_busy_mode != 0;
   printf("#%llu op %s s%d %016llx %016llx\n", (unsigned long long)call_no, cur.name, cur.stream, (unsigned long long)cur.digest, (unsigned long long)cur.bounds);
+  if (sim_roles && roles_n)
+    printf("args %s%s\n", cur.name, roles);
+  for (uint32_t i = 0; i < n_pinned_in; i++)
+  {
+    Pending q = {cur.stream, st->seq, 'c', (void *)(uintptr_t)pinned_in[i].p, pinned_in[i].n, hash_bytes(pinned_in[i].p, pinned_in[i].n), false, "", 0, 0};
+    memcpy(q.name, cur.name, sizeof(q.name));
+    add_pending(q);
+  }
+  if (cur_late && cur.fill && sim_late_posts && sim_busy_mode)
+  {
+    Pending q = {cur.stream, st->seq, 'f', cur.fill, cur.fill_bytes, 0, cur.fill_counts, "", cur.fill_pitch, cur.fill_rows};
+    const int bi = block_of((uintptr_t)cur.fill);
+    if (bi < 0 || blocks[bi].live)
+      fill_words(cur.fill, cur.fill_bytes, cur.fill_pitch, cur.fill_rows, false, SIM_POISON), add_pending(q);
+    return 0;
+  }
   run_effect(&cur);
   return 0;
 }
@@ -634,6 +862,15 @@ void sim_api_return(void)
       streams[i].cap = 0;
     open_cap = 0, open_origin = -1;
   }
+  if (range_depth)
+  {
+    sim_violations++;
+    printf("VIOLATION C2 %d profiler ranges are open when the API call returns\n", range_depth);
+    range_depth = 0;
+  }
+  for (uint32_t i = 0; i < n_pend; i++) /* caller memory does not outlive the call: a copy into it that nothing waited for never arrives */
+    if (pend[i].kind == 'f' && block_of((uintptr_t)pend[i].p) < 0)
+      pend[i].kind = 0;
 }
 /* C3: what is still live */
 void sim_report_ledger(void)
@@ -668,6 +905,8 @@ void sim_finish(void)
   for (uint32_t i = 0; i < n_execs; i++)
     free(execs[i].recs);
   free(cap_recs);
+  free(pend), free(deps);
+  pend = NULL, deps = NULL, n_pend = room_pend = n_deps = room_deps = 0;
   cap_recs = NULL, cap_room = cap_n = 0;
   n_blocks = 0;
 }
@@ -676,41 +915,46 @@ void sim_finish(void)
 int vksift_hip_memcpy_h2d(void *dst, const void *src, size_t n, vksift_hip_stream s)
 {
   OP("memcpy_h2d", s);
-  P(dst), P(src), V(n);
+  WR(dst, n), RD(src, n), V(n);
   END;
 }
 int vksift_hip_memcpy_d2h(void *dst, const void *src, size_t n, vksift_hip_stream s)
 {
   OP("memcpy_d2h", s);
-  P(dst), P(src), V(n);
+  WR(dst, n), RD(src, n), V(n);
+  cur_late = true;
   cur.fill = (uint32_t *)dst, cur.fill_bytes = n, cur.fill_counts = false;
   END;
 }
 int vksift_hip_memcpy_d2d(void *dst, const void *src, size_t n, vksift_hip_stream s)
 {
   OP("memcpy_d2d", s);
-  P(dst), P(src), V(n);
+  WR(dst, n), RD(src, n), V(n);
   END;
 }
 int vksift_hip_memcpy2d_d2h(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width_bytes, size_t height, vksift_hip_stream s)
 {
   OP("memcpy2d_d2h", s);
-  P(dst), V(dpitch), P(src), V(spitch), V(width_bytes), V(height);
+  WR(dst, height ? (height - 1u) * dpitch + width_bytes : 0u), V(dpitch), RD(src, height ? (height - 1u) * spitch + width_bytes : 0u), V(spitch), V(width_bytes), V(height);
+  cur_late = true;
   if (dpitch == width_bytes)
     cur.fill = (uint32_t *)dst, cur.fill_bytes = width_bytes * height, cur.fill_counts = false;
+  else if (sim_late_posts) /* (row by row, the gaps untouched; without the switch a pitched copy leaves its destination as it is, as it always did) */
+    cur.fill = (uint32_t *)dst, cur.fill_bytes = width_bytes, cur.fill_pitch = dpitch, cur.fill_rows = height, cur.fill_counts = false;
   END;
 }
 int vksift_hip_post_words(uint32_t *host_mapped_dst, const uint32_t *src, size_t n_words, vksift_hip_stream s)
 {
   OP("post_words", s);
-  P(host_mapped_dst), P(src), V(n_words);
+  WR(host_mapped_dst, 4u * n_words), RD(src, 4u * n_words), V(n_words);
+  cur_late = true;
   cur.fill = host_mapped_dst, cur.fill_bytes = 4 * n_words, cur.fill_counts = true;
   END;
 }
 int vksift_hip_memset(void *dst, int value, size_t n, vksift_hip_stream s)
 {
   OP("memset", s);
-  P(dst), V(value), V(n);
+  WR(dst, n), V(value), V(n);
   END;
 }
 
@@ -863,7 +1107,8 @@ int vksift_hip_filter_matches(const uint8_t *fwd, uint64_t fwd_slot_stride, cons
                               float ratio, uint32_t nslots, uint8_t *out, uint64_t out_slot_stride, uint32_t *out_n, vksift_hip_stream s)
 {
   OP("filter_matches", s);
-  P(fwd), V(fwd_slot_stride), P(rev), V(rev_slot_stride), P(n_fwd), V(n_stride), V(ratio), V(nslots), P(out), V(out_slot_stride), P(out_n);
+  RD(fwd, fwd_slot_stride * nslots), V(fwd_slot_stride), RD(rev, rev ? rev_slot_stride * nslots : 0u), V(rev_slot_stride), RD(n_fwd, STRIDED(nslots, n_stride, 2)), V(n_stride),
+      V(ratio), V(nslots), WR(out, out_slot_stride * nslots), V(out_slot_stride), WR(out_n, 4u * nslots);
   END;
 }
 int vksift_hip_pack_features(const uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, const uint32_t *out_rows, uint32_t nslots, uint32_t nsec,
@@ -871,21 +1116,22 @@ int vksift_hip_pack_features(const uint8_t *feats_base, uint64_t buf_stride, con
                              uint32_t *found_post, vksift_hip_stream s)
 {
   OP("pack_features", s);
-  P(feats_base), V(buf_stride), A(buf_ids, 4u * nslots), A(out_rows, 4u * nslots), V(nslots), V(nsec), A(sec_off, 4u * nsec), A(sec_cap, 4u * nsec), P(found_base),
-      V(found_buf_stride), P(out), T(max_rows), P(found_post);
+  RD(feats_base, 0), V(buf_stride), A(buf_ids, 4u * nslots), A(out_rows, 4u * nslots), V(nslots), V(nsec), A(sec_off, 4u * nsec), A(sec_cap, 4u * nsec), RD(found_base, 0),
+      V(found_buf_stride), WR(out, 0), T(max_rows), WR(found_post, 0);
   END;
 }
-#define SECTION_ARGS                                                                                                                                          \
-  P(feats_base), V(buf_stride), A(buf_ids, 4u * nslots), V(nslots), V(nsec), A(sec_off, 4u * nsec), A(sec_cap, 4u * nsec), A(fixed_counts, 4u * nsec), P(found_base), \
+/* (the records and cache entries are addressed by buffer id: the header states no extent in the launch's own scalars. FEATS / FOUND: the role of the two) */
+#define SECTION_ARGS(FEATS, FOUND)                                                                                                                                 \
+  FEATS(feats_base, 0), V(buf_stride), A(buf_ids, 4u * nslots), V(nslots), V(nsec), A(sec_off, 4u * nsec), A(sec_cap, 4u * nsec), A(fixed_counts, 4u * nsec), FOUND(found_base, 0), \
       V(found_buf_stride)
-#define CACHE_ARGS V(pad_rows_to), P(desc), V(desc_stride), P(norms), V(norm_stride), P(n_out_dev), V(n_stride)
+#define CACHE_ARGS V(pad_rows_to), WR(desc, 0), V(desc_stride), WR(norms, 0), V(norm_stride), WR(n_out_dev, 0), V(n_stride)
 int vksift_hip_gather_sections(const uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, uint32_t nslots, uint32_t nsec, const uint32_t *sec_off,
                                const uint32_t *sec_cap, const uint32_t *fixed_counts, const uint32_t *found_base, uint32_t found_buf_stride, uint32_t max_rows,
                                uint32_t pad_rows_to, uint8_t *desc, uint64_t desc_stride, uint32_t *norms, uint64_t norm_stride, uint32_t *n_out_dev, uint32_t n_stride,
                                vksift_hip_stream s)
 {
   OP("gather_sections", s);
-  SECTION_ARGS, T(max_rows), CACHE_ARGS;
+  SECTION_ARGS(RD, RD), T(max_rows), CACHE_ARGS;
   END;
 }
 int vksift_hip_keep_strongest(uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, uint32_t nslots, uint32_t nsec, const uint32_t *sec_off,
@@ -894,7 +1140,7 @@ int vksift_hip_keep_strongest(uint8_t *feats_base, uint64_t buf_stride, const ui
                               uint32_t n_stride, vksift_hip_stream s)
 {
   OP("keep_strongest", s);
-  SECTION_ARGS, P(found_post), V(max_features), CACHE_ARGS;
+  SECTION_ARGS(WR, WR), WR(found_post, 0), V(max_features), CACHE_ARGS;
   END;
 }
 int vksift_hip_keep_grid(uint8_t *feats_base, uint64_t buf_stride, const uint32_t *buf_ids, uint32_t nslots, uint32_t nsec, const uint32_t *sec_off, const uint32_t *sec_cap,
@@ -903,7 +1149,7 @@ int vksift_hip_keep_grid(uint8_t *feats_base, uint64_t buf_stride, const uint32_
                          uint64_t norm_stride, uint32_t *n_out_dev, uint32_t n_stride, vksift_hip_stream s)
 {
   OP("keep_grid", s);
-  SECTION_ARGS, P(found_post), V(max_features), V(grid_cols), V(grid_rows), A(col_bounds, grid_cols ? 4u * (grid_cols - 1u) : 0u),
+  SECTION_ARGS(WR, WR), WR(found_post, 0), V(max_features), V(grid_cols), V(grid_rows), A(col_bounds, grid_cols ? 4u * (grid_cols - 1u) : 0u),
       A(row_bounds, grid_rows ? 4u * (grid_rows - 1u) : 0u), CACHE_ARGS;
   END;
 }
@@ -913,7 +1159,7 @@ int vksift_hip_root_descriptors(uint8_t *feats_base, uint64_t buf_stride, const 
                                 vksift_hip_stream s)
 {
   OP("root_descriptors", s);
-  SECTION_ARGS, T(max_rows), CACHE_ARGS;
+  SECTION_ARGS(WR, RD), T(max_rows), CACHE_ARGS;
   END;
 }
 int vksift_hip_match_2nn_async(const uint8_t *cache_desc, const uint32_t *cache_norm, const uint32_t *cache_n, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t max_na,
@@ -922,29 +1168,35 @@ int vksift_hip_match_2nn_async(const uint8_t *cache_desc, const uint32_t *cache_
                                vksift_hip_stream s)
 {
   OP("match_2nn_async", s);
-  P(cache_desc), P(cache_norm), P(cache_n), A(ids_a, 4u * nslots), A(ids_b, 4u * nslots), T(max_na), T(max_nb), T(nb_exact), P(redo), P(n_dev), P(matches), V(nslots),
-      V(cache_desc_stride), V(cache_norm_stride), V(redo_slot_stride), V(match_slot_stride), V(n_slot_stride), P(partial_scratch);
+  RD(cache_desc, 0), RD(cache_norm, 0), RD(cache_n, 0), A(ids_a, 4u * nslots), A(ids_b, 4u * nslots), T(max_na), T(max_nb), T(nb_exact), WR(redo, 4u * redo_slot_stride * nslots),
+      WR(n_dev, STRIDED(nslots, n_slot_stride, 2)), WR(matches, match_slot_stride * nslots), V(nslots), V(cache_desc_stride), V(cache_norm_stride), V(redo_slot_stride),
+      V(match_slot_stride), V(n_slot_stride), WR(partial_scratch, partial_scratch ? (size_t)20u * max_na * VKSIFT_HIP_MATCH_CHUNKS : 0u);
   END;
 }
 
 /* ------------------------------------------------------------------------------------------------ the stages behind a filtered matching */
+/* a pair table's layouts: at most one per buffer, two buffers per slot, 33 words each (include/vksift_hip.h) */
+#define LAYOUT_BYTES(nslots) ((size_t)2u * (nslots) * 33u * 4u)
 int vksift_hip_gather_correspondences(const uint8_t *feats_base, uint64_t buf_stride, const uint32_t *found_base, uint32_t found_buf_stride, const uint32_t *slot_tab,
                                       const uint32_t *layouts, const uint8_t *filtered, uint64_t filtered_slot_stride, const uint32_t *filtered_n, uint32_t max_n,
                                       uint32_t nslots, float *corr, uint64_t corr_slot_stride, vksift_hip_stream s)
 {
   OP("gather_correspondences", s);
-  P(feats_base), V(buf_stride), P(found_base), V(found_buf_stride), P(slot_tab), P(layouts), P(filtered), V(filtered_slot_stride), P(filtered_n), V(max_n), V(nslots), P(corr),
-      V(corr_slot_stride);
+  RD(feats_base, 0), V(buf_stride), RD(found_base, 0), V(found_buf_stride), RD(slot_tab, 16u * nslots), RD(layouts, LAYOUT_BYTES(nslots)), RD(filtered, filtered_slot_stride * nslots),
+      V(filtered_slot_stride), RD(filtered_n, 4u * nslots), V(max_n), V(nslots), WR(corr, corr_slot_stride * nslots), V(corr_slot_stride),
+      FITS(corr, 16u * (uint64_t)max_n, corr_slot_stride), FITS(filtered, 16u * (uint64_t)max_n, filtered_slot_stride);
   END;
 }
 #define RANSAC_ARGS                                                                                                                                                \
-  P(corr), V(corr_slot_stride), P(n_dev), V(n_stride), V(max_n), V(nslots), V(nb_hypotheses), V(threshold_px), V(seed), P(results), P(masks), V(mask_slot_stride), \
-      P(scratch), V(scratch_u32)
+  RD(corr, corr_slot_stride * nslots), V(corr_slot_stride), RD(n_dev, STRIDED(nslots, n_stride, 1)), V(n_stride), V(max_n), V(nslots), V(nb_hypotheses), V(threshold_px), V(seed), \
+      WR(results, (size_t)RES_BYTES * nslots), WR(masks, mask_slot_stride * nslots), V(mask_slot_stride), WR(scratch, 4u * scratch_u32), V(scratch_u32),      \
+      FITS(corr, 16u * (uint64_t)max_n, corr_slot_stride), FITS(masks, max_n, mask_slot_stride)
 int vksift_hip_ransac_homography(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
                                  uint32_t nb_hypotheses, float threshold_px, uint64_t seed, uint8_t *results, uint8_t *masks, uint64_t mask_slot_stride, uint32_t *scratch,
                                  size_t scratch_u32, vksift_hip_stream s)
 {
   OP("ransac_homography", s);
+  enum { RES_BYTES = 52 };
   RANSAC_ARGS;
   END;
 }
@@ -953,17 +1205,20 @@ int vksift_hip_ransac_fundamental(const float *corr, uint64_t corr_slot_stride, 
                                   size_t scratch_u32, vksift_hip_stream s)
 {
   OP("ransac_fundamental", s);
+  enum { RES_BYTES = 56 };
   RANSAC_ARGS;
   END;
 }
 #define REFIT_ARGS                                                                                                                                                 \
-  P(corr), V(corr_slot_stride), P(n_dev), V(n_stride), V(max_n), V(nslots), P(start_results), P(start_masks), V(mask_slot_stride), V(nb_rounds), V(threshold_px), \
-      P(results), P(masks_out)
+  RD(corr, corr_slot_stride * nslots), V(corr_slot_stride), RD(n_dev, STRIDED(nslots, n_stride, 1)), V(n_stride), V(max_n), V(nslots), RD(start_results, (size_t)START_BYTES * nslots), \
+      RD(start_masks, mask_slot_stride * nslots), V(mask_slot_stride), V(nb_rounds), V(threshold_px), WR(results, (size_t)52u * nslots), WR(masks_out, mask_slot_stride * nslots), \
+      FITS(corr, 16u * (uint64_t)max_n, corr_slot_stride), FITS(masks_out, max_n, mask_slot_stride)
 int vksift_hip_refit_homography(const float *corr, uint64_t corr_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, uint32_t nslots,
                                 const uint8_t *start_results, const uint8_t *start_masks, uint64_t mask_slot_stride, uint32_t nb_rounds, float threshold_px,
                                 uint8_t *results, uint8_t *masks_out, vksift_hip_stream s)
 {
   OP("refit_homography", s);
+  enum { START_BYTES = 52 };
   REFIT_ARGS;
   END;
 }
@@ -972,6 +1227,7 @@ int vksift_hip_refit_fundamental(const float *corr, uint64_t corr_slot_stride, c
                                  uint8_t *results, uint8_t *masks_out, vksift_hip_stream s)
 {
   OP("refit_fundamental", s);
+  enum { START_BYTES = 56 };
   REFIT_ARGS;
   END;
 }
@@ -979,7 +1235,8 @@ int vksift_hip_gather_xy(const uint8_t *feats_base, uint64_t buf_stride, const u
                          const uint32_t *layouts, uint32_t max_n, uint32_t nslots, float *xy, uint64_t xy_side_stride, vksift_hip_stream s)
 {
   OP("gather_xy", s);
-  P(feats_base), V(buf_stride), P(found_base), V(found_buf_stride), P(slot_tab), P(layouts), V(max_n), V(nslots), P(xy), V(xy_side_stride);
+  RD(feats_base, 0), V(buf_stride), RD(found_base, 0), V(found_buf_stride), RD(slot_tab, 16u * nslots), RD(layouts, LAYOUT_BYTES(nslots)), V(max_n), V(nslots),
+      WR(xy, (size_t)2u * nslots * xy_side_stride * 8u), V(xy_side_stride), FITS(xy, max_n, xy_side_stride);
   END;
 }
 int vksift_hip_match_guided(const uint8_t *cache_desc, uint64_t cache_desc_stride, const uint32_t *cache_norm, uint64_t cache_norm_stride, const uint32_t *slot_tab,
@@ -989,8 +1246,27 @@ int vksift_hip_match_guided(const uint8_t *cache_desc, uint64_t cache_desc_strid
                             vksift_hip_stream s)
 {
   OP("match_guided", s);
-  P(cache_desc), V(cache_desc_stride), P(cache_norm), V(cache_norm_stride), P(slot_tab), V(slot_tab_stride), P(xy), V(xy_side_stride), P(n_dev), V(n_stride), V(max_n),
-      P(models), V(model_stride), P(valid), V(valid_stride), V(model_kind), V(t2), V(ratio), V(max_distance), V(cross_check), V(nslots), P(out), V(out_slot_stride), P(out_n),
-      P(scratch), V(scratch_u32);
+  RD(cache_desc, 0), V(cache_desc_stride), RD(cache_norm, 0), V(cache_norm_stride), RD(slot_tab, STRIDED(nslots, slot_tab_stride, 2)), V(slot_tab_stride),
+      RD(xy, (size_t)2u * nslots * xy_side_stride * 8u), V(xy_side_stride), RD(n_dev, STRIDED(nslots, n_stride, 2)), V(n_stride), V(max_n), RD(models, STRIDED(nslots, model_stride, 9)),
+      V(model_stride), RD(valid, STRIDED(nslots, valid_stride, 1)), V(valid_stride), V(model_kind), V(t2), V(ratio), V(max_distance), V(cross_check), V(nslots),
+      WR(out, out_slot_stride * nslots), V(out_slot_stride), WR(out_n, 4u * nslots), WR(scratch, 4u * scratch_u32), V(scratch_u32), FITS(out, 16u * (uint64_t)max_n, out_slot_stride),
+      FITS(xy, max_n, xy_side_stride), FITS(cache_desc, 128u * (uint64_t)max_n, cache_desc_stride), FITS(cache_norm, max_n, cache_norm_stride);
+  END;
+}
+
+/* ------------------------------------------------------------------------------------------------ feature tracks */
+int vksift_hip_build_tracks(const uint8_t *records, uint64_t rec_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, const uint8_t *masks,
+                            uint64_t mask_slot_stride, const uint32_t *valid, uint32_t valid_stride, const uint32_t *slot_tab, uint32_t slot_tab_stride, uint32_t nslots,
+                            const uint32_t *buf_tab, uint32_t nbufs, const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows, uint32_t *node_words,
+                            uint8_t *tracks, uint64_t tracks_cap, uint32_t *stats, uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s)
+{
+  OP("build_tracks", s);
+  RD(records, rec_slot_stride * nslots), V(rec_slot_stride), RD(n_dev, STRIDED(nslots, n_stride, 1)), V(n_stride), V(max_n), RD(masks, masks ? mask_slot_stride * nslots : 0u),
+      V(mask_slot_stride), RD(valid, valid ? STRIDED(nslots, valid_stride, 1) : 0u), V(valid_stride), RD(slot_tab, STRIDED(nslots, slot_tab_stride, 2)), V(slot_tab_stride), V(nslots),
+      RD(buf_tab, 8u * nbufs), V(nbufs), RD(rows_dev, 0), V(node_stride), T(max_rows), WR(node_words, (size_t)4u * nbufs * node_stride), WR(tracks, (size_t)16u * tracks_cap),
+      V(tracks_cap), WR(stats, 16u), WR(scratch, 4u * scratch_u32), V(scratch_u32), FITS(records, 16u * (uint64_t)max_n, rec_slot_stride),
+      FITS(masks, masks ? max_n : 0u, mask_slot_stride);
+  if (sim_roles && (uint64_t)nbufs * max_rows / 2u > tracks_cap)
+    slot_fits("tracks: nbufs * max_rows / 2 records against tracks_cap", (uint64_t)nbufs * max_rows / 2u, tracks_cap, 2);
   END;
 }

@@ -19,19 +19,11 @@ import subprocess
 
 import pytest
 
+import plan_build
 import plan_scripts as PS
 from plan_model import GIVE_UP_AFTER, GRAPH_CACHE, Model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vulkansift_amd", "csrc")
 VULKAN_ERROR = 2      # VKSIFT_VULKAN_ERROR
-
-
-def host_sources():
-    """HOST_SRCS of vulkansift_amd/build.py, read without importing the package's build (which needs hipcc)"""
-    text = open(os.path.join(ROOT, "vulkansift_amd", "build.py")).read()
-    block = re.search(r"HOST_SRCS = \[(.*?)\]", text, re.S).group(1)
-    return [os.path.join(CSRC, s) for s in re.findall(r'"(host/[a-z_]+\.c)"', block)]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the log
@@ -99,15 +91,8 @@ def parse(stdout):
 
 
 @pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("plan") / "plan_harness")
-    san = []
-    runtimes = [subprocess.run(["gcc", "-print-file-name=" + n], capture_output=True, text=True).stdout.strip() for n in ("libasan.so", "libubsan.so")]
-    if all(os.path.isabs(p) and os.path.exists(p) for p in runtimes):
-        san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
-    srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("sim_device.c", "plan_harness.c")] + host_sources()
-    subprocess.run(["gcc", "-O1", "-std=gnu11", "-Wall", "-Wextra", "-Wno-unused-parameter", "-Werror", "-DVKSIFT_BUILD"] + san +
-                   ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(CSRC, "host"), "-I" + CSRC] + srcs + ["-lm", "-lpthread", "-o", exe], check=True)
+def harness():
+    exe = plan_build.executable()      # one build for this file and tests/test_pair_plan.py
     memo = {}
 
     def run(script, graph=None, prelude=(), ok=True):

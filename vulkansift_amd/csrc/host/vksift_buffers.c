@@ -289,8 +289,10 @@ void vksift_uploadFeatures(vksift_Instance instance, const vksift_Feature *feats
   vksift_Instance inst = instance;
   wait_for_buffer(inst, gpu_buffer_id);
   BufferInfo *b = &inst->bufs[gpu_buffer_id];
+  bool copied = false;
   HIP_CHECK(vksift_hip_memcpy_h2d(inst->d_feats + (uint64_t)gpu_buffer_id * inst->buf_stride, feats_ptr, (size_t)nb_feats * FEAT_BYTES, inst->stream),
             "feature upload");
+  copied = true;
   HIP_CHECK(vksift_hip_stream_sync(inst->stream), "feature upload");
   /* the buffer becomes one packed section (sift_memory.c:1262-1266) */
   b->is_packed = true;
@@ -300,6 +302,13 @@ void vksift_uploadFeatures(vksift_Instance instance, const vksift_Feature *feats
   b->seq = 0; /* host-filled: nothing to wait for, and no longer part of a detection's packed download */
   return;
 gpu_error:
+  if (copied)
+  {
+    /* the copy was queued over the records the buffer held and nothing says how far it got: like a failed detection's, the buffer is complete and
+     * empty (one packed section of no features), not the new bytes under the old section table */
+    b->is_packed = true, b->nb_stored = 0, b->nb_sections = 0, b->seq = 0;
+    inst->cache_valid[gpu_buffer_id] = false;
+  }
   logError(LOG_TAG, "vksift_uploadFeatures(): the host-to-device copy of the features failed.");
   instance->error_cb(VKSIFT_VULKAN_ERROR);
 }

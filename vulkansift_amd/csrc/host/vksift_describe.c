@@ -108,24 +108,24 @@ static int enqueue_describe(DetectCtx *c, const DescribeArgs *a)
     for (uint32_t k = 0; k <= inst->S; k++)
       steps[k] = (float)((double)inst->cfg.seed_scale_sigma * pow(2.0, ((double)k + 0.5) / (double)inst->S));
     vksift_hip_range_push("PlaceKeypoints");
-    TRY(vksift_hip_place_keypoints((const vksift_hip_Keypoint *)(inst->d_kps + a->off_bytes), (const uint32_t *)inst->d_kps, oct, n_oct, steps, inst->S,
+    TRY_IN_RANGE(vksift_hip_place_keypoints((const vksift_hip_Keypoint *)(inst->d_kps + a->off_bytes), (const uint32_t *)inst->d_kps, oct, n_oct, steps, inst->S,
                                    a->mode == VKSIFT_EXT_DESCRIBE_GIVEN ? 1u : 0u, c->count, inst->d_placed + c->first_buf, st),
         "keypoint placement");
     vksift_hip_range_pop();
     if (a->mode == VKSIFT_EXT_DESCRIBE_ORIENT)
     {
       vksift_hip_range_push("ComputeOrientation");
-      TRY(vksift_hip_orientations_multi(c->jobs, n_oct, c->count, st), "orientation");
+      TRY_IN_RANGE(vksift_hip_orientations_multi(c->jobs, n_oct, c->count, st), "orientation");
       vksift_hip_range_pop();
     }
     vksift_hip_range_push("ComputeDescriptors");
     if (c->dense)
     {
       const vksift_hip_DenseRows dr = dense_rows(c);
-      TRY(vksift_hip_descriptors_multi_dense(c->jobs, n_oct, c->count, &dr, st), "descriptor");
+      TRY_IN_RANGE(vksift_hip_descriptors_multi_dense(c->jobs, n_oct, c->count, &dr, st), "descriptor");
     }
     else
-      TRY(vksift_hip_descriptors_multi(c->jobs, n_oct, c->count, st), "descriptor");
+      TRY_IN_RANGE(vksift_hip_descriptors_multi(c->jobs, n_oct, c->count, st), "descriptor");
     vksift_hip_range_pop();
     if (c->overlap)
     {

@@ -301,11 +301,11 @@ static int enqueue_pyramid(DetectCtx *c, uint32_t o, vksift_hip_stream sp, uint3
   {
     if (group_flags & PYR_FIRST_GROUP)
       prof_mark(c, c->PS->ev_pt[0], sp);
-    TRY(enqueue_seed(c, sp, first, count, group_flags), "seed");
+    TRY_IN_RANGE(enqueue_seed(c, sp, first, count, group_flags), "seed");
     nb_o++;
   }
   else if (!c->g0_done)
-    TRY(vksift_hip_downsample(plane_sub(c, o - 1, inst->S, first), plane_sub(c, o, 0, first), count, sp), "downsample");
+    TRY_IN_RANGE(vksift_hip_downsample(plane_sub(c, o - 1, inst->S, first), plane_sub(c, o, 0, first), count, sp), "downsample");
   c->g0_done = false;
   /* consecutive launches of the chain walk the batch in opposite directions: a launch starts on the planes its predecessor wrote
    * last, which are still in the Infinity Cache (a whole-batch plane is 2.5x the cache: in the same direction every read misses);
@@ -327,18 +327,18 @@ static int enqueue_pyramid(DetectCtx *c, uint32_t o, vksift_hip_stream sp, uint3
     {
       vksift_hip_Plane dst2 = plane_sub(c, o, s + 1, first);
       dst2.reverse = dstp.reverse;
-      TRY(optional(vksift_hip_blur_pair(srcp, dstp, dst2, scale_taps(inst, s), inst->ntaps[s], scale_taps(inst, s + 1), inst->ntaps[s + 1], count, sp), &done),
+      TRY_IN_RANGE(optional(vksift_hip_blur_pair(srcp, dstp, dst2, scale_taps(inst, s), inst->ntaps[s], scale_taps(inst, s + 1), inst->ntaps[s + 1], count, sp), &done),
           "two-scale blur");
       s += done ? 1u : 0u; /* (the single-scale launch below then has nothing left to do) */
     }
     else if (s == inst->S && o + 1 < c->L->n_oct)
     {
       /* scale S also seeds the next octave (sift_detector.c:1003-1034): stored by the same pass when the sizes halve exactly */
-      TRY(optional(vksift_hip_blur_downsample(srcp, dstp, plane_sub(c, o + 1, 0, first), scale_taps(inst, s), inst->ntaps[s], count, sp), &done), "blur + down-sampling");
+      TRY_IN_RANGE(optional(vksift_hip_blur_downsample(srcp, dstp, plane_sub(c, o + 1, 0, first), scale_taps(inst, s), inst->ntaps[s], count, sp), &done), "blur + down-sampling");
       c->g0_done = done;
     }
     if (!done)
-      TRY(vksift_hip_blur(srcp, dstp, scale_taps(inst, s), inst->ntaps[s], count, sp), "blur");
+      TRY_IN_RANGE(vksift_hip_blur(srcp, dstp, scale_taps(inst, s), inst->ntaps[s], count, sp), "blur");
   }
   c->jobs[o].scan_reverse = alt_dir(inst, li + 1u);
   vksift_hip_range_pop();
@@ -554,21 +554,21 @@ static int enqueue_keypoint_stages(const DetectCtx *c)
   const uint32_t n_oct = c->L->n_oct;
   prof_mark(c, c->PS->ev_t[2], st);
   vksift_hip_range_push("ExtractKeypoints");
-  TRY(vksift_hip_extract_keypoints_multi(c->jobs, n_oct, c->count, st, c->prof ? c->PS->ev_scan : NULL), "keypoint extraction");
+  TRY_IN_RANGE(vksift_hip_extract_keypoints_multi(c->jobs, n_oct, c->count, st, c->prof ? c->PS->ev_scan : NULL), "keypoint extraction");
   vksift_hip_range_pop();
   prof_mark(c, c->PS->ev_t[3], st);
   vksift_hip_range_push("ComputeOrientation");
-  TRY(vksift_hip_orientations_multi(c->jobs, n_oct, c->count, st), "orientation");
+  TRY_IN_RANGE(vksift_hip_orientations_multi(c->jobs, n_oct, c->count, st), "orientation");
   vksift_hip_range_pop();
   prof_mark(c, c->PS->ev_t[4], st);
   vksift_hip_range_push("ComputeDescriptors");
   if (c->dense || c->post)
   {
     const vksift_hip_DenseRows dr = dense_rows(c);
-    TRY(vksift_hip_descriptors_multi_dense(c->jobs, n_oct, c->count, &dr, st), "descriptor");
+    TRY_IN_RANGE(vksift_hip_descriptors_multi_dense(c->jobs, n_oct, c->count, &dr, st), "descriptor");
   }
   else
-    TRY(vksift_hip_descriptors_multi(c->jobs, n_oct, c->count, st), "descriptor");
+    TRY_IN_RANGE(vksift_hip_descriptors_multi(c->jobs, n_oct, c->count, st), "descriptor");
   vksift_hip_range_pop();
   if (c->overlap)
   {

@@ -20,6 +20,18 @@
       return _e;                                                               \
     }                                                                          \
   } while (0)
+/* TRY between vksift_hip_range_push and its vksift_hip_range_pop: the failure exit closes the range it leaves */
+#define TRY_IN_RANGE(expr, what)                                               \
+  do                                                                           \
+  {                                                                            \
+    int _e = (expr);                                                           \
+    if (_e != 0)                                                               \
+    {                                                                          \
+      logError(LOG_TAG, "%s failed: %s", what, vksift_hip_error_string(_e));   \
+      vksift_hip_range_pop();                                                  \
+      return _e;                                                               \
+    }                                                                          \
+  } while (0)
 
 
 /* ------------------------------------------------------------------------------------------------ */

@@ -176,6 +176,7 @@ uint32_t vksift_ext_exportDescriptorsDevice(vksift_Instance instance, uint32_t g
   }
   return n;
 gpu_error:
+  (void)vksift_hip_stream_sync(inst->stream); /* whatever was queued reads the buffer's cache entry: the call is synchronous, its error exit too */
   logError(LOG_TAG, "vksift_ext_exportDescriptorsDevice() error when exporting descriptors.");
   instance->error_cb(VKSIFT_VULKAN_ERROR);
   return 0;

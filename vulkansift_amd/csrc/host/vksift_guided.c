@@ -92,6 +92,7 @@ void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, co
                                       cross_check ? 1u : 0u, n, own->d_payload + own->stride * r, own->stride, own->d_words + r,
                                       inst->d_gkeys, inst->gkeys_u32, inst->stream),
               "guided matching");
+    own->slots_used = 0; /* the launch replaces the set: not served until the whole sequence has been queued */
   }
   HIP_CHECK(vksift_hip_event_record(inst->ev_gtab, inst->stream), "event record");
   inst->gtab_pending = true;
@@ -100,7 +101,7 @@ void vksift_ext_matchFeaturesGuided(vksift_Instance instance, uint32_t model, co
   own->slots_used = count;
   return;
 gpu_error:
-  (void)stage_abort(&frame);
+  stage_fail(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count);
   logError(LOG_TAG, GUIDED_FN " error: Failed to start the guided-matching pipeline.");
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }

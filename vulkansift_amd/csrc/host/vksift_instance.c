@@ -299,14 +299,18 @@ int inplace_begin(vksift_Instance inst, uint32_t first, uint32_t count, uint32_t
 
 int inplace_end(vksift_Instance inst, StageFrame *f)
 {
-  (void)stage_end(inst, f, NULL, NULL, 0);
-  return vksift_hip_event_record(inst->det_ring[inst->det_seq % VKSIFT_DETECT_RING].ev, inst->stream);
+  const int e = stage_end(inst, f, NULL, NULL, 0);
+  const int r = vksift_hip_event_record(inst->det_ring[inst->det_seq % VKSIFT_DETECT_RING].ev, inst->stream);
+  return e ? e : r;
 }
 
 void inplace_fail(vksift_Instance inst, StageFrame *f, const char *msg)
 {
-  if (stage_abort(f)) /* the buffers carry the new sequence number: its event stands behind whatever part of the call was queued */
-    (void)vksift_hip_event_record(inst->det_ring[inst->det_seq % VKSIFT_DETECT_RING].ev, inst->stream);
+  (void)stage_abort(f);
+  /* the buffers carry the new sequence number: its event stands behind whatever part of the call was queued (recorded again if it was the record
+   * that failed; behind a drained stream if it fails twice) */
+  if (f->begun && vksift_hip_event_record(inst->det_ring[inst->det_seq % VKSIFT_DETECT_RING].ev, inst->stream) != 0)
+    (void)vksift_hip_stream_sync(inst->stream);
   logError(LOG_TAG, "%s", msg);
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }

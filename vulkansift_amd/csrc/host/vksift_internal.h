@@ -452,10 +452,15 @@ typedef struct
 {
   StageTimer *timer;
   bool open;
+  bool begun; /* stage_begin has succeeded: launches of the call may be queued */
 } StageFrame;
 VKSIFT_INTERNAL int stage_begin(vksift_Instance inst, StageFrame *f, uint32_t timer, const char *range);
 VKSIFT_INTERNAL int stage_end(vksift_Instance inst, StageFrame *f, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count);
 VKSIFT_INTERNAL bool stage_abort(StageFrame *f);
+/* The error exit of a stage queued on the matching's contract. Whatever part of the call was queued still reads the pairs' buffers (and posts into the
+ * words the accessors read): the range is closed and, once stage_begin has succeeded, the sequence ends the way a complete one does (match_follow) — or,
+ * if that record fails too, behind a drained stream — so that vksift_isBufferAvailable and the accessors wait for it. */
+VKSIFT_INTERNAL void stage_fail(vksift_Instance inst, StageFrame *f, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count);
 
 /* vksift_instance.c, behind take_sequence: what the calls that rewrite a range of SIFT buffers in place share (vksift_strongest.c, vksift_rootsift.c). They are queued like a
  * detection: between the two halves the caller opens its stage, takes the sequence number (take_sequence) and makes one launch per layout run. */

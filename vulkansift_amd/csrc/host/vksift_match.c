@@ -180,13 +180,21 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
   HIP_CHECK(refresh_match_cache(inst, ids_b, count), "descriptor gather");
   /* one launch sequence serves up to VKSIFT_HIP_MATCH_SLOTS pairs; a longer list goes in runs of that many, run r into the slots from r on */
   for (uint32_t r = 0; r < count; r += VKSIFT_HIP_MATCH_SLOTS)
+  {
     HIP_CHECK(match_slots(inst, &fwd, ids_a + r, ids_b + r, count - r < VKSIFT_HIP_MATCH_SLOTS ? count - r : VKSIFT_HIP_MATCH_SLOTS, r), "2-NN matching");
+    if (r == 0)
+    {
+      /* the first launch that overwrites the previous matching's records and counts has been queued: nothing of that matching is served any more,
+       * whatever becomes of this call (it marks its own results once the whole sequence has been queued) */
+      pair_results_invalidate(inst);
+      inst->tracks.valid = false; /* tracks are built from the pairs of a matching (vksift_tracks.c) */
+      inst->match_slots_used = 0;
+      inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
+    }
+  }
   HIP_CHECK(vksift_hip_post_words(inst->h_match_n, inst->d_match_n, (size_t)4 * count, inst->stream), "match count read-back");
   if (inst->desc_start_valid && vksift_hip_tune_get(VKSIFT_TUNE_PYR_GATE) == 1)
     vksift_hip_event_record(inst->ev_desc_start, inst->stream); /* experiment: the next scale-space behind this matching, not beside it */
-  pair_results_invalidate(inst);
-  inst->tracks.valid = false; /* tracks are built from the pairs of a matching (vksift_tracks.c) */
-  inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
   if (filter)
   {
     /* the reverse matching, then cross-check + ratio test on the device; only the survivors are read back */
@@ -208,16 +216,17 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
                 "match filtering");
     }
     HIP_CHECK(vksift_hip_post_words(filt->h_words, filt->d_words, count, inst->stream), "filtered count read-back");
-    filt->slots_used = count;
     /* the pairs, for vksift_ext_verifyHomography */
     memcpy(inst->filt_ids, ids_a, sizeof(uint32_t) * count);
     memcpy(inst->filt_ids + inst->batch_cap, ids_b, sizeof(uint32_t) * count);
   }
   HIP_CHECK(stage_end(inst, &frame, ids_a, ids_b, count), "event record");
-  inst->match_slots_used = count;
+  inst->match_slots_used = count; /* (served only now: the accessors wait for the event stage_end has recorded) */
+  if (filter)
+    inst->res[PR_FILTERED].slots_used = count;
   return;
 gpu_error:
-  (void)stage_abort(&frame);
+  stage_fail(inst, &frame, ids_a, ids_b, count);
   logError(LOG_TAG, "%s error: Failed to start the matching pipeline.", fn);
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }

@@ -19,12 +19,13 @@ static int timer_start(vksift_Instance inst, StageTimer *t)
   return vksift_hip_event_record(t->ev[0], inst->stream);
 }
 
-static void timer_stop(vksift_Instance inst, StageTimer *t)
+static int timer_stop(vksift_Instance inst, StageTimer *t)
 {
   if (!inst->profiling)
-    return;
-  vksift_hip_event_record(t->ev[1], inst->stream);
-  t->valid = true;
+    return 0;
+  const int e = vksift_hip_event_record(t->ev[1], inst->stream);
+  t->valid = e == 0; /* (an interval whose end was never recorded is none) */
+  return e;
 }
 
 float timer_read(vksift_Instance inst, uint32_t which)
@@ -34,7 +35,12 @@ float timer_read(vksift_Instance inst, uint32_t which)
   if (!inst->profiling || !t->valid)
     return -1.f;
   vksift_hip_set_device(inst->device);
-  wait_all(inst);
+  if (wait_all(inst) != 0)
+  {
+    logError(LOG_TAG, "stage time: the stream synchronisation failed.");
+    inst->error_cb(VKSIFT_VULKAN_ERROR);
+    return -1.f;
+  }
   return vksift_hip_event_elapsed_ms(t->ev[0], t->ev[1]);
 }
 
@@ -54,15 +60,24 @@ int stage_begin(vksift_Instance inst, StageFrame *f, uint32_t timer, const char 
   if (e)
     return e;
   vksift_hip_range_push(range);
-  f->open = true;
+  f->open = f->begun = true;
   return 0;
 }
 
 int stage_end(vksift_Instance inst, StageFrame *f, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count)
 {
   (void)stage_abort(f);
-  timer_stop(inst, f->timer);
+  const int e = timer_stop(inst, f->timer);
+  if (e)
+    return e;
   return ids_a ? match_follow(inst, ids_a, ids_b, count) : 0;
+}
+
+void stage_fail(vksift_Instance inst, StageFrame *f, const uint32_t *ids_a, const uint32_t *ids_b, uint32_t count)
+{
+  (void)stage_abort(f);
+  if (f->begun && match_follow(inst, ids_a, ids_b, count) != 0)
+    (void)vksift_hip_stream_sync(inst->stream);
 }
 
 bool stage_abort(StageFrame *f)

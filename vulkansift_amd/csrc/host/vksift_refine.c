@@ -57,12 +57,13 @@ static void refine(vksift_Instance inst, const RefineModel *m, uint32_t nb_round
   HIP_CHECK(m->refit(inst->d_corr, filt->stride, filt->d_words, 1, inst->cfg.max_nb_sift_per_buffer, count, (const uint8_t *)start->d_words, start->d_payload,
                      start->stride, nb_rounds, threshold_px, (uint8_t *)own->d_words, own->d_payload, inst->stream),
             "refit");
+  own->slots_used = 0; /* the launch replaces the set: not served until the whole sequence has been queued */
   HIP_CHECK(vksift_hip_post_words(own->h_words, own->d_words, (size_t)REFINE_RES_WORDS * count, inst->stream), "refinement read-back");
   HIP_CHECK(stage_end(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
   own->slots_used = count;
   return;
 gpu_error:
-  (void)stage_abort(&frame);
+  stage_fail(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count);
   logError(LOG_TAG, "%s() error: Failed to start the refinement.", m->entry);
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }

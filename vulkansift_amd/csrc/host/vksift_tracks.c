@@ -70,7 +70,6 @@ void vksift_ext_buildTracks(vksift_Instance instance, uint32_t source)
     HIP_CHECK(vksift_hip_event_sync(inst->ev_ttab), "event synchronisation");
     t->tab_pending = false;
   }
-  t->valid = false;
   /* ranks: the buffers of the pair list in increasing gpu_buffer_id. A buffer's row count is the word the matching left in d_match_n for the first pair
    * that names it ({N_A, N_B, spare, spare} per slot): on the device, so nothing here waits for it */
   const uint32_t *ids_a = inst->filt_ids, *ids_b = inst->filt_ids + inst->batch_cap;
@@ -93,7 +92,7 @@ void vksift_ext_buildTracks(vksift_Instance instance, uint32_t source)
       buf_tab[2u * r] = id, buf_tab[2u * r + 1u] = t->count_word[r] = 4u * i + side;
       rows = rows_bound(inst, id) > rows ? rows_bound(inst, id) : rows;
     }
-  t->max_rows = rows < nb ? rows : nb;
+  const uint32_t max_rows = rows < nb ? rows : nb; /* (stored with `valid`: the tracks of an earlier build are read with theirs until then) */
   const TrackSource *src = &sources[source];
   const PairResults *rec = &inst->res[src->records], *sel = src->masked_by == PR_COUNT ? NULL : &inst->res[src->masked_by];
   HIP_CHECK(stage_begin(inst, &frame, T_TRACKS, "Tracks"), "timer start");
@@ -103,16 +102,18 @@ void vksift_ext_buildTracks(vksift_Instance instance, uint32_t source)
   t->tab_pending = true;
   /* a record set's first word is its count; a mask set's last word is `valid` (vksift_ext_Homography ... vksift_ext_RefinedFundamental). No pair holds
    * more records than its buffer A has rows */
-  HIP_CHECK(vksift_hip_build_tracks(rec->d_payload, rec->stride, rec->d_words, rec->words, t->max_rows, sel ? sel->d_payload : NULL, sel ? sel->stride : 0,
+  HIP_CHECK(vksift_hip_build_tracks(rec->d_payload, rec->stride, rec->d_words, rec->words, max_rows, sel ? sel->d_payload : NULL, sel ? sel->stride : 0,
                                     sel ? sel->d_words + sel->words - 1u : NULL, sel ? sel->words : 0, t->d_tab, 2u, count, t->d_tab + buf_tab_at, t->nbufs, inst->d_match_n, nb,
-                                    t->max_rows, t->d_node_words, t->d_records, ((uint64_t)t->cap_bufs * nb) / 2u, t->d_stats, t->d_scratch, t->scratch_u32, inst->stream),
+                                    max_rows, t->d_node_words, t->d_records, ((uint64_t)t->cap_bufs * nb) / 2u, t->d_stats, t->d_scratch, t->scratch_u32, inst->stream),
             "track building");
+  t->valid = false; /* the launch replaces the tracks: not served until the whole sequence has been queued */
   HIP_CHECK(vksift_hip_post_words(t->h_stats, t->d_stats, 4u, inst->stream), "track statistics read-back");
   HIP_CHECK(stage_end(inst, &frame, ids_a, ids_b, count), "event record");
+  t->max_rows = max_rows;
   t->valid = true;
   return;
 gpu_error:
-  (void)stage_abort(&frame);
+  stage_fail(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count);
   logError(LOG_TAG, TRACKS_FN " error: Failed to start the track building.");
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }

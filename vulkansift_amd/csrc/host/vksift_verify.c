@@ -79,16 +79,18 @@ static void verify(vksift_Instance inst, const VerifyModel *m, uint32_t nb_hypot
             "correspondence gather");
   HIP_CHECK(vksift_hip_event_record(inst->ev_vtab, inst->stream), "event record");
   inst->vtab_pending = true;
-  inst->res[m->refit].slots_used = 0; /* the launch below replaces the records and masks the refinement (vksift_refine.c) was computed from */
   HIP_CHECK(m->ransac(inst->d_corr, filt->stride, filt->d_words, 1, inst->cfg.max_nb_sift_per_buffer, count, nb_hypotheses, threshold_px, seed,
                       (uint8_t *)own->d_words, own->d_payload, own->stride, inst->d_vscratch, inst->vscratch_u32, inst->stream),
             "RANSAC");
+  /* the launch replaces the model's records and masks, and with them what the refinement (vksift_refine.c) was computed from: neither is served any
+   * more, whatever becomes of this call (the model's set is marked again once the whole sequence has been queued) */
+  own->slots_used = inst->res[m->refit].slots_used = 0;
   HIP_CHECK(vksift_hip_post_words(own->h_words, own->d_words, (size_t)m->res_words * count, inst->stream), "verification read-back");
   HIP_CHECK(stage_end(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
   own->slots_used = count;
   return;
 gpu_error:
-  (void)stage_abort(&frame);
+  stage_fail(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count);
   logError(LOG_TAG, "%s() error: Failed to start the verification pipeline.", m->entry);
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }
