@@ -6,12 +6,12 @@
  *
  *   create BC MAX_PX MAX_FEATS NBUF UPSAMPLE FP16   vksift_loadVulkan + vksift_createInstance (BC 1) / vksift_ext_createInstanceBatched
  *   detect W H BUF | batch W H FIRST COUNT | batchdev W H FIRST COUNT WHICH (device input block 0 or 1)
- *   num BUF | download BUF | avail BUF | match A B | prof 0|1 | describe W H BUF N [GIVEN] | destroy
+ *   num BUF | download BUF | downloadp BUF (a page-locked destination) | avail BUF | match A B | prof 0|1 | describe W H BUF N [GIVEN] | destroy
  *   busy 0|1 | drain | covered 0|1 | counts V | failin K [J] | ledger
  * and, for the stages behind a matching (tests/test_pair_plan.py):
  *   bmatch N A0 B0 A1 B1 ... | filtered CROSS N A0 B0 ...   vksift_ext_matchFeaturesBatch / vksift_ext_matchFeaturesFiltered (ratio 0.8)
  *   pmatch A B                                               vksift_matchFeatures alone (`match` also reads the result)
- *   mnum PAIR | mdl PAIR | mnum0 | mdl0                      the matching's number and download accessors, batch and plain
+ *   mnum PAIR | mdl PAIR | mdlp PAIR | mnum0 | mdl0          the matching's number and download accessors, batch and plain (mdlp: a page-locked destination)
  *   verify M NH SEED | refine M ROUNDS | guided M SUPPLIED CROSS | tracks SOURCE      (M: 0 homography, 1 fundamental matrix; threshold 2.5)
  *   acc K PAIR                                               accessor K of `accnames` (the order of tests/api_model.py: ACCESSORS)
  *   tstats | tdl | tfeat BUF                                 the tracks' accessors
@@ -42,6 +42,8 @@ void sim_finish(void);
 uint32_t sim_live_execs(void);
 void *vksift_hip_malloc(size_t bytes);
 void vksift_hip_free(void *p);
+void *vksift_hip_host_malloc(size_t bytes);
+void vksift_hip_host_free(void *p);
 
 static vksift_Instance inst;
 static vksift_Config cfg;
@@ -62,6 +64,26 @@ static void report(const char *cmd, const void *p, size_t bytes, uint32_t n, uin
     poison = w == SIM_POISON;
   }
   printf("< %s served=%d n=%u hash=%llu poison=%d errors=%u\n", cmd, errors == errors_before, n, (unsigned long long)(h >> 1), poison, errors - errors_before);
+}
+
+/* the caller's destination of a download: pageable, or page-locked (vksift_hip_is_pinned answers 1 for it). The harness's own block: not a
+ * counted call of the entry. Released behind the call, so that the ledger of a script is what the library left */
+static void *caller_block(size_t bytes, bool pinned)
+{
+  if (!pinned)
+    return malloc(bytes);
+  const int counted = sim_count_allocs;
+  sim_count_allocs = 0;
+  void *p = vksift_hip_host_malloc(bytes);
+  sim_count_allocs = counted;
+  return p;
+}
+static void caller_release(void *p, bool pinned)
+{
+  if (pinned)
+    vksift_hip_host_free(p);
+  else
+    free(p);
 }
 
 static const char *const acc_names[12] = {"filtered n", "filtered", "H", "H mask", "F", "F mask", "refined H", "refined H mask", "refined F", "refined F mask", "guided n", "guided"};
@@ -143,13 +165,19 @@ static int run(char *line)
     const uint32_t k = vksift_getFeaturesNumber(inst, (uint32_t)a[0]);
     printf("< num n=%u errors=%u\n", k, errors - errors_before);
   }
-  else if (!strcmp(cmd, "download"))
+  else if (!strcmp(cmd, "download") || !strcmp(cmd, "downloadp"))
   {
     const uint32_t k = vksift_getFeaturesNumber(inst, (uint32_t)a[0]);
-    vksift_Feature *f = (vksift_Feature *)malloc(sizeof(vksift_Feature) * (k ? k : 1));
+    const size_t bytes = sizeof(vksift_Feature) * (k ? k : 1);
+    vksift_Feature *f = (vksift_Feature *)caller_block(bytes, cmd[8] != 0);
+    for (size_t i = 0; i + 4 <= bytes; i += 4) /* whatever the call leaves unwritten reads as poison */
+      memcpy((uint8_t *)f + i, &(uint32_t){SIM_POISON}, 4);
     vksift_downloadFeatures(inst, f, (uint32_t)a[0]);
-    free(f);
-    printf("< download n=%u errors=%u\n", k, errors - errors_before);
+    bool poison = false;
+    for (size_t i = 0; i + 4 <= sizeof(vksift_Feature) * k && !poison; i += 4)
+      poison = memcmp((const uint8_t *)f + i, &(uint32_t){SIM_POISON}, 4) == 0;
+    caller_release(f, cmd[8] != 0);
+    printf("< %s n=%u poison=%d errors=%u\n", cmd, k, poison, errors - errors_before);
   }
   else if (!strcmp(cmd, "avail"))
   {
@@ -214,16 +242,18 @@ static int run(char *line)
     const uint32_t k = cmd[4] ? vksift_getMatchesNumber(inst) : vksift_ext_getMatchesNumberBatch(inst, (uint32_t)a[0]);
     report(cmd, &k, 4, k, errors_before);
   }
-  else if (!strcmp(cmd, "mdl") || !strcmp(cmd, "mdl0"))
+  else if (!strcmp(cmd, "mdl") || !strcmp(cmd, "mdl0") || !strcmp(cmd, "mdlp"))
   {
     const size_t bytes = (size_t)cfg.max_nb_sift_per_buffer * sizeof(vksift_Match_2NN);
-    vksift_Match_2NN *m = (vksift_Match_2NN *)calloc(1, bytes);
-    if (cmd[3])
+    const bool pinned = cmd[3] == 'p';
+    vksift_Match_2NN *m = (vksift_Match_2NN *)caller_block(bytes, pinned);
+    memset(m, 0, bytes);
+    if (cmd[3] == '0')
       vksift_downloadMatches(inst, m);
     else
       vksift_ext_downloadMatchesBatch(inst, (uint32_t)a[0], m);
     report(cmd, m, bytes, 0, errors_before);
-    free(m);
+    caller_release(m, pinned);
   }
   else if (!strcmp(cmd, "verify"))
   {
