@@ -211,7 +211,7 @@ extern "C"
    * every row of b or VKSIFT_EXT_NO_TRACK; b must be a buffer of the pair list.
    * Deterministic: the same inputs give the same bytes on every run, whatever the scheduling; the numbering depends on nothing but the graph
    * (tests/np_tracks.py restates it).
-   * Not attempted: no member list per track (the caller groups the per-feature words in one pass); no splitting of conflicting tracks; no tracks across two
+   * Not attempted: no member list per track here (vksift_ext_selectTrackObservations, below, builds it); no splitting of conflicting tracks; no tracks across two
    * matching calls.
    * Contract of guided matching: asynchronous, queued on the instance stream behind the matching and whatever produced the source, the pairs' buffers stay
    * busy, the accessors wait; results of its own (every pair result stays readable and unchanged), replaced by the next vksift_ext_buildTracks, invalidated by
@@ -241,6 +241,48 @@ extern "C"
   VKSIFT_EXPORT void vksift_ext_downloadFeatureTracks(vksift_Instance instance, uint32_t gpu_buffer_id, uint32_t *track_ids);
   /* Time (ms) of the last vksift_ext_buildTracks (its launches + the statistics' posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getTracksTime(vksift_Instance instance);
+
+  /* ---- GPU-side track observations ----------------------------------------------------------------------------------------
+   * What triangulation and bundle adjustment read: the table track -> [(image, feature, x, y)] of the tracks a caller keeps, built on the device from the
+   * tracks of the last vksift_ext_buildTracks, in two or three downloads however many buffers took part — instead of one word array and every 164-byte feature
+   * record per buffer, a host sort and a host filter (OpenMVG's TracksBuilder::Filter, OpenSfM's min_track_length, COLMAP's track-length options).
+   * Input: the tracks of the last vksift_ext_buildTracks.
+   * Selection: track t is selected iff length >= min_length, and (max_length == 0 or length <= max_length), and (conflicts ==
+   * VKSIFT_EXT_OBS_KEEP_CONFLICTING or length == nb_buffers).
+   * Rejection counts: nb_rejected_length counts the tracks that fail the length test, nb_rejected_conflicting those that pass it and are dropped as
+   * conflicting; nb_tracks + nb_rejected_length + nb_rejected_conflicting == vksift_ext_TrackStats.nb_tracks.
+   * Numbering: selected tracks keep their relative order, which is that of their smallest member; track_ids[m] is the number of selected track m in
+   * vksift_ext_downloadTracks.
+   * Layout: offsets[m] .. offsets[m+1] are the observations of selected track m; offsets[0] == 0 and offsets[nb_tracks] == nb_observations; inside a track
+   * the members come in increasing (gpu_buffer_id, row).
+   * Positions: x, y are the first two floats of the stored feature at that row (download order), bit for bit.
+   * Deterministic: the same inputs give the same bytes on every run, whatever the scheduling (tests/np_observations.py restates the rule).
+   * With no selected track, offsets is the single word 0.
+   * Not attempted: no per-view index (the observations of one image), no splitting of conflicting tracks, no threshold on nb_buffers.
+   * Contract of vksift_ext_buildTracks: asynchronous, queued on the instance stream behind the build, the pairs' buffers stay busy until it has run, the
+   * accessors wait; results of its own (the tracks and every pair result stay readable and byte-identical), replaced by the next
+   * vksift_ext_selectTrackObservations, invalidated by a new vksift_ext_buildTracks and by a new matching, plain or filtered. Precondition, as for guided
+   * matching: the buffers of the pairs still hold the features that were matched.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, earlier observations untouched): no tracks built for the present matching, min_length < 2, max_length neither 0
+   * nor >= min_length, an unknown conflicts, out == NULL, an accessor called before any selection. A launch or allocation failure is VKSIFT_VULKAN_ERROR. */
+#define VKSIFT_EXT_OBS_KEEP_CONFLICTING 0u
+#define VKSIFT_EXT_OBS_DROP_CONFLICTING 1u /* tracks with length > nb_buffers are not selected */
+  typedef struct
+  {
+    uint32_t gpu_buffer_id, row;
+    float x, y;
+  } vksift_ext_Observation; /* 16 bytes */
+  typedef struct
+  {
+    uint32_t nb_tracks, nb_observations, nb_rejected_length, nb_rejected_conflicting;
+  } vksift_ext_ObservationStats; /* 16 bytes */
+  VKSIFT_EXPORT void vksift_ext_selectTrackObservations(vksift_Instance instance, uint32_t min_length, uint32_t max_length, uint32_t conflicts);
+  VKSIFT_EXPORT void vksift_ext_getObservationStats(vksift_Instance instance, vksift_ext_ObservationStats *out);
+  VKSIFT_EXPORT void vksift_ext_downloadObservationOffsets(vksift_Instance instance, uint32_t *offsets);     /* nb_tracks + 1 words */
+  VKSIFT_EXPORT void vksift_ext_downloadObservationTrackIds(vksift_Instance instance, uint32_t *track_ids);  /* nb_tracks words */
+  VKSIFT_EXPORT void vksift_ext_downloadObservations(vksift_Instance instance, vksift_ext_Observation *obs); /* nb_observations records */
+  /* Time (ms) of the last vksift_ext_selectTrackObservations (its launches + the statistics' posting), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getObservationsTime(vksift_Instance instance);
 
   /* ---- GPU-side feature budget ------------------------------------------------------------------------------------------
    * Every SIFT buffer of [first_gpu_buffer_id, first_gpu_buffer_id + count) keeps its max_features strongest features (OpenCV's nfeatures, SiftGPU's -tc,

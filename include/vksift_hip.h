@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 12u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks */
+#define VKSIFT_HIP_ABI_VERSION 13u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks, 13: vksift_hip_track_observations */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -698,6 +698,34 @@ extern "C"
                               uint32_t nslots, const uint32_t *buf_tab, uint32_t nbufs, const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows,
                               uint32_t *node_words, uint8_t *tracks, uint64_t tracks_cap, uint32_t *stats, uint32_t *scratch, size_t scratch_u32,
                               vksift_hip_stream s);
+
+  /* ------------------------------------------------------------------ track observations (observations.hip; no counterpart in the reference) */
+  /* The observation table of the tracks vksift_hip_build_tracks left: which tracks a caller keeps, and their members with positions, grouped by track.
+   * READ: node_words, tracks (the 16-byte records) and track_stats[0] (the track count, on the device: clamped to nbufs * max_rows / 2) as
+   * vksift_hip_build_tracks wrote them, with the buf_tab, rows_dev, node_stride and max_rows of that call (read at the same words and nowhere else); the
+   * first two floats of the stored record of every row: buffer b's records at feats_base + b*buf_stride bytes, its section counters at found_base +
+   * b*found_buf_stride words, rank_layouts[r] the layout word of the buffer of rank r and layouts the section tables those words name, in the convention of
+   * vksift_hip_gather_correspondences (VKSIFT_LAYOUT_DENSE | n, or the index of a table of 33 words); rank_layouts and layouts are read by the launches
+   * (device or mapped pinned memory).
+   * Track t is SELECTED iff length >= min_length and (max_length == 0 or length <= max_length) and (conflicts == 0 or length == nb_buffers). Selected tracks
+   * keep their order: selected track m has track_ids[m] = t and the observations offsets[m] .. offsets[m+1], its members in increasing (gpu_buffer_id, row);
+   * an observation is the 16 bytes {gpu_buffer_id, row, x, y}, x and y bit for bit. stats: {selected tracks M, observations, tracks that fail the length
+   * test, tracks that pass it and are dropped as conflicting}; offsets[0] = 0 (with M = 0 too), offsets[M] = observations. A row the tracks know and the
+   * layout does not hold (a buffer refilled since the matching) has x = y = 0. Deterministic: every output depends on the inputs alone (a stable radix sort
+   * of the nodes by their track's new number; no atomics on global memory). tests/np_observations.py restates it.
+   * scratch: scratch_u32 >= vksift_hip_observations_scratch_u32(nbufs, node_stride, max_rows) words, 8-byte aligned, need not be initialised, contents
+   * unspecified afterwards. WRITTEN: the four words of stats, offsets[0 .. M], track_ids[0 .. M), observations 0 .. stats[1]-1, the scratch, nothing else.
+   * offsets holds tracks_cap + 1 words, track_ids tracks_cap, observations obs_cap records.
+   * hipErrorInvalidValue, nothing launched: nbufs or max_rows 0, max_rows above node_stride, nbufs * node_stride above 2^32 - 2 or the rows of whole
+   * blocks of 2048 above 2^31 - 1, min_length below 2, max_length neither 0 nor >= min_length, conflicts above 1, tracks or feats_base not 4-byte aligned,
+   * buf_stride not a multiple of 4, observations not 16-byte aligned, scratch not 8-byte aligned, tracks_cap below nbufs * max_rows / 2, obs_cap below
+   * nbufs * max_rows, too little scratch. */
+  size_t vksift_hip_observations_scratch_u32(uint32_t nbufs, uint32_t node_stride, uint32_t max_rows);
+  int vksift_hip_track_observations(const uint32_t *node_words, const uint8_t *tracks, const uint32_t *track_stats, const uint32_t *buf_tab, uint32_t nbufs,
+                                    const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows, const uint8_t *feats_base, uint64_t buf_stride,
+                                    const uint32_t *found_base, uint32_t found_buf_stride, const uint32_t *rank_layouts, const uint32_t *layouts,
+                                    uint32_t min_length, uint32_t max_length, uint32_t conflicts, uint32_t *offsets, uint32_t *track_ids, uint64_t tracks_cap,
+                                    uint8_t *observations, uint64_t obs_cap, uint32_t *stats, uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
 
 #ifdef __cplusplus
 }

@@ -181,6 +181,13 @@ def lib():
     L.vksift_ext_downloadFeatureTracks.restype = None
     L.vksift_ext_getTracksTime.argtypes = [inst]
     L.vksift_ext_getTracksTime.restype = C.c_float
+    L.vksift_ext_selectTrackObservations.argtypes = [inst, u32, u32, u32]
+    L.vksift_ext_selectTrackObservations.restype = None
+    for name in ("getObservationStats", "downloadObservationOffsets", "downloadObservationTrackIds", "downloadObservations"):
+        getattr(L, "vksift_ext_" + name).argtypes = [inst, C.c_void_p]
+        getattr(L, "vksift_ext_" + name).restype = None
+    L.vksift_ext_getObservationsTime.argtypes = [inst]
+    L.vksift_ext_getObservationsTime.restype = C.c_float
     L.vksift_ext_keepStrongestFeatures.argtypes = [inst, u32, u32, u32]
     L.vksift_ext_keepStrongestFeatures.restype = None
     L.vksift_ext_getKeepStrongestTime.argtypes = [inst]
@@ -274,6 +281,12 @@ def lib():
     L.vksift_hip_build_tracks.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, u32, u32, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p, u32,
                                           C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.vksift_hip_build_tracks.restype = C.c_int
+    L.vksift_hip_observations_scratch_u32.argtypes = [u32, u32, u32]
+    L.vksift_hip_observations_scratch_u32.restype = C.c_size_t
+    L.vksift_hip_track_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p, C.c_uint64, C.c_void_p, u32,
+                                                C.c_void_p, C.c_void_p, u32, u32, u32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_void_p]
+    L.vksift_hip_track_observations.restype = C.c_int
     _lib = L
     return L
 
@@ -434,6 +447,9 @@ TRACKS_FILTERED, TRACKS_VERIFIED_H, TRACKS_VERIFIED_F, TRACKS_REFINED_H, TRACKS_
 NO_TRACK = 0xFFFFFFFF
 TRACK_DTYPE = np.dtype([("gpu_buffer_id", "<u4"), ("row", "<u4"), ("length", "<u4"), ("nb_buffers", "<u4")])
 TRACK_STATS_DTYPE = np.dtype([("nb_tracks", "<u4"), ("nb_conflicting", "<u4"), ("nb_features", "<u4"), ("nb_edges", "<u4")])
+OBS_KEEP_CONFLICTING, OBS_DROP_CONFLICTING = 0, 1
+OBSERVATION_DTYPE = np.dtype([("gpu_buffer_id", "<u4"), ("row", "<u4"), ("x", "<f4"), ("y", "<f4")])
+OBSERVATION_STATS_DTYPE = np.dtype([("nb_tracks", "<u4"), ("nb_observations", "<u4"), ("nb_rejected_length", "<u4"), ("nb_rejected_conflicting", "<u4")])
 
 
 def guided_match(desc_a, xy_a, desc_b, xy_b, n, models, valid, model_kind, t2, ratio, max_distance, cross_check, scratch_u32=None, strides=None, buffers=None):
@@ -708,6 +724,47 @@ class Instance:
 
     def getTracksTime(self):
         return lib().vksift_ext_getTracksTime(self._h)
+
+    def selectTrackObservations(self, min_length=2, max_length=0, conflicts=OBS_KEEP_CONFLICTING):
+        """builds the observation table of the tracks of the last buildTracks on the GPU (vksift_ext_selectTrackObservations): the tracks of at least
+        min_length and (unless 0) at most max_length members, without the conflicting ones under OBS_DROP_CONFLICTING; asynchronous like the build"""
+        lib().vksift_ext_selectTrackObservations(self._h, min_length, max_length, conflicts)
+        _check_pending()
+
+    def getObservationStats(self):
+        """{nb_tracks, nb_observations, nb_rejected_length, nb_rejected_conflicting} of the last selectTrackObservations"""
+        out = np.zeros(1, OBSERVATION_STATS_DTYPE)
+        lib().vksift_ext_getObservationStats(self._h, out.ctypes.data)
+        _check_pending()
+        return {k: int(out[0][k]) for k in OBSERVATION_STATS_DTYPE.names}
+
+    def downloadObservationOffsets(self):
+        """nb_tracks + 1 uint32: the observations of selected track m are offsets[m] .. offsets[m + 1]"""
+        out = np.zeros(self.getObservationStats()["nb_tracks"] + 1, np.uint32)
+        lib().vksift_ext_downloadObservationOffsets(self._h, out.ctypes.data)
+        _check_pending()
+        return out
+
+    def downloadObservationTrackIds(self):
+        """per selected track its number in downloadTracks()"""
+        n = self.getObservationStats()["nb_tracks"]
+        out = np.zeros(n, np.uint32)
+        if n:
+            lib().vksift_ext_downloadObservationTrackIds(self._h, out.ctypes.data)
+            _check_pending()
+        return out
+
+    def downloadObservations(self):
+        """the observation records (OBSERVATION_DTYPE), grouped by selected track"""
+        n = self.getObservationStats()["nb_observations"]
+        out = np.zeros(n, OBSERVATION_DTYPE)
+        if n:
+            lib().vksift_ext_downloadObservations(self._h, out.ctypes.data)
+            _check_pending()
+        return out
+
+    def getObservationsTime(self):
+        return lib().vksift_ext_getObservationsTime(self._h)
 
     def keepStrongestFeatures(self, first_buffer, count, max_features):
         """every SIFT buffer of [first_buffer, first_buffer + count) keeps its max_features strongest features (|DoG response|, ties by download

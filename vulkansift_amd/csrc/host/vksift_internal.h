@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -76,7 +76,7 @@ typedef struct
 } MatchScratch;
 
 /* the interval of a stage's last run under vksift_ext_setProfiling (vksift_pairs.c). One per getter: both verification models share T_VERIFY */
-enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_COUNT };
+enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_OBSERVATIONS, T_COUNT };
 typedef struct
 {
   vksift_hip_event ev[2];
@@ -114,6 +114,19 @@ typedef struct
   uint32_t cap_bufs, nbufs, max_rows;
   bool valid, tab_pending;
 } TrackResults;
+
+/* What vksift_ext_selectTrackObservations keeps (vksift_observations.c), sized like the tracks it reads: at most cap_bufs * max_nb_sift_per_buffer
+ * observations of half as many tracks. Allocated by the first selection. `valid`: cleared wherever tracks.valid is, and by a new build. */
+typedef struct
+{
+  uint32_t *d_offsets, *d_track_ids; /* CSR offsets (tracks + 1 words) and the selected tracks' numbers */
+  uint8_t *d_obs;                    /* the vksift_ext_Observation records */
+  uint32_t *d_stats, *h_stats;       /* the four words of vksift_ext_ObservationStats, posted */
+  uint32_t *d_scratch;               /* coordinates, sort lists, digit table, map (vksift_hip_observations_scratch_u32) */
+  size_t scratch_u32;
+  uint32_t *h_tab;                   /* mapped pinned memory read by the launches: a pair table (pair_tables), then one layout word per rank */
+  bool valid, tab_pending;
+} ObservationResults;
 
 typedef struct
 {
@@ -257,6 +270,8 @@ struct vksift_Instance_T
   bool gtab_pending;
   /* feature tracks over the pair list (vksift_ext_buildTracks, vksift_tracks.c) */
   TrackResults tracks;
+  /* the observation table of selected tracks (vksift_ext_selectTrackObservations, vksift_observations.c) */
+  ObservationResults obs;
 
   /* ---- caller-supplied keypoints (vksift_describe.c); everything allocated by the first describe call */
   uint8_t *d_kps, *h_kps;        /* one call's keypoint offsets (count + 1 words, padded to 256 bytes) and, behind them, its keypoints: pinned staging and the device copy */
@@ -312,6 +327,7 @@ struct vksift_Instance_T
   vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab (created by the first verification) */
   vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created by the first guided matching) */
   vksift_hip_event ev_ttab; /* the last track build has copied tracks.h_tab (created by the first build) */
+  vksift_hip_event ev_otab; /* the last observation launches have read obs.h_tab (created by the first selection) */
   vksift_hip_event ev_kps;  /* the last describe call's copy has read h_kps (created by the first describe call) */
   bool desc_start_valid, input_free_valid, staging_pending, kps_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];
