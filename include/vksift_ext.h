@@ -284,6 +284,66 @@ extern "C"
   /* Time (ms) of the last vksift_ext_selectTrackObservations (its launches + the statistics' posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getObservationsTime(vksift_Instance instance);
 
+  /* ---- GPU-side triangulation of the selected tracks ----------------------------------------------------------------------
+   * One 3-D point per selected track of the last vksift_ext_selectTrackObservations, under cameras the caller knows (a calibrated rig, odometry, poses with
+   * priors: COLMAP's point_triangulator, OpenMVG's ComputeStructureFromKnownPoses, OpenSfM's triangulation of shots with priors), where the table lies on the
+   * device: nothing is downloaded or uploaded except the camera table, and a table of 32-byte points leaves the device instead of the observations.
+   * Cameras: 12 floats per SIFT buffer of the instance, indexed by gpu_buffer_id, a row-major 3x4 P. With (u, v, w) = P (X, Y, Z, 1) the pixel is (u / w,
+   * v / w); w > 0 means the point is in front of the camera. Only the cameras of the buffers that took part in the last vksift_ext_buildTracks are read; those
+   * must be finite. The cameras are copied before the call returns. Precondition (stated, not checked): the left 3x3 block has a positive determinant, so
+   * that P = K [R | t].
+   * Point m belongs to selected track m of the observation table. status is 0 for an accepted point, otherwise all the flags that apply;
+   * cos_min_angle >= 1 switches the angle test off. nb_accepted + nb_failed + nb_rejected == nb_points == vksift_ext_ObservationStats.nb_tracks.
+   * THE RULE, per selected track with members i = 0 .. n-1 in table order. Arithmetic is fp32 add, subtract, multiply, divide and sqrtf, each rounded once, in
+   * a written order, with no fmaf (the order is spelled out at vksift_hip_triangulate_tracks in vksift_hip.h; tests/np_triangulate.py restates it bit for bit).
+   *  1 Bearings: with rows m1, m2, m3 of the left 3x3 block, b_i = x_i (m2 x m3) + y_i (m3 x m1) + (m1 x m2), scaled by 1 / sqrtf(b.b). min_cos is the minimum
+   *    of b_i . b_j over all i < j.
+   *  2 Linear start: each member gives the rows x_i P3 - P1 and y_i P3 - P2, each scaled by 1 / sqrtf of the squared length of its first three entries; the
+   *    3x3 normal equations of the inhomogeneous solution (X, Y, Z, 1) are solved by Gauss-Jordan with the refits' pivot rule (rows below compared in turn by
+   *    |entry| bit pattern, the row multiplied by 1 / pivot).
+   *  3 Up to two Gauss-Newton steps on the summed squared reprojection error (residuals u/w - x and v/w - y, analytic Jacobian, the same 3x3 solve). A step is
+   *    accepted iff it can be computed (every w normal and finite, every pivot usable, the new point finite) and the cost at the new point is not larger
+   *    than at the old one; the first step that is not accepted ends the loop.
+   *  4 Scoring at the final X: max_sq_error is the largest (u/w - x)^2 + (v/w - y)^2; BEHIND iff some w <= 0; ERROR iff not max_sq_error < threshold_px^2;
+   *    ANGLE iff cos_min_angle < 1 and not min_cos < cos_min_angle; DEGENERATE when a bearing, a row scale, a pivot or the start cannot be computed or is not
+   *    finite (a scale or pivot that is zero, subnormal or not finite), or a member names a buffer without a camera.
+   *  5 Sums over members have one order whatever the scheduling: a group of G = 16 lanes owns a track, lane j adds members j, j + 16, ... in increasing
+   *    order, the lanes are then added by the refits' xor butterfly (offsets 8, 4, 2, 1). G is part of the rule.
+   * Deterministic: the same inputs give the same bytes on every run.
+   * Not attempted: no removal of single outlying observations (a track is taken or left whole); no bundle adjustment; no estimation of the cameras; no
+   * conditioning of the world frame — the arithmetic is fp32, so a caller puts the origin near the scene.
+   * Contract of vksift_ext_selectTrackObservations: asynchronous, queued on the instance stream behind the selection, the pairs' buffers stay busy until it
+   * has run, the accessors wait; results of its own (tracks, observations and every pair result stay readable and byte-identical), replaced by the next
+   * vksift_ext_triangulateTracks, invalidated wherever the observations are: by a new selection, a new vksift_ext_buildTracks, a new matching. Failures as
+   * stated at vksift_ext_matchFeaturesBatch.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, earlier points untouched): no observations selected for the present tracks, cameras == NULL, a camera that is
+   * read is not finite, threshold_px not positive and finite or its fp32 square zero or not finite, cos_min_angle NaN, out == NULL, an accessor called
+   * before any triangulation. A launch or allocation failure is VKSIFT_VULKAN_ERROR. */
+#define VKSIFT_EXT_POINT_DEGENERATE 1u /* no solution: see the rule; X = 0 and every other field but nb_observations is 0 */
+#define VKSIFT_EXT_POINT_TOO_LONG 2u   /* more than VKSIFT_EXT_TRIANGULATE_MAX_OBSERVATIONS members: not computed, fields as for DEGENERATE */
+#define VKSIFT_EXT_POINT_BEHIND 4u     /* some observation has w <= 0 at X */
+#define VKSIFT_EXT_POINT_ERROR 8u      /* max_sq_error is not below threshold_px^2 */
+#define VKSIFT_EXT_POINT_ANGLE 16u     /* min_cos is not below cos_min_angle */
+#define VKSIFT_EXT_TRIANGULATE_MAX_OBSERVATIONS 1024u
+  typedef struct
+  {
+    float X[3];         /* world coordinates */
+    float max_sq_error; /* largest squared reprojection error over the members, pixels^2 */
+    float min_cos;      /* smallest cosine between two members' bearing rays: the largest triangulation angle */
+    uint32_t status;    /* 0: accepted; otherwise the flags above, all that apply */
+    uint32_t steps;     /* accepted Gauss-Newton steps, 0 .. 2 */
+    uint32_t nb_observations;
+  } vksift_ext_Point; /* 32 bytes; point m belongs to selected track m of the observation table */
+  typedef struct
+  {
+    uint32_t nb_points, nb_accepted, nb_failed /* DEGENERATE or TOO_LONG */, nb_rejected /* computed, some of BEHIND / ERROR / ANGLE */;
+  } vksift_ext_PointStats; /* 16 bytes */
+  VKSIFT_EXPORT void vksift_ext_triangulateTracks(vksift_Instance instance, const float *cameras, float threshold_px, float cos_min_angle);
+  VKSIFT_EXPORT void vksift_ext_getPointStats(vksift_Instance instance, vksift_ext_PointStats *out);
+  VKSIFT_EXPORT void vksift_ext_downloadPoints(vksift_Instance instance, vksift_ext_Point *points); /* nb_points records */
+  /* Time (ms) of the last vksift_ext_triangulateTracks (the camera upload, its launches + the statistics' posting), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getTriangulateTime(vksift_Instance instance);
+
   /* ---- GPU-side feature budget ------------------------------------------------------------------------------------------
    * Every SIFT buffer of [first_gpu_buffer_id, first_gpu_buffer_id + count) keeps its max_features strongest features (OpenCV's nfeatures, SiftGPU's -tc,
    * PopSift's --filter-max-extrema), selected and compacted on the device: no download, host sort and upload. The capacity max_nb_sift_per_buffer drops the

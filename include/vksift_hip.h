@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 13u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks, 13: vksift_hip_track_observations */
+#define VKSIFT_HIP_ABI_VERSION 14u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks, 13: vksift_hip_track_observations, 14: vksift_hip_triangulate_tracks */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -726,6 +726,41 @@ extern "C"
                                     const uint32_t *found_base, uint32_t found_buf_stride, const uint32_t *rank_layouts, const uint32_t *layouts,
                                     uint32_t min_length, uint32_t max_length, uint32_t conflicts, uint32_t *offsets, uint32_t *track_ids, uint64_t tracks_cap,
                                     uint8_t *observations, uint64_t obs_cap, uint32_t *stats, uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
+
+  /* ------------------------------------------------------------------ triangulation (triangulate.hip; no counterpart in the reference) */
+  /* The selected tracks of an observation table triangulated under caller-supplied cameras: one 32-byte point {X[3], max_sq_error, min_cos, status, steps,
+   * nb_observations} per selected track (vksift_ext_Point).
+   * READ: obs_stats[0] (the track count M, on the device: clamped to points_cap) and obs_stats[1] (the observation count), offsets[0 .. M] and the
+   * observations offsets[m] .. offsets[m+1] of every track m < M as vksift_hip_track_observations wrote them (a track whose offsets decrease or end beyond
+   * obs_stats[1] is DEGENERATE with nb_observations 0 and none of its observations is read; of a TOO_LONG track none is read either); cameras: 12 floats per
+   * gpu_buffer_id, a row-major 3x4 P with (u, v, w) = P (X, Y, Z, 1), pixel (u / w, v / w); the cameras the read observations name and, where one names
+   * gpu_buffer_id >= nb_cameras (its track is DEGENERATE), camera 0. t2: the squared threshold in pixels^2.
+   * THE RULE, per track with members i = 0 .. n-1 in table order. fp32 add, sub, mul, div and sqrtf, each rounded once, in this order, no fmaf. "unusable":
+   * zero, subnormal or not finite. n > 1024: TOO_LONG. n < 2: DEGENERATE.
+   *  1 bearings: with rows m1, m2, m3 of P's left 3x3 block and a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0): b = (x (m2 x m3) + y (m3 x m1)) + (m1 x m2)
+   *    per component, q = (b0 b0 + b1 b1) + b2 b2, s = 1 / sqrtf(q), b = b s; q or s unusable: DEGENERATE. min_cos = the minimum over all i < j of
+   *    (bi0 bj0 + bi1 bj1) + bi2 bj2, taken on the integer key that orders floats (-0 below +0).
+   *  2 linear start: per member the rows e = x P3 - P1 and y P3 - P2 (four entries, each t P3[c] - Pr[c]), q = (e0 e0 + e1 e1) + e2 e2, s = 1 / sqrtf(q),
+   *    p = (e0 s, e1 s, e2 s), pr = e3 s (q or s unusable: DEGENERATE). With the two rows p, q of a member, the nine sums S00 S01 S02 S11 S12 S22 r0 r1 r2
+   *    receive (pa pb + qa qb) and (pa pr + qa qr); the start solves S X = -r by Gauss-Jordan with refit.h's pivot rule: for column k the rows below are
+   *    compared with row k in turn and exchanged when their |entry| (bit pattern) is strictly larger, row k times 1 / pivot, every other row r minus
+   *    a[r][k] times row k; an unusable pivot or a solution entry that is not finite: DEGENERATE.
+   *  3 up to two Gauss-Newton steps on the summed squared reprojection error. At X per member: u = ((P0 X + P1 Y) + P2 Z) + P3 and v, w alike; pu = u / w,
+   *    pv = v / w, ru = pu - x, rv = pv - y, e2 = ru ru + rv rv, iw = 1 / w, ju[c] = (P1[c] - pu P3[c]) iw, jv[c] = (P2[c] - pv P3[c]) iw; the cost is the
+   *    sum of e2, the normal equations the nine sums of the rows (ju | ru), (jv | rv) as in 2, the step d solves N d = -g, the new point is X + d. A step is
+   *    accepted iff no w at X is unusable, the solve succeeds, X + d is finite and cost(X + d) <= cost(X); the first step that is not accepted ends the loop.
+   *  4 scoring at the final X: max_sq_error = the largest e2 by |bit pattern| (any NaN reads 0x7fc00000); BEHIND iff some w <= 0; ERROR iff not
+   *    max_sq_error < t2; ANGLE iff cos_min_angle < 1 and not min_cos < cos_min_angle. DEGENERATE and TOO_LONG points hold zeros but for status and
+   *    nb_observations.
+   *  5 every sum over members: a group of G = 16 lanes owns a track; lane j adds members j, j + 16, ... in increasing order to a partial sum that starts at
+   *    +0; the lanes are added by the xor butterfly p + p[lane ^ off], off = 8, 4, 2, 1.
+   * stats = {points M, accepted (status 0), failed (DEGENERATE or TOO_LONG), rejected (the others)}, integer counts. Deterministic: every output depends on
+   * the inputs alone. No scratch, no atomics on global memory. tests/np_triangulate.py restates the rule.
+   * WRITTEN: the M records of points, the four words of stats, nothing else. points holds points_cap records.
+   * hipErrorInvalidValue, nothing launched: a NULL pointer, nb_cameras 0, points_cap 0 or above 2^31 - 1, t2 not positive and finite, cos_min_angle NaN,
+   * offsets, obs_stats or stats not 4-byte aligned, observations, cameras or points not 16-byte aligned. */
+  int vksift_hip_triangulate_tracks(const uint32_t *offsets, const uint8_t *observations, const uint32_t *obs_stats, const float *cameras, uint32_t nb_cameras,
+                                    float t2, float cos_min_angle, uint8_t *points, uint64_t points_cap, uint32_t *stats, vksift_hip_stream s);
 
 #ifdef __cplusplus
 }

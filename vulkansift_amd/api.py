@@ -188,6 +188,13 @@ def lib():
         getattr(L, "vksift_ext_" + name).restype = None
     L.vksift_ext_getObservationsTime.argtypes = [inst]
     L.vksift_ext_getObservationsTime.restype = C.c_float
+    L.vksift_ext_triangulateTracks.argtypes = [inst, C.c_void_p, C.c_float, C.c_float]
+    L.vksift_ext_triangulateTracks.restype = None
+    for name in ("getPointStats", "downloadPoints"):
+        getattr(L, "vksift_ext_" + name).argtypes = [inst, C.c_void_p]
+        getattr(L, "vksift_ext_" + name).restype = None
+    L.vksift_ext_getTriangulateTime.argtypes = [inst]
+    L.vksift_ext_getTriangulateTime.restype = C.c_float
     L.vksift_ext_keepStrongestFeatures.argtypes = [inst, u32, u32, u32]
     L.vksift_ext_keepStrongestFeatures.restype = None
     L.vksift_ext_getKeepStrongestTime.argtypes = [inst]
@@ -287,6 +294,8 @@ def lib():
                                                 C.c_void_p, C.c_void_p, u32, u32, u32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
                                                 C.c_void_p, C.c_size_t, C.c_void_p]
     L.vksift_hip_track_observations.restype = C.c_int
+    L.vksift_hip_triangulate_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_float, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.vksift_hip_triangulate_tracks.restype = C.c_int
     _lib = L
     return L
 
@@ -450,6 +459,10 @@ TRACK_STATS_DTYPE = np.dtype([("nb_tracks", "<u4"), ("nb_conflicting", "<u4"), (
 OBS_KEEP_CONFLICTING, OBS_DROP_CONFLICTING = 0, 1
 OBSERVATION_DTYPE = np.dtype([("gpu_buffer_id", "<u4"), ("row", "<u4"), ("x", "<f4"), ("y", "<f4")])
 OBSERVATION_STATS_DTYPE = np.dtype([("nb_tracks", "<u4"), ("nb_observations", "<u4"), ("nb_rejected_length", "<u4"), ("nb_rejected_conflicting", "<u4")])
+POINT_DEGENERATE, POINT_TOO_LONG, POINT_BEHIND, POINT_ERROR, POINT_ANGLE = 1, 2, 4, 8, 16
+TRIANGULATE_MAX_OBSERVATIONS = 1024
+POINT_DTYPE = np.dtype([("X", "<f4", (3,)), ("max_sq_error", "<f4"), ("min_cos", "<f4"), ("status", "<u4"), ("steps", "<u4"), ("nb_observations", "<u4")])
+POINT_STATS_DTYPE = np.dtype([("nb_points", "<u4"), ("nb_accepted", "<u4"), ("nb_failed", "<u4"), ("nb_rejected", "<u4")])
 
 
 def guided_match(desc_a, xy_a, desc_b, xy_b, n, models, valid, model_kind, t2, ratio, max_distance, cross_check, scratch_u32=None, strides=None, buffers=None):
@@ -765,6 +778,35 @@ class Instance:
 
     def getObservationsTime(self):
         return lib().vksift_ext_getObservationsTime(self._h)
+
+    def triangulateTracks(self, cameras, threshold_px, cos_min_angle=1.0):
+        """triangulates every selected track of the last selectTrackObservations on the GPU (vksift_ext_triangulateTracks). cameras: float32
+        [sift_buffer_count, 3, 4] (or None, which the library refuses), row-major P per gpu_buffer_id; a point is accepted when its largest reprojection error
+        is below threshold_px and, with cos_min_angle < 1, its largest triangulation angle is wide enough; asynchronous like the selection"""
+        if cameras is not None:
+            cameras = np.ascontiguousarray(cameras, np.float32)
+            assert cameras.size == 12 * self.cfg.sift_buffer_count, "one 3x4 camera per SIFT buffer"
+        lib().vksift_ext_triangulateTracks(self._h, None if cameras is None else cameras.ctypes.data, threshold_px, cos_min_angle)
+        _check_pending()
+
+    def getPointStats(self):
+        """{nb_points, nb_accepted, nb_failed, nb_rejected} of the last triangulateTracks"""
+        out = np.zeros(1, POINT_STATS_DTYPE)
+        lib().vksift_ext_getPointStats(self._h, out.ctypes.data)
+        _check_pending()
+        return {k: int(out[0][k]) for k in POINT_STATS_DTYPE.names}
+
+    def downloadPoints(self):
+        """the point records (POINT_DTYPE): point m belongs to selected track m of the observation table"""
+        n = self.getPointStats()["nb_points"]
+        out = np.zeros(n, POINT_DTYPE)
+        if n:
+            lib().vksift_ext_downloadPoints(self._h, out.ctypes.data)
+            _check_pending()
+        return out
+
+    def getTriangulateTime(self):
+        return lib().vksift_ext_getTriangulateTime(self._h)
 
     def keepStrongestFeatures(self, first_buffer, count, max_features):
         """every SIFT buffer of [first_buffer, first_buffer + count) keeps its max_features strongest features (|DoG response|, ties by download

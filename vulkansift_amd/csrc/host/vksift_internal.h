@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_triangulate.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -76,7 +76,7 @@ typedef struct
 } MatchScratch;
 
 /* the interval of a stage's last run under vksift_ext_setProfiling (vksift_pairs.c). One per getter: both verification models share T_VERIFY */
-enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_OBSERVATIONS, T_COUNT };
+enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_OBSERVATIONS, T_TRIANGULATE, T_COUNT };
 typedef struct
 {
   vksift_hip_event ev[2];
@@ -127,6 +127,16 @@ typedef struct
   uint32_t *h_tab;                   /* mapped pinned memory read by the launches: a pair table (pair_tables), then one layout word per rank */
   bool valid, tab_pending;
 } ObservationResults;
+
+/* What vksift_ext_triangulateTracks keeps (vksift_triangulate.c): one point per selected track, at most half as many as there are nodes. Allocated by the
+ * first triangulation. `valid`: cleared wherever obs.valid is, and by a new selection. */
+typedef struct
+{
+  uint8_t *d_points;           /* the vksift_ext_Point records */
+  uint32_t *d_stats, *h_stats; /* the four words of vksift_ext_PointStats, posted */
+  float *h_cameras, *d_cameras; /* 12 floats per SIFT buffer: filled in pinned memory by the call, copied to the device in front of the launches */
+  bool valid, cam_pending;
+} TriangulateResults;
 
 typedef struct
 {
@@ -272,6 +282,8 @@ struct vksift_Instance_T
   TrackResults tracks;
   /* the observation table of selected tracks (vksift_ext_selectTrackObservations, vksift_observations.c) */
   ObservationResults obs;
+  /* the points of the selected tracks under caller-supplied cameras (vksift_ext_triangulateTracks, vksift_triangulate.c) */
+  TriangulateResults tri;
 
   /* ---- caller-supplied keypoints (vksift_describe.c); everything allocated by the first describe call */
   uint8_t *d_kps, *h_kps;        /* one call's keypoint offsets (count + 1 words, padded to 256 bytes) and, behind them, its keypoints: pinned staging and the device copy */
@@ -328,6 +340,7 @@ struct vksift_Instance_T
   vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created by the first guided matching) */
   vksift_hip_event ev_ttab; /* the last track build has copied tracks.h_tab (created by the first build) */
   vksift_hip_event ev_otab; /* the last observation launches have read obs.h_tab (created by the first selection) */
+  vksift_hip_event ev_ctab; /* the last triangulation has copied tri.h_cameras (created by the first triangulation) */
   vksift_hip_event ev_kps;  /* the last describe call's copy has read h_kps (created by the first describe call) */
   bool desc_start_valid, input_free_valid, staging_pending, kps_pending;
   DetectSlot det_ring[VKSIFT_DETECT_RING];
