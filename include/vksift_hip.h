@@ -115,8 +115,12 @@ extern "C"
     VKSIFT_TUNE_TAIL_FUSED = 13, /* tail of the keypoint extraction (ballots -> records): 0 = built-in (batches of 64 images and more take one launch with one
                                   * workgroup per image and octave, smaller calls the four sparse launches), 1: always the four launches, 2: always the one, 3: as 2 with the 512-thread workgroups that launches
                                   * of 512 workgroups and more take (tests of that form at small sizes) */
+    VKSIFT_TUNE_DESC_SOLO_R = 14, /* two-wave descriptor launch (batches of 8 and more): the largest window radius R at which a keypoint is described by one
+                                   * wave alone, two such keypoints per workgroup; 0: none (every keypoint on both waves, one keypoint per workgroup), 63 and
+                                   * more: every keypoint with R <= 63. Built-in: VKSIFT_HIP_DESC_SOLO_R */
     VKSIFT_TUNE_COUNT = 16
   };
+#define VKSIFT_HIP_DESC_SOLO_R 63 /* built-in value of VKSIFT_TUNE_DESC_SOLO_R */
   int vksift_hip_tune(int knob, int value);
   int vksift_hip_tune_get(int knob);
 

@@ -7,8 +7,10 @@ against the hardware's own instruction count and the measured time (VERDICT r04 
         downloaded and, per keypoint, the kernel's own sample enumeration restated in numpy (window, analytic row spans: features.hip
         k_descriptor) -> samples, wave steps, loop iterations; runs tools/_valu_cost_table (tools/microbench/valu_cost_table.hip)
     python tools/descriptor_floor.py report --inputs <json> [--sq profiles/r05_sq_counters.json] [--out profiles/r05_descriptor_floor]   (anywhere with hipcc)
-        compiles features.hip to ISA, splits k_descriptor<2, true, false> into its regions (per keypoint / row-span pass / sample loop /
-        odd tail / epilogue), counts every mnemonic, prices it, writes the reconciliation (markdown + json)
+        compiles features.hip to ISA, splits k_descriptor<2, false, false> into its regions — the pair predicate and, for each of the two modes
+        of the pair-mode kernel (solo: one wave per keypoint in DESC_SOLO_PHASES phases, team: two waves), per keypoint / per phase / sample
+        loop / odd tail / epilogue — counts every mnemonic, prices it, writes the reconciliation (markdown + json)
+        (--costs-from <json>: take the issue-cost table of an earlier inputs file when tools/_valu_cost_table was not run)
 """
 import argparse
 import collections
@@ -70,6 +72,21 @@ def sample_counts(feats, w0, h0, upsampling=True):
     return out
 
 
+def desc_radius(feats):
+    """R of every record's descriptor window (features.hip desc_radius), float32 arithmetic in the kernel's order"""
+    import numpy as np
+    f32 = np.float32
+    sf = np.exp2(feats["octave_idx"].astype(f32)).astype(f32)
+    lam = f32(3.0) * (feats["sigma"].astype(f32) / sf)
+    radius = f32(math.sqrt(2.0)) * lam * f32(5.0) * f32(0.5)
+    return np.floor(radius + f32(0.5)).astype(np.int64)
+
+
+def solo_phases():
+    src = open(os.path.join(ROOT, "vulkansift_amd", "csrc", "hip", "features.hip")).read()
+    return int(re.search(r"#define DESC_SOLO_PHASES (\d+)", src).group(1))
+
+
 def orientation_counts(feats, w0, h0, upsampling=True):
     """k_orientation's work for one image: it runs once per KEYPOINT (the records of one keypoint's orientations share position, scale and
     sigma), one wave each, npix = (2 r + 1)^2 window texels in steps of 64; keypoints whose window touches the image border take the general loop.
@@ -119,6 +136,10 @@ def collect(args):
     inst.setProfiling(False)
     stage = {k: acc[k] / max(acc["nb_calls"], 1) for k in ("pyramid_ms", "scan_ms", "orientation_ms", "descriptor_ms", "total_ms")}
     K = steps = samples = iters = odd = 0
+    solo_r = api.lib().vksift_hip_tune_get(14)  # VKSIFT_TUNE_DESC_SOLO_R
+    nph = solo_phases()
+    modes = {"solo": collections.Counter(), "team": collections.Counter()}
+    pair_slots = 0
     ori = [0, 0, 0, 0]
     hist = collections.Counter()
     per_oct = collections.Counter()
@@ -131,12 +152,31 @@ def collect(args):
         t = (n + 63) // 64
         # two waves per keypoint (batch >= 8): the first takes ceil(t / 2) steps, the second floor(t / 2); a wave's loop does two
         # steps per iteration and one odd step in the tail
-        r0, r1 = (t + 1) // 2, t // 2
         K += len(f)
         samples += int(n.sum())
         steps += int(t.sum())
-        iters += int((r0 // 2).sum() + (r1 // 2).sum())
-        odd += int((r0 % 2).sum() + (r1 % 2).sum())
+        # pair mode (features.hip k_descriptor): keypoints 2 kb, 2 kb + 1 of a section (= octave) go solo when both have R <= solo_r
+        R = desc_radius(f)
+        solo = np.zeros(len(f), bool)
+        for o in np.unique(f["octave_idx"]):
+            idx = np.flatnonzero(f["octave_idx"] == o)
+            pair_slots += (len(idx) + 1) // 2 if solo_r else len(idx)
+            if solo_r:
+                m = len(idx) // 2 * 2
+                ok = (R[idx[:m:2]] <= min(solo_r, 63)) & (R[idx[1:m:2]] <= min(solo_r, 63))
+                solo[idx[:m:2]] = ok
+                solo[idx[1:m:2]] = ok
+        for name, sel, parts in (("solo", solo, nph), ("team", ~solo, 2)):
+            ts = t[sel]
+            md = modes[name]
+            md["keypoints"] += int(sel.sum())
+            md["wave_steps"] += int(ts.sum())
+            for p in range(parts):  # desc_run: whole steps, the first T % parts shares take one more
+                sp = ts // parts + (p < ts % parts)
+                md["pair_iterations"] += int((sp // 2).sum())
+                md["odd_tail_steps"] += int((sp % 2).sum())
+                iters += int((sp // 2).sum())
+                odd += int((sp % 2).sum())
         for o in f["octave_idx"]:
             per_oct[int(o)] += 1
         for v in t:
@@ -151,6 +191,8 @@ def collect(args):
         "stage_ms_per_call": stage,
         "keypoints": K * scale, "samples": samples * scale, "wave_steps": steps * scale, "pair_iterations": iters * scale, "odd_tail_steps": odd * scale,
         "waves_per_keypoint": 2,
+        "solo_r": solo_r, "solo_phases": nph, "pair_slots": pair_slots * scale,
+        "modes": {k: {kk: vv * scale for kk, vv in v.items()} for k, v in modes.items()},
         "mean_samples_per_keypoint": samples / max(K, 1), "mean_steps_per_keypoint": steps / max(K, 1),
         "lane_fill": samples / max(steps * 64, 1),
         "keypoints_per_octave": dict(sorted(per_oct.items())),
@@ -163,7 +205,7 @@ def collect(args):
 
 
 # ------------------------------------------------------------------------------------------------ report
-KERNEL = "_ZN12_GLOBAL__N_112k_descriptorILi2ELb1ELb0EEEv5MultiINS_8FeatArgsEE"
+KERNEL = "_ZN12_GLOBAL__N_112k_descriptorILi2ELb0ELb0EEEv5MultiINS_8FeatArgsEE"  # two waves, keypoint index fastest (what batches launch), fp32 planes
 
 
 ORI_KERNEL = "_ZN12_GLOBAL__N_113k_orientationILb1ELb0EEEv5MultiINS_8FeatArgsEE"
@@ -212,42 +254,79 @@ def blocks_of(lines):
 
 
 def regions(blocks):
-    """text-order split: the sample loop is the innermost-depth run of blocks holding the eight ds_add_u64 of two samples"""
+    """text-order split of the pair-mode kernel. Its keypoint loop holds the pair predicate and two bodies (desc_keypoint for one wave in phases,
+    and for two waves); each body is per-keypoint blocks, the blocks of its phase loop in front of the sample loop (run search), the sample loop
+    (the innermost blocks with the eight ds_add_u64 of two samples, from the block that loads and prices the samples to where the depth drops),
+    the odd tail step (four more); the two epilogues are laid out behind both bodies. The body with an s_barrier is the two-wave one.
+    -> ({region name: [block index, ...]}, slow-path blocks left out, {mode: depth of its phase loop's blocks})"""
     n_add = [sum(1 for m in b[2] if m == "ds_add_u64") for b in blocks]
-    # main loop: the contiguous run of blocks at depth >= 3 that contains 8 atomics
-    runs, cur = [], []
-    for i, b in enumerate(blocks):
-        if b[1] >= 3:
+    valu = [sum(1 for m in b[2] if m.startswith("v_")) for b in blocks]
+    groups, cur = [], []  # runs of consecutive blocks with an atomic each
+    for i, n in enumerate(n_add):
+        if n:
             cur.append(i)
-        else:
-            if cur:
-                runs.append(cur)
+        elif cur:
+            groups.append(cur)
             cur = []
     if cur:
-        runs.append(cur)
-    main = next(r for r in runs if sum(n_add[i] for i in r) == 8)
-    # the slow path inside it: the block a s_cbranch_vccnz of the loop jumps to (inputs below 2^-96: never seen)
-    targets = {t.split()[-1] for i in main for t in blocks[i][3] if t.startswith("s_cbranch_vccnz")}
-    slow = []
-    for i in main:
-        if blocks[i][0] in targets:  # ... and the blocks behind it up to the unconditional branch back into the loop
-            j = i
-            while j in main:
-                slow.append(j)
-                if any(t.startswith("s_branch") for t in blocks[j][3]):
-                    break
-                j += 1
-    after = main[-1] + 1
-    epi = next(i for i in range(after, len(blocks)) if blocks[i][1] <= 1)
-    tail = list(range(after, epi))
-    reg = {
-        "entry (once per workgroup)": [0],
-        "per keypoint: constants, zeroing, row spans, prefix scan, run search": list(range(1, main[0])),
-        "sample loop, two samples per lane per iteration": [i for i in main if i not in slow],
-        "odd tail step": tail,
-        "epilogue (wave 0: normalise, clamp, pack)": list(range(epi, len(blocks))),
-    }
-    return reg, slow
+        groups.append(cur)
+    loops = [g for g in groups if sum(n_add[i] for i in g) == 8]
+    tails = [g for g in groups if sum(n_add[i] for i in g) == 4]
+    assert len(loops) == 2 and len(tails) == 2, "two sample loops and two odd tail steps: solo and team"
+    first_kp = next(i for i, b in enumerate(blocks) if b[1] >= 1)
+    bodies, start, slow_all = [], None, []
+    for lp, tl in zip(loops, tails):
+        d = blocks[lp[0]][1]
+        m1 = lp[-1]
+        while m1 + 1 < tl[0] and blocks[m1 + 1][1] >= d:
+            m1 += 1
+        # the loop's header: the first block in front of the atomics that a branch of the loop goes back to (next sample, taps, arithmetic follow it)
+        back = {t.split()[-1] for i in range(lp[0], m1 + 1) for t in blocks[i][3] if t.startswith(("s_cbranch", "s_branch"))}
+        m0 = min(i for i in range(lp[0]) if blocks[i][0] in back and blocks[i][1] == d and i > (bodies[-1]["end"] if bodies else 0))
+        assert any(m.startswith("buffer_load") for i in range(m0, lp[0]) for m in blocks[i][2]), "the taps are loaded inside the loop"
+        main = list(range(m0, m1 + 1))
+        targets = {t.split()[-1] for i in main for t in blocks[i][3] if t.startswith("s_cbranch_vccnz")}
+        slow = []
+        for i in main:
+            if blocks[i][0] in targets:  # the general-form fallback of a step and the blocks behind it up to the branch back into the loop
+                j = i
+                while j in main:
+                    slow.append(j)
+                    if any(t.startswith("s_branch") for t in blocks[j][3]):
+                        break
+                    j += 1
+        ph0 = m0
+        while blocks[ph0 - 1][1] >= d - 1:
+            ph0 -= 1
+        bodies.append({"main": [i for i in main if i not in slow], "tail": list(range(m1 + 1, tl[-1] + 1)), "phase": list(range(ph0, m0)), "m0": m0, "end": tl[-1], "depth": d - 1})
+        slow_all += slow
+    # the bodies' first blocks: the set-up (sincos, divisions: > 100 VALU at depth <= 2) of each; the predicate lies in front of the first one
+    setups = [i for i, b in enumerate(blocks) if valu[i] > 100 and b[1] <= 2 and i < bodies[1]["m0"] and not any(m.startswith("global_store") for m in b[2])]
+    assert any(i < bodies[0]["m0"] for i in setups) and any(i > bodies[0]["end"] for i in setups)
+    s0 = 1 + next(i for i in range(first_kp, len(blocks)) if any(m.startswith("v_rcp_f32") for m in blocks[i][2]))  # the predicate ends with desc_radius' division
+    bodies[0]["kp"] = list(range(s0, bodies[0]["phase"][0]))
+    bodies[1]["kp"] = list(range(bodies[0]["end"] + 1, bodies[1]["phase"][0]))
+    epi_all = list(range(bodies[1]["end"] + 1, len(blocks)))
+    heads = [i for i in epi_all if valu[i] > 100 and any(m.startswith("global_store") for m in blocks[i][2])]
+    assert len(heads) == 2, "two epilogues"
+    epis = [list(range(heads[0], heads[1])), list(range(heads[1], len(blocks)))]
+    for bd in bodies:
+        bd["team"] = any(m == "s_barrier" for i in bd["kp"] + bd["phase"] for m in blocks[i][2])
+    assert bodies[0]["team"] != bodies[1]["team"]
+    epis.sort(key=lambda e: -blocks[e[0]][1])  # the team's epilogue lies inside the loop over the keypoints of a pair: one level deeper
+    reg = {"entry (once per workgroup)": list(range(0, first_kp)), "pair predicate (both waves, once per pair)": list(range(first_kp, s0))}
+    depth = {}
+    for bd in bodies:
+        mode = "team" if bd["team"] else "solo"
+        if bd["team"]:  # one phase: its run search is part of the per-keypoint work
+            bd["kp"], bd["phase"] = bd["kp"] + bd["phase"], []
+        depth[mode] = bd["depth"]
+        reg[f"{mode}: per keypoint: constants, zeroing, row spans, prefix scan"] = bd["kp"]
+        reg[f"{mode}: per phase: run search"] = bd["phase"]
+        reg[f"{mode}: sample loop, two samples per lane per iteration"] = bd["main"]
+        reg[f"{mode}: odd tail step"] = bd["tail"]
+        reg[f"{mode}: epilogue (normalise, clamp, pack)"] = epis[0] if bd["team"] else epis[1]
+    return reg, slow_all, depth
 
 
 def klass(m):
@@ -288,6 +367,8 @@ def cost_key(m):
 
 def report(args):
     inp = json.load(open(args.inputs))
+    if not inp.get("costs_ps") and args.costs_from:
+        inp["costs_ps"] = json.load(open(args.costs_from))["costs_ps"]
     costs = dict(inp["costs_ps"])
     # 128 back-to-back v_cndmask_b32_e32 on a VCC that an s_mov wrote long before measure 9.5 ns each — five times the e64 form on an SGPR
     # pair, and five times what the same instruction costs behind the v_cmp that wrote its VCC (the triple v_cmp + s_nop 1 + v_cndmask:
@@ -295,18 +376,20 @@ def report(args):
     anomaly = costs["v_cndmask_b32_e32"]
     costs["v_cndmask_b32_e32"] = costs["v_cndmask_b32_e64"]
     blocks = blocks_of(kernel_isa())
-    reg, slow = regions(blocks)
-    K, IT, ODD = inp["keypoints"], inp["pair_iterations"], inp["odd_tail_steps"]
-    WPK = inp["waves_per_keypoint"]
-    # executions per call of each region (wave-level): per-keypoint regions run in both waves of the keypoint's workgroup; the epilogue's
-    # body in wave 0 only (wave 1 takes the branch around it: a handful of instructions, counted as the body's 1/2)
-    execs = {
-        "entry (once per workgroup)": None,
-        "per keypoint: constants, zeroing, row spans, prefix scan, run search": K * WPK,
-        "sample loop, two samples per lane per iteration": IT,
-        "odd tail step": ODD,
-        "epilogue (wave 0: normalise, clamp, pack)": K * WPK / 2,
-    }
+    reg, slow, phase_depth = regions(blocks)
+    md = inp["modes"]
+    NPH = inp["solo_phases"]
+    IT, ODD = inp["pair_iterations"], inp["odd_tail_steps"]
+    # executions per call of each region (wave-level). Solo: one wave per keypoint, the run search once per phase. Team: the per-keypoint
+    # regions run in both waves of the workgroup, the epilogue's body in wave 0 only. The predicate: both waves, once per pair slot.
+    execs = {"entry (once per workgroup)": None, "pair predicate (both waves, once per pair)": 2 * inp["pair_slots"]}
+    for mode, waves, phases in (("solo", 1, NPH), ("team", 2, 1)):
+        k = md[mode]["keypoints"]
+        execs[f"{mode}: per keypoint: constants, zeroing, row spans, prefix scan"] = k * waves
+        execs[f"{mode}: per phase: run search"] = k * waves * phases
+        execs[f"{mode}: sample loop, two samples per lane per iteration"] = md[mode]["pair_iterations"]
+        execs[f"{mode}: odd tail step"] = md[mode]["odd_tail_steps"]
+        execs[f"{mode}: epilogue (normalise, clamp, pack)"] = k
     # inner loops of the per-keypoint part that run more than once per keypoint: the binary search over the prefix array
     mean_rows = 2.0 * math.sqrt(inp["mean_samples_per_keypoint"] / 0.5) / 2.0 + 1  # window side ~ sqrt(2 N)
     search_iters = max(1.0, math.log2(max(mean_rows, 2.0)))
@@ -316,14 +399,14 @@ def report(args):
     total_ps = 0.0
     for name, idxs in reg.items():
         n = execs[name]
-        if n is None:
+        if n is None or not idxs:
             continue
         cnt = collections.Counter()
         ps = 0.0
         for i in idxs:
             b = blocks[i]
             mult = 1.0
-            if name.startswith("per keypoint") and b[1] >= 3 and len(b[2]) <= 20 and any(t.startswith("s_cbranch_execnz") for t in b[3]) and any(m == "ds_read_b32" for m in b[2]) and not any(m.startswith("v_cvt") for m in b[2]):
+            if ("per keypoint" in name or "per phase" in name) and b[1] >= 3 and len(b[2]) <= 20 and any(t.startswith("s_cbranch_execnz") for t in b[3]) and any(m == "ds_read_b32" for m in b[2]) and not any(m.startswith("v_cvt") for m in b[2]):
                 mult = search_iters  # the bisection loop (one LDS read, a compare, two selects per step)
             for m in b[2]:
                 k = klass(m)
@@ -345,15 +428,14 @@ def report(args):
     n_atomics = IT * 8 + ODD * 4
     lds_ms = n_atomics * costs["ds_add_u64@16"] / 256 * 1e-9
     # the sample loop's VALU instructions by cost class
-    loop = next(r for r in rows if r["region"].startswith("sample loop"))
     by_key = collections.Counter()
-    for i in reg["sample loop, two samples per lane per iteration"]:
+    for i in reg["solo: sample loop, two samples per lane per iteration"]:
         for m in blocks[i][2]:
             if klass(m) == "valu":
                 by_key[cost_key(m)] += 1
     loop_table = sorted(((k, c, costs.get(k, costs["v_cvt_u32_f32_e32"])) for k, c in by_key.items()), key=lambda x: -x[1] * x[2])
     res = {
-        "kernel": "k_descriptor<2, true, false> (two waves per keypoint, image index fastest, fp32 planes)",
+        "kernel": "k_descriptor<2, false, false> (pair mode: one wave per keypoint in phases, or two waves; keypoint index fastest, fp32 planes)",
         "inputs": {k: v for k, v in inp.items() if k != "costs_ps"},
         "regions": rows,
         "predicted_wave_instructions_per_call": {k: v for k, v in total.items()},
@@ -399,7 +481,7 @@ def report(args):
           f"{costs['ds_add_u64@64'] / 1e3:.2f}, 8: {costs['ds_add_u64@8'] / 1e3:.2f}, one: {costs['ds_add_u64@1'] / 1e3:.1f}) = {lds_ms:.2f} ms on each CU's LDS pipe, concurrent with the VALU.\n\n")
         w(f"(`v_cndmask_b32_e32` is priced as the e64 form: back to back on a VCC written by an `s_mov` long before it measures {anomaly / 1e3:.1f} ns, behind the `v_cmp` that "
           f"wrote its VCC — every select of this kernel — the triple v_cmp + s_nop 1 + v_cndmask measures {costs['triple:v_cmp+s_nop1+v_cndmask'] / 1e3:.2f} ns in all.)\n\n")
-        w("Sample loop, VALU instructions per iteration (two samples per lane) by mnemonic, most expensive first:\n\n| mnemonic | per iteration | ps each | ns |\n|---|---|---|---|\n")
+        w("Sample loop (solo), VALU instructions per iteration (two samples per lane) by mnemonic, most expensive first:\n\n| mnemonic | per iteration | ps each | ns |\n|---|---|---|---|\n")
         for k, c, p in loop_table:
             w(f"| `{k}` | {c} | {p:.0f} | {c * p / 1e3:.2f} |\n")
         if ori:
@@ -504,6 +586,7 @@ def main():
     c.add_argument("--out", default="gpurun_out/descriptor_floor_inputs.json")
     r = sub.add_parser("report")
     r.add_argument("--inputs", required=True)
+    r.add_argument("--costs-from", default=None, help="an earlier inputs file whose issue-cost table is used when --inputs has none")
     r.add_argument("--sq", default=os.path.join(ROOT, "profiles", "r05_sq_counters.json"))
     r.add_argument("--out", default=os.path.join(ROOT, "profiles", "r05_descriptor_floor"))
     a = ap.parse_args()

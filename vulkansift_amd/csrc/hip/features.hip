@@ -425,7 +425,10 @@ __device__ __forceinline__ DescSample desc_sample(const DescCtx &c, int cdx, int
 // VALU issue.) Only the 16 grid cells are ever touched.
 constexpr int DESC_PAD = 1, DESC_ROW_CELLS = 8; // rows of 8 cells: a grid column keeps the LDS banks it had in the dense 4x4 layout
 constexpr int DESC_HIST_WORDS = (4 + 2 * DESC_PAD) * DESC_ROW_CELLS * 16; // 6 rows x 8 cells x (8 + 8) words = 3 KiB
-constexpr int DESC_WORK_WORDS = DESC_HIST_WORDS;
+// what a workgroup keeps of it: up to the last grid cell (the array cells behind it are never addressed by an executed add). The two-wave form holds two
+// histograms; with whole arrays its 10 252 bytes of LDS would leave a CU 15 workgroups (30 waves) instead of the 16 its eight waves per SIMD allow.
+constexpr int DESC_WORK_WORDS = ((4 + DESC_PAD - 1) * DESC_ROW_CELLS + (4 + DESC_PAD - 1) + 1) * 16; // 592 words
+static_assert(DESC_WORK_WORDS <= DESC_HIST_WORDS && DESC_WORK_WORDS % 2 == 0, "64-bit slots");
 __device__ __forceinline__ int desc_cell_word(int cell) // first word of grid cell cy * 4 + cx
 {
   return (((cell >> 2) + DESC_PAD) * DESC_ROW_CELLS + (cell & 3) + DESC_PAD) * 16;
@@ -515,6 +518,15 @@ __device__ __forceinline__ void desc_dense_prologue(const FeatArgs &a, const vks
   }
 }
 
+// ---- step: the window radius R of a keypoint (ComputeDescriptors.comp:107-109) and the bin width lambda it comes from
+__device__ __forceinline__ int desc_radius(float sigma, int octave_idx, float *lambda)
+{
+  float scale_factor = dm_pow2i(octave_idx);
+  *lambda = 3.0f * (sigma / scale_factor);
+  float radius = sqrtf(2.f) * *lambda * 5.f * 0.5f;
+  return (int)floorf(radius + 0.5f);
+}
+
 // ---- step: per-keypoint set-up
 __device__ __forceinline__ DescCtx desc_setup(const FeatArgs &a, const ImageView &g, const KeyHead &kh)
 {
@@ -523,10 +535,8 @@ __device__ __forceinline__ DescCtx desc_setup(const FeatArgs &a, const ImageView
   c.rs = kh.rs;
   c.pitch = g.pitch, c.pitch4 = g.pitch * 4;
   c.bin_scale = a.use_vlfeat ? 8.f : -8.f;
-  float scale_factor = dm_pow2i(kh.octave_idx);
-  float lambda = 3.0f * (kh.sigma / scale_factor);
-  float radius = sqrtf(2.f) * lambda * 5.f * 0.5f;
-  int R = (int)floorf(radius + 0.5f);
+  float lambda;
+  const int R = desc_radius(kh.sigma, kh.octave_idx, &lambda);
   float sn, cs;
   dm_sincosf(c.kori, &sn, &cs);
   c.kcos = cs / lambda, c.ksin = sn / lambda;
@@ -797,19 +807,107 @@ __device__ __forceinline__ void desc_epilogue(const vksift_hip_DenseRows &dr, co
     desc_dense_row(dr, b, *s_row0, k, ln, p0, p1);
 }
 
+// ---- one keypoint, set-up to epilogue, on NW waves of the workgroup (wave = 0 .. NW - 1, tid = 0 .. 64 * NW - 1 among them) with their histogram,
+// row arrays of MAXR entries and prefix array (MAXR + 1). NW = 1: the wave shares nothing with its neighbours and only its own program order
+// separates the steps (LDS executes a wave's operations in order); otherwise workgroup barriers do, and the first one stands between the previous
+// keypoint's epilogue and the zeroing.
+// NPH: every wave walks its share of the steps in NPH phases, one after the other — the runs desc_run deals out to NW * NPH waves. What costs a
+// wave alone on a keypoint is not its number of steps but the length of its lanes' runs: with T steps in one phase the 64 lanes of a load sit T
+// samples apart, one or two to a window row, each in a cache line of its own. Counted on 512 frames with every keypoint on one wave in one phase
+// against two waves: SQ_VMEM_TA_ADDR_FIFO_FULL 2.65 G against 0.24 G cycles, L1 misses (TCP_TCC_READ_REQ) 1.24 G against 0.69 G, 5 % fewer VALU
+// instructions and 11.2 ms against 6.85 (the "55 % slower" of every earlier one-wave form). Phases give the lanes the short runs of a team.
+template <int NW>
+__device__ __forceinline__ void desc_sync()
+{
+  if (NW == 1)
+    __builtin_amdgcn_wave_barrier();
+  else
+    __syncthreads();
+}
+template <int NW, int NPH, int MAXR, bool PAIRS, bool CAN_POST, bool F16>
+__device__ __forceinline__ void desc_keypoint(const FeatArgs &a, const vksift_hip_DenseRows &dr, const ImageView &g, int b, uint32_t k, int wave, int tid,
+                                              uint32_t *s_work, int *s_lo, uint32_t *s_cnt, uint32_t *s_pre, const uint32_t *s_row0)
+{
+  // (PAIRS, the kernel with two call sites in its keypoint loop: opaque copies of the thread index for the steps around the sample loop, as in
+  // desc_epilogue — the LDS addresses derived from it were hoisted out of the loop into registers the sample loop cannot spare, and one of them spilled)
+  desc_sync<NW>(); // the previous keypoint's epilogue has read the histogram
+  {
+    int zt = tid;
+    if (PAIRS)
+      asm volatile("" : "+v"(zt));
+    for (int i = zt; i < 256; i += 64 * NW)
+      s_work[desc_cell_word(i >> 4) + (i & 15)] = 0; // the 16 grid cells; made visible by the barrier behind the row-span pass below
+  }
+
+  const KeyHead kh = keypoint_head<F16>(a, g, b, k);
+  const DescCtx c = desc_setup(a, g, kh);
+  const int bh = c.dy1 - c.dy0 + 1;
+  for (int rb = 0; rb < bh; rb += MAXR)
+  {
+    const DescRows rows{s_lo, s_cnt, s_pre, c.dy0 + rb, min(MAXR, bh - rb)};
+    int rt = tid;
+    if (PAIRS)
+      asm volatile("" : "+v"(rt));
+    desc_sync<NW>();
+    desc_row_spans<64 * NW>(c, rows, rt);
+    desc_sync<NW>();
+    desc_row_prefix(rows, s_pre, rt & 63);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int ph = 0; ph < NPH; ph++)
+    {
+      int pt = tid;
+      if (PAIRS)
+        asm volatile("" : "+v"(pt));
+      DescRun run = desc_run<NW * NPH>(rows, wave * NPH + ph, pt & 63);
+      uint32_t it = 0;
+      for (; it + 1 < run.steps; it += 2)
+        desc_step_pair<F16>(c, rows, run, s_work);
+      if (it < run.steps) // odd number of steps
+        desc_step_odd<F16>(c, rows, run, s_work);
+    }
+  }
+  desc_sync<NW>();
+  if (wave == 0)
+    desc_epilogue<CAN_POST>(dr, g, b, k, kh.rec, s_work, s_row0, tid & 63);
+}
+
+// ---- pair mode of the two-wave form: are the windows of keypoints k0 and k0 + 1 both small enough (R <= solo_r) for one wave each? Even lanes
+// derive R of the first, odd lanes of the second, as desc_setup does; every wave of the workgroup gets the same answer.
+// Phases of a solo wave, 512 frames, descriptor stage against the two-wave launch of the same build and call: 1: +67 %, 2: 0 %, 3: -8.2 %, 4: -9 %,
+// 5: -8 %, 6: -5.5 %, 8: -1.2 % (short phases end in an odd step more often, and each phase searches its runs).
+#ifndef DESC_SOLO_PHASES
+#define DESC_SOLO_PHASES 4
+#endif
+constexpr int DESC_SOLO_MAX_R = 63; // a solo wave owns half of the row arrays: 2 R + 1 <= DESC_MAX_ROWS / 2
+__device__ __forceinline__ bool desc_pair_small(const ImageView &g, uint32_t k0, int lane, uint32_t solo_r)
+{
+  const float *rec = (const float *)(g.feats + (size_t)(k0 + ((uint32_t)lane & 1u)) * VKSIFT_RECORD_BYTES);
+  float lambda;
+  const int R = desc_radius(rec[6], ((const int *)rec)[5], &lambda);
+  return __ballot(R > (int)solo_r) == 0ull;
+}
+
+// solo_r (two-wave form only, 0 .. DESC_SOLO_MAX_R; 0: every keypoint on the whole workgroup, one keypoint per workgroup and sweep): a workgroup owns the
+// keypoints 2 kb and 2 kb + 1 of a sweep. Where both windows have R <= solo_r, wave i runs keypoint 2 kb + i alone (solo: the set-up once per keypoint
+// instead of once per wave, no workgroup barrier, no wave idle during the epilogue); otherwise — and for an odd last keypoint — both waves run the
+// two keypoints one after the other (team). The histogram sums are integer adds: the bytes do not depend on the split.
+// LDS: 8 848 bytes per workgroup (two histograms of 2 368, row arrays 2 048, two prefix arrays 2 056, s_row0), 18 workgroups per CU by LDS: the 16 of
+// eight waves per SIMD stay the limit.
 template <int NWV, bool IMG_FAST, bool F16>
 __global__ void __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu((NWV == 2 && !F16) ? 8 : 6, 8)))
-k_descriptor(Multi<FeatArgs> m, vksift_hip_DenseRows dr)
+k_descriptor(Multi<FeatArgs> m, vksift_hip_DenseRows dr, uint32_t solo_r)
 {
   const VBlock vb = vblock(m); // virtual grid (images, blocks) when IMG_FAST, (blocks, images) otherwise
   const FeatArgs &a = m.oct[vb.o];
-  constexpr int NT_ = 64 * NWV;
-  __shared__ __attribute__((aligned(8))) uint32_t s_work[DESC_WORK_WORDS]; // see desc_scatter
+  constexpr int NSOLO = NWV == 2 ? 2 : 1; // histograms: one per solo wave
+  static_assert(2 * DESC_SOLO_MAX_R + 1 <= DESC_MAX_ROWS / 2, "a solo window's rows fit half of the row arrays");
+  __shared__ __attribute__((aligned(8))) uint32_t s_work[NSOLO][DESC_WORK_WORDS]; // see desc_scatter
   __shared__ int s_row_lo[DESC_MAX_ROWS];
   __shared__ uint32_t s_row_cnt[DESC_MAX_ROWS];
   __shared__ uint32_t s_row_pre[NWV][DESC_MAX_ROWS + 1];
   __shared__ uint32_t s_row0;
-  const int tid = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tid = threadIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = (int)(IMG_FAST ? vb.x : vb.y);
   const ImageView g = image_view(a, b);
   const uint32_t bk = IMG_FAST ? vb.y : vb.x, nbk = IMG_FAST ? vb.gy : vb.gx;
@@ -818,33 +916,22 @@ k_descriptor(Multi<FeatArgs> m, vksift_hip_DenseRows dr)
   constexpr bool CAN_POST = NWV == 4;
   desc_dense_prologue<CAN_POST>(a, dr, b, bk == 0, tid, &s_row0);
 
-  for (uint32_t k = bk; k < g.n; k += nbk)
+  const uint32_t per = (NWV == 2 && solo_r != 0u) ? 2u : 1u; // keypoints per workgroup and sweep
+  if (per == 2u)
+    __syncthreads(); // s_row0: a solo wave 1 reads it with no other workgroup barrier behind wave 0's store
+  for (uint32_t k0 = bk * per; k0 < g.n; k0 += nbk * per)
   {
-    __syncthreads(); // the previous keypoint's epilogue has read the histogram
-    for (int i = tid; i < 256; i += NT_)
-      s_work[desc_cell_word(i >> 4) + (i & 15)] = 0; // the 16 grid cells; made visible by the barrier behind the row-span pass below
-
-    const KeyHead kh = keypoint_head<F16>(a, g, b, k);
-    const DescCtx c = desc_setup(a, g, kh);
-    const int bh = c.dy1 - c.dy0 + 1;
-    for (int rb = 0; rb < bh; rb += DESC_MAX_ROWS)
-    {
-      const DescRows rows{s_row_lo, s_row_cnt, s_row_pre[wave], c.dy0 + rb, min(DESC_MAX_ROWS, bh - rb)};
-      __syncthreads();
-      desc_row_spans<NT_>(c, rows, tid);
-      __syncthreads();
-      desc_row_prefix(rows, s_row_pre[wave], lane);
-      __builtin_amdgcn_wave_barrier();
-      DescRun run = desc_run<NWV>(rows, wave, lane);
-      uint32_t it = 0;
-      for (; it + 1 < run.steps; it += 2)
-        desc_step_pair<F16>(c, rows, run, s_work);
-      if (it < run.steps) // odd number of steps
-        desc_step_odd<F16>(c, rows, run, s_work);
-    }
-    __syncthreads();
-    if (wave == 0)
-      desc_epilogue<CAN_POST>(dr, g, b, k, kh.rec, s_work, &s_row0, lane);
+    if constexpr (NWV == 2)
+      if (per == 2u && k0 + 1u < g.n && desc_pair_small(g, k0, lane, solo_r))
+      {
+        constexpr int HALF = DESC_MAX_ROWS / 2;
+        desc_keypoint<1, DESC_SOLO_PHASES, HALF, true, CAN_POST, F16>(a, dr, g, b, k0 + (uint32_t)wave, 0, lane, s_work[wave], s_row_lo + wave * HALF, s_row_cnt + wave * HALF,
+                                              s_row_pre[wave], &s_row0);
+        continue;
+      }
+    const uint32_t k1 = min(k0 + per, g.n);
+    for (uint32_t k = k0; k < k1; k++)
+      desc_keypoint<NWV, 1, DESC_MAX_ROWS, NWV == 2, CAN_POST, F16>(a, dr, g, b, k, wave, tid, s_work[0], s_row_lo, s_row_cnt, s_row_pre[wave], &s_row0);
   }
 }
 
@@ -940,12 +1027,16 @@ static int descriptor_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t
   Multi<FeatArgs> md;
   md.n = 0;
   const bool f = img_fast(batch, true);
-  for (uint32_t i = 0; i < n; i++)
-    if (!add_octave(md, make_args(&jobs[i]), f, batch, octave_blocks(&jobs[i], batch, 1, 2048)))
-      return (int)hipErrorInvalidValue;
   /* waves per keypoint: 4 keep the critical path of a single image short (1 wave: 55 % slower, 8: no faster than 4); a batch has keypoints
    * to spare and runs 3-4 % faster with 2 (less redundant per-keypoint work, measured under the overlapped batch schedule) */
   const bool two_waves = batch >= 8u;
+  /* pair mode of the two-wave form (k_descriptor): the largest R a wave takes alone; 0: none, one keypoint per workgroup as in the four-wave form.
+   * Swept on 512 frames (R there is 17 .. 34): the descriptor stage falls as the threshold rises, 0: 6.96, 28: 6.78, 63: 6.36 ms */
+  const int tune_r = vksift_hip_tune_get(VKSIFT_TUNE_DESC_SOLO_R);
+  const uint32_t solo_r = !two_waves || tune_r <= 0 ? 0u : (tune_r > DESC_SOLO_MAX_R ? (uint32_t)DESC_SOLO_MAX_R : (uint32_t)tune_r);
+  for (uint32_t i = 0; i < n; i++)
+    if (!add_octave(md, make_args(&jobs[i]), f, batch, octave_blocks(&jobs[i], batch, solo_r ? 2 : 1, 2048)))
+      return (int)hipErrorInvalidValue;
   if (dr.post && two_waves)
     return (int)hipErrorInvalidValue; /* posting is compiled into the four-wave form only */
   const bool f16 = md.oct[0].fp16 != 0;
@@ -954,7 +1045,7 @@ static int descriptor_run(const vksift_hip_OctaveJob *jobs, uint32_t n, uint32_t
     constexpr int NWV = decltype(TWO)::value ? 2 : 4;
     with_bool(f, [&](auto IMG_FAST) {
       with_bool(f16, [&](auto F16) {
-        hipLaunchKernelGGL((k_descriptor<NWV, decltype(IMG_FAST)::value, decltype(F16)::value>), grid, dim3(64 * NWV), 0, hs, md, dr);
+        hipLaunchKernelGGL((k_descriptor<NWV, decltype(IMG_FAST)::value, decltype(F16)::value>), grid, dim3(64 * NWV), 0, hs, md, dr, solo_r);
       });
     });
   });
