@@ -5,11 +5,11 @@ against the hardware's own instruction count and the measured time (VERDICT r04 
     python tools/descriptor_floor.py collect [--frames 512] [--out gpurun_out/descriptor_floor_inputs.json]      (on the GPU box)
         the bench's frames through one batched detection with stage timing: descriptor_ms / orientation_ms; every feature record
         downloaded and, per keypoint, the kernel's own sample enumeration restated in numpy (window, analytic row spans: features.hip
-        k_descriptor) -> samples, wave steps, loop iterations; runs tools/_valu_cost_table (tools/microbench/valu_cost_table.hip)
+        k_descriptor) -> samples, pair slots, wave steps = loop iterations; runs tools/_valu_cost_table (tools/microbench/valu_cost_table.hip)
     python tools/descriptor_floor.py report --inputs <json> [--sq profiles/r05_sq_counters.json] [--out profiles/r05_descriptor_floor]   (anywhere with hipcc)
         compiles features.hip to ISA, splits k_descriptor<2, false, false> into its regions — the pair predicate and, for each of the two modes
         of the pair-mode kernel (solo: one wave per keypoint in DESC_SOLO_PHASES phases, team: two waves), per keypoint / per phase / sample
-        loop / odd tail / epilogue — counts every mnemonic, prices it, writes the reconciliation (markdown + json)
+        loop / epilogue — counts every mnemonic, prices it, writes the reconciliation (markdown + json)
         (--costs-from <json>: take the issue-cost table of an earlier inputs file when tools/_valu_cost_table was not run)
 """
 import argparse
@@ -27,14 +27,15 @@ sys.path.insert(0, ROOT)
 
 # ------------------------------------------------------------------------------------------------ collect (GPU box)
 def sample_counts(feats, w0, h0, upsampling=True):
-    """per keypoint: N = samples enumerated by k_descriptor (the concatenated analytic row spans of its clipped window).
+    """per keypoint: (N, P) = samples enumerated by k_descriptor (the concatenated analytic row spans of its clipped window) and the pair slots
+    it walks them in (a span of cnt samples is (cnt + 1) // 2 slots of two row neighbours: features.hip desc_row_prefix).
     float32 arithmetic in the kernel's order; the kernel's fused operations make single spans differ by one texel now and then
     (the spans are conservative by construction, the exact cells are re-derived per sample): a count, not a bit-exact restatement."""
     import numpy as np
     f32 = np.float32
     K = len(feats)
     if K == 0:
-        return np.zeros(0, np.int64)
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
     o = feats["octave_idx"].astype(np.int64)
     oi = o + 1 if upsampling else o  # octave_idx is relative to the input resolution: -1 is the up-sampled octave
     ow = (w0 * 2 if upsampling else w0) >> oi
@@ -68,8 +69,8 @@ def sample_counts(feats, w0, h0, upsampling=True):
         hi = np.where(ok, np.minimum(hi, ctr + half), np.where(np.abs(bb) < T, hi, lo - f32(2.0)))
     xl = np.maximum(np.ceil(lo - f32(0.01)).astype(np.int64), dx0)
     xh = np.minimum(np.floor(hi + f32(0.01)).astype(np.int64), dx1)
-    out = (np.maximum(xh - xl + 1, 0) * live).sum(axis=1)
-    return out
+    cnt = np.maximum(xh - xl + 1, 0) * live
+    return cnt.sum(axis=1), ((cnt + 1) // 2).sum(axis=1)
 
 
 def desc_radius(feats):
@@ -135,7 +136,7 @@ def collect(args):
     acc = inst.getAccumulatedDetectTimings()
     inst.setProfiling(False)
     stage = {k: acc[k] / max(acc["nb_calls"], 1) for k in ("pyramid_ms", "scan_ms", "orientation_ms", "descriptor_ms", "total_ms")}
-    K = steps = samples = iters = odd = 0
+    K = steps = samples = slots = iters = 0
     solo_r = api.lib().vksift_hip_tune_get(14)  # VKSIFT_TUNE_DESC_SOLO_R
     nph = solo_phases()
     modes = {"solo": collections.Counter(), "team": collections.Counter()}
@@ -146,14 +147,15 @@ def collect(args):
     nfr = min(B, args.count_frames)
     for b in range(nfr):
         f = inst.downloadFeatures(b)
-        n = sample_counts(f, W, H)
+        n, p = sample_counts(f, W, H)
         for k, v in enumerate(orientation_counts(f, W, H)):
             ori[k] += v
-        t = (n + 63) // 64
-        # two waves per keypoint (batch >= 8): the first takes ceil(t / 2) steps, the second floor(t / 2); a wave's loop does two
-        # steps per iteration and one odd step in the tail
+        t = (p + 63) // 64
+        # a wave step is one slot — two samples — per lane = one iteration of the sample loop; the steps are dealt out whole to the waves of a
+        # team (batch >= 8: two) or the phases of a solo wave
         K += len(f)
         samples += int(n.sum())
+        slots += int(p.sum())
         steps += int(t.sum())
         # pair mode (features.hip k_descriptor): keypoints 2 kb, 2 kb + 1 of a section (= octave) go solo when both have R <= solo_r
         R = desc_radius(f)
@@ -173,10 +175,9 @@ def collect(args):
             md["wave_steps"] += int(ts.sum())
             for p in range(parts):  # desc_run: whole steps, the first T % parts shares take one more
                 sp = ts // parts + (p < ts % parts)
-                md["pair_iterations"] += int((sp // 2).sum())
-                md["odd_tail_steps"] += int((sp % 2).sum())
-                iters += int((sp // 2).sum())
-                odd += int((sp % 2).sum())
+                md["pair_iterations"] += int(sp.sum())
+                md["shares_without_a_step"] += int((sp == 0).sum())
+                iters += int(sp.sum())
         for o in f["octave_idx"]:
             per_oct[int(o)] += 1
         for v in t:
@@ -189,12 +190,12 @@ def collect(args):
     out = {
         "workload": f"{B} x {W}x{H} frames in one detection call (bench.py's frames)", "frames": B, "counted_frames": nfr,
         "stage_ms_per_call": stage,
-        "keypoints": K * scale, "samples": samples * scale, "wave_steps": steps * scale, "pair_iterations": iters * scale, "odd_tail_steps": odd * scale,
+        "keypoints": K * scale, "samples": samples * scale, "slots": slots * scale, "wave_steps": steps * scale, "pair_iterations": iters * scale,
         "waves_per_keypoint": 2,
         "solo_r": solo_r, "solo_phases": nph, "pair_slots": pair_slots * scale,
         "modes": {k: {kk: vv * scale for kk, vv in v.items()} for k, v in modes.items()},
         "mean_samples_per_keypoint": samples / max(K, 1), "mean_steps_per_keypoint": steps / max(K, 1),
-        "lane_fill": samples / max(steps * 64, 1),
+        "lane_fill": samples / max(steps * 128, 1), "slot_fill": samples / max(slots * 2, 1),
         "keypoints_per_octave": dict(sorted(per_oct.items())),
         "orientation": {"keypoints": ori[0] * (B / nfr), "interior_steps": ori[1] * (B / nfr), "border_steps": ori[2] * (B / nfr), "weight_sum_iterations": ori[3] * (B / nfr)},
         "costs_ps": costs,
@@ -256,8 +257,8 @@ def blocks_of(lines):
 def regions(blocks):
     """text-order split of the pair-mode kernel. Its keypoint loop holds the pair predicate and two bodies (desc_keypoint for one wave in phases,
     and for two waves); each body is per-keypoint blocks, the blocks of its phase loop in front of the sample loop (run search), the sample loop
-    (the innermost blocks with the eight ds_add_u64 of two samples, from the block that loads and prices the samples to where the depth drops),
-    the odd tail step (four more); the two epilogues are laid out behind both bodies. The body with an s_barrier is the two-wave one.
+    (the innermost blocks with the eight ds_add_u64 of two samples, from the block that loads and prices the samples to where the depth drops);
+    the two epilogues are laid out behind both bodies. The body with an s_barrier is the two-wave one.
     -> ({region name: [block index, ...]}, slow-path blocks left out, {mode: depth of its phase loop's blocks})"""
     n_add = [sum(1 for m in b[2] if m == "ds_add_u64") for b in blocks]
     valu = [sum(1 for m in b[2] if m.startswith("v_")) for b in blocks]
@@ -271,14 +272,13 @@ def regions(blocks):
     if cur:
         groups.append(cur)
     loops = [g for g in groups if sum(n_add[i] for i in g) == 8]
-    tails = [g for g in groups if sum(n_add[i] for i in g) == 4]
-    assert len(loops) == 2 and len(tails) == 2, "two sample loops and two odd tail steps: solo and team"
+    assert len(loops) == 2 and len(groups) == 2, "two sample loops, solo and team, and no other step with atomics"
     first_kp = next(i for i, b in enumerate(blocks) if b[1] >= 1)
     bodies, start, slow_all = [], None, []
-    for lp, tl in zip(loops, tails):
+    for lp in loops:
         d = blocks[lp[0]][1]
         m1 = lp[-1]
-        while m1 + 1 < tl[0] and blocks[m1 + 1][1] >= d:
+        while m1 + 1 < len(blocks) and blocks[m1 + 1][1] >= d:
             m1 += 1
         # the loop's header: the first block in front of the atomics that a branch of the loop goes back to (next sample, taps, arithmetic follow it)
         back = {t.split()[-1] for i in range(lp[0], m1 + 1) for t in blocks[i][3] if t.startswith(("s_cbranch", "s_branch"))}
@@ -298,7 +298,7 @@ def regions(blocks):
         ph0 = m0
         while blocks[ph0 - 1][1] >= d - 1:
             ph0 -= 1
-        bodies.append({"main": [i for i in main if i not in slow], "tail": list(range(m1 + 1, tl[-1] + 1)), "phase": list(range(ph0, m0)), "m0": m0, "end": tl[-1], "depth": d - 1})
+        bodies.append({"main": [i for i in main if i not in slow], "phase": list(range(ph0, m0)), "m0": m0, "end": m1, "depth": d - 1})
         slow_all += slow
     # the bodies' first blocks: the set-up (sincos, divisions: > 100 VALU at depth <= 2) of each; the predicate lies in front of the first one
     setups = [i for i, b in enumerate(blocks) if valu[i] > 100 and b[1] <= 2 and i < bodies[1]["m0"] and not any(m.startswith("global_store") for m in b[2])]
@@ -324,7 +324,6 @@ def regions(blocks):
         reg[f"{mode}: per keypoint: constants, zeroing, row spans, prefix scan"] = bd["kp"]
         reg[f"{mode}: per phase: run search"] = bd["phase"]
         reg[f"{mode}: sample loop, two samples per lane per iteration"] = bd["main"]
-        reg[f"{mode}: odd tail step"] = bd["tail"]
         reg[f"{mode}: epilogue (normalise, clamp, pack)"] = epis[0] if bd["team"] else epis[1]
     return reg, slow_all, depth
 
@@ -379,7 +378,7 @@ def report(args):
     reg, slow, phase_depth = regions(blocks)
     md = inp["modes"]
     NPH = inp["solo_phases"]
-    IT, ODD = inp["pair_iterations"], inp["odd_tail_steps"]
+    IT = inp["pair_iterations"]
     # executions per call of each region (wave-level). Solo: one wave per keypoint, the run search once per phase. Team: the per-keypoint
     # regions run in both waves of the workgroup, the epilogue's body in wave 0 only. The predicate: both waves, once per pair slot.
     execs = {"entry (once per workgroup)": None, "pair predicate (both waves, once per pair)": 2 * inp["pair_slots"]}
@@ -388,7 +387,6 @@ def report(args):
         execs[f"{mode}: per keypoint: constants, zeroing, row spans, prefix scan"] = k * waves
         execs[f"{mode}: per phase: run search"] = k * waves * phases
         execs[f"{mode}: sample loop, two samples per lane per iteration"] = md[mode]["pair_iterations"]
-        execs[f"{mode}: odd tail step"] = md[mode]["odd_tail_steps"]
         execs[f"{mode}: epilogue (normalise, clamp, pack)"] = k
     # inner loops of the per-keypoint part that run more than once per keypoint: the binary search over the prefix array
     mean_rows = 2.0 * math.sqrt(inp["mean_samples_per_keypoint"] / 0.5) / 2.0 + 1  # window side ~ sqrt(2 N)
@@ -425,7 +423,7 @@ def report(args):
     simds = 1024
     valu_ms = total_ps / simds * 1e-9
     # LDS: the 64-bit atomics of the sample loop at the measured rate for 16+ distinct addresses per wave (a CU's LDS serves all its waves)
-    n_atomics = IT * 8 + ODD * 4
+    n_atomics = IT * 8
     lds_ms = n_atomics * costs["ds_add_u64@16"] / 256 * 1e-9
     # the sample loop's VALU instructions by cost class
     by_key = collections.Counter()
@@ -463,8 +461,8 @@ def report(args):
         w = f.write
         w("# k_descriptor: ISA x work x measured issue costs against the measured time\n\n")
         w(f"Workload: {inp['workload']}; {inp['keypoints']:.0f} keypoints, {inp['samples'] / 1e6:.1f} M samples "
-          f"({inp['mean_samples_per_keypoint']:.0f} per keypoint, lanes {100 * inp['lane_fill']:.1f} % filled), {inp['wave_steps'] / 1e6:.2f} M wave steps = "
-          f"{inp['pair_iterations'] / 1e6:.2f} M two-sample iterations + {inp['odd_tail_steps'] / 1e6:.2f} M odd tail steps.\n\n")
+          f"({inp['mean_samples_per_keypoint']:.0f} per keypoint) in {inp['slots'] / 1e6:.1f} M pair slots ({100 * inp['slot_fill']:.1f} % of their halves live), "
+          f"{inp['wave_steps'] / 1e6:.2f} M wave steps = two-sample iterations ({100 * inp['lane_fill']:.1f} % of their sample positions live).\n\n")
         w("| region | executions per call (waves) | VALU | SALU | LDS | VMEM | VALU issue time each (ns per SIMD) |\n|---|---|---|---|---|---|---|\n")
         for r in rows:
             i = r["instructions"]

@@ -559,7 +559,7 @@ struct DescRows
 {
   int *lo;             // first dx of a row's span
   uint32_t *cnt;       // its length
-  const uint32_t *pre; // this wave's exclusive prefix of the lengths, pre[nrows] = N
+  const uint32_t *pre; // this wave's exclusive prefix of the rows' pair slots, pre[nrows] = P (desc_row_prefix)
   int y0, nrows;
 };
 
@@ -597,15 +597,16 @@ __device__ __forceinline__ void desc_row_spans(const DescCtx &c, const DescRows 
   }
 }
 
-// ---- step: exclusive scan of the row counts (nrows <= DESC_MAX_ROWS), total in pre[nrows]. Every wave computes it for itself from the counts
-// (read-only here) into its own copy of the prefix array: no workgroup barrier afterwards.
+// ---- step: exclusive scan of the rows' pair slots (nrows <= DESC_MAX_ROWS), total in pre[nrows]. A slot is two row neighbours (dx, dx + 1): a span
+// of cnt samples is (cnt + 1) / 2 slots, and the second half of the last slot of an odd span is dead. Every wave computes the scan for itself from
+// the counts (read-only here) into its own copy of the prefix array: no workgroup barrier afterwards.
 __device__ __forceinline__ void desc_row_prefix(const DescRows &rows, uint32_t *pre, int lane)
 {
   uint32_t carry = 0;
   for (int base = 0; base < rows.nrows; base += 64)
   {
     const int i = base + lane;
-    const uint32_t v = i < rows.nrows ? rows.cnt[i] : 0u;
+    const uint32_t v = i < rows.nrows ? (rows.cnt[i] + 1u) >> 1 : 0u;
     const uint32_t incl = wave_scan_incl_u32(v, lane);
     if (i < rows.nrows)
       pre[i] = carry + incl - v;
@@ -615,31 +616,35 @@ __device__ __forceinline__ void desc_row_prefix(const DescRows &rows, uint32_t *
     pre[rows.nrows] = carry;
 }
 
-// ---- step: the run of a wave and of a lane. The concatenated spans form the index space [0, N); the N samples need T = ceil(N / 64) wave-steps,
-// dealt out to the waves in whole steps (the first T % NWV waves take one more), so only the last step of the last wave has idle lanes. Splitting
-// N into NWV equal parts first and rounding each up to whole steps cost up to NWV - 1 extra steps (11 % of a typical 25-step keypoint). Inside its
+// ---- step: the run of a wave and of a lane. The concatenated slots of the spans form the index space [0, P); the P slots need T = ceil(P / 64)
+// wave-steps of two samples per lane, dealt out to the waves in whole steps (the first T % NWV waves take one more), so only the last step of the
+// last wave has idle lanes. Splitting P into NWV equal parts first and rounding each up to whole steps cost up to NWV - 1 extra steps. Inside its
 // wave's share lane l walks its own contiguous run — at any step the 64 lanes sit a run length apart and spread over all 16 spatial cells, so the
 // 8 fixed-point LDS atomics of a step hit mostly distinct addresses (row-adjacent samples pile onto 1-2 cells and serialise: measured 8 % slower).
-// Integer adds commute: the result does not depend on the order.
+// Integer adds commute: the result does not depend on the order. (Enumerating samples instead of slots — 3.7 % fewer sample positions — gave a
+// lane pairs that straddle two rows in 85 % of the steps: the second sample's taps loaded twice, a row advance per sample, and a last step of
+// one sample per lane for runs of odd length.)
 struct DescRun
 {
-  uint32_t steps;      // samples per lane = steps of this wave
-  uint32_t sidx, send; // the lane's samples [sidx, send) of [0, N)
-  int row, cdx;        // row and dx of sample sidx
-  uint32_t row_end;    // pre[row + 1]
+  uint32_t steps;      // slots per lane = steps of this wave
+  uint32_t sidx, send; // the lane's slots [sidx, send) of [0, P)
+  int row, cdx;        // row and dx of the first sample of slot sidx
+  int xend;            // lo[row] + cnt[row]: the row's span ends in front of it
 };
 template <int NWV>
 __device__ __forceinline__ DescRun desc_run(const DescRows &rows, int wave, int lane)
 {
   const uint32_t *s_pre = rows.pre;
-  const uint32_t N = s_pre[rows.nrows];
-  const uint32_t T = (N + 63u) / 64u, tq = T / NWV, tr = T % NWV;
+  const uint32_t P = s_pre[rows.nrows];
+  const uint32_t T = (P + 63u) / 64u, tq = T / NWV, tr = T % NWV;
   DescRun r;
   r.steps = tq + ((uint32_t)wave < tr ? 1u : 0u);
   const uint32_t step0 = (uint32_t)wave * tq + min((uint32_t)wave, tr);
-  r.sidx = min(N, step0 * 64u + (uint32_t)lane * r.steps);
-  r.send = min(N, r.sidx + r.steps);
-  // locate the row of the first sample of this lane's run: largest row with pre[row] <= sidx
+  r.sidx = min(P, step0 * 64u + (uint32_t)lane * r.steps);
+  r.send = min(P, r.sidx + r.steps);
+  // locate the row of the first slot of this lane's run: largest row with pre[row] <= sidx. (Locating the runs of all lanes and phases in one walk
+  // without dependent reads — a count per row added at the first lane it counts for, an inclusive sum over the lanes — was measured: no gain,
+  // NOTEBOOK section 39.)
   int row = 0;
   if (r.sidx < r.send)
   {
@@ -657,73 +662,62 @@ __device__ __forceinline__ DescRun desc_run(const DescRows &rows, int wave, int 
       row++;
   }
   r.row = row;
-  r.cdx = rows.lo[row] + (int)(r.sidx - s_pre[row]);
-  r.row_end = s_pre[row + 1];
+  const int lo = rows.lo[row];
+  r.cdx = lo + 2 * (int)(r.sidx - s_pre[row]);
+  r.xend = lo + (int)rows.cnt[row];
   return r;
 }
 
-// the lane's next sample: its window offset (sx, sy); false for a lane whose run has ended (it gets a dead one)
-__device__ __forceinline__ bool desc_next_sample(const DescRows &rows, DescRun &r, int &sx, int &sy)
+// the lane's next slot: the window offset (sx, sy) of its first sample — the second is (sx + 1, sy) — and whether each is live (neither for a
+// lane whose run has ended; the second not in the last slot of an odd span). One row advance per slot: a slot never straddles two rows.
+__device__ __forceinline__ void desc_next_slot(const DescRows &rows, DescRun &r, int &sx, int &sy, bool live[2])
 {
-  const bool live = r.sidx < r.send;
-  if (live && r.sidx >= r.row_end)
+  live[0] = r.sidx < r.send;
+  if (live[0] && r.cdx >= r.xend)
   {
+    uint32_t n;
     do
-      r.row++;
-    while (rows.pre[r.row + 1] <= r.sidx);
-    r.row_end = rows.pre[r.row + 1];
+      n = rows.cnt[++r.row];
+    while (n == 0u); // a live slot lies ahead: the walk ends on its row
     r.cdx = rows.lo[r.row];
+    r.xend = r.cdx + (int)n;
   }
   sx = r.cdx, sy = rows.y0 + r.row;
-  r.cdx++, r.sidx++;
-  return live;
+  live[1] = live[0] && r.cdx + 1 < r.xend;
+  r.cdx += 2, r.sidx++;
 }
 
-// ---- step: two samples per lane. Their (straight-line) contribution code is independent, so the scheduler interleaves the two dependency chains
-// instead of padding every compare -> select and transcendental with wait states. A lane whose run has ended carries a dead sample: the taps go
-// through the buffer resource (any offset is safe) and no contribution is executed.
+// ---- step: one slot per lane, two samples. Their (straight-line) contribution code is independent, so the scheduler interleaves the two dependency
+// chains instead of padding every compare -> select and transcendental with wait states. A dead sample — both of a lane whose run has ended, the
+// second of a span's odd end — takes whatever the loads return: they go through the buffer resource (any offset is safe, the texel past a span's
+// end included) and no contribution is executed.
 template <bool F16>
 __device__ __forceinline__ void desc_step_pair(const DescCtx &c, const DescRows &rows, DescRun &run, uint32_t *s_work)
 {
-  int sx[2], sy[2];
-  const bool live[2] = {desc_next_sample(rows, run, sx[0], sy[0]), desc_next_sample(rows, run, sx[1], sy[1])};
+  int sx, sy;
+  bool live[2];
+  desc_next_slot(rows, run, sx, sy, live);
   DescTaps t0, t1;
-  const unsigned v0 = desc_tap_base(c, sx[0], sy[0]);
+  const unsigned v0 = desc_tap_base(c, sx, sy);
   if (F16)
   {
     t0 = desc_taps<F16>(c, v0);
-    t1 = desc_taps<F16>(c, desc_tap_base(c, sx[1], sy[1]));
+    t1 = desc_taps<F16>(c, desc_tap_base(c, sx + 1, sy));
   }
   else
-  {
-    // (a dead second sample takes whatever the pair load returns: it contributes nothing; the loads go through the buffer resource, so the texels
-    // past a row end are harmless too)
     desc_taps_pair(c, v0, t0, t1);
-    if (live[1] && !(sy[1] == sy[0] && sx[1] == sx[0] + 1))
-      t1 = desc_taps<F16>(c, desc_tap_base(c, sx[1], sy[1])); // the run crossed into the next row span
-  }
   bool o0, o1;
-  DescSample s0 = desc_sample<true>(c, sx[0], sy[0], t0, &o0), s1 = desc_sample<true>(c, sx[1], sy[1], t1, &o1);
+  DescSample s0 = desc_sample<true>(c, sx, sy, t0, &o0), s1 = desc_sample<true>(c, sx + 1, sy, t1, &o1);
   float f0 = angle_bin<true>(s0.xb), f1 = angle_bin<true>(s1.xb);
   o0 |= angle_bin_odd(s0.xb), o1 |= angle_bin_odd(s1.xb);
   if (__builtin_expect(__ballot(o0 || o1) != 0ull, 0))
   {
     // some lane holds a value outside the ranges of the short forms (see desc_sample): the general forms for this step
-    s0 = desc_sample<false>(c, sx[0], sy[0], t0, nullptr), s1 = desc_sample<false>(c, sx[1], sy[1], t1, nullptr);
+    s0 = desc_sample<false>(c, sx, sy, t0, nullptr), s1 = desc_sample<false>(c, sx + 1, sy, t1, nullptr);
     f0 = angle_bin<false>(s0.xb), f1 = angle_bin<false>(s1.xb);
   }
   desc_scatter(c, s0, f0, live[0], s_work);
   desc_scatter(c, s1, f1, live[1], s_work);
-}
-
-// ---- step: the last step of a wave with an odd number of them, one sample per lane (general forms)
-template <bool F16>
-__device__ __forceinline__ void desc_step_odd(const DescCtx &c, const DescRows &rows, DescRun &run, uint32_t *s_work)
-{
-  int sx, sy;
-  const bool live = desc_next_sample(rows, run, sx, sy);
-  const DescSample s0 = desc_sample<false>(c, sx, sy, desc_taps<F16>(c, desc_tap_base(c, sx, sy)), nullptr);
-  desc_scatter(c, s0, angle_bin<false>(s0.xb), live, s_work);
 }
 
 // ---- step: the epilogue (wave 0), in three parts.
@@ -860,11 +854,8 @@ __device__ __forceinline__ void desc_keypoint(const FeatArgs &a, const vksift_hi
       if (PAIRS)
         asm volatile("" : "+v"(pt));
       DescRun run = desc_run<NW * NPH>(rows, wave * NPH + ph, pt & 63);
-      uint32_t it = 0;
-      for (; it + 1 < run.steps; it += 2)
+      for (uint32_t it = 0; it < run.steps; it++)
         desc_step_pair<F16>(c, rows, run, s_work);
-      if (it < run.steps) // odd number of steps
-        desc_step_odd<F16>(c, rows, run, s_work);
     }
   }
   desc_sync<NW>();
@@ -875,7 +866,8 @@ __device__ __forceinline__ void desc_keypoint(const FeatArgs &a, const vksift_hi
 // ---- pair mode of the two-wave form: are the windows of keypoints k0 and k0 + 1 both small enough (R <= solo_r) for one wave each? Even lanes
 // derive R of the first, odd lanes of the second, as desc_setup does; every wave of the workgroup gets the same answer.
 // Phases of a solo wave, 512 frames, descriptor stage against the two-wave launch of the same build and call: 1: +67 %, 2: 0 %, 3: -8.2 %, 4: -9 %,
-// 5: -8 %, 6: -5.5 %, 8: -1.2 % (short phases end in an odd step more often, and each phase searches its runs).
+// 5: -8 %, 6: -5.5 %, 8: -1.2 % (measured when a lane walked samples and a phase of odd length ended in a one-sample step; each phase searches its
+// runs. With pair slots 3, 4 and 5 phases were measured again: NOTEBOOK section 39).
 #ifndef DESC_SOLO_PHASES
 #define DESC_SOLO_PHASES 4
 #endif
