@@ -258,7 +258,7 @@ extern "C"
    * Positions: x, y are the first two floats of the stored feature at that row (download order), bit for bit.
    * Deterministic: the same inputs give the same bytes on every run, whatever the scheduling (tests/np_observations.py restates the rule).
    * With no selected track, offsets is the single word 0.
-   * Not attempted: no per-view index (the observations of one image), no splitting of conflicting tracks, no threshold on nb_buffers.
+   * Not attempted: no splitting of conflicting tracks, no threshold on nb_buffers. (The observations of one image: vksift_ext_indexObservationsByView, below.)
    * Contract of vksift_ext_buildTracks: asynchronous, queued on the instance stream behind the build, the pairs' buffers stay busy until it has run, the
    * accessors wait; results of its own (the tracks and every pair result stay readable and byte-identical), replaced by the next
    * vksift_ext_selectTrackObservations, invalidated by a new vksift_ext_buildTracks and by a new matching, plain or filtered. Precondition, as for guided
@@ -310,8 +310,9 @@ extern "C"
    *  5 Sums over members have one order whatever the scheduling: a group of G = 16 lanes owns a track, lane j adds members j, j + 16, ... in increasing
    *    order, the lanes are then added by the refits' xor butterfly (offsets 8, 4, 2, 1). G is part of the rule.
    * Deterministic: the same inputs give the same bytes on every run.
-   * Not attempted: no removal of single outlying observations (a track is taken or left whole); no bundle adjustment; no estimation of the cameras; no
-   * conditioning of the world frame — the arithmetic is fp32, so a caller puts the origin near the scene.
+   * Not attempted: no removal of single outlying observations (a track is taken or left whole); no joint bundle adjustment and no camera from scratch (the
+   * cameras are refined on these points, the points held fixed, by vksift_ext_refineCameras, below: the two calls alternate); no conditioning of the world
+   * frame — the arithmetic is fp32, so a caller puts the origin near the scene.
    * Contract of vksift_ext_selectTrackObservations: asynchronous, queued on the instance stream behind the selection, the pairs' buffers stay busy until it
    * has run, the accessors wait; results of its own (tracks, observations and every pair result stay readable and byte-identical), replaced by the next
    * vksift_ext_triangulateTracks, invalidated wherever the observations are: by a new selection, a new vksift_ext_buildTracks, a new matching. Failures as
@@ -343,6 +344,91 @@ extern "C"
   VKSIFT_EXPORT void vksift_ext_downloadPoints(vksift_Instance instance, vksift_ext_Point *points); /* nb_points records */
   /* Time (ms) of the last vksift_ext_triangulateTracks (the camera upload, its launches + the statistics' posting), HIP events; needs profiling on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getTriangulateTime(vksift_Instance instance);
+
+  /* ---- GPU-side per-view index of the observation table -------------------------------------------------------------------
+   * The observation table of the last vksift_ext_selectTrackObservations inverted by view — the observations of one image, each with the number of its
+   * selected track —, on the device: what camera refinement, resection and any per-image pass over the tracks read, without a download and a host sort of the
+   * table by gpu_buffer_id.
+   * view_offsets has sift_buffer_count + 1 words, indexed by gpu_buffer_id: records view_offsets[b] .. view_offsets[b+1] are the observations of buffer b
+   * (none for a buffer that took no part); view_offsets[0] == 0 and view_offsets[sift_buffer_count] == nb_observations ==
+   * vksift_ext_ObservationStats.nb_observations. Inside a view the records are in table order: increasing point — the number m of the selected track, which
+   * is also the number of its vksift_ext_Point —, the two members of a conflicting track in one view in increasing row. x, y are copied bit for bit.
+   * Deterministic: a stable radix sort keyed on the buffer, linear in the observations, no atomics on global memory; the same inputs give the same bytes on
+   * every run (tests/np_cameras.py restates the rule, vksift_hip_index_views in vksift_hip.h spells it out).
+   * Contract of vksift_ext_selectTrackObservations: asynchronous, queued on the instance stream behind the selection, the pairs' buffers stay busy until it
+   * has run, the accessors wait; results of its own (tracks, observations, points and every pair result stay readable and byte-identical), replaced by the
+   * next index, invalidated wherever the observations are: by a new selection, a new vksift_ext_buildTracks, a new matching.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, an earlier index untouched): no observations selected for the present tracks, out == NULL, an accessor called
+   * before any index. A launch or allocation failure is VKSIFT_VULKAN_ERROR. */
+  typedef struct
+  {
+    uint32_t point, row; /* the selected track (= point) number m, and the feature's row in its buffer */
+    float x, y;
+  } vksift_ext_ViewObservation; /* 16 bytes */
+  typedef struct
+  {
+    uint32_t nb_views /* buffers with at least one observation */, nb_observations, largest_view, reserved /* 0 */;
+  } vksift_ext_ViewStats; /* 16 bytes */
+  VKSIFT_EXPORT void vksift_ext_indexObservationsByView(vksift_Instance instance);
+  VKSIFT_EXPORT void vksift_ext_getViewStats(vksift_Instance instance, vksift_ext_ViewStats *out);
+  VKSIFT_EXPORT void vksift_ext_downloadViewOffsets(vksift_Instance instance, uint32_t *view_offsets);                 /* sift_buffer_count + 1 words */
+  VKSIFT_EXPORT void vksift_ext_downloadViewObservations(vksift_Instance instance, vksift_ext_ViewObservation *obs); /* nb_observations records */
+  /* Time (ms) of the last vksift_ext_indexObservationsByView (its launches + the statistics' posting), HIP events; needs profiling on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getIndexViewsTime(vksift_Instance instance);
+
+  /* ---- GPU-side camera refinement on the triangulated points ---------------------------------------------------------------
+   * The motion half of resection-intersection bundle adjustment, where vksift_ext_triangulateTracks is the structure half: every camera that took part in
+   * the last vksift_ext_buildTracks refined on the accepted points of its view, the points held fixed, by up to nb_steps (1 .. 8) Gauss-Newton steps on the
+   * summed squared reprojection error. Input: the view index (built first if the present observation table has none), the points of the last
+   * vksift_ext_triangulateTracks and the camera table that call copied to the device; nothing is uploaded. Output: one record per SIFT buffer, indexed by
+   * gpu_buffer_id. The refined P goes back into vksift_ext_triangulateTracks as it is: that is the alternation. Every participating camera is refined; the
+   * caller keeps the input camera of whichever it wants fixed.
+   * THE RULE, per view with the members of its index range in order. Arithmetic is fp32 add, subtract, multiply and divide, each rounded once, in a written
+   * order, with no fmaf (the order is spelled out at vksift_hip_refine_cameras in vksift_hip.h; tests/np_cameras.py restates it bit for bit).
+   *  1 A member is USED iff the status of its point is 0. Fewer than VKSIFT_EXT_CAMERA_MIN_OBSERVATIONS used members: TOO_FEW.
+   *  2 At a camera P every used member gives the residuals u/w - x, v/w - y and their Jacobian rows with respect to a rigid motion of the world
+   *    (omega, tau): (X x j, j) with j the triangulation's Jacobian row; the cost, the 6x6 normal equations and their right-hand side are summed.
+   *  3 A step solves N d = -g by Gauss-Jordan with the refits' pivot rule, forms the Cayley rotation C of omega = d[0..2] — rational in omega, so no sine or
+   *    cosine is needed — and P' = P [[C, tau], [0, 1]]: a right-multiplied rigid update keeps P = K [R | t] with the same K without ever decomposing P. The
+   *    step is accepted iff it can be computed (every w normal and finite, every pivot usable, P' finite) and cost(P') <= cost(P); the first step that is not
+   *    accepted ends the loop.
+   *  4 Sums over members have one order whatever the scheduling: a workgroup of 256 lanes owns a view, lane j adds members j, j + 256, ... in increasing
+   *    order, the lanes are added by the refits' block sum. The 256 is part of the rule.
+   * nb_views == nb_refined + nb_unchanged + nb_failed. Deterministic: the same inputs give the same bytes on every run.
+   * Not attempted: no estimation of K; no camera from scratch (no minimal solver, no RANSAC: the input camera must be close enough for Gauss-Newton); no
+   * joint solve of cameras and points (the two halves alternate); no gauge fixing (refining all cameras lets the frame drift with the points: keep some input
+   * cameras to pin it); no conditioning of the world frame — the arithmetic is fp32, so a caller keeps the origin near the scene, as for triangulation.
+   * Contract of vksift_ext_triangulateTracks: asynchronous, queued on the instance stream behind the triangulation, the pairs' buffers stay busy until it has
+   * run, the accessors wait; results of its own (tracks, observations, points and every pair result stay readable and byte-identical), replaced by the next
+   * vksift_ext_refineCameras, invalidated wherever the points are — by a new selection, a new vksift_ext_buildTracks, a new matching — and by a new
+   * vksift_ext_triangulateTracks, whose points and cameras they would no longer refer to.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, earlier results untouched): no triangulation for the present observations, nb_steps 0 or above
+   * VKSIFT_EXT_CAMERA_MAX_STEPS, out == NULL, an accessor called before any refinement. A launch or allocation failure is VKSIFT_VULKAN_ERROR. */
+#define VKSIFT_EXT_CAMERA_ABSENT 1u     /* the buffer took no part in the last build: every other field is 0 */
+#define VKSIFT_EXT_CAMERA_TOO_FEW 2u    /* fewer than VKSIFT_EXT_CAMERA_MIN_OBSERVATIONS used observations: P is the input camera, the costs and steps are 0 */
+#define VKSIFT_EXT_CAMERA_DEGENERATE 4u /* the cost at the input camera cannot be computed (some w zero, subnormal or not finite, or a cost that is not finite): as TOO_FEW */
+#define VKSIFT_EXT_CAMERA_BEHIND 8u     /* some used observation has w <= 0 at the final camera */
+#define VKSIFT_EXT_CAMERA_MIN_OBSERVATIONS 6u
+#define VKSIFT_EXT_CAMERA_MAX_STEPS 8u
+  typedef struct
+  {
+    float P[12];              /* row-major 3x4: the refined camera, or the input camera where no step was accepted */
+    float cost_start, cost;   /* summed squared reprojection error over the used observations, before and after */
+    float max_sq_error;       /* largest squared error at the final camera */
+    uint32_t nb_observations; /* used observations */
+    uint32_t steps;           /* accepted steps, 0 .. nb_steps */
+    uint32_t status;          /* 0, or the flags above */
+  } vksift_ext_RefinedCamera; /* 72 bytes */
+  typedef struct
+  {
+    uint32_t nb_views /* not ABSENT */, nb_refined /* steps > 0 */, nb_unchanged /* status 0 or BEHIND only, steps 0 */, nb_failed /* TOO_FEW or DEGENERATE */;
+  } vksift_ext_CameraStats; /* 16 bytes */
+  VKSIFT_EXPORT void vksift_ext_refineCameras(vksift_Instance instance, uint32_t nb_steps);
+  VKSIFT_EXPORT void vksift_ext_getCameraStats(vksift_Instance instance, vksift_ext_CameraStats *out);
+  VKSIFT_EXPORT void vksift_ext_downloadRefinedCameras(vksift_Instance instance, vksift_ext_RefinedCamera *cameras); /* sift_buffer_count records */
+  /* Time (ms) of the last vksift_ext_refineCameras (the index where the call built it, its launches + the statistics' posting), HIP events; needs profiling
+   * on. -1 when there is none. */
+  VKSIFT_EXPORT float vksift_ext_getRefineCamerasTime(vksift_Instance instance);
 
   /* ---- GPU-side feature budget ------------------------------------------------------------------------------------------
    * Every SIFT buffer of [first_gpu_buffer_id, first_gpu_buffer_id + count) keeps its max_features strongest features (OpenCV's nfeatures, SiftGPU's -tc,

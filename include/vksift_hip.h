@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 14u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks, 13: vksift_hip_track_observations, 14: vksift_hip_triangulate_tracks */
+#define VKSIFT_HIP_ABI_VERSION 15u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks, 13: vksift_hip_track_observations, 14: vksift_hip_triangulate_tracks, 15: vksift_hip_index_views, vksift_hip_refine_cameras */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -765,6 +765,67 @@ extern "C"
    * offsets, obs_stats or stats not 4-byte aligned, observations, cameras or points not 16-byte aligned. */
   int vksift_hip_triangulate_tracks(const uint32_t *offsets, const uint8_t *observations, const uint32_t *obs_stats, const float *cameras, uint32_t nb_cameras,
                                     float t2, float cos_min_angle, uint8_t *points, uint64_t points_cap, uint32_t *stats, vksift_hip_stream s);
+
+  /* ------------------------------------------------------------------ per-view index and camera refinement (cameras.hip; no counterpart in the reference) */
+  /* The observation table inverted by view: the observations of every gpu_buffer_id below nb_cameras, each with the number of its selected track.
+   * READ: obs_stats[0] (the track count M, on the device: clamped to tracks_cap) and obs_stats[1] (the observation count n, clamped to obs_cap),
+   * offsets[0 .. M] and observations 0 .. n-1 as vksift_hip_track_observations wrote them.
+   * Observation i < n is INDEXED iff its gpu_buffer_id is below nb_cameras and the search lo = 0, hi = M; while hi - lo > 1: mid = lo + (hi - lo) / 2,
+   * offsets[mid] <= i ? lo = mid : hi = mid ends at a track m = lo with offsets[m] <= i < offsets[m+1] <= n (the triangulation's test of an extent; with
+   * M = 0 nothing is indexed). What is not indexed is counted in nothing. view_offsets[0 .. nb_cameras] is the prefix sum of the indexed observations per
+   * gpu_buffer_id (view_offsets[0] = 0, view_offsets[nb_cameras] their number); the records view_offsets[b] .. view_offsets[b+1] of view_observations
+   * are the indexed observations of buffer b in table order (increasing i: increasing m, the two members of a conflicting track in one view in increasing
+   * row), each the 16 bytes {point m, row, x, y} (vksift_ext_ViewObservation), x and y bit for bit. stats = {views with an observation, indexed
+   * observations, the largest view, 0}. Deterministic: a stable LSD radix sort of the observation numbers by gpu_buffer_id (8-bit digits, as many as
+   * nb_cameras needs), linear in obs_cap; no atomics on global memory. tests/np_cameras.py restates it.
+   * scratch: scratch_u32 >= vksift_hip_views_scratch_u32(obs_cap) words, 4-byte aligned, need not be initialised, contents unspecified afterwards.
+   * WRITTEN: view_offsets[0 .. nb_cameras], the indexed records of view_observations, the four words of stats, the scratch, nothing else.
+   * view_observations holds obs_cap records.
+   * hipErrorInvalidValue, nothing launched: a NULL pointer, nb_cameras 0 or 2^32 - 1, tracks_cap 0 or above 2^31 - 1, obs_cap 0 or its whole blocks of
+   * 2048 above 2^31 - 1, offsets, obs_stats, view_offsets, stats or scratch not 4-byte aligned, observations or view_observations not 16-byte aligned, too
+   * little scratch. */
+  size_t vksift_hip_views_scratch_u32(uint64_t obs_cap);
+  int vksift_hip_index_views(const uint32_t *offsets, const uint8_t *observations, const uint32_t *obs_stats, uint64_t tracks_cap, uint64_t obs_cap,
+                             uint32_t nb_cameras, uint32_t *view_offsets, uint8_t *view_observations, uint32_t *stats, uint32_t *scratch, size_t scratch_u32,
+                             vksift_hip_stream s);
+
+  /* Every camera refined on the points of its view, the points held fixed (the motion half of resection-intersection): one 72-byte record {P[12],
+   * cost_start, cost, max_sq_error, nb_observations, steps, status} per gpu_buffer_id below nb_cameras (vksift_ext_RefinedCamera).
+   * READ: view_offsets, view_observations and view_stats[1] (the indexed count, on the device: clamped to obs_cap) as vksift_hip_index_views wrote them
+   * (view b: its extent with view_offsets[b+1] clamped to that count and view_offsets[b] to the clamped end); the 32-byte points as
+   * vksift_hip_triangulate_tracks wrote them: of every member whose point number is below points_cap the status word, and of the used ones X; cameras: 12
+   * floats per gpu_buffer_id, the row-major 3x4 P of vksift_hip_triangulate_tracks; buf_tab[2 r], r < nbufs: the gpu_buffer_ids that took part in the build
+   * (the table vksift_hip_build_tracks read). A buffer that is not among them is ABSENT: every word of its record is 0 but status.
+   * THE RULE, per view with the members of its index range in order. fp32 add, sub, mul and div, each rounded once, in this order, no fmaf. "unusable":
+   * zero, subnormal or not finite.
+   *  1 a member is USED iff its point number is below points_cap and the status word of that point is 0; nb_observations counts them. Fewer than 6: TOO_FEW.
+   *  2 evaluation at P, per used member with X its point: u, v, w, pu, pv, ru, rv, e2, iw, ju, jv as in step 3 of vksift_hip_triangulate_tracks; au = X x ju,
+   *    av = X x jv with a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0); the rows p = (au0, au1, au2, ju0, ju1, ju2 | ru) and q alike from av, jv, rv.
+   *    28 sums: cost += e2; the 21 upper entries of N row by row, N[a][b] += (pa pb + qa qb); g[a] += (pa ru + qa rv). Flags: some w unusable; some
+   *    w <= 0. max_e2 = the largest e2 by |bit pattern|. The cost at the input camera cannot be computed (DEGENERATE) iff some w is unusable there or the
+   *    cost is not finite.
+   *  3 a step: N d = -g (N filled symmetrically, the right-hand side -g[a]) by the 6x7 Gauss-Jordan with refit.h's pivot rule — for column k the rows below
+   *    compared with row k in turn and exchanged when their |entry| (bit pattern) is strictly larger, row k times 1 / pivot, every other row r minus a[r][k]
+   *    times row k; an unusable pivot or a solution entry that is not finite fails. omega = d[0..2], tau = d[3..5]; a = 0.5 omega, b = 2 a,
+   *    q = (a0 a0 + a1 a1) + a2 a2, s = 1 / (1 + q), t = 1 - q; the Cayley rotation C[i][i] = (t + b[i] a[i]) s, C[0][1] = (b0 a1 - b2) s,
+   *    C[0][2] = (b0 a2 + b1) s, C[1][0] = (b1 a0 + b2) s, C[1][2] = (b1 a2 - b0) s, C[2][0] = (b2 a0 - b1) s, C[2][1] = (b2 a1 + b0) s; P' = P [[C, tau],
+   *    [0, 1]]: P'[r][c] = (P[r][0] C[0][c] + P[r][1] C[1][c]) + P[r][2] C[2][c] for c < 3 and P'[r][3] = ((P[r][0] tau0 + P[r][1] tau1) + P[r][2] tau2) +
+   *    P[r][3]. The step is accepted iff no w at P is unusable, the solve succeeds, every entry of P' is finite and cost(P') <= cost(P); the first step that is
+   *    not accepted ends the loop; at most nb_steps steps.
+   *  4 every sum over members: a workgroup of 256 lanes owns a view; lane j visits positions j, j + 256, ... of the view's range in increasing order and adds
+   *    the used ones to partial sums that start at +0; the 64 lanes of a wave are added by the xor butterfly p + p[lane ^ off], off = 32 .. 1, the four
+   *    waves as ((w0 + w1) + w2) + w3 (refit.h's block sum). The 256 is part of the rule.
+   *  5 the record: P the final camera (the input camera where no step was accepted), cost_start and cost the cost at the input and at the final camera,
+   *    max_sq_error = max_e2 at the final camera (any NaN reads 0x7fc00000), steps the accepted steps, status BEHIND iff some w <= 0 at the final camera.
+   *    TOO_FEW and DEGENERATE records hold the input camera and nb_observations; the costs, max_sq_error and steps are 0 and no other flag is set.
+   * stats = {views (not ABSENT), refined (steps > 0), unchanged (neither TOO_FEW nor DEGENERATE, no step), failed (TOO_FEW or DEGENERATE)}. Deterministic:
+   * every output depends on the inputs alone. No scratch, no atomics on global memory. tests/np_cameras.py restates the rule.
+   * WRITTEN: the nb_cameras records of refined, the four words of stats, nothing else.
+   * hipErrorInvalidValue, nothing launched: a NULL pointer, nb_cameras 0 or above 2^31 - 1, nbufs 0, obs_cap or points_cap 0 or above 2^31 - 1, nb_steps 0
+   * or above 8, view_offsets, view_stats, buf_tab, refined or stats not 4-byte aligned, view_observations, points or cameras not 16-byte aligned. */
+  int vksift_hip_refine_cameras(const uint32_t *view_offsets, const uint8_t *view_observations, const uint32_t *view_stats, uint64_t obs_cap,
+                                const uint8_t *points, uint64_t points_cap, const float *cameras, uint32_t nb_cameras, const uint32_t *buf_tab, uint32_t nbufs,
+                                uint32_t nb_steps, uint8_t *refined, uint32_t *stats, vksift_hip_stream s);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,16 @@ def lib():
         getattr(L, "vksift_ext_" + name).restype = None
     L.vksift_ext_getTriangulateTime.argtypes = [inst]
     L.vksift_ext_getTriangulateTime.restype = C.c_float
+    L.vksift_ext_indexObservationsByView.argtypes = [inst]
+    L.vksift_ext_indexObservationsByView.restype = None
+    L.vksift_ext_refineCameras.argtypes = [inst, u32]
+    L.vksift_ext_refineCameras.restype = None
+    for name in ("getViewStats", "downloadViewOffsets", "downloadViewObservations", "getCameraStats", "downloadRefinedCameras"):
+        getattr(L, "vksift_ext_" + name).argtypes = [inst, C.c_void_p]
+        getattr(L, "vksift_ext_" + name).restype = None
+    for name in ("getIndexViewsTime", "getRefineCamerasTime"):
+        getattr(L, "vksift_ext_" + name).argtypes = [inst]
+        getattr(L, "vksift_ext_" + name).restype = C.c_float
     L.vksift_ext_keepStrongestFeatures.argtypes = [inst, u32, u32, u32]
     L.vksift_ext_keepStrongestFeatures.restype = None
     L.vksift_ext_getKeepStrongestTime.argtypes = [inst]
@@ -296,6 +306,12 @@ def lib():
     L.vksift_hip_track_observations.restype = C.c_int
     L.vksift_hip_triangulate_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_float, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.vksift_hip_triangulate_tracks.restype = C.c_int
+    L.vksift_hip_views_scratch_u32.argtypes = [C.c_uint64]
+    L.vksift_hip_views_scratch_u32.restype = C.c_size_t
+    L.vksift_hip_index_views.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.vksift_hip_index_views.restype = C.c_int
+    L.vksift_hip_refine_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vksift_hip_refine_cameras.restype = C.c_int
     _lib = L
     return L
 
@@ -463,6 +479,13 @@ POINT_DEGENERATE, POINT_TOO_LONG, POINT_BEHIND, POINT_ERROR, POINT_ANGLE = 1, 2,
 TRIANGULATE_MAX_OBSERVATIONS = 1024
 POINT_DTYPE = np.dtype([("X", "<f4", (3,)), ("max_sq_error", "<f4"), ("min_cos", "<f4"), ("status", "<u4"), ("steps", "<u4"), ("nb_observations", "<u4")])
 POINT_STATS_DTYPE = np.dtype([("nb_points", "<u4"), ("nb_accepted", "<u4"), ("nb_failed", "<u4"), ("nb_rejected", "<u4")])
+VIEW_OBSERVATION_DTYPE = np.dtype([("point", "<u4"), ("row", "<u4"), ("x", "<f4"), ("y", "<f4")])
+VIEW_STATS_DTYPE = np.dtype([("nb_views", "<u4"), ("nb_observations", "<u4"), ("largest_view", "<u4"), ("reserved", "<u4")])
+CAMERA_ABSENT, CAMERA_TOO_FEW, CAMERA_DEGENERATE, CAMERA_BEHIND = 1, 2, 4, 8
+CAMERA_MIN_OBSERVATIONS, CAMERA_MAX_STEPS = 6, 8
+REFINED_CAMERA_DTYPE = np.dtype([("P", "<f4", (12,)), ("cost_start", "<f4"), ("cost", "<f4"), ("max_sq_error", "<f4"), ("nb_observations", "<u4"), ("steps", "<u4"),
+                                 ("status", "<u4")])
+CAMERA_STATS_DTYPE = np.dtype([("nb_views", "<u4"), ("nb_refined", "<u4"), ("nb_unchanged", "<u4"), ("nb_failed", "<u4")])
 
 
 def guided_match(desc_a, xy_a, desc_b, xy_b, n, models, valid, model_kind, t2, ratio, max_distance, cross_check, scratch_u32=None, strides=None, buffers=None):
@@ -807,6 +830,61 @@ class Instance:
 
     def getTriangulateTime(self):
         return lib().vksift_ext_getTriangulateTime(self._h)
+
+    def indexObservationsByView(self):
+        """inverts the observation table of the last selectTrackObservations by view on the GPU (vksift_ext_indexObservationsByView); asynchronous like the
+        selection"""
+        lib().vksift_ext_indexObservationsByView(self._h)
+        _check_pending()
+
+    def getViewStats(self):
+        """{nb_views, nb_observations, largest_view, reserved} of the last view index"""
+        out = np.zeros(1, VIEW_STATS_DTYPE)
+        lib().vksift_ext_getViewStats(self._h, out.ctypes.data)
+        _check_pending()
+        return {k: int(out[0][k]) for k in VIEW_STATS_DTYPE.names}
+
+    def downloadViewOffsets(self):
+        """uint32 [sift_buffer_count + 1], indexed by gpu_buffer_id: view b holds the records view_offsets[b] .. view_offsets[b + 1]"""
+        out = np.zeros(self.cfg.sift_buffer_count + 1, np.uint32)
+        lib().vksift_ext_downloadViewOffsets(self._h, out.ctypes.data)
+        _check_pending()
+        return out
+
+    def downloadViewObservations(self):
+        """the index's records (VIEW_OBSERVATION_DTYPE), grouped by view"""
+        n = self.getViewStats()["nb_observations"]
+        out = np.zeros(n, VIEW_OBSERVATION_DTYPE)
+        if n:
+            lib().vksift_ext_downloadViewObservations(self._h, out.ctypes.data)
+            _check_pending()
+        return out
+
+    def getIndexViewsTime(self):
+        return lib().vksift_ext_getIndexViewsTime(self._h)
+
+    def refineCameras(self, nb_steps=4):
+        """refines every camera of the last triangulateTracks on the accepted points of its view, the points held fixed, by up to nb_steps Gauss-Newton
+        steps on the GPU (vksift_ext_refineCameras); builds the view index first if there is none; asynchronous like the triangulation"""
+        lib().vksift_ext_refineCameras(self._h, nb_steps)
+        _check_pending()
+
+    def getCameraStats(self):
+        """{nb_views, nb_refined, nb_unchanged, nb_failed} of the last refineCameras"""
+        out = np.zeros(1, CAMERA_STATS_DTYPE)
+        lib().vksift_ext_getCameraStats(self._h, out.ctypes.data)
+        _check_pending()
+        return {k: int(out[0][k]) for k in CAMERA_STATS_DTYPE.names}
+
+    def downloadRefinedCameras(self):
+        """one record per SIFT buffer (REFINED_CAMERA_DTYPE), indexed by gpu_buffer_id; rec["P"].reshape(-1, 3, 4) goes back into triangulateTracks"""
+        out = np.zeros(self.cfg.sift_buffer_count, REFINED_CAMERA_DTYPE)
+        lib().vksift_ext_downloadRefinedCameras(self._h, out.ctypes.data)
+        _check_pending()
+        return out
+
+    def getRefineCamerasTime(self):
+        return lib().vksift_ext_getRefineCamerasTime(self._h)
 
     def keepStrongestFeatures(self, first_buffer, count, max_features):
         """every SIFT buffer of [first_buffer, first_buffer + count) keeps its max_features strongest features (|DoG response|, ties by download

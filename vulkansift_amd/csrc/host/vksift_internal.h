@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_triangulate.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_triangulate.c, vksift_cameras.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -76,7 +76,7 @@ typedef struct
 } MatchScratch;
 
 /* the interval of a stage's last run under vksift_ext_setProfiling (vksift_pairs.c). One per getter: both verification models share T_VERIFY */
-enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_OBSERVATIONS, T_TRIANGULATE, T_COUNT };
+enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_OBSERVATIONS, T_TRIANGULATE, T_VIEWS, T_CAMERAS, T_COUNT };
 typedef struct
 {
   vksift_hip_event ev[2];
@@ -137,6 +137,27 @@ typedef struct
   float *h_cameras, *d_cameras; /* 12 floats per SIFT buffer: filled in pinned memory by the call, copied to the device in front of the launches */
   bool valid, cam_pending;
 } TriangulateResults;
+
+/* What vksift_ext_indexObservationsByView keeps (vksift_cameras.c): the observation table by view, an entry per observation at most and an offset per
+ * SIFT buffer. Allocated by the first index. `valid`: cleared wherever obs.valid is. */
+typedef struct
+{
+  uint32_t *d_offsets;         /* sift_buffer_count + 1 words, indexed by gpu_buffer_id */
+  uint8_t *d_obs;              /* the vksift_ext_ViewObservation records */
+  uint32_t *d_stats, *h_stats; /* the four words of vksift_ext_ViewStats, posted */
+  uint32_t *d_scratch;         /* sort lists, the observations' points, digit table (vksift_hip_views_scratch_u32) */
+  size_t scratch_u32;
+  bool valid;
+} ViewResults;
+
+/* What vksift_ext_refineCameras keeps (vksift_cameras.c): one record per SIFT buffer. Allocated by the first refinement. `valid`: cleared wherever
+ * tri.valid is, and by a new triangulation (the records refer to its points and cameras). */
+typedef struct
+{
+  uint8_t *d_refined;          /* the vksift_ext_RefinedCamera records */
+  uint32_t *d_stats, *h_stats; /* the four words of vksift_ext_CameraStats, posted */
+  bool valid;
+} CameraResults;
 
 typedef struct
 {
@@ -284,6 +305,9 @@ struct vksift_Instance_T
   ObservationResults obs;
   /* the points of the selected tracks under caller-supplied cameras (vksift_ext_triangulateTracks, vksift_triangulate.c) */
   TriangulateResults tri;
+  /* the observation table by view, and the cameras refined on the points (vksift_ext_indexObservationsByView, vksift_ext_refineCameras, vksift_cameras.c) */
+  ViewResults views;
+  CameraResults cams;
 
   /* ---- caller-supplied keypoints (vksift_describe.c); everything allocated by the first describe call */
   uint8_t *d_kps, *h_kps;        /* one call's keypoint offsets (count + 1 words, padded to 256 bytes) and, behind them, its keypoints: pinned staging and the device copy */

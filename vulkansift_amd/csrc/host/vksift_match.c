@@ -187,7 +187,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
       /* the first launch that overwrites the previous matching's records and counts has been queued: nothing of that matching is served any more,
        * whatever becomes of this call (it marks its own results once the whole sequence has been queued) */
       pair_results_invalidate(inst);
-      inst->tracks.valid = inst->obs.valid = inst->tri.valid = false; /* tracks are built from the pairs of a matching (vksift_tracks.c), observations from tracks, points from observations */
+      inst->tracks.valid = inst->obs.valid = inst->tri.valid = inst->views.valid = inst->cams.valid = false; /* tracks are built from the pairs of a matching (vksift_tracks.c), observations from tracks, points and the view index from observations, refined cameras from both */
       inst->match_slots_used = 0;
       inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
     }

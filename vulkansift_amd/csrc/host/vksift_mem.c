@@ -114,6 +114,8 @@ static const Block blocks[] = {
     LAZY(obs.d_offsets, MEM_DEVICE), LAZY(obs.d_track_ids, MEM_DEVICE), LAZY(obs.d_obs, MEM_DEVICE), LAZY(obs.d_stats, MEM_DEVICE), LAZY(obs.h_stats, MEM_PINNED),
     LAZY(obs.d_scratch, MEM_DEVICE), LAZY(obs.h_tab, MEM_PINNED),
     LAZY(tri.d_points, MEM_DEVICE), LAZY(tri.d_stats, MEM_DEVICE), LAZY(tri.h_stats, MEM_PINNED), LAZY(tri.h_cameras, MEM_PINNED), LAZY(tri.d_cameras, MEM_DEVICE),
+    LAZY(views.d_offsets, MEM_DEVICE), LAZY(views.d_obs, MEM_DEVICE), LAZY(views.d_stats, MEM_DEVICE), LAZY(views.h_stats, MEM_PINNED), LAZY(views.d_scratch, MEM_DEVICE),
+    LAZY(cams.d_refined, MEM_DEVICE), LAZY(cams.d_stats, MEM_DEVICE), LAZY(cams.h_stats, MEM_PINNED),
     PAIR_RESULTS(PR_FILTERED), PAIR_RESULTS(PR_VERIFY_H), PAIR_RESULTS(PR_VERIFY_F), PAIR_RESULTS(PR_REFINE_H), PAIR_RESULTS(PR_REFINE_F), PAIR_RESULTS(PR_GUIDED),
     LAZY(d_dl, MEM_DEVICE), LAZY(h_dl, MEM_PINNED), LAZY(dl_row, MEM_HEAP), LAZY(h_post[0], MEM_PINNED), LAZY(h_post[1], MEM_PINNED),
     LAZY(d_kps, MEM_DEVICE), LAZY(h_kps, MEM_PINNED), LAZY(d_placed, MEM_DEVICE), LAZY(h_placed, MEM_PINNED), LAZY(placed_seq, MEM_HEAP),
@@ -199,7 +201,7 @@ typedef struct
 {
   size_t field;
   uint16_t count, step;
-  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_triangulate.c, vksift_pairs.c, vksift_describe.c), destroyed here */
+  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_triangulate.c, vksift_cameras.c, vksift_pairs.c, vksift_describe.c), destroyed here */
 } Handle;
 #define EVENTS(f, n, step, lazy) {FIELD(f), n, step, false, lazy}
 #define STREAM(f) {FIELD(f), 1, 0, true, false}
@@ -215,7 +217,7 @@ static const Handle handles[] = {
     EVENTS(prof[0].ev_pt, 3, sizeof(vksift_hip_event), false), EVENTS(prof[1].ev_pt, 3, sizeof(vksift_hip_event), false),
     EVENTS(prof[0].ev_scan, 2, sizeof(ProfSet), false), TIMER(T_MATCH, false),
     EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_gtab, 1, 0, true), EVENTS(ev_ttab, 1, 0, true), EVENTS(ev_otab, 1, 0, true), EVENTS(ev_ctab, 1, 0, true), EVENTS(ev_kps, 1, 0, true),
-    TIMER(T_VERIFY, true), TIMER(T_REFINE_H, true), TIMER(T_REFINE_F, true), TIMER(T_GUIDED, true), TIMER(T_BUDGET, true), TIMER(T_BUDGET_GRID, true), TIMER(T_ROOTSIFT, true), TIMER(T_TRACKS, true), TIMER(T_OBSERVATIONS, true), TIMER(T_TRIANGULATE, true),
+    TIMER(T_VERIFY, true), TIMER(T_REFINE_H, true), TIMER(T_REFINE_F, true), TIMER(T_GUIDED, true), TIMER(T_BUDGET, true), TIMER(T_BUDGET_GRID, true), TIMER(T_ROOTSIFT, true), TIMER(T_TRACKS, true), TIMER(T_OBSERVATIONS, true), TIMER(T_TRIANGULATE, true), TIMER(T_VIEWS, true), TIMER(T_CAMERAS, true),
 };
 #define N_HANDLES (sizeof(handles) / sizeof(handles[0]))
 

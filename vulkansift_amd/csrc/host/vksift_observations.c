@@ -81,8 +81,10 @@ void vksift_ext_selectTrackObservations(vksift_Instance instance, uint32_t min_l
                                           max_length, conflicts, o->d_offsets, o->d_track_ids, cap_nodes / 2u, o->d_obs, cap_nodes, o->d_stats, o->d_scratch,
                                           o->scratch_u32, inst->stream),
             "observation building");
-  o->valid = inst->tri.valid = false; /* the launch replaces the observations: not served until the whole sequence has been queued; the points of the earlier
-                                       * observations are not served any more (vksift_triangulate.c) */
+  o->valid = inst->tri.valid = inst->views.valid = inst->cams.valid = false; /* the launch replaces the observations: not served until the whole sequence has
+                                                                              * been queued; the points of the earlier observations, their view index and the
+                                                                              * cameras refined on them are not served any more (vksift_triangulate.c,
+                                                                              * vksift_cameras.c) */
   HIP_CHECK(vksift_hip_event_record(inst->ev_otab, inst->stream), "event record");
   o->tab_pending = true;
   HIP_CHECK(vksift_hip_post_words(o->h_stats, o->d_stats, 4u, inst->stream), "observation statistics read-back");

@@ -106,8 +106,10 @@ void vksift_ext_buildTracks(vksift_Instance instance, uint32_t source)
                                     sel ? sel->d_words + sel->words - 1u : NULL, sel ? sel->words : 0, t->d_tab, 2u, count, t->d_tab + buf_tab_at, t->nbufs, inst->d_match_n, nb,
                                     max_rows, t->d_node_words, t->d_records, ((uint64_t)t->cap_bufs * nb) / 2u, t->d_stats, t->d_scratch, t->scratch_u32, inst->stream),
             "track building");
-  t->valid = inst->obs.valid = inst->tri.valid = false; /* the launch replaces the tracks: not served until the whole sequence has been queued; observations
-                                                          * of the earlier tracks, and their points, are not served any more */
+  t->valid = inst->obs.valid = inst->tri.valid = inst->views.valid = inst->cams.valid = false; /* the launch replaces the tracks: not served until the whole
+                                                                                                * sequence has been queued; observations of the earlier tracks,
+                                                                                                * their points, view index and refined cameras are not served
+                                                                                                * any more */
   HIP_CHECK(vksift_hip_post_words(t->h_stats, t->d_stats, 4u, inst->stream), "track statistics read-back");
   HIP_CHECK(stage_end(inst, &frame, ids_a, ids_b, count), "event record");
   t->max_rows = max_rows;

@@ -96,7 +96,8 @@ void vksift_ext_triangulateTracks(vksift_Instance instance, const float *cameras
   HIP_CHECK(vksift_hip_triangulate_tracks(o->d_offsets, o->d_obs, o->d_stats, p->d_cameras, inst->cfg.sift_buffer_count, t2, cos_min_angle, p->d_points,
                                           bound < points_cap(inst) ? (bound ? bound : 1u) : points_cap(inst), p->d_stats, inst->stream),
             "triangulation");
-  p->valid = false; /* the launch replaces the points: not served until the whole sequence has been queued */
+  p->valid = inst->cams.valid = false; /* the launch replaces the points: not served until the whole sequence has been queued; the cameras refined on the earlier
+                                        * points are not served any more (vksift_cameras.c) */
   HIP_CHECK(vksift_hip_post_words(p->h_stats, p->d_stats, 4u, inst->stream), "point statistics read-back");
   HIP_CHECK(stage_end(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
   p->valid = true;
