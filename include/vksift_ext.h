@@ -211,8 +211,8 @@ extern "C"
    * every row of b or VKSIFT_EXT_NO_TRACK; b must be a buffer of the pair list.
    * Deterministic: the same inputs give the same bytes on every run, whatever the scheduling; the numbering depends on nothing but the graph
    * (tests/np_tracks.py restates it).
-   * Not attempted: no member list per track here (vksift_ext_selectTrackObservations, below, builds it); no splitting of conflicting tracks; no tracks across two
-   * matching calls.
+   * Not attempted: no member list per track here (vksift_ext_selectTrackObservations, below, builds it); no splitting of conflicting tracks. (Tracks across
+   * several matching calls: vksift_ext_beginTrackAccumulation, below.)
    * Contract of guided matching: asynchronous, queued on the instance stream behind the matching and whatever produced the source, the pairs' buffers stay
    * busy, the accessors wait; results of its own (every pair result stays readable and unchanged), replaced by the next vksift_ext_buildTracks, invalidated by
    * a new matching, plain or filtered. A verification or refit queued after a build does not touch the tracks already built. Precondition, as for guided
@@ -239,8 +239,58 @@ extern "C"
   VKSIFT_EXPORT void vksift_ext_getTrackStats(vksift_Instance instance, vksift_ext_TrackStats *out);
   VKSIFT_EXPORT void vksift_ext_downloadTracks(vksift_Instance instance, vksift_ext_Track *tracks);
   VKSIFT_EXPORT void vksift_ext_downloadFeatureTracks(vksift_Instance instance, uint32_t gpu_buffer_id, uint32_t *track_ids);
-  /* Time (ms) of the last vksift_ext_buildTracks (its launches + the statistics' posting), HIP events; needs profiling on. -1 when there is none. */
+  /* Time (ms) of the last vksift_ext_buildTracks or vksift_ext_buildTracksAccumulated (its launches + the statistics' posting), HIP events; needs profiling
+   * on. -1 when there is none. */
   VKSIFT_EXPORT float vksift_ext_getTracksTime(vksift_Instance instance);
+
+  /* ---- Tracks across matching calls ---------------------------------------------------------------------------------------
+   * A matching call takes at most batch_capacity pairs, and vksift_ext_buildTracks sees the pairs of the last call only. A view graph with more pairs goes
+   * through a device-resident EDGE STORE that outlives a matching: begin once, match a chunk of the pair list and accumulate, as often as needed, then build.
+   * ACCUMULATE(source) takes the edges vksift_ext_buildTracks(source) would take from the present matching — the same selection byte for byte: the source's
+   * records, its mask bytes equal to 1, the pair's valid word, both rows stored — and appends them as vksift_ext_TrackEdge {A[p], idx_a, B[p], idx_b} behind
+   * what the store holds, slot ascending and within a slot record ascending. max_edges is the store's capacity: positions at or beyond it are not written,
+   * nb_dropped counts the edges that were not, nb_edges = min(total, max_edges); nb_calls counts the accumulate calls.
+   * ROW TABLE: the store keeps one row count per SIFT buffer. The first call that names a buffer records the count the matching left for it (the word
+   * vksift_ext_buildTracks reads, on the device: the host waits for nothing). A later call whose count for that buffer differs adds 1 to nb_changed_buffers
+   * and leaves the table as it was: the precondition "the buffers still hold the features that were matched" is broken, and the caller can see it.
+   * BEGIN empties the store and the row table and sets the capacity. Nothing else clears the store: not a new matching, verification, refit or guided
+   * matching, not a build of either kind.
+   * BUILD computes the tracks of the graph whose nodes are the stored rows — those below min(table[b], max_nb_sift_per_buffer) — of every buffer b the
+   * store's calls named and whose edges are the store's; an edge that names a row that is not stored is no edge. Numbering, vksift_ext_Track,
+   * vksift_ext_TrackStats and the per-feature words are exactly those of vksift_ext_buildTracks; nb_edges counts the store's edges that were taken. The result
+   * REPLACES the instance's tracks: vksift_ext_getTrackStats, vksift_ext_downloadTracks, vksift_ext_downloadFeatureTracks (for every buffer the store's
+   * calls named; it writes min(table[b], max_nb_sift_per_buffer) words, the count of the first call that named b), vksift_ext_selectTrackObservations and everything behind it serve it unchanged. It is invalidated where tracks are, by a new matching or a
+   * new build of either kind; the store survives, so a caller who matches again simply builds again.
+   * EQUIVALENCE: one accumulate followed by one build gives, byte for byte, what vksift_ext_buildTracks(source) gives for the same matching.
+   * Deterministic (tests/np_track_edges.py restates the rule).
+   * Not attempted: edges are not de-duplicated; a single edge or call cannot be removed; conflicting tracks are not split; the store does not grow.
+   * Contract of vksift_ext_buildTracks: asynchronous on the instance stream, the accessors wait, every pair result stays readable and byte-identical. Busy
+   * buffers: an accumulate keeps the pairs' buffers busy; the accumulated build and every stage that reads its tracks keep ALL participating buffers busy,
+   * not only those of the last pair list.
+   * Memory: 16 bytes per edge of max_edges. vksift_ext_beginTrackAccumulation waits for everything the instance has in flight; since an accumulation can
+   * involve every buffer, the first begin of an instance with 2 batch_capacity < sift_buffer_count releases the storage of the tracks, observations, points
+   * and view index (and invalidates those results), which from then on is allocated for sift_buffer_count buffers instead of 2 batch_capacity: per node
+   * (buffer x max_nb_sift_per_buffer) 32 bytes for the tracks, about 48 for the observations, 16 for the points and about 37 for the view index, scratch included. An instance with
+   * 2 batch_capacity >= sift_buffer_count releases nothing.
+   * VKSIFT_INVALID_INPUT_ERROR (nothing queued, the store untouched): max_edges == 0, accumulate or build with no accumulation begun, accumulate with no
+   * filtered matching, an unknown source, a source whose stage has not been run for the present matching, build before any accumulate, out == NULL, an
+   * accessor called before begin. A launch or allocation failure is VKSIFT_VULKAN_ERROR; after it every entry but begin refuses the store. */
+  typedef struct
+  {
+    uint32_t gpu_buffer_id_a, row_a, gpu_buffer_id_b, row_b;
+  } vksift_ext_TrackEdge; /* 16 bytes */
+  typedef struct
+  {
+    uint32_t nb_edges, nb_dropped, nb_calls, nb_changed_buffers;
+  } vksift_ext_TrackEdgeStats; /* 16 bytes */
+  VKSIFT_EXPORT void vksift_ext_beginTrackAccumulation(vksift_Instance instance, uint32_t max_edges);
+  VKSIFT_EXPORT void vksift_ext_accumulateTrackEdges(vksift_Instance instance, uint32_t source); /* the VKSIFT_EXT_TRACKS_* sources */
+  VKSIFT_EXPORT void vksift_ext_getTrackEdgeStats(vksift_Instance instance, vksift_ext_TrackEdgeStats *out);
+  VKSIFT_EXPORT void vksift_ext_downloadTrackEdges(vksift_Instance instance, vksift_ext_TrackEdge *edges); /* nb_edges records */
+  VKSIFT_EXPORT void vksift_ext_buildTracksAccumulated(vksift_Instance instance);
+  /* Time (ms) of the last vksift_ext_accumulateTrackEdges (table upload + launches + the statistics' posting), HIP events; needs profiling on. -1 when there
+   * is none. */
+  VKSIFT_EXPORT float vksift_ext_getAccumulateTime(vksift_Instance instance);
 
   /* ---- GPU-side track observations ----------------------------------------------------------------------------------------
    * What triangulation and bundle adjustment read: the table track -> [(image, feature, x, y)] of the tracks a caller keeps, built on the device from the

@@ -34,7 +34,7 @@ extern "C"
 /* u32 words of scratch vksift_hip_match_2nn_desc needs for na query rows against nb reference rows (norms of A and B, row flags /
  * row list, per-row partial lists of the decomposed kernels: 16 words per piece for the cell scan of large reference sets) */
 #define VKSIFT_HIP_MATCH_SCRATCH_U32(na, nb) (2u * (size_t)(na) + (size_t)(nb) + 72u + (size_t)(na) * 16u * VKSIFT_HIP_MATCH_CHUNKS)
-#define VKSIFT_HIP_ABI_VERSION 15u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks, 13: vksift_hip_track_observations, 14: vksift_hip_triangulate_tracks, 15: vksift_hip_index_views, vksift_hip_refine_cameras */
+#define VKSIFT_HIP_ABI_VERSION 16u     /* bumped whenever a signature or a scratch contract of this header changes (vksift_hip_abi_version); 12: vksift_hip_build_tracks, 13: vksift_hip_track_observations, 14: vksift_hip_triangulate_tracks, 15: vksift_hip_index_views, vksift_hip_refine_cameras, 16: vksift_hip_append_track_edges, vksift_hip_build_tracks_from_edges */
 #define VKSIFT_HIP_GATHER_SLOTS 512u   /* SIFT buffers one vksift_hip_gather_sections launch serves */
 #define VKSIFT_HIP_MATCH_SLOTS 256u    /* pairs one vksift_hip_match_2nn_async launch sequence serves */
 #define VKSIFT_HIP_MATCH_PK_NB 32768u  /* reference sets of at most this many rows take the branch-free packed-key kernel (k_match_pk) */
@@ -702,6 +702,39 @@ extern "C"
                               uint32_t nslots, const uint32_t *buf_tab, uint32_t nbufs, const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows,
                               uint32_t *node_words, uint8_t *tracks, uint64_t tracks_cap, uint32_t *stats, uint32_t *scratch, size_t scratch_u32,
                               vksift_hip_stream s);
+
+  /* ------------------------------------------------------------------ tracks across matching calls (track_edges.hip; no counterpart in the reference) */
+  /* An edge store that outlives a matching. edges: max_edges 16-byte records {gpu_buffer_id A, row A, gpu_buffer_id B, row B}; stats: the four words {edges
+   * held, edges dropped, calls, changed buffers}; row_table: one word per gpu_buffer_id below nb_buffers, 0xFFFFFFFF until a call records the buffer's row
+   * count there. The caller zeroes stats and fills row_table with 0xFF bytes to empty the store. APPEND takes the records, counts, masks, valid words,
+   * slot_tab, buf_tab, rows_dev and max_rows of vksift_hip_build_tracks and selects the edges that launcher would take, by the same rule (both ranks below
+   * nbufs, the mask byte 1, the pair valid, both rows below min(rows_dev[word], max_rows)). With held = min(stats[0], max_edges) the edges go to positions held,
+   * held + 1, ... in the order slot ascending, record ascending, as {buf_tab[2 rank A], idx_a, buf_tab[2 rank B], idx_b}; positions at or beyond max_edges are
+   * not written. Afterwards stats[0] = min(held + taken, max_edges), stats[1] has grown by the edges that were not written (it stops at 2^32 - 1), stats[2] by 1.
+   * For every rank r < nbufs with buf_tab[2 r] < nb_buffers (the ids of buf_tab are distinct): c = min(rows_dev[buf_tab[2 r + 1]], 2^32 - 2); a word of
+   * row_table that is 0xFFFFFFFF becomes c, one that holds another count than c stays and adds 1 to stats[3]. Deterministic, no atomics, three launch phases
+   * that each read the plain stores of the one before. scratch: scratch_u32 >= vksift_hip_track_edges_scratch_u32(nslots, max_n) words, need not be
+   * initialised, unspecified afterwards. WRITTEN: stats, the new edges, the words of row_table that were 0xFFFFFFFF, the scratch, nothing else.
+   * hipErrorInvalidValue, nothing launched: nslots, nbufs, max_n, max_rows, nb_buffers, max_edges or n_stride 0, slot_tab_stride below 2, valid given with
+   * valid_stride 0, records not 4-byte or edges not 16-byte aligned, rec_slot_stride not a multiple of 4, scratch not 4-byte aligned, with nslots > 1 a stride
+   * below max_n records, nslots * ceil(max_n / 256) above 2^31 - 1, too little scratch.
+   *
+   * BUILD FROM EDGES computes what vksift_hip_build_tracks computes — the same node numbering, node_words, track records and statistics, the same scratch
+   * (vksift_hip_tracks_scratch_u32) and the same meaning of buf_tab, rows_dev, node_stride and max_rows — for the graph whose edges are records 0 ..
+   * min(edge_count[0], max_edges) - 1 of edges (edge_count on the device, e.g. word 0 of the store's stats). rank_tab: nb_buffers words, the rank of each
+   * gpu_buffer_id in buf_tab or 0xFFFFFFFF for a buffer that takes no part. A record is an edge iff both ids are below nb_buffers, both ranks below nbufs
+   * and both rows stored; stats[3] counts those. With rows_dev = row_table the word index buf_tab[2 r + 1] is the gpu_buffer_id. One append followed by one
+   * build gives the bytes vksift_hip_build_tracks gives for the same input. hipErrorInvalidValue, nothing launched: max_edges or nb_buffers 0, edges not
+   * 16-byte aligned, and every refusal of vksift_hip_build_tracks that concerns nbufs, node_stride, max_rows, tracks, tracks_cap and the scratch.
+   * tests/np_track_edges.py restates both. */
+  size_t vksift_hip_track_edges_scratch_u32(uint32_t nslots, uint32_t max_n);
+  int vksift_hip_append_track_edges(const uint8_t *records, uint64_t rec_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, const uint8_t *masks,
+                                    uint64_t mask_slot_stride, const uint32_t *valid, uint32_t valid_stride, const uint32_t *slot_tab, uint32_t slot_tab_stride,
+                                    uint32_t nslots, const uint32_t *buf_tab, uint32_t nbufs, const uint32_t *rows_dev, uint32_t max_rows, uint32_t *row_table,
+                                    uint32_t nb_buffers, uint8_t *edges, uint32_t max_edges, uint32_t *stats, uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
+  int vksift_hip_build_tracks_from_edges(const uint8_t *edges, const uint32_t *edge_count, uint32_t max_edges, const uint32_t *rank_tab, uint32_t nb_buffers,
+                                         const uint32_t *buf_tab, uint32_t nbufs, const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows, uint32_t *node_words,
+                                         uint8_t *tracks, uint64_t tracks_cap, uint32_t *stats, uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s);
 
   /* ------------------------------------------------------------------ track observations (observations.hip; no counterpart in the reference) */
   /* The observation table of the tracks vksift_hip_build_tracks left: which tracks a caller keeps, and their members with positions, grouped by track.

@@ -181,6 +181,18 @@ def lib():
     L.vksift_ext_downloadFeatureTracks.restype = None
     L.vksift_ext_getTracksTime.argtypes = [inst]
     L.vksift_ext_getTracksTime.restype = C.c_float
+    L.vksift_ext_beginTrackAccumulation.argtypes = [inst, u32]
+    L.vksift_ext_beginTrackAccumulation.restype = None
+    L.vksift_ext_accumulateTrackEdges.argtypes = [inst, u32]
+    L.vksift_ext_accumulateTrackEdges.restype = None
+    L.vksift_ext_getTrackEdgeStats.argtypes = [inst, C.c_void_p]
+    L.vksift_ext_getTrackEdgeStats.restype = None
+    L.vksift_ext_downloadTrackEdges.argtypes = [inst, C.c_void_p]
+    L.vksift_ext_downloadTrackEdges.restype = None
+    L.vksift_ext_buildTracksAccumulated.argtypes = [inst]
+    L.vksift_ext_buildTracksAccumulated.restype = None
+    L.vksift_ext_getAccumulateTime.argtypes = [inst]
+    L.vksift_ext_getAccumulateTime.restype = C.c_float
     L.vksift_ext_selectTrackObservations.argtypes = [inst, u32, u32, u32]
     L.vksift_ext_selectTrackObservations.restype = None
     for name in ("getObservationStats", "downloadObservationOffsets", "downloadObservationTrackIds", "downloadObservations"):
@@ -298,6 +310,14 @@ def lib():
     L.vksift_hip_build_tracks.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, u32, u32, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p, u32,
                                           C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.vksift_hip_build_tracks.restype = C.c_int
+    L.vksift_hip_track_edges_scratch_u32.argtypes = [u32, u32]
+    L.vksift_hip_track_edges_scratch_u32.restype = C.c_size_t
+    L.vksift_hip_append_track_edges.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, u32, u32, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p, u32,
+                                                C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.vksift_hip_append_track_edges.restype = C.c_int
+    L.vksift_hip_build_tracks_from_edges.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.vksift_hip_build_tracks_from_edges.restype = C.c_int
     L.vksift_hip_observations_scratch_u32.argtypes = [u32, u32, u32]
     L.vksift_hip_observations_scratch_u32.restype = C.c_size_t
     L.vksift_hip_track_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p, C.c_uint64, C.c_void_p, u32,
@@ -472,6 +492,8 @@ TRACKS_FILTERED, TRACKS_VERIFIED_H, TRACKS_VERIFIED_F, TRACKS_REFINED_H, TRACKS_
 NO_TRACK = 0xFFFFFFFF
 TRACK_DTYPE = np.dtype([("gpu_buffer_id", "<u4"), ("row", "<u4"), ("length", "<u4"), ("nb_buffers", "<u4")])
 TRACK_STATS_DTYPE = np.dtype([("nb_tracks", "<u4"), ("nb_conflicting", "<u4"), ("nb_features", "<u4"), ("nb_edges", "<u4")])
+TRACK_EDGE_DTYPE = np.dtype([("gpu_buffer_id_a", "<u4"), ("row_a", "<u4"), ("gpu_buffer_id_b", "<u4"), ("row_b", "<u4")])
+TRACK_EDGE_STATS_DTYPE = np.dtype([("nb_edges", "<u4"), ("nb_dropped", "<u4"), ("nb_calls", "<u4"), ("nb_changed_buffers", "<u4")])
 OBS_KEEP_CONFLICTING, OBS_DROP_CONFLICTING = 0, 1
 OBSERVATION_DTYPE = np.dtype([("gpu_buffer_id", "<u4"), ("row", "<u4"), ("x", "<f4"), ("y", "<f4")])
 OBSERVATION_STATS_DTYPE = np.dtype([("nb_tracks", "<u4"), ("nb_observations", "<u4"), ("nb_rejected_length", "<u4"), ("nb_rejected_conflicting", "<u4")])
@@ -760,6 +782,45 @@ class Instance:
 
     def getTracksTime(self):
         return lib().vksift_ext_getTracksTime(self._h)
+
+    def beginTrackAccumulation(self, max_edges):
+        """empties the instance's edge store and sets its capacity (vksift_ext_beginTrackAccumulation): the start of tracks across several
+        matchFeaturesFiltered calls; waits for what the instance has in flight"""
+        lib().vksift_ext_beginTrackAccumulation(self._h, max_edges)
+        _check_pending()
+
+    def accumulateTrackEdges(self, source=TRACKS_FILTERED):
+        """appends the edges buildTracks(source) would take from the present matching to the edge store (vksift_ext_accumulateTrackEdges); asynchronous
+        like the pair stages"""
+        lib().vksift_ext_accumulateTrackEdges(self._h, source)
+        _check_pending()
+
+    def getTrackEdgeStats(self):
+        """{nb_edges, nb_dropped, nb_calls, nb_changed_buffers} of the edge store"""
+        out = np.zeros(1, TRACK_EDGE_STATS_DTYPE)
+        lib().vksift_ext_getTrackEdgeStats(self._h, out.ctypes.data)
+        _check_pending()
+        return {k: int(out[0][k]) for k in TRACK_EDGE_STATS_DTYPE.names}
+
+    def downloadTrackEdges(self):
+        """the edges the store holds (TRACK_EDGE_DTYPE), in the order they were accumulated"""
+        n = self.getTrackEdgeStats()["nb_edges"]
+        out = np.zeros(n, TRACK_EDGE_DTYPE)
+        if n:
+            lib().vksift_ext_downloadTrackEdges(self._h, out.ctypes.data)
+            _check_pending()
+        return out
+
+    def buildTracksAccumulated(self):
+        """the tracks of every edge the store holds, over every buffer its calls named (vksift_ext_buildTracksAccumulated): they replace the instance's
+        tracks, and getTrackStats, downloadTracks, downloadFeatureTracks, selectTrackObservations and what follows serve them. downloadFeatureTracks(b)
+        then holds the row count of the first call that named b: pass nb_features if the buffer has been rewritten since (getTrackEdgeStats()
+        ["nb_changed_buffers"] != 0)"""
+        lib().vksift_ext_buildTracksAccumulated(self._h)
+        _check_pending()
+
+    def getAccumulateTime(self):
+        return lib().vksift_ext_getAccumulateTime(self._h)
 
     def selectTrackObservations(self, min_length=2, max_length=0, conflicts=OBS_KEEP_CONFLICTING):
         """builds the observation table of the tracks of the last buildTracks on the GPU (vksift_ext_selectTrackObservations): the tracks of at least

@@ -25,8 +25,8 @@ LIB_PATH = os.path.join(OUT_DIR, "libvulkansift.so")
 HOST_SRCS = ["host/vksift_api.c", "host/vksift_instance.c", "host/vksift_mem.c", "host/vksift_detect.c", "host/vksift_stage.c", "host/vksift_defer.c", "host/vksift_buffers.c", "host/vksift_match.c", "host/vksift_runs.c", "host/vksift_verify.c", "host/vksift_refine.c", "host/vksift_guided.c", "host/vksift_strongest.c", "host/vksift_rootsift.c", "host/vksift_describe.c", "host/vksift_pairs.c",
              "host/vksift_ext.c", "host/vksift_sharded.c", "host/vksift_hostmath.c", "host/vksift_log.c", "host/vksift_synth.c"]
 # (behind the list: tests/native/sim_device.c, which the host scheduler's tests link the list above against, stands in for the launchers those files call)
-HOST_SRCS += ["host/vksift_tracks.c", "host/vksift_observations.c", "host/vksift_triangulate.c", "host/vksift_cameras.c"]
-HIP_SRCS = ["hip/runtime.hip", "hip/pyramid.hip", "hip/extrema.hip", "hip/extract_tail.hip", "hip/features.hip", "hip/features_selftest.hip", "hip/match.hip", "hip/records.hip", "hip/strongest.hip", "hip/spread.hip", "hip/rootsift.hip", "hip/place.hip", "hip/verify.hip", "hip/refine.hip", "hip/refine_f.hip", "hip/guided.hip", "hip/tracks.hip", "hip/observations.hip", "hip/triangulate.hip", "hip/cameras.hip"]
+HOST_SRCS += ["host/vksift_tracks.c", "host/vksift_observations.c", "host/vksift_triangulate.c", "host/vksift_cameras.c", "host/vksift_track_edges.c"]
+HIP_SRCS = ["hip/runtime.hip", "hip/pyramid.hip", "hip/extrema.hip", "hip/extract_tail.hip", "hip/features.hip", "hip/features_selftest.hip", "hip/match.hip", "hip/records.hip", "hip/strongest.hip", "hip/spread.hip", "hip/rootsift.hip", "hip/place.hip", "hip/verify.hip", "hip/refine.hip", "hip/refine_f.hip", "hip/guided.hip", "hip/tracks.hip", "hip/observations.hip", "hip/triangulate.hip", "hip/cameras.hip", "hip/track_edges.hip"]
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")

@@ -17,61 +17,9 @@
 // the XCDs' L2s are not coherent with each other. No lane ever waits for another workgroup: a failed CAS means another lane has linked
 // that root, which is progress; finds walk strictly decreasing indices.
 #include "vksift_hip.h"
-#include "wave.h"
+#include "tracks.h"
 
 #include <hip/hip_runtime.h>
-
-#define TRK_THREADS 256u
-#define TRK_NONE 0xFFFFFFFFu
-#define TRK_GROUP 64u /* buffers per presence launch: the bits of one presence word */
-#define TRK_ECNT 64u  /* words the hook launch's edge count is spread over: thousands of atomic adds on ONE word cost more than the union-find */
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ uint32_t par_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// true: *p was `expect` and is `desired` now; otherwise `expect` holds what was found
-__device__ __forceinline__ bool par_cas(uint32_t *p, uint32_t &expect, uint32_t desired)
-{
-  return __hip_atomic_compare_exchange_strong(p, &expect, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of x. parent[v] <= v everywhere, so the walk strictly decreases until it meets a word that names itself. A stale "I am a root"
-// is possible (the word was linked since); the caller's CAS on that word then fails and it walks on from what the CAS found.
-template <bool SHORTEN> __device__ __forceinline__ uint32_t find_root(uint32_t *parent, uint32_t x)
-{
-  for (;;)
-  {
-    uint32_t p = par_load(parent + x);
-    if (p == x)
-      return x;
-    if (SHORTEN)
-    {
-      // path halving, also through CAS: x is no root, its parent may only move to an ancestor, and never back to an older value
-      const uint32_t gp = par_load(parent + p);
-      if (gp != p)
-        (void)par_cas(parent + x, p, gp);
-    }
-    x = p;
-  }
-}
-
-// the stored rows of the buffer of rank `rank` the launches touch
-__device__ __forceinline__ uint32_t buf_rows(const uint32_t *buf_tab, const uint32_t *rows_dev, uint32_t rank, uint32_t max_rows)
-{
-  const uint32_t n = rows_dev[buf_tab[2u * rank + 1u]];
-  return n < max_rows ? n : max_rows;
-}
-
-// what the per-node launches share: block b serves rows [256 (b % bpb), ...) of the buffer of rank first_rank + b / bpb. Returns the node index, or
-// TRK_NONE for a lane without a stored row
-__device__ __forceinline__ uint32_t block_node(const uint32_t *buf_tab, const uint32_t *rows_dev, uint32_t first_rank, uint32_t bpb, uint32_t node_stride, uint32_t max_rows,
-                                               uint32_t &rank, uint32_t &row)
-{
-  rank = first_rank + blockIdx.x / bpb;
-  row = (blockIdx.x % bpb) * TRK_THREADS + threadIdx.x;
-  return row < buf_rows(buf_tab, rows_dev, rank, max_rows) ? rank * node_stride + row : TRK_NONE;
-}
 
 __global__ __launch_bounds__(TRK_THREADS) void k_tracks_init(const uint32_t *buf_tab, const uint32_t *rows_dev, uint32_t bpb, uint32_t node_stride, uint32_t max_rows,
                                                              uint32_t *parent, uint32_t *len, uint32_t *nbuf, u64 *bits, uint32_t *ecnt)
@@ -93,44 +41,14 @@ __global__ __launch_bounds__(TRK_THREADS) void k_tracks_hook(const uint8_t *reco
                                                              const uint32_t *slot_tab, uint32_t slot_tab_stride, const uint32_t *buf_tab, uint32_t nbufs,
                                                              const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows, uint32_t *parent, uint32_t *ecnt)
 {
-  const uint32_t p = blockIdx.y, e = blockIdx.x * TRK_THREADS + threadIdx.x;
-  uint32_t n = n_dev[(size_t)p * n_stride];
-  n = n < max_n ? n : max_n;
-  if (blockIdx.x * TRK_THREADS >= n || (valid != nullptr && valid[(size_t)p * valid_stride] == 0))
-    return; // (uniform over the workgroup)
-  const uint32_t ra = slot_tab[(size_t)p * slot_tab_stride], rb = slot_tab[(size_t)p * slot_tab_stride + 1u];
-  bool edge = e < n && ra < nbufs && rb < nbufs;
-  if (edge && masks != nullptr)
-    edge = masks[p * mask_slot_stride + e] == 1u;
-  uint32_t u = 0, v = 0;
-  if (edge)
-  {
-    const uint32_t *rec = (const uint32_t *)(records + p * rec_slot_stride + (uint64_t)e * 16u);
-    const uint32_t ia = rec[0], ib = rec[1];
-    // (a record of the library's own producers always names stored rows; anything else is no edge, so that no word outside the rows is touched)
-    edge = ia < buf_rows(buf_tab, rows_dev, ra, max_rows) && ib < buf_rows(buf_tab, rows_dev, rb, max_rows);
-    u = ra * node_stride + ia, v = rb * node_stride + ib;
-  }
-  const uint32_t in_block = (uint32_t)__syncthreads_count(edge);
-  if (threadIdx.x == 0 && in_block)
-    atomicAdd(ecnt + ((blockIdx.y * gridDim.x + blockIdx.x) & (TRK_ECNT - 1u)), in_block);
-  if (!edge)
+  const PairEdges in = {records, rec_slot_stride, n_dev, n_stride, max_n, masks, mask_slot_stride, valid, valid_stride, slot_tab, slot_tab_stride, buf_tab, nbufs, rows_dev, max_rows};
+  if (pair_block_idle(in))
     return;
-  // Link the larger root under the smaller: every component's root ends up its smallest member, whatever the schedule. A root stops being one
-  // exactly once, through a CAS on its own word; a failed CAS returns the parent it got, and the walk goes on from there.
-  for (;;)
-  {
-    u = find_root<true>(parent, u);
-    v = find_root<true>(parent, v);
-    if (u == v)
-      break;
-    uint32_t hi = u > v ? u : v;
-    const uint32_t lo = u > v ? v : u;
-    uint32_t found = hi;
-    if (par_cas(parent + hi, found, lo))
-      break;
-    u = found, v = lo;
-  }
+  uint32_t ra, ia, rb, ib;
+  const bool edge = pair_edge(in, ra, ia, rb, ib);
+  count_block_edges(edge, blockIdx.y * gridDim.x + blockIdx.x, ecnt);
+  if (edge)
+    union_nodes(parent, ra * node_stride + ia, rb * node_stride + ib);
 }
 
 __global__ __launch_bounds__(TRK_THREADS) void k_tracks_flatten(const uint32_t *buf_tab, const uint32_t *rows_dev, uint32_t bpb, uint32_t node_stride, uint32_t max_rows,
@@ -280,12 +198,41 @@ __global__ __launch_bounds__(TRK_THREADS) void k_tracks_label(const uint32_t *bu
     node_words[node] = node_words[root]; // (the roots' words are the previous launch's: no lane of this one writes them)
 }
 
-static inline uint64_t trk_blocks_per_buffer(uint32_t rows) { return ((uint64_t)rows + TRK_THREADS - 1u) / TRK_THREADS; }
-
 extern "C" size_t vksift_hip_tracks_scratch_u32(uint32_t nbufs, uint32_t node_stride)
 {
   const uint64_t nodes = (uint64_t)nbufs * node_stride;
   return (size_t)(5u * nodes + 3u * (uint64_t)nbufs * trk_blocks_per_buffer(node_stride) + TRK_ECNT + 2u);
+}
+
+int tracks_args_check(uint32_t nbufs, uint32_t node_stride, uint32_t max_rows, const uint8_t *tracks, uint64_t tracks_cap, const uint32_t *scratch, size_t scratch_u32)
+{
+  const uint64_t nodes = (uint64_t)nbufs * node_stride;
+  if (nbufs == 0 || max_rows == 0 || max_rows > node_stride || nodes >= 0xFFFFFFFFull || ((uintptr_t)tracks & 3u) || ((uintptr_t)scratch & 7u) ||
+      tracks_cap < (uint64_t)nbufs * max_rows / 2u || scratch_u32 < vksift_hip_tracks_scratch_u32(nbufs, node_stride) ||
+      (uint64_t)nbufs * trk_blocks_per_buffer(max_rows) > 0x7FFFFFFFull)
+    return (int)hipErrorInvalidValue;
+  return 0;
+}
+
+void tracks_queue_init(const uint32_t *buf_tab, const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows, const TrackScratch &t, hipStream_t st)
+{
+  k_tracks_init<<<t.nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, t.bpb, node_stride, max_rows, t.parent, t.len, t.nbuf, t.bits, t.ecnt);
+}
+
+void tracks_queue_tail(const uint32_t *buf_tab, uint32_t nbufs, const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows, const TrackScratch &t, uint32_t *node_words,
+                       uint32_t *tracks, uint32_t *stats, hipStream_t st)
+{
+  const uint32_t bpb = t.bpb, nblocks = t.nblocks;
+  k_tracks_flatten<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, t.parent, t.len);
+  for (uint32_t g = 0; g < nbufs; g += TRK_GROUP)
+  {
+    const uint32_t nb = nbufs - g < TRK_GROUP ? nbufs - g : TRK_GROUP;
+    k_tracks_presence<<<nb * bpb, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, g, bpb, node_stride, max_rows, t.parent, t.len, t.bits);
+    k_tracks_fold<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, t.parent, t.len, t.nbuf, t.bits, g + TRK_GROUP >= nbufs ? t.bsum : nullptr);
+  }
+  k_tracks_scan<<<1, 1024, 0, st>>>(t.bsum, nblocks, t.ecnt, stats);
+  k_tracks_number<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, t.parent, t.len, t.nbuf, t.bsum, node_words, tracks);
+  k_tracks_label<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, t.parent, node_words);
 }
 
 extern "C" int vksift_hip_build_tracks(const uint8_t *records, uint64_t rec_slot_stride, const uint32_t *n_dev, uint32_t n_stride, uint32_t max_n, const uint8_t *masks,
@@ -293,21 +240,13 @@ extern "C" int vksift_hip_build_tracks(const uint8_t *records, uint64_t rec_slot
                                        uint32_t nslots, const uint32_t *buf_tab, uint32_t nbufs, const uint32_t *rows_dev, uint32_t node_stride, uint32_t max_rows,
                                        uint32_t *node_words, uint8_t *tracks, uint64_t tracks_cap, uint32_t *stats, uint32_t *scratch, size_t scratch_u32, vksift_hip_stream s)
 {
-  const uint64_t nodes = (uint64_t)nbufs * node_stride;
-  if (nslots == 0 || nbufs == 0 || max_n == 0 || max_rows == 0 || max_rows > node_stride || nodes >= 0xFFFFFFFFull || n_stride == 0 || slot_tab_stride < 2u ||
-      (valid != nullptr && valid_stride == 0) || ((uintptr_t)records & 3u) || (rec_slot_stride & 3u) || ((uintptr_t)tracks & 3u) || ((uintptr_t)scratch & 7u) ||
-      (nslots > 1u && (rec_slot_stride < 16ull * max_n || (masks != nullptr && mask_slot_stride < max_n))) || tracks_cap < (uint64_t)nbufs * max_rows / 2u ||
-      scratch_u32 < vksift_hip_tracks_scratch_u32(nbufs, node_stride))
+  if (nslots == 0 || max_n == 0 || n_stride == 0 || slot_tab_stride < 2u || (valid != nullptr && valid_stride == 0) || ((uintptr_t)records & 3u) || (rec_slot_stride & 3u) ||
+      (nslots > 1u && (rec_slot_stride < 16ull * max_n || (masks != nullptr && mask_slot_stride < max_n))) ||
+      tracks_args_check(nbufs, node_stride, max_rows, tracks, tracks_cap, scratch, scratch_u32) != 0)
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)s;
-  const uint32_t bpb = (uint32_t)trk_blocks_per_buffer(max_rows);
-  const uint64_t nblocks64 = (uint64_t)nbufs * bpb;
-  if (nblocks64 > 0x7FFFFFFFull)
-    return (int)hipErrorInvalidValue;
-  const uint32_t nblocks = (uint32_t)nblocks64;
-  u64 *bits = (u64 *)scratch;
-  uint32_t *parent = scratch + 2u * nodes, *len = parent + nodes, *nbuf = len + nodes, *bsum = nbuf + nodes, *ecnt = bsum + 3u * (size_t)nblocks;
-  k_tracks_init<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, parent, len, nbuf, bits, ecnt);
+  const TrackScratch t = track_scratch(scratch, nbufs, node_stride, max_rows);
+  tracks_queue_init(buf_tab, rows_dev, node_stride, max_rows, t, st);
   const uint32_t eblocks = (max_n + TRK_THREADS - 1u) / TRK_THREADS;
   for (uint32_t r = 0; r < nslots; r += 65535u)
   {
@@ -315,17 +254,8 @@ extern "C" int vksift_hip_build_tracks(const uint8_t *records, uint64_t rec_slot
     k_tracks_hook<<<dim3(eblocks, n), TRK_THREADS, 0, st>>>(records + r * rec_slot_stride, rec_slot_stride, n_dev + (size_t)r * n_stride, n_stride, max_n,
                                                             masks ? masks + r * mask_slot_stride : nullptr, mask_slot_stride, valid ? valid + (size_t)r * valid_stride : nullptr,
                                                             valid_stride, slot_tab + (size_t)r * slot_tab_stride, slot_tab_stride, buf_tab, nbufs, rows_dev, node_stride,
-                                                            max_rows, parent, ecnt);
+                                                            max_rows, t.parent, t.ecnt);
   }
-  k_tracks_flatten<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, parent, len);
-  for (uint32_t g = 0; g < nbufs; g += TRK_GROUP)
-  {
-    const uint32_t nb = nbufs - g < TRK_GROUP ? nbufs - g : TRK_GROUP;
-    k_tracks_presence<<<nb * bpb, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, g, bpb, node_stride, max_rows, parent, len, bits);
-    k_tracks_fold<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, parent, len, nbuf, bits, g + TRK_GROUP >= nbufs ? bsum : nullptr);
-  }
-  k_tracks_scan<<<1, 1024, 0, st>>>(bsum, nblocks, ecnt, stats);
-  k_tracks_number<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, parent, len, nbuf, bsum, node_words, (uint32_t *)tracks);
-  k_tracks_label<<<nblocks, TRK_THREADS, 0, st>>>(buf_tab, rows_dev, bpb, node_stride, max_rows, parent, node_words);
+  tracks_queue_tail(buf_tab, nbufs, rows_dev, node_stride, max_rows, t, node_words, (uint32_t *)tracks, stats, st);
   return (int)hipGetLastError();
 }

@@ -3,7 +3,7 @@
  * (vksift_ext_indexObservationsByView and its accessors) and the refinement of every camera on the points of the last triangulation, the points held
  * fixed (vksift_ext_refineCameras and its accessors). No counterpart in the reference: its callers download the table and the points, invert the table
  * by view on the host and run a Gauss-Newton per view there. Same contract as the stages they follow (vksift_observations.c, vksift_triangulate.c):
- * queued on the instance stream, the pairs' buffers busy, the accessors wait; results in storage of their own.
+ * queued on the instance stream, the tracks' participating buffers busy, the accessors wait; results in storage of their own.
  */
 #include "vksift_internal.h"
 
@@ -66,8 +66,8 @@ void vksift_ext_indexObservationsByView(vksift_Instance instance)
   StageFrame frame = {0};
   vksift_hip_set_device(inst->device);
   defer_sync(inst);
-  const uint32_t count = inst->res[PR_FILTERED].slots_used;
-  if (!inst->obs.valid || !inst->tracks.valid || count == 0)
+  const TrackResults *t = &inst->tracks;
+  if (!inst->obs.valid || !t->valid)
   {
     logError(LOG_TAG, IDX_FN " error: invalid input.");
     inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
@@ -85,11 +85,11 @@ void vksift_ext_indexObservationsByView(vksift_Instance instance)
   }
   HIP_CHECK(stage_begin(inst, &frame, T_VIEWS, "View index"), "timer start");
   HIP_CHECK(queue_index(inst), "view indexing");
-  HIP_CHECK(stage_end(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
+  HIP_CHECK(stage_end(inst, &frame, t->ids, t->ids, t->nbufs), "event record");
   inst->views.valid = true;
   return;
 gpu_error:
-  stage_fail(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count);
+  stage_fail(inst, &frame, t->ids, t->ids, t->nbufs);
   logError(LOG_TAG, IDX_FN " error: Failed to start the view indexing.");
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }
@@ -153,8 +153,7 @@ void vksift_ext_refineCameras(vksift_Instance instance, uint32_t nb_steps)
   StageFrame frame = {0};
   vksift_hip_set_device(inst->device);
   defer_sync(inst);
-  const uint32_t count = inst->res[PR_FILTERED].slots_used;
-  if (!inst->tri.valid || !inst->obs.valid || !t->valid || count == 0 || nb_steps == 0 || nb_steps > VKSIFT_EXT_CAMERA_MAX_STEPS)
+  if (!inst->tri.valid || !inst->obs.valid || !t->valid || nb_steps == 0 || nb_steps > VKSIFT_EXT_CAMERA_MAX_STEPS)
   {
     logError(LOG_TAG, CAM_FN " error: invalid input.");
     inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
@@ -181,11 +180,11 @@ void vksift_ext_refineCameras(vksift_Instance instance, uint32_t nb_steps)
             "camera refinement");
   c->valid = false; /* the launch replaces the records: not served until the whole sequence has been queued */
   HIP_CHECK(vksift_hip_post_words(c->h_stats, c->d_stats, 4u, inst->stream), "camera statistics read-back");
-  HIP_CHECK(stage_end(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
+  HIP_CHECK(stage_end(inst, &frame, t->ids, t->ids, t->nbufs), "event record");
   inst->views.valid = c->valid = true;
   return;
 gpu_error:
-  stage_fail(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count);
+  stage_fail(inst, &frame, t->ids, t->ids, t->nbufs);
   logError(LOG_TAG, CAM_FN " error: Failed to start the camera refinement.");
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }

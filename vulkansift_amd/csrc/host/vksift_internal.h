@@ -1,6 +1,6 @@
 /*
  * vksift_internal.h — private definitions shared by the host translation units behind the vksift_* C API
- * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_triangulate.c, vksift_cameras.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
+ * (vksift_api.c, vksift_instance.c, vksift_mem.c, vksift_detect.c, vksift_stage.c, vksift_defer.c, vksift_buffers.c, vksift_match.c, vksift_verify.c, vksift_refine.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_triangulate.c, vksift_cameras.c, vksift_track_edges.c, vksift_strongest.c, vksift_rootsift.c, vksift_runs.c, vksift_describe.c, vksift_pairs.c, vksift_ext.c).
  * Nothing here is part of the public ABI; every function is hidden from the shared library's export table.
  */
 #ifndef VKSIFT_INTERNAL_H
@@ -76,7 +76,7 @@ typedef struct
 } MatchScratch;
 
 /* the interval of a stage's last run under vksift_ext_setProfiling (vksift_pairs.c). One per getter: both verification models share T_VERIFY */
-enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_OBSERVATIONS, T_TRIANGULATE, T_VIEWS, T_CAMERAS, T_COUNT };
+enum { T_MATCH, T_VERIFY, T_REFINE_H, T_REFINE_F, T_GUIDED, T_BUDGET, T_BUDGET_GRID, T_ROOTSIFT, T_TRACKS, T_OBSERVATIONS, T_TRIANGULATE, T_VIEWS, T_CAMERAS, T_ACCUMULATE, T_COUNT };
 typedef struct
 {
   vksift_hip_event ev[2];
@@ -97,9 +97,10 @@ typedef struct
   uint32_t slots_used;
 } PairResults;
 
-/* What vksift_ext_buildTracks keeps (vksift_tracks.c): not per pair, so not a PairResults. Sized by the configuration when the first build allocates it:
- * cap_bufs = min(2 batch_cap, sift_buffer_count) participating buffers of max_nb_sift_per_buffer nodes each. `valid`: the accessors have something to
- * read; cleared by a new matching (beside pair_results_invalidate). */
+/* What vksift_ext_buildTracks and vksift_ext_buildTracksAccumulated keep (vksift_tracks.c, vksift_track_edges.c): not per pair, so not a PairResults. Sized by
+ * the configuration when the first build allocates it: cap_bufs participating buffers of max_nb_sift_per_buffer nodes each, cap_bufs = min(2 batch_cap,
+ * sift_buffer_count), or sift_buffer_count once an accumulation has been begun (all_bufs). `valid`: the accessors have something to read; cleared by a new
+ * matching (beside pair_results_invalidate). */
 typedef struct
 {
   uint32_t *d_node_words; /* per node (rank * max_nb_sift_per_buffer + row): its track number */
@@ -107,13 +108,37 @@ typedef struct
   uint32_t *d_stats, *h_stats; /* the four words of vksift_ext_TrackStats, posted */
   uint32_t *d_scratch;    /* parent, length, buffer count and presence words (vksift_hip_tracks_scratch_u32) */
   size_t scratch_u32;
-  uint32_t *h_tab, *d_tab; /* {rank A, rank B} per slot of batch_cap, then {gpu_buffer_id, word of d_match_n} per rank: filled in pinned memory, copied to the
-                            * device in front of the launches (every edge reads its pair's and its buffers' entries) */
-  uint32_t *rank_of;      /* per SIFT buffer: its rank in the last build, VKSIFT_EXT_NO_TRACK outside the pair list */
-  uint32_t *count_word;   /* per rank: the word of h_match_n / d_match_n that holds the buffer's row count */
+  uint32_t *h_tab, *d_tab; /* {rank A, rank B} per slot of batch_cap, then {gpu_buffer_id, word of d_rows} per rank of cap_bufs, then (accumulated build) the rank
+                            * of every SIFT buffer: filled in pinned memory, copied to the device in front of the launches (every edge reads its pair's and
+                            * its buffers' entries) */
+  uint32_t *rank_of;      /* per SIFT buffer: its rank in the last build, VKSIFT_EXT_NO_TRACK for a buffer that took no part */
+  uint32_t *ids;          /* per rank: the gpu_buffer_id. The participating buffers of the last build: the sides of the last pair list for a plain build, every
+                           * buffer the store's calls named for an accumulated one. The stages that read the tracks keep THESE busy */
+  uint32_t *count_word;   /* per rank: the word of h_rows / d_rows that holds the buffer's row count */
+  const uint32_t *d_rows, *h_rows; /* the row-count words the launches read and their host mirror: d_match_n / h_match_n for a plain build, d_rows_acc /
+                                    * h_rows_acc for an accumulated one */
+  uint32_t *d_rows_acc, *h_rows_acc; /* per SIFT buffer: the accumulated build's copy of the store's row table, and the copy posted */
   uint32_t cap_bufs, nbufs, max_rows;
+  bool all_bufs;          /* sized for sift_buffer_count buffers, not min(2 batch_cap, sift_buffer_count): since the first vksift_ext_beginTrackAccumulation */
   bool valid, tab_pending;
 } TrackResults;
+
+/* What vksift_ext_beginTrackAccumulation ... vksift_ext_buildTracksAccumulated keep (vksift_track_edges.c): the edges of every accumulated matching, on the
+ * device, and one row count per SIFT buffer. Outlives matchings and builds; emptied by begin alone. */
+typedef struct
+{
+  uint8_t *d_edges;            /* max_edges vksift_ext_TrackEdge records */
+  uint32_t *d_stats, *h_stats; /* the four words of vksift_ext_TrackEdgeStats, posted by every accumulate */
+  uint32_t *d_rows;            /* per SIFT buffer: the row count the first call that named it found, 0xFFFFFFFF before */
+  uint32_t *d_scratch;         /* the append's block counts (vksift_hip_track_edges_scratch_u32) */
+  size_t scratch_u32;
+  uint32_t *h_tab, *d_tab;     /* one accumulate's {rank A, rank B} per slot of batch_cap, then {gpu_buffer_id, word of d_match_n} per buffer of the call: filled
+                                * in pinned memory, copied to the device in front of the launches */
+  uint32_t *rank_of;           /* per SIFT buffer: scratch of one accumulate's ranking */
+  bool *named;                 /* per SIFT buffer: a call of the store has named it */
+  uint32_t max_edges, max_rows, nb_calls; /* max_rows: the largest rows_bound() of a named buffer when its call was queued */
+  bool begun, failed, tab_pending;
+} EdgeStore;
 
 /* What vksift_ext_selectTrackObservations keeps (vksift_observations.c), sized like the tracks it reads: at most cap_bufs * max_nb_sift_per_buffer
  * observations of half as many tracks. Allocated by the first selection. `valid`: cleared wherever tracks.valid is, and by a new build. */
@@ -124,7 +149,7 @@ typedef struct
   uint32_t *d_stats, *h_stats;       /* the four words of vksift_ext_ObservationStats, posted */
   uint32_t *d_scratch;               /* coordinates, sort lists, digit table, map (vksift_hip_observations_scratch_u32) */
   size_t scratch_u32;
-  uint32_t *h_tab;                   /* mapped pinned memory read by the launches: a pair table (pair_tables), then one layout word per rank */
+  uint32_t *h_tab;                   /* mapped pinned memory read by the launches: cap_bufs section tables (buffer_layouts), then one layout word per rank */
   bool valid, tab_pending;
 } ObservationResults;
 
@@ -301,6 +326,8 @@ struct vksift_Instance_T
   bool gtab_pending;
   /* feature tracks over the pair list (vksift_ext_buildTracks, vksift_tracks.c) */
   TrackResults tracks;
+  /* the edge store of tracks across matching calls (vksift_ext_beginTrackAccumulation, vksift_track_edges.c) */
+  EdgeStore edges;
   /* the observation table of selected tracks (vksift_ext_selectTrackObservations, vksift_observations.c) */
   ObservationResults obs;
   /* the points of the selected tracks under caller-supplied cameras (vksift_ext_triangulateTracks, vksift_triangulate.c) */
@@ -363,6 +390,7 @@ struct vksift_Instance_T
   vksift_hip_event ev_vtab; /* the last gather launch has read h_vtab (created by the first verification) */
   vksift_hip_event ev_gtab; /* the last guided matching has read h_gtab (created by the first guided matching) */
   vksift_hip_event ev_ttab; /* the last track build has copied tracks.h_tab (created by the first build) */
+  vksift_hip_event ev_etab; /* the last accumulate has copied edges.h_tab (created by the first accumulation) */
   vksift_hip_event ev_otab; /* the last observation launches have read obs.h_tab (created by the first selection) */
   vksift_hip_event ev_ctab; /* the last triangulation has copied tri.h_cameras (created by the first triangulation) */
   vksift_hip_event ev_kps;  /* the last describe call's copy has read h_kps (created by the first describe call) */
@@ -492,6 +520,22 @@ VKSIFT_INTERNAL int match_follow(vksift_Instance inst, const uint32_t *ids_a, co
 static inline uint32_t *pair_layouts(const struct vksift_Instance_T *inst, uint32_t *tab) { return tab + (size_t)PAIR_SLOT_WORDS * inst->batch_cap; }
 static inline size_t pair_table_words(const struct vksift_Instance_T *inst) { return ((size_t)PAIR_SLOT_WORDS + (size_t)VKSIFT_LAYOUT_WORDS * 2u) * inst->batch_cap; }
 VKSIFT_INTERNAL void pair_tables(vksift_Instance inst, uint32_t *tab, uint32_t count, uint32_t *max_rows);
+/* the layout words of n buffers, whichever pair list they were in: words[i] names the section table of ids[i] among those appended to `layouts` (at most n
+ * tables of VKSIFT_LAYOUT_WORDS), as the layout words of a pair table do */
+VKSIFT_INTERNAL void buffer_layouts(vksift_Instance inst, const uint32_t *ids, uint32_t n, uint32_t *words, uint32_t *layouts);
+
+/* vksift_tracks.c */
+/* the record set (and the set whose masks and valid words select among its records, or NULL) a VKSIFT_EXT_TRACKS_* source takes its edges from; false: no
+ * filtered matching, an unknown source, or a source whose stage has not run for the present matching */
+VKSIFT_INTERNAL bool track_source(vksift_Instance inst, uint32_t source, const PairResults **rec, const PairResults **sel);
+/* the tracks' storage for tracks.cap_bufs buffers (allocated by the first build of either kind); false: out of memory */
+VKSIFT_INTERNAL bool track_storage_ensure(vksift_Instance inst);
+/* what both builds fill for one pair list: rank_of (per SIFT buffer; VKSIFT_EXT_NO_TRACK outside the list), {rank A, rank B} per slot, {gpu_buffer_id, word of
+ * d_match_n} per rank and, unless NULL, ids and count_word per rank. Returns the number of buffers; *max_rows: the largest rows_bound() among them, 1 at least */
+VKSIFT_INTERNAL uint32_t pair_list_ranks(vksift_Instance inst, uint32_t count, uint32_t *rank_of, uint32_t *slot_tab, uint32_t *buf_tab, uint32_t *ids, uint32_t *count_word,
+                                         uint32_t *max_rows);
+/* a build of either kind replaces the tracks: they and everything computed from them are not served any more */
+static inline void tracks_invalidate(vksift_Instance inst) { inst->tracks.valid = inst->obs.valid = inst->tri.valid = inst->views.valid = inst->cams.valid = false; }
 
 
 /* vksift_pairs.c */

@@ -57,6 +57,13 @@ void pair_tables(vksift_Instance inst, uint32_t *tab, uint32_t count, uint32_t *
     *max_rows = rows < inst->cfg.max_nb_sift_per_buffer ? rows : inst->cfg.max_nb_sift_per_buffer;
 }
 
+void buffer_layouts(vksift_Instance inst, const uint32_t *ids, uint32_t n, uint32_t *words, uint32_t *layouts)
+{
+  uint32_t nlay = 0;
+  for (uint32_t i = 0; i < n; i++)
+    words[i] = layout_word(&inst->bufs[ids[i]], layouts, &nlay);
+}
+
 /* The matcher's input of a SIFT buffer — dense 128-byte descriptor rows in download order, their shifted norms and the row
  * count — lives in a per-buffer cache entry, filled by ONE device-side gather the first time the buffer is matched after it
  * changed (detection, upload) and reused by every later matching: a self-match gathers once instead of twice, the two
@@ -187,7 +194,7 @@ static void match_impl(vksift_Instance inst, const uint32_t *ids_a, const uint32
       /* the first launch that overwrites the previous matching's records and counts has been queued: nothing of that matching is served any more,
        * whatever becomes of this call (it marks its own results once the whole sequence has been queued) */
       pair_results_invalidate(inst);
-      inst->tracks.valid = inst->obs.valid = inst->tri.valid = inst->views.valid = inst->cams.valid = false; /* tracks are built from the pairs of a matching (vksift_tracks.c), observations from tracks, points and the view index from observations, refined cameras from both */
+      tracks_invalidate(inst); /* tracks are built from the pairs of a matching (vksift_tracks.c), observations from tracks, points and the view index from observations, refined cameras from both */
       inst->match_slots_used = 0;
       inst->md_valid = false, inst->md_hits = 0, inst->md_direct = false, inst->md_asked = false;
     }

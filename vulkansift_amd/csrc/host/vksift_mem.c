@@ -110,7 +110,9 @@ static const Block blocks[] = {
     LAZY(rev.matches, MEM_DEVICE), LAZY(rev.redo, MEM_DEVICE), LAZY(rev.match_n, MEM_DEVICE),
     LAZY(filt_ids, MEM_HEAP), LAZY(d_corr, MEM_DEVICE), LAZY(d_vscratch, MEM_DEVICE), LAZY(h_vtab, MEM_PINNED), LAZY(d_gxy, MEM_DEVICE), LAZY(d_gkeys, MEM_DEVICE), LAZY(h_gtab, MEM_PINNED),
     LAZY(tracks.d_node_words, MEM_DEVICE), LAZY(tracks.d_records, MEM_DEVICE), LAZY(tracks.d_stats, MEM_DEVICE), LAZY(tracks.h_stats, MEM_PINNED), LAZY(tracks.d_scratch, MEM_DEVICE),
-    LAZY(tracks.h_tab, MEM_PINNED), LAZY(tracks.d_tab, MEM_DEVICE), LAZY(tracks.rank_of, MEM_HEAP), LAZY(tracks.count_word, MEM_HEAP),
+    LAZY(tracks.h_tab, MEM_PINNED), LAZY(tracks.d_tab, MEM_DEVICE), LAZY(tracks.rank_of, MEM_HEAP), LAZY(tracks.count_word, MEM_HEAP), LAZY(tracks.ids, MEM_HEAP), LAZY(tracks.d_rows_acc, MEM_DEVICE), LAZY(tracks.h_rows_acc, MEM_PINNED),
+    LAZY(edges.d_edges, MEM_DEVICE), LAZY(edges.d_stats, MEM_DEVICE), LAZY(edges.h_stats, MEM_PINNED), LAZY(edges.d_rows, MEM_DEVICE), LAZY(edges.d_scratch, MEM_DEVICE),
+    LAZY(edges.h_tab, MEM_PINNED), LAZY(edges.d_tab, MEM_DEVICE), LAZY(edges.rank_of, MEM_HEAP), LAZY(edges.named, MEM_HEAP),
     LAZY(obs.d_offsets, MEM_DEVICE), LAZY(obs.d_track_ids, MEM_DEVICE), LAZY(obs.d_obs, MEM_DEVICE), LAZY(obs.d_stats, MEM_DEVICE), LAZY(obs.h_stats, MEM_PINNED),
     LAZY(obs.d_scratch, MEM_DEVICE), LAZY(obs.h_tab, MEM_PINNED),
     LAZY(tri.d_points, MEM_DEVICE), LAZY(tri.d_stats, MEM_DEVICE), LAZY(tri.h_stats, MEM_PINNED), LAZY(tri.h_cameras, MEM_PINNED), LAZY(tri.d_cameras, MEM_DEVICE),
@@ -201,7 +203,7 @@ typedef struct
 {
   size_t field;
   uint16_t count, step;
-  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_tracks.c, vksift_observations.c, vksift_triangulate.c, vksift_cameras.c, vksift_pairs.c, vksift_describe.c), destroyed here */
+  bool is_stream, lazy; /* lazy: created by its user (vksift_buffers.c, vksift_verify.c, vksift_guided.c, vksift_tracks.c, vksift_track_edges.c, vksift_observations.c, vksift_triangulate.c, vksift_cameras.c, vksift_pairs.c, vksift_describe.c), destroyed here */
 } Handle;
 #define EVENTS(f, n, step, lazy) {FIELD(f), n, step, false, lazy}
 #define STREAM(f) {FIELD(f), 1, 0, true, false}
@@ -216,8 +218,8 @@ static const Handle handles[] = {
     EVENTS(prof[0].ev_t, 8, sizeof(vksift_hip_event), false), EVENTS(prof[1].ev_t, 8, sizeof(vksift_hip_event), false),
     EVENTS(prof[0].ev_pt, 3, sizeof(vksift_hip_event), false), EVENTS(prof[1].ev_pt, 3, sizeof(vksift_hip_event), false),
     EVENTS(prof[0].ev_scan, 2, sizeof(ProfSet), false), TIMER(T_MATCH, false),
-    EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_gtab, 1, 0, true), EVENTS(ev_ttab, 1, 0, true), EVENTS(ev_otab, 1, 0, true), EVENTS(ev_ctab, 1, 0, true), EVENTS(ev_kps, 1, 0, true),
-    TIMER(T_VERIFY, true), TIMER(T_REFINE_H, true), TIMER(T_REFINE_F, true), TIMER(T_GUIDED, true), TIMER(T_BUDGET, true), TIMER(T_BUDGET_GRID, true), TIMER(T_ROOTSIFT, true), TIMER(T_TRACKS, true), TIMER(T_OBSERVATIONS, true), TIMER(T_TRIANGULATE, true), TIMER(T_VIEWS, true), TIMER(T_CAMERAS, true),
+    EVENTS(dl_ev, VKSIFT_DL_CHUNKS, sizeof(vksift_hip_event), true), EVENTS(ev_vtab, 1, 0, true), EVENTS(ev_gtab, 1, 0, true), EVENTS(ev_ttab, 1, 0, true), EVENTS(ev_etab, 1, 0, true), EVENTS(ev_otab, 1, 0, true), EVENTS(ev_ctab, 1, 0, true), EVENTS(ev_kps, 1, 0, true),
+    TIMER(T_VERIFY, true), TIMER(T_REFINE_H, true), TIMER(T_REFINE_F, true), TIMER(T_GUIDED, true), TIMER(T_BUDGET, true), TIMER(T_BUDGET_GRID, true), TIMER(T_ROOTSIFT, true), TIMER(T_TRACKS, true), TIMER(T_OBSERVATIONS, true), TIMER(T_TRIANGULATE, true), TIMER(T_VIEWS, true), TIMER(T_CAMERAS, true), TIMER(T_ACCUMULATE, true),
 };
 #define N_HANDLES (sizeof(handles) / sizeof(handles[0]))
 

@@ -2,7 +2,7 @@
  * vksift_observations.c — the observation table of the tracks of the last vksift_ext_buildTracks (vksift_ext_selectTrackObservations and its
  * accessors): which tracks a caller keeps, and their members with positions, grouped by track on the device. No counterpart in the reference:
  * its callers download the per-feature words and every feature record of every buffer and group them with a host sort. Same contract as the
- * build it follows (vksift_tracks.c): queued on the instance stream, the pairs' buffers busy, the accessors wait; results in storage of its own.
+ * build it follows (vksift_tracks.c): queued on the instance stream, the tracks' participating buffers busy, the accessors wait; results in storage of its own.
  */
 #include "vksift_internal.h"
 
@@ -30,7 +30,7 @@ static bool ensure_observation_storage(vksift_Instance inst)
                   mem_ensure(&o->d_track_ids, sizeof(uint32_t) * (nodes / 2u) + 8u, MEM_DEVICE) &&
                   mem_ensure(&o->d_obs, sizeof(vksift_ext_Observation) * nodes + 16u, MEM_DEVICE) && mem_ensure(&o->d_stats, sizeof(uint32_t) * 4u, MEM_DEVICE) &&
                   mem_ensure(&o->h_stats, sizeof(uint32_t) * 4u, MEM_PINNED) && mem_ensure(&o->d_scratch, sizeof(uint32_t) * o->scratch_u32 + 8u, MEM_DEVICE) &&
-                  mem_ensure(&o->h_tab, sizeof(uint32_t) * (pair_table_words(inst) + cap_bufs), MEM_PINNED);
+                  mem_ensure(&o->h_tab, sizeof(uint32_t) * ((size_t)VKSIFT_LAYOUT_WORDS + 1u) * cap_bufs, MEM_PINNED);
   if (!inst->ev_otab)
     inst->ev_otab = vksift_hip_event_create();
   return ok && inst->ev_otab;
@@ -44,8 +44,8 @@ void vksift_ext_selectTrackObservations(vksift_Instance instance, uint32_t min_l
   StageFrame frame = {0};
   vksift_hip_set_device(inst->device);
   defer_sync(inst);
-  const uint32_t count = inst->res[PR_FILTERED].slots_used, nb = inst->cfg.max_nb_sift_per_buffer;
-  if (!t->valid || count == 0 || min_length < 2u || (max_length != 0u && max_length < min_length) || conflicts > VKSIFT_EXT_OBS_DROP_CONFLICTING)
+  const uint32_t nb = inst->cfg.max_nb_sift_per_buffer;
+  if (!t->valid || min_length < 2u || (max_length != 0u && max_length < min_length) || conflicts > VKSIFT_EXT_OBS_DROP_CONFLICTING)
   {
     logError(LOG_TAG, OBS_FN " error: invalid input.");
     inst->error_cb(VKSIFT_INVALID_INPUT_ERROR);
@@ -67,17 +67,15 @@ void vksift_ext_selectTrackObservations(vksift_Instance instance, uint32_t min_l
     HIP_CHECK(vksift_hip_event_sync(inst->ev_otab), "event synchronisation");
     o->tab_pending = false;
   }
-  /* one layout word per rank, from the pair table of the matching's pairs (every buffer of the build is a side of one of them) */
-  pair_tables(inst, o->h_tab, count, NULL);
-  uint32_t *rank_layouts = o->h_tab + pair_table_words(inst);
-  for (uint32_t i = 0; i < count; i++)
-    for (uint32_t side = 0; side < 2u; side++)
-      rank_layouts[t->rank_of[o->h_tab[PAIR_SLOT_WORDS * i + side]]] = o->h_tab[PAIR_SLOT_WORDS * i + 2u + side];
+  /* one layout word per rank and the section tables they name, for the participating buffers of the build (the sides of the last pair list, or every
+   * buffer an accumulation named) */
+  uint32_t *layouts = o->h_tab, *rank_layouts = o->h_tab + (size_t)VKSIFT_LAYOUT_WORDS * t->cap_bufs;
+  buffer_layouts(inst, t->ids, t->nbufs, rank_layouts, layouts);
   const uint64_t cap_nodes = (uint64_t)t->cap_bufs * nb;
   HIP_CHECK(stage_begin(inst, &frame, T_OBSERVATIONS, "Track observations"), "timer start");
   /* the tables and counts of the build, where it left them on the device (tracks.d_tab is rewritten by the next build only, which invalidates this) */
-  HIP_CHECK(vksift_hip_track_observations(t->d_node_words, t->d_records, t->d_stats, t->d_tab + (size_t)2u * inst->batch_cap, t->nbufs, inst->d_match_n, nb, t->max_rows,
-                                          inst->d_feats, inst->buf_stride, inst->d_found, VKSIFT_MAX_OCTAVES, rank_layouts, pair_layouts(inst, o->h_tab), min_length,
+  HIP_CHECK(vksift_hip_track_observations(t->d_node_words, t->d_records, t->d_stats, t->d_tab + (size_t)2u * inst->batch_cap, t->nbufs, t->d_rows, nb, t->max_rows,
+                                          inst->d_feats, inst->buf_stride, inst->d_found, VKSIFT_MAX_OCTAVES, rank_layouts, layouts, min_length,
                                           max_length, conflicts, o->d_offsets, o->d_track_ids, cap_nodes / 2u, o->d_obs, cap_nodes, o->d_stats, o->d_scratch,
                                           o->scratch_u32, inst->stream),
             "observation building");
@@ -88,11 +86,11 @@ void vksift_ext_selectTrackObservations(vksift_Instance instance, uint32_t min_l
   HIP_CHECK(vksift_hip_event_record(inst->ev_otab, inst->stream), "event record");
   o->tab_pending = true;
   HIP_CHECK(vksift_hip_post_words(o->h_stats, o->d_stats, 4u, inst->stream), "observation statistics read-back");
-  HIP_CHECK(stage_end(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
+  HIP_CHECK(stage_end(inst, &frame, t->ids, t->ids, t->nbufs), "event record");
   o->valid = true;
   return;
 gpu_error:
-  stage_fail(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count);
+  stage_fail(inst, &frame, t->ids, t->ids, t->nbufs);
   logError(LOG_TAG, OBS_FN " error: Failed to start the observation building.");
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }

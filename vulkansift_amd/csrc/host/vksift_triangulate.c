@@ -2,7 +2,7 @@
  * vksift_triangulate.c — the selected tracks of the last vksift_ext_selectTrackObservations triangulated under caller-supplied cameras
  * (vksift_ext_triangulateTracks and its accessors): one point per selected track, computed where the observation table lies. No counterpart in the
  * reference: its callers download the table and triangulate track by track on the host. Same contract as the selection it follows
- * (vksift_observations.c): queued on the instance stream, the pairs' buffers busy, the accessors wait; results in storage of its own.
+ * (vksift_observations.c): queued on the instance stream, the tracks' participating buffers busy, the accessors wait; results in storage of its own.
  */
 #include "vksift_internal.h"
 
@@ -52,9 +52,9 @@ void vksift_ext_triangulateTracks(vksift_Instance instance, const float *cameras
   StageFrame frame = {0};
   vksift_hip_set_device(inst->device);
   defer_sync(inst);
-  const uint32_t count = inst->res[PR_FILTERED].slots_used;
+  const TrackResults *t = &inst->tracks;
   const float t2 = threshold_px * threshold_px;
-  if (!o->valid || !inst->tracks.valid || count == 0 || cameras == NULL || !(threshold_px > 0.f) || !isfinite(threshold_px) || !(t2 > 0.f) || !isfinite(t2) ||
+  if (!o->valid || !t->valid || cameras == NULL || !(threshold_px > 0.f) || !isfinite(threshold_px) || !(t2 > 0.f) || !isfinite(t2) ||
       isnan(cos_min_angle) || !cameras_finite(inst, cameras))
   {
     logError(LOG_TAG, TRI_FN " error: invalid input.");
@@ -99,11 +99,11 @@ void vksift_ext_triangulateTracks(vksift_Instance instance, const float *cameras
   p->valid = inst->cams.valid = false; /* the launch replaces the points: not served until the whole sequence has been queued; the cameras refined on the earlier
                                         * points are not served any more (vksift_cameras.c) */
   HIP_CHECK(vksift_hip_post_words(p->h_stats, p->d_stats, 4u, inst->stream), "point statistics read-back");
-  HIP_CHECK(stage_end(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count), "event record");
+  HIP_CHECK(stage_end(inst, &frame, t->ids, t->ids, t->nbufs), "event record");
   p->valid = true;
   return;
 gpu_error:
-  stage_fail(inst, &frame, inst->filt_ids, inst->filt_ids + inst->batch_cap, count);
+  stage_fail(inst, &frame, t->ids, t->ids, t->nbufs);
   logError(LOG_TAG, TRI_FN " error: Failed to start the triangulation.");
   inst->error_cb(VKSIFT_VULKAN_ERROR);
 }
